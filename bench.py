@@ -21,14 +21,8 @@ import time
 # it when it initialises, i.e. it must be in the environment before the first HIP call of the process (torch is imported
 # below).  The image exports it already; a caller's shell that dropped it gets it back here.  (One-rank runs do not need it.)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-# The contexts' streams must not share hardware queues: the ROCm runtime multiplexes a process's HIP streams onto
-# GPU_MAX_HW_QUEUES hardware queues (default 4), and with the null stream holding one of them the fourth context's kernels queue
-# behind another stream's (measured: 166 k frames/s instead of 200 k for four contexts on the runtime's default).  Read by the
-# runtime when it initialises, like the variable above; INTEGRATION.md tells C/C++ callers the same.  12: four context streams, the
-# null stream, and -- in multi-rank runs -- the gather stream and RCCL's own streams each get a queue (one-GPU run: 5 .. 12 queues all give
-# ~195 k; with RCCL initialised 6 / 8 / 12 queues give 155 / 182 / 195 k).  Five contexts and RCCL (round 3, one-rank rehearsal with
-# the per-step gather): 12 / 16 / 24 queues give 213.6 / 213.9 / 218.8 k against 232 k without the gather -- 24 for multi-rank runs.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24" if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("OCVAR_BENCH_FORCE_DIST") else "12")
+# The contexts' streams share the process's hardware queues; how many the runtime opens is the host's setting, never changed
+# here ("Hardware queues").
 
 import numpy as np
 
@@ -94,6 +88,28 @@ def check_results(det, d_frames_ptr, cfg, truths, W, Hh, n):
             assert off <= 12, f"frame {f}: decoded square {sq.tolist()} is {off} px off every planted marker"
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, markers, counts, suffix="", limit=DUMP_BYTES):
+    """Writes what a caller of the timed path receives -- per frame its full marker count and its CvarMarker records (unused
+    slots zeroed) -- as one float32 / float64 .npy per field.  A batch whose arrays exceed `limit` bytes is sampled: a fixed,
+    seeded set of frames, listed in frame_index.npy."""
+    n, k = markers.shape
+    markers = markers.copy()
+    markers[np.arange(k)[None, :] >= np.minimum(counts, k)[:, None]] = np.zeros((), markers.dtype)
+    fields = {"counts": counts.astype(np.float64)}
+    for name in markers.dtype.names:
+        fields[name] = markers[name].astype(np.float32 if markers[name].dtype == np.float32 else np.float64)
+    frame_bytes = sum(a.nbytes for a in fields.values()) // n + 8   # + frame_index
+    keep = min(n, (limit - 4096) // frame_bytes)                    # (4 KB for the .npy headers)
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, f"frame_index{suffix}.npy"), idx.astype(np.float64))
+    for name, a in fields.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a[idx])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -110,7 +126,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the one-frame-per-call latency leg (child process)")
     ap.add_argument("--no-check", action="store_true", help="skip the result check before the warm-up (profile runs: keeps every launch of a kernel full-size)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's results (marker records and "
+                    "counts of every frame of the batch) as DIR/<name>.npy, at most 64 MB (multi-rank: DIR/<name>_rank<r>.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import helpers as H
@@ -199,6 +219,8 @@ def main():
     spans = {0: [], 5: []}   # (start, end) in ms after ref_event of every full-size launch of the two binarise kernels (timed region)
     frames_done = [0]
     last = {}
+    at = {}      # context -> first batch frame of its launch in flight
+    final = []   # (first batch frame, (markers, counts)) of every collect of a run's last step
 
     # The gather runs on its own high-priority stream and is never waited for on the host inside a step: a launch that writes a
     # result buffer again waits (stream-ordered) for the gather that last read it.  (Waiting on the host after every gather
@@ -216,6 +238,7 @@ def main():
         if gather_done[buf] is not None:
             streams[i].wait_event(gather_done[buf])
         dets[i].enqueue_device(d_frames.data_ptr() + o * frame_bytes, W, Hh, n)
+        at[i] = o
         if gathering and "blocks" not in dist_skip:
             dets[i].results_to_device(d_res[buf].data_ptr() + o * GATHER_K * S.MARKER_BYTES,
                                       d_res[buf].data_ptr() + nbytes_m + 4 * o, streams[i].cuda_stream, per_frame=GATHER_K)
@@ -235,11 +258,14 @@ def main():
     def run(K, timed):
         first = [max(1, ((i + 1) * sub[i]) // NS) for i in range(NS)]
         parts = [None] * NS
+        final.clear()
         for i in range(NS):
             enqueue(i, first[i], 0)
         for k in range(K):
             for i in range(NS):
                 parts[i] = collect(i, timed)
+                if k == K - 1:
+                    final.append((at[i], parts[i]))
                 n = sub[i] if k < K - 1 else sub[i] - first[i]
                 if n > 0:   # the last, partial launch covers the frames the first one left out
                     enqueue(i, n, (k + 1) % 2, skip=0 if k < K - 1 else first[i])
@@ -258,6 +284,7 @@ def main():
                     assert max(c for c, _ in got.values()) <= GATHER_K, "a frame has more markers than the gathered block keeps"
         for i in list(last):
             parts[i] = collect(i, timed)
+            final.append((at[i], parts[i]))
             last.pop(i)
         if gathering:
             gather_stream.synchronize()   # every gather of this run has arrived
@@ -282,6 +309,16 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        # every frame of the batch from the last step's launch that covered it (a later launch overwrites an earlier one)
+        out_m = np.zeros((B, final[0][1][0].shape[1]), oa.MARKER_DTYPE)
+        out_c = np.zeros(B, np.int32)
+        covered = np.zeros(B, bool)
+        for o, (m, c) in final:
+            out_m[o:o + len(c)], out_c[o:o + len(c)] = m, c
+            covered[o:o + len(c)] = True
+        assert covered.all(), "the last step's launches do not cover the batch"
+        dump_outputs(args.dump_outputs, out_m, out_c, f"_rank{rank}" if world > 1 else "", DUMP_BYTES // world)
 
     # Outside the timed region: per-kernel durations of launches that run alone on the GPU (one context, its
     # sub-batch).  With several streams the timed region's launches overlap each other, so their event-to-event

@@ -43,9 +43,6 @@ extern "C" int ocvar_hip_pipe_create(OcvarPipe** out, int device, int max_width,
                                      int gate_width) {
     if (!out || chunk_frames < 1 || n_contexts < 1 || n_contexts > 16 || gate_width < 0) return OCVAR_E_ARG;
     *out = nullptr;
-    // every context's stream needs a hardware queue of its own ("Hardware queues"): effective only when this is the
-    // process's first HIP call -- a process that touched HIP earlier exports GPU_MAX_HW_QUEUES itself
-    (void)setenv("GPU_MAX_HW_QUEUES", n_contexts + 4 > 8 ? "20" : "8", 0);
     OcvarPipe* p = new (std::nothrow) OcvarPipe();
     if (!p) return OCVAR_E_HIP;
     *out = p;   // returned even on failure below so that the caller can read the error text, then destroy

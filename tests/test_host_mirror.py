@@ -171,14 +171,45 @@ def test_png_reader_colour_types_and_filters(host):
             assert host.cvarLoadTemplateTag(C.byref(H.Template()), p.encode(), 0.01) == 0, label
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/template/2x2-01.png"), reason="reference tree not present (build container only)")
-def test_reference_template_files_give_appendix_c_codes(host):
-    """The reference's own three template PNGs (the 2x2 is an RGB file), read where they lie: SURVEY Appendix C's codes."""
+def _reference_like_png(grid, rgb):
+    """A PNG laid out like the reference's template files: 8-bit grey (RGB for the 2x2), sRGB / pHYs / tIME / tEXt chunks ahead
+    of the one IDAT, the row filter changing from row to row (None, Sub, Up, Average, Paeth, ...)."""
+    import struct
+    import zlib
+    bpp = 3 if rgb else 1
+    rows = np.repeat(np.asarray(grid, np.uint8), bpp, axis=1).astype(int)
+    raw, up = b"", np.zeros(rows.shape[1], int)
+    for y, cur in enumerate(rows):
+        ft = y % 5
+        out = []
+        for i, v in enumerate(cur):
+            a, b, c = (cur[i - bpp] if i >= bpp else 0), up[i], (up[i - bpp] if i >= bpp else 0)
+            p = a + b - c
+            paeth = a if abs(p - a) <= abs(p - b) and abs(p - a) <= abs(p - c) else (b if abs(p - b) <= abs(p - c) else c)
+            out.append((v - (0, a, b, (a + b) >> 1, paeth)[ft]) & 255)
+        raw += bytes([ft] + out)
+        up = cur
+
+    def chunk(t, d):
+        return struct.pack(">I", len(d)) + t + d + struct.pack(">I", zlib.crc32(t + d) & 0xffffffff)
+    h, w = len(grid), len(grid[0])
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2 if rgb else 0, 0, 0, 0)) +
+            chunk(b"sRGB", b"\0") + chunk(b"pHYs", struct.pack(">IIB", 2835, 2835, 1)) +
+            chunk(b"tIME", struct.pack(">HBBBBB", 2012, 1, 1, 0, 0, 0)) + chunk(b"tEXt", b"Comment\0template") +
+            chunk(b"IDAT", zlib.compress(raw)) + chunk(b"IEND", b""))
+
+
+def test_reference_template_files_give_appendix_c_codes(host, tmp_path):
+    """The three shipped templates in files laid out like the reference's own template PNGs (the 2x2 is an RGB file, the
+    others grey; ancillary chunks ahead of the pixel data; mixed row filters): SURVEY Appendix C's codes."""
     host.cvarLoadTemplateTag.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
     expect = {"2x2-01": [0x8, 0x2, 0x1, 0x4], "3x3-01": [0x174, 0x117, 0x5d, 0x1d1], "4x4-01": [0xdeed, 0x96ff, 0xb77b, 0xff69]}
+    tp = H.template_pixels()
     for name, codes in expect.items():
+        path = tmp_path / (name + ".png")
+        path.write_bytes(_reference_like_png(tp[name][0], rgb=name == "2x2-01"))
         t = H.Template()
-        assert host.cvarLoadTemplateTag(C.byref(t), f"/root/reference/template/{name}.png".encode(), 0.01) == 1
+        assert host.cvarLoadTemplateTag(C.byref(t), str(path).encode(), 0.01) == 1
         assert [int(c) for c in t.code] == codes, name
 
 

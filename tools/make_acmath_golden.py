@@ -56,6 +56,16 @@ for k in range(24):
         b = C.c_longlong(bit0)
         ref.acBitRotate(C.byref(b), rot, 8, 8)
         out["bit_rotate"].append({"n": 8, "bit": bit0, "rot": rot, "out": b.value})
+# the 200 seeded rotations of tests/test_oracle.py::test_acmath_against_compiled_reference (same draws, own generator)
+rng5 = np.random.default_rng(5)
+out["bit_rotate_seed5"] = []
+for _ in range(200):
+    n = int(rng5.integers(1, 9))
+    bit0 = int(rng5.integers(0, 2 ** min(62, n * n)))
+    rot = int(rng5.integers(0, 4))
+    b = C.c_longlong(bit0)
+    ref.acBitRotate(C.byref(b), rot, n, n)
+    out["bit_rotate_seed5"].append({"n": n, "bit": bit0, "rot": rot, "out": b.value})
 def rot_m(axis, ang):
     c, s = np.cos(ang), np.sin(ang)
     R = {0: [[1,0,0],[0,c,-s],[0,s,c]], 1: [[c,0,s],[0,1,0],[-s,0,c]], 2: [[c,-s,0],[s,c,0],[0,0,1]]}[axis]
