@@ -175,8 +175,12 @@ int ocvar_hip_pipe_track_device(OcvarPipe* pipe, uint8_t* d_bgr, int width, int 
  * a chunk of n_frames <= chunk_frames device-resident frames to the next context and returns at once (OCVAR_E_BUSY when every
  * context already has a chunk in flight); collect waits for the OLDEST chunk in flight, writes its markers [n][max_per_frame]
  * and counts [n], stores the tag it was submitted under and returns its frame count n (0: nothing in flight, < 0: error).
- * Stateless.  set_result_limit (only while nothing is in flight): how many marker records per frame the chunks bring to the
- * host, as ocvar_hip_set_result_limit. */
+ * Stateless.  set_result_limit (only while nothing is in flight; 1..OCVAR_MAX_MARKERS, default OCVAR_MAX_MARKERS): how many
+ * marker records per frame the submitted chunks bring to the host, as ocvar_hip_set_result_limit.  collect returns OCVAR_E_ARG,
+ * and leaves the chunk in flight, when max_per_frame exceeds that limit (rows the chunk never brought back).  The markers
+ * buffer must hold n rows of max_per_frame records, n up to chunk_frames.  detect_device / track_device bring back
+ * max_per_frame records per frame for their own call and leave the limit as it was; they fail with OCVAR_E_ARG while a
+ * submitted chunk is in flight. */
 enum { OCVAR_E_BUSY = -6 };
 int ocvar_hip_pipe_submit(OcvarPipe* pipe, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride, int n_frames,
                           int grey_in_place, long long tag);

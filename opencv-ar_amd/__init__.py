@@ -198,6 +198,7 @@ class Pipe:
     def __init__(self, max_width, max_height, chunk_frames=2048, n_contexts=4, gate_width=2, device=0):
         self._lib = hip_lib()
         self._p = C.c_void_p()
+        self.chunk_frames = chunk_frames
         rc = self._lib.ocvar_hip_pipe_create(C.byref(self._p), device, max_width, max_height, chunk_frames, n_contexts, gate_width)
         if rc != 0:
             msg = self._lib.ocvar_hip_pipe_last_error(self._p).decode() if self._p else ""
@@ -246,9 +247,12 @@ class Pipe:
         return True
 
     def collect(self, max_frames, max_per_frame=MAX_MARKERS):
-        """the oldest chunk in flight: (tag, markers [n][max_per_frame], counts [n]) or None when nothing is in flight"""
-        markers = np.zeros((max_frames, max_per_frame), MARKER_DTYPE)
-        counts = np.zeros(max_frames, np.int32)
+        """the oldest chunk in flight: (tag, markers [n][max_per_frame], counts [n]) or None when nothing is in flight.
+        max_per_frame must not exceed the pipe's result limit (set_result_limit)."""
+        # the C call writes one row per frame of the chunk, up to chunk_frames of them, whatever max_frames says
+        rows = max(max_frames, self.chunk_frames)
+        markers = np.zeros((rows, max_per_frame), MARKER_DTYPE)
+        counts = np.zeros(rows, np.int32)
         tag = C.c_longlong(0)
         n = self._lib.ocvar_hip_pipe_collect(self._p, C.byref(tag), _ptr(markers), _ptr(counts), max_per_frame)
         if n < 0:

@@ -16,6 +16,7 @@
 
 struct OcvarPipe {
     int device = 0, n_ctx = 0, chunk = 0;
+    int limit = OCVAR_MAX_MARKERS;   // records per frame the streaming form brings to the host (ocvar_hip_pipe_set_result_limit)
     std::vector<OcvarHip*> ctx;
     OcvarGate* gate = nullptr;
     // tracking state of ocvar_hip_pipe_track_device: every stream's markers of the last step, on the device
@@ -91,7 +92,9 @@ extern "C" int ocvar_hip_pipe_set_camera(OcvarPipe* p, const OcvarCamera* cam) {
 static int pipe_run(OcvarPipe* p, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride, long long n_frames,
                     int grey_in_place, bool tracked, OcvarMarker* markers, int* counts, int max_per_frame) {
     const int K = p->n_ctx;
-    // the contexts bring back as many records per frame as the caller keeps (24 MB per 2048-frame chunk at 64, 3 MB at 8)
+    if (p->head != p->tail) { p->err = "a context of the pipe still has a submitted chunk in flight: collect it first"; return OCVAR_E_ARG; }
+    // the contexts bring back as many records per frame as the caller keeps (24 MB per 2048-frame chunk at 64, 3 MB at 8), for
+    // this call only: the streaming form's limit is restored at the end (it would otherwise clamp a later collect's records)
     const int limit = max_per_frame < 1 ? 1 : (max_per_frame > OCVAR_MAX_MARKERS ? OCVAR_MAX_MARKERS : max_per_frame);
     for (OcvarHip* c : p->ctx) {
         const int rc = ocvar_hip_set_result_limit(c, limit);
@@ -147,6 +150,7 @@ static int pipe_run(OcvarPipe* p, uint8_t* d_bgr, int width, int height, int row
             }
         }
     }
+    for (OcvarHip* c : p->ctx) (void)ocvar_hip_set_result_limit(c, p->limit);   // (every chunk collected above)
     return first_err;
 }
 
@@ -215,6 +219,10 @@ extern "C" int ocvar_hip_pipe_submit(OcvarPipe* p, uint8_t* d_bgr, int width, in
 extern "C" int ocvar_hip_pipe_collect(OcvarPipe* p, long long* tag, OcvarMarker* markers, int* counts, int max_per_frame) {
     if (!p || !counts || max_per_frame < 0 || (max_per_frame > 0 && !markers)) return OCVAR_E_ARG;
     if (p->head == p->tail) return 0;   // nothing in flight
+    if (max_per_frame > p->limit) {       // rows the chunk never brought to the host (the chunk stays in flight)
+        p->err = "max_per_frame exceeds the pipe's result limit (ocvar_hip_pipe_set_result_limit)";
+        return OCVAR_E_ARG;
+    }
     const int i = (int)(p->tail % p->n_ctx);
     const int rc = ocvar_hip_collect(p->ctx[i], markers, counts, max_per_frame);
     p->tail++;   // (the chunk is gone either way: a failed batch is not collected twice)
@@ -224,10 +232,11 @@ extern "C" int ocvar_hip_pipe_collect(OcvarPipe* p, long long* tag, OcvarMarker*
 }
 
 extern "C" int ocvar_hip_pipe_set_result_limit(OcvarPipe* p, int max_per_frame) {
-    if (!p || p->head != p->tail) return OCVAR_E_ARG;
+    if (!p || p->head != p->tail || max_per_frame < 1 || max_per_frame > OCVAR_MAX_MARKERS) return OCVAR_E_ARG;
     for (OcvarHip* c : p->ctx) {
         const int rc = ocvar_hip_set_result_limit(c, max_per_frame);
         if (rc) return rc;
     }
+    p->limit = max_per_frame;
     return OCVAR_OK;
 }

@@ -32,36 +32,77 @@ def make_detector(oa, cfg, names, batch):
     return det, tpls, cam
 
 
-def check_frame(det, f, frame_bgr, tpls, cam, markers, counts, prev=None):
-    ref_m, ref_c, grey = H.oracle_registration(frame_bgr, tpls, cam, prev=prev)
-    h, w = frame_bgr.shape[:2]
-    # grey plane and binary image (interior; the HIP path stores it with cvFindContours' zeroed frame)
-    assert np.array_equal(det.debug_gray(f, w, h), grey[..., 0])
-    b_ref = H.oracle_binarise(np.ascontiguousarray(grey[..., 0]))
-    b_gpu = det.debug_binary(f, w, h)
-    assert np.array_equal(b_gpu[1:-1, 1:-1], b_ref[1:-1, 1:-1])
-    # every bit of the neighbour-mask plane the border followers walk on
-    assert np.array_equal(det.debug_masks(f, w, h), H.neighbour_masks(b_ref))
-    if prev is None:
-        q_ref = H.oracle_find_squares(np.ascontiguousarray(grey[..., 0]))
+class OracleFrame:
+    """The oracle's results for one distinct frame, computed once and checked against every batch position that holds it."""
+
+    def __init__(self, frame_bgr, tpls, cam, prev=None, planes=True):
+        self.markers, self.cands, grey = H.oracle_registration(frame_bgr, tpls, cam, prev=prev)
+        self.h, self.w = frame_bgr.shape[:2]
+        self.grey = self.binary = self.masks = self.quads = self.cand_arr = None
+        if planes:
+            self.grey = np.ascontiguousarray(grey[..., 0])
+            self.binary = H.oracle_binarise(self.grey)
+            self.masks = H.neighbour_masks(self.binary)
+            if prev is None:
+                self.quads = H.oracle_find_squares(self.grey)
+
+
+def check_planes(det, f, ref, where=""):
+    """grey plane, binary image (interior; the HIP path stores it with cvFindContours' zeroed frame), every bit of the
+    neighbour-mask plane the border followers walk on, and the frame pass's quads, of batch position f of det's last batch"""
+    w, h = ref.w, ref.h
+    assert np.array_equal(det.debug_gray(f, w, h), ref.grey), ("grey plane", where, f)
+    assert np.array_equal(det.debug_binary(f, w, h)[1:-1, 1:-1], ref.binary[1:-1, 1:-1]), ("binary image", where, f)
+    assert np.array_equal(det.debug_masks(f, w, h), ref.masks), ("mask plane", where, f)
+    if ref.quads is not None:
         q_gpu = det.debug_frame_quads(f)
-        assert q_ref.shape == q_gpu.shape and np.array_equal(q_ref, q_gpu)
+        assert ref.quads.shape == q_gpu.shape and np.array_equal(ref.quads, q_gpu), ("frame quads", where, f)
+
+
+CAND_FIELDS = ("markerId", "templateId", "orient", "bit", "square", "patPoint")
+
+
+def cand_array(cands):
+    """candidates (ctypes Candidate) as a structured array of the fields the bars compare"""
+    dt = np.dtype(H.Candidate)
+    a = np.frombuffer(b"".join(bytes(c) for c in cands), dt) if cands else np.zeros(0, dt)
+    return a[list(CAND_FIELDS)]
+
+
+def check_candidates(det, f, ref, where=""):
+    """the pre-dedupe decoded candidates of batch position f of det's last batch"""
     cands = det.debug_candidates(f)
-    assert len(cands) == len(ref_c)
-    for a, b in zip(cands, ref_c):
-        assert (a.markerId, a.templateId, a.orient, a.bit) == (b.markerId, b.templateId, b.orient, b.bit)
-        assert np.array_equal(np.array(a.square), np.array(b.square))
-        assert np.array_equal(np.array(a.patPoint), np.array(b.patPoint))
-    assert counts[f] == len(ref_m)
-    for k, r in enumerate(ref_m):
+    assert len(cands) == len(ref.cands), ("candidate count", where, f, len(cands), len(ref.cands))
+    if ref.cand_arr is None:
+        ref.cand_arr = cand_array(ref.cands)
+    if np.array_equal(cand_array(cands), ref.cand_arr):   # (the per-record loop below says which record differs)
+        return
+    for k, (a, b) in enumerate(zip(cands, ref.cands)):
+        assert (a.markerId, a.templateId, a.orient, a.bit) == (b.markerId, b.templateId, b.orient, b.bit), ("candidate", where, f, k)
+        assert np.array_equal(np.array(a.square), np.array(b.square)), ("candidate square", where, f, k)
+        assert np.array_equal(np.array(a.patPoint), np.array(b.patPoint)), ("candidate patPoint", where, f, k)
+
+
+def check_markers(f, ref, markers, counts, where=""):
+    """row f of a collect's (markers, counts): the full count and every record the oracle returns (the first markers.shape[1]
+    of them: a collect with a smaller max_per_frame keeps only those)"""
+    assert counts[f] == len(ref.markers), ("count", where, f, int(counts[f]), len(ref.markers))
+    for k, r in enumerate(ref.markers[:markers.shape[1]]):
         m = markers[f, k]
-        assert m["templateId"] == r.templateId and m["markerId"] == r.markerId and m["score"] == r.score
-        assert np.abs(m["square"] - np.array(r.square)).max() <= CORNER_TOL
-        assert m["aspectRatio"] == r.aspectRatio
+        assert m["templateId"] == r.templateId and m["markerId"] == r.markerId and m["score"] == r.score, ("marker ids / score", where, f, k)
+        assert np.abs(m["square"] - np.array(r.square)).max() <= CORNER_TOL, ("marker square", where, f, k)
+        assert m["aspectRatio"] == r.aspectRatio, ("marker aspectRatio", where, f, k)
         g = np.array(r.glMatrix)
         assert np.abs(m["glMatrix"] - g).max() <= POSE_RTOL * max(1.0, np.abs(g).max()), (
-            "pose", f, k, float(np.abs(m["glMatrix"] - g).max()), float(np.abs(g).max()), np.array(r.square).tolist(), g.tolist(), m["glMatrix"].tolist())
-    return ref_m, len(ref_c)
+            "pose", where, f, k, float(np.abs(m["glMatrix"] - g).max()), float(np.abs(g).max()), np.array(r.square).tolist(), g.tolist(), m["glMatrix"].tolist())
+
+
+def check_frame(det, f, frame_bgr, tpls, cam, markers, counts, prev=None):
+    ref = OracleFrame(frame_bgr, tpls, cam, prev=prev)
+    check_planes(det, f, ref)
+    check_candidates(det, f, ref)
+    check_markers(f, ref, markers, counts)
+    return ref.markers, len(ref.cands)
 
 
 def test_config1_single_frame_host_entry(oa):

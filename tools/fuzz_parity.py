@@ -6,6 +6,10 @@ the HIP path and the oracle, compared with the same bars as tests/test_gpu_parit
 decoded candidates bit-exact; markers exact / pose 1e-4).  Not part of the default test run (minutes of CPU oracle time).
 
     python tools/fuzz_parity.py [n_scenes] [seed]      (FUZZ_RANDOM_SIZES=1: random frame sizes instead of the fixed list)
+
+FUZZ_BATCH=N: every scene runs as an N-frame batch (N >= 20): its frames sit at random positions >= 16 (round 3's store hazard
+corrupted mask words only from the 16th frame of a busy batch on), the other positions hold copies of them, and the
+scene's frames are checked at those positions.
 """
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,6 +22,21 @@ import test_gpu_parity as T
 n_scenes = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 sizes = [(640, 480), (641, 479), (800, 600), (1001, 701), (1280, 720), (333, 517), (1920, 1080), (96, 64), (250, 250)]
+batch_n = int(os.environ.get("FUZZ_BATCH", "0"))
+assert batch_n == 0 or batch_n >= 20, "FUZZ_BATCH: at least 20 frames (positions >= 16 for up to 3 scene frames)"
+
+
+def detect(det, frames, prev=None):
+    """the batch through the host entry, or with FUZZ_BATCH as ONE device launch (the host entry runs sub-batches of 64 frames,
+    and the parity hooks see only the last one)"""
+    if not batch_n:
+        return det.detect_host(frames.copy(), prev=prev)
+    import torch
+    d = torch.from_numpy(frames).cuda()
+    torch.cuda.synchronize()
+    return det.detect_device(d.data_ptr(), frames.shape[2], frames.shape[1], len(frames), prev=prev)
+
+
 t0 = time.time()
 frames_checked = markers_seen = cands_seen = 0
 for s in range(n_scenes):
@@ -64,29 +83,34 @@ for s in range(n_scenes):
             img = (img + np.roll(img, 1, 1) + np.roll(img, -1, 1)) // 3
         frames.append(np.clip(img, 0, 255).astype(np.uint8))
     frames = np.ascontiguousarray(np.stack(frames))
-    det, tpls, cam = T.make_detector(oa, cfg, names, nb)
+    at = list(range(nb))   # batch position of scene frame f
+    if batch_n:
+        at = [int(p) for p in np.sort(rng.choice(np.arange(16, batch_n), size=nb, replace=False))]
+        frames = np.ascontiguousarray(frames[np.arange(batch_n) % nb])
+        frames[at] = frames[:nb].copy()
+    det, tpls, cam = T.make_detector(oa, cfg, names, len(frames))
     if os.environ.get("FUZZ_VERBOSE") == "1":
         print(f"scene {s}: {w}x{h}, {nb} frames, templates {names}", flush=True)
     # the crop pass's two forms (follow.hip::follow_mid_kernel): the batch-size default, one launch, two launches with pruning
     det.set_tuning(crop_phases=s % 3)   # 0: the default for the batch size
     if s % 4 == 3:     # stateful: every lane is a video stream, the scene drifts a few pixels per step (opencvar.cpp:635-668)
-        from opencv_ar_amd.tracking import StreamTracker
-        tracker = StreamTracker(det, nb)
+        lanes = [[] for _ in range(len(frames))]   # every lane's markers of the last step (as opencv_ar_amd.tracking.StreamTracker)
         prev = [None] * nb
         cur = frames
         for step in range(3):
-            markers, counts = tracker.step(cur.copy())
+            markers, counts = detect(det, cur, prev=lanes)
+            lanes = [[markers[l, k].copy() for k in range(min(int(counts[l]), markers.shape[1]))] for l in range(len(frames))]
             for f in range(nb):
-                ref_m, n_c = T.check_frame(det, f, cur[f], tpls, cam, markers, counts, prev=prev[f])
+                ref_m, n_c = T.check_frame(det, at[f], cur[at[f]], tpls, cam, markers, counts, prev=prev[f])
                 prev[f] = ref_m
                 frames_checked += 1; markers_seen += len(ref_m); cands_seen += n_c
             cur = np.ascontiguousarray(np.roll(cur, (int(rng.integers(-6, 7)), int(rng.integers(-6, 7))), axis=(1, 2)))
     else:
-        markers, counts = det.detect_host(frames.copy())
+        markers, counts = detect(det, frames)
         for f in range(nb):
-            ref_m, n_c = T.check_frame(det, f, frames[f], tpls, cam, markers, counts)
+            ref_m, n_c = T.check_frame(det, at[f], frames[at[f]], tpls, cam, markers, counts)
             frames_checked += 1; markers_seen += len(ref_m); cands_seen += n_c
     del det
     if (s + 1) % 10 == 0:
         print(f"scene {s + 1}/{n_scenes}: {frames_checked} frames equal so far ({cands_seen} decoded candidates, {markers_seen} markers), {time.time() - t0:.0f} s", flush=True)
-print(f"fuzz_parity: {frames_checked} frames, {cands_seen} candidates, {markers_seen} markers: all equal")
+print(f"fuzz_parity{f' (FUZZ_BATCH={batch_n}: batch positions >= 16)' if batch_n else ''}: {frames_checked} frames, {cands_seen} candidates, {markers_seen} markers: all equal")
