@@ -54,7 +54,10 @@ enum {
     OCVAR_E_CAPACITY = -4     /* a device work list overflowed (frame too cluttered for the configured limits) */
 };
 
-enum { OCVAR_MAX_TEMPLATES = 16, OCVAR_MAX_QUADS = 256, OCVAR_MAX_MARKERS = 64,
+/* Templates per context: up to OCVAR_MAX_TEMPLATES, each of at most 64 code cells (width x height), in at most
+ * OCVAR_MAX_TEMPLATE_SIZES distinct (width, height) code sizes; ocvar_hip_set_templates returns OCVAR_E_ARG beyond either.
+ * Identical templates and rotationally symmetric codes are allowed, as in the reference. */
+enum { OCVAR_MAX_TEMPLATES = 4096, OCVAR_MAX_TEMPLATE_SIZES = 16, OCVAR_MAX_QUADS = 256, OCVAR_MAX_MARKERS = 64,
        OCVAR_MAX_QUADS_EX = 1792 /* most squares per frame a context can be created for (ocvar_hip_create_ex) */ };
 
 /* Creates a context on `device` with workspace for batches of up to max_batch frames of up to
@@ -204,6 +207,8 @@ int ocvar_hip_debug_binary(OcvarHip* ctx, int frame, uint8_t* h_bin /* (w&~1)*(h
 /* the frame pass's 8-neighbour masks, untiled: bit s of pixel (x,y) = the neighbour in direction s (0..7 = E,NE,N,NW,W,SW,S,SE) is set */
 int ocvar_hip_debug_masks(OcvarHip* ctx, int frame, uint8_t* h_masks /* (w&~1)*(h&~1) */);
 int ocvar_hip_debug_frame_quads(OcvarHip* ctx, int frame, int* quads /* OCVAR_MAX_QUADS*8 */, int* n_quads);
+/* the pre-dedupe candidates in the reference's order (square-major, all templates of every square with a crop quad); at most
+ * max_cands are written, *n_cands is the full count */
 int ocvar_hip_debug_candidates(OcvarHip* ctx, int frame, OcvarCandidate* cands, int max_cands, int* n_cands);
 
 /* Measurement aid: runs a dword-per-lane copy of `bytes` bytes (the binarise kernel's access widths) so that a

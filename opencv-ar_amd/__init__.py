@@ -17,7 +17,7 @@ HIP_LIB = os.environ.get("OCVAR_HIP_LIB") or os.path.join(LIB_DIR, "libocvar_hip
 SYNTH_LIB = os.path.join(LIB_DIR, "libocvar_synth.so")
 HOST_LIB = os.path.join(LIB_DIR, "libopencv-ar.so.1.0.0")
 
-MAX_TEMPLATES, MAX_QUADS, MAX_MARKERS = 16, 256, 64
+MAX_TEMPLATES, MAX_TEMPLATE_SIZES, MAX_QUADS, MAX_MARKERS = 4096, 16, 256, 64
 
 # every symbol include/ocvar_hip.h declares
 HIP_SYMBOLS = [
@@ -430,9 +430,14 @@ class Detector:
         self._check(self._lib.ocvar_hip_debug_frame_quads(self._ctx, frame, _ptr(quads), C.byref(n)), "debug_frame_quads")
         return quads[:min(n.value, MAX_QUADS)].copy()
 
-    def debug_candidates(self, frame, max_cands=MAX_QUADS * MAX_TEMPLATES):
-        arr = (Candidate * max_cands)()
+    def debug_candidates(self, frame, max_cands=None):
+        """the pre-dedupe candidates of batch position `frame` (all of them by default: the frame's squares x n_templates at most)"""
         n = C.c_int(0)
+        if max_cands is None:
+            one = (Candidate * 1)()
+            self._check(self._lib.ocvar_hip_debug_candidates(self._ctx, frame, one, 1, C.byref(n)), "debug_candidates")
+            max_cands = max(n.value, 1)
+        arr = (Candidate * max_cands)()
         self._check(self._lib.ocvar_hip_debug_candidates(self._ctx, frame, arr, max_cands, C.byref(n)), "debug_candidates")
         return [arr[i] for i in range(min(n.value, max_cands))]
 

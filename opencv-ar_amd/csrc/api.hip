@@ -17,6 +17,7 @@
 using namespace ocvar;
 
 static_assert(sizeof(TemplateRec) == sizeof(OcvarTemplate) && sizeof(TemplateRec) == 48, "CvarTemplate layout");
+static_assert(MAX_SIZE_CLASSES == OCVAR_MAX_TEMPLATE_SIZES, "size classes");
 static_assert(sizeof(CameraRec) == sizeof(OcvarCamera) && sizeof(CameraRec) == 248, "CvarCamera layout");
 static_assert(sizeof(MarkerRec) == sizeof(OcvarMarker) && sizeof(MarkerRec) == 184, "CvarMarker layout");
 
@@ -56,6 +57,8 @@ struct OcvarHip {
     int* h_counters = nullptr;       // pinned
     bool pending = false;
     bool have_templates = false, have_camera = false;
+    Library lib;              // the templates' table as uploaded (ocvar_hip_debug_candidates expands a square with it)
+    size_t sq_codes_bytes = 0, sq_match_bytes = 0;   // allocations of ws.sq_codes / ws.sq_match (they grow with the library)
     int capacity_flags = 0;   // flag word of the last batch that failed with OCVAR_E_CAPACITY
     std::string err;
 };
@@ -108,7 +111,6 @@ extern "C" int ocvar_hip_create_ex(OcvarHip** out, int device, int max_width, in
     w.max_h = max_height;
     w.max_batch = max_batch;
     w.maxq = max_quads;
-    w.maxc = max_quads;   // set with the templates (maxq * n_templates, at most what 64 KB of LDS hold)
     const size_t B = (size_t)max_batch, WH = (size_t)max_width * max_height;
     size_t per_frame_cands = WH / 16 < 16384 ? 16384 : WH / 16;
     w.cap_frame_cands = (int)std::min<size_t>(B * per_frame_cands, (size_t)1 << 30);
@@ -151,7 +153,7 @@ extern "C" int ocvar_hip_create_ex(OcvarHip** out, int device, int max_width, in
     if ((rc = dev_alloc(c, &w.crop_min_rest, (size_t)w.cap_crop_rois))) return rc;
     if ((rc = dev_alloc(c, &w.ring_frame, B))) return rc;
     if ((rc = dev_alloc(c, &w.ring_crop, (size_t)w.cap_crop_rois))) return rc;
-    if ((rc = dev_alloc(c, &w.cand_recs, B * max_quads * MAXT))) return rc;
+    if ((rc = dev_alloc(c, &w.sq_recs, B * max_quads))) return rc;   // (sq_codes, sq_match: ocvar_hip_set_templates)
     if ((rc = dev_alloc(c, &w.prev, B * MAXM))) return rc;
     if ((rc = dev_alloc(c, &w.n_prev, B))) return rc;
     if ((rc = dev_alloc(c, &w.reserve, B * MAXM))) return rc;
@@ -160,6 +162,10 @@ extern "C" int ocvar_hip_create_ex(OcvarHip** out, int device, int max_width, in
     if ((rc = dev_alloc(c, &w.pose_jobs, B * MAXM))) return rc;
     if ((rc = dev_alloc(c, &w.n_markers, B))) return rc;
     if ((rc = dev_alloc(c, &w.templates, (size_t)MAXT))) return rc;
+    if ((rc = dev_alloc(c, &w.sizes, (size_t)MAX_SIZE_CLASSES))) return rc;
+    if ((rc = dev_alloc(c, &w.lut, (size_t)4 * MAXT))) return rc;
+    if ((rc = dev_alloc(c, &w.group_off, (size_t)MAXT + 1))) return rc;
+    if ((rc = dev_alloc(c, &w.group_members, (size_t)MAXT))) return rc;
     if ((rc = dev_alloc(c, &w.camera, (size_t)1))) return rc;
     if ((rc = dev_alloc(c, &w.counters, (size_t)CNT_COUNT))) return rc;
 
@@ -179,6 +185,8 @@ extern "C" void ocvar_hip_destroy(OcvarHip* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void* p : c->allocs) (void)hipFree(p);
+    if (c->ws.sq_codes) (void)hipFree(c->ws.sq_codes);
+    if (c->ws.sq_match) (void)hipFree(c->ws.sq_match);
     if (c->d_frames) (void)hipFree(c->d_frames);
     for (auto p : c->h_stage)
         if (p) (void)hipHostFree(p);
@@ -251,14 +259,54 @@ extern "C" void* ocvar_hip_stream(const OcvarHip* c) { return c ? (void*)c->stre
 extern "C" const char* ocvar_hip_last_error(const OcvarHip* c) { return c ? c->err.c_str() : "null context"; }
 extern "C" int ocvar_hip_capacity_flags(const OcvarHip* c) { return c ? c->capacity_flags : 0; }
 
+// A per-square array of the workspace that grows with the library: reallocated when the new library needs more.
+template <typename T>
+static int grow(OcvarHip* c, T** p, size_t* have, size_t bytes) {
+    if (bytes <= *have) return OCVAR_OK;
+    if (*p) HIP_TRY(c, hipFree(*p));
+    *p = nullptr;
+    *have = 0;
+    void* q = nullptr;
+    HIP_TRY(c, hipMalloc(&q, bytes));
+    *p = static_cast<T*>(q);
+    *have = bytes;
+    return OCVAR_OK;
+}
+
 extern "C" int ocvar_hip_set_templates(OcvarHip* c, const OcvarTemplate* t, int n) {
-    if (!c || !t || n < 1 || n > MAXT) return OCVAR_E_ARG;
+    if (!c) return OCVAR_E_ARG;
+    if (!t || n < 1 || n > MAXT) {
+        c->err = "ocvar_hip_set_templates: need 1.." + std::to_string(MAXT) + " templates";
+        return OCVAR_E_ARG;
+    }
     for (int i = 0; i < n; i++)
-        if (t[i].width < 1 || t[i].height < 1 || t[i].width * t[i].height > 64) return OCVAR_E_ARG;
+        if (t[i].width < 1 || t[i].height < 1 || t[i].width * t[i].height > 64) {
+            c->err = "ocvar_hip_set_templates: template " + std::to_string(i) + " is not 1..64 code cells";
+            return OCVAR_E_ARG;
+        }
+    Library lib;
+    if (!build_library(reinterpret_cast<const TemplateRec*>(t), n, &lib)) {
+        c->err = "ocvar_hip_set_templates: more than " + std::to_string(MAX_SIZE_CLASSES) + " distinct template sizes";
+        return OCVAR_E_ARG;
+    }
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpy(c->ws.templates, t, n * sizeof(OcvarTemplate), hipMemcpyHostToDevice));
-    c->ws.n_templates = n;
-    c->ws.maxc = std::min(c->ws.maxq * n, 7000);   // 9 bytes of LDS per candidate, 64 KB per workgroup
+    if (c->pending) HIP_TRY(c, hipStreamSynchronize(c->last_stream));   // (the batch in flight reads the tables)
+    Workspace& w = c->ws;
+    const size_t squares = (size_t)w.max_batch * w.maxq;
+    c->have_templates = false;   // (until the tables below are all in place)
+    int rc;
+    if ((rc = grow(c, &w.sq_codes, &c->sq_codes_bytes, squares * lib.sizes.size() * sizeof(long long)))) return rc;
+    if ((rc = grow(c, &w.sq_match, &c->sq_match_bytes, squares * lib.max_match * sizeof(int)))) return rc;
+    HIP_TRY(c, hipMemcpy(w.templates, t, n * sizeof(OcvarTemplate), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(w.sizes, lib.sizes.data(), lib.sizes.size() * sizeof(SizeClass), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(w.lut, lib.lut.data(), lib.lut.size() * sizeof(LutEntry), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(w.group_off, lib.group_off.data(), lib.group_off.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(w.group_members, lib.members.data(), lib.members.size() * sizeof(int), hipMemcpyHostToDevice));
+    w.n_templates = n;
+    w.n_sizes = (int)lib.sizes.size();
+    w.n_groups = lib.n_groups();
+    w.max_match = lib.max_match;
+    c->lib = std::move(lib);
     c->have_templates = true;
     return OCVAR_OK;
 }
@@ -893,26 +941,47 @@ extern "C" int ocvar_hip_debug_candidates(OcvarHip* c, int frame, OcvarCandidate
     int nsq = 0;
     HIP_TRY(c, hipMemcpy(&nsq, c->ws.n_squares + frame, sizeof(int), hipMemcpyDeviceToHost));
     if (nsq > c->ws.maxq) nsq = c->ws.maxq;
-    std::vector<CandRec> recs((size_t)c->ws.maxq * MAXT);
-    HIP_TRY(c, hipMemcpy(recs.data(), c->ws.cand_recs + (size_t)frame * c->ws.maxq * MAXT, recs.size() * sizeof(CandRec), hipMemcpyDeviceToHost));
-    int n = 0;
-    for (int i = 0; i < nsq; i++)
-        for (int j = 0; j < c->ws.n_templates; j++) {
-            const CandRec& r = recs[(size_t)i * MAXT + j];
-            if (!r.valid) continue;
-            if (n < max_cands) {
-                OcvarCandidate& o = cands[n];
-                o.markerId = i;
-                o.templateId = j;
-                o.orient = r.orient;
-                o.valid = 1;
-                o.bit = r.bit;
-                std::memcpy(o.square, r.square, sizeof o.square);
-                std::memcpy(o.patPoint, r.patPoint, sizeof o.patPoint);
-            }
-            n++;
+    // the compact records of the frame's squares, expanded to the reference's list: K candidates per square with a crop quad,
+    // in template order, the orient 2/4 rotations accumulating over the square's templates
+    const Workspace& w = c->ws;
+    const Library& L = c->lib;
+    const size_t first = (size_t)frame * w.maxq;
+    std::vector<SquareRec> recs(nsq > 0 ? nsq : 1);
+    std::vector<long long> codes((size_t)(nsq > 0 ? nsq : 1) * w.n_sizes);
+    std::vector<int> match((size_t)(nsq > 0 ? nsq : 1) * w.max_match);
+    if (nsq > 0) {
+        HIP_TRY(c, hipMemcpy(recs.data(), w.sq_recs + first, nsq * sizeof(SquareRec), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(codes.data(), w.sq_codes + first * w.n_sizes, codes.size() * sizeof(long long), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(match.data(), w.sq_match + first * w.max_match, match.size() * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    std::vector<int> orient_of(L.n_groups(), 0);
+    long long n = 0;
+    for (int i = 0; i < nsq; i++) {
+        const SquareRec& r = recs[i];
+        if (r.n_match < 0) continue;
+        if (n >= max_cands) {   // (only the count is still wanted)
+            n += w.n_templates;
+            continue;
         }
-    *n_cands = n;
+        const int* m = match.data() + (size_t)i * w.max_match;
+        for (int k = 0; k < r.n_match; k++) orient_of[match_group(m[k])] = match_orient_of(m[k]);
+        int sh = 0;
+        for (int j = 0; j < w.n_templates; j++, n++) {
+            const int orient = orient_of[L.group_of[j]];
+            sh = (sh + orient_shift(orient)) & 3;
+            if (n >= max_cands) continue;
+            OcvarCandidate& o = cands[n];
+            o.markerId = i;
+            o.templateId = j;
+            o.orient = orient;
+            o.valid = 1;
+            o.bit = codes[(size_t)i * w.n_sizes + L.size_of[j]];
+            shift_square(r.square, sh, o.square);
+            std::memcpy(o.patPoint, r.patPoint, sizeof o.patPoint);
+        }
+        for (int k = 0; k < r.n_match; k++) orient_of[match_group(m[k])] = 0;
+    }
+    *n_cands = n > 0x7fffffff ? 0x7fffffff : (int)n;
     return OCVAR_OK;
 }
 

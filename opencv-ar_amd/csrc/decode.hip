@@ -3,10 +3,13 @@
 // decode_kernel replaces the inner template loop of cvarArMultRegistration
 // (/root/reference/src/opencvar.cpp:700-774) for one frame-pass quad per wave.  The reference re-runs the whole
 // square finder on the crop once per template with an identical result; here the crop pass ran
-// once and every template reads the same crop quad.  Templates are visited in order inside the lane because
-// the orient 2/4 corner rotation of one template leaks into the next.
-// finalise_kernel replaces opencvar.cpp:662-668 and 780-801 for one frame per workgroup (the order-dependent elimination,
-// replayed 64 comparisons at a time, and the marker records); pose_kernel solves the survivors' poses (cvarSquareToMatrix
+// once and every template reads the same crop quad.  The read code depends on a template only through its size, so a
+// square is read once per size class and the code is looked up in the library's sorted table (library_core.h): the work per
+// square grows with the number of sizes and of matches, not with the number of templates.  What decode keeps per square is
+// compact (SquareRec, one code per size class, the matched groups); the reference's K candidates per square are implied by it
+// (ocvar_hip_debug_candidates spells them out on the host).
+// finalise_kernel replaces opencvar.cpp:662-668 and 780-801 for one frame per workgroup (the order-dependent elimination in
+// its sparse form, tail_core.h, and the marker records); pose_kernel solves the survivors' poses (cvarSquareToMatrix
 // 524-540), one lane per marker over the whole batch.
 #include "kernels.h"
 
@@ -14,21 +17,25 @@ namespace ocvar {
 
 // One wave per (frame, quarter of the frame's quads): workgroups of 64 threads, because with several contexts in flight a
 // workgroup has to fit into the gap one retiring binarise wave leaves (round 2's 256-thread workgroups at 128 registers took 5 ms
-// in-region for 0.3 ms of work).  Two phases per chunk of 8 quads.  Phase 1, one lane per (quad, template): the inverse
+// in-region for 0.3 ms of work).  Four phases per chunk of 8 quads.  Phase 1, one lane per (quad, size class): the inverse
 // homography (closed form in double, rounded to float32 and inverted; the destination quad is (tw+2) x (th+2), so it depends on
-// the template) into LDS.  Phase 2, quad by quad, one lane per code cell: lane L samples the cell whose bit is bit L of the
+// the size) into LDS.  Phase 2, quad by quad, one lane per code cell: lane L samples the cell whose bit is bit L of the
 // code -- acArray2DToBit packs row-major, columns right to left, first cell in the most significant bit (acmath.cpp:546-554)
-// -- so the code is the ballot of the thresholded samples.
+// -- so the code is the ballot of the thresholded samples.  Phase 3, one lane per (quad, size class): the code's run in the
+// size class's table.  Phase 4, one lane per quad: the runs merged into the quad's match list, ascending by group (= by
+// first template).
 constexpr int DECODE_SLICES = 4;   // waves per frame: quad i belongs to slice i % 4
-constexpr int DECODE_CHUNK = 8;    // quads of a slice per phase-1 round (x templates <= 64 lanes for up to 8 templates; more: lanes loop)
+constexpr int DECODE_CHUNK = 8;    // quads of a slice per round (x size classes <= 128 lanes of phases 1 and 3)
 
 __global__ __launch_bounds__(64) void decode_kernel(Workspace ws) {
-    extern __shared__ double sM_dyn[];   // [DECODE_CHUNK][n_templates][9]
+    extern __shared__ double sM_dyn[];   // [DECODE_CHUNK][n_sizes][9]
     __shared__ int s_roi[DECODE_CHUNK];        // crop ROI of the chunk's quad, -1: no quad in its crop
     __shared__ unsigned s_slot[DECODE_CHUNK];  // quads_crop slot of the crop's quad
+    __shared__ long long s_code[DECODE_CHUNK * MAX_SIZE_CLASSES];
+    __shared__ int s_lo[DECODE_CHUNK * MAX_SIZE_CLASSES], s_cnt[DECODE_CHUNK * MAX_SIZE_CLASSES];
     const int f = blockIdx.x / DECODE_SLICES, slice = blockIdx.x % DECODE_SLICES;
     const int lane = threadIdx.x;
-    const int T = ws.n_templates;
+    const int NS = ws.n_sizes;
     int nsq = ws.n_squares[f];
     nsq = nsq < ws.maxq ? nsq : ws.maxq;
     const int mine = (nsq - slice + DECODE_SLICES - 1) / DECODE_SLICES;   // quads slice, slice + 4, ... < nsq
@@ -43,144 +50,117 @@ __global__ __launch_bounds__(64) void decode_kernel(Workspace ws) {
             s_slot[lane] = (unsigned)(best & 0xffffffffu);
         }
         __syncthreads();
-        for (int pair = lane; pair < cnt * T; pair += 64) {
-            const int qi = pair / T, j = pair - qi * T;
+        for (int pair = lane; pair < cnt * NS; pair += 64) {
+            const int qi = pair / NS, s = pair - qi * NS;
             if (s_roi[qi] < 0) continue;
             const QuadRec q = ws.quads_crop[s_slot[qi]];
             float pat[8], m32[9];
             for (int k = 0; k < 8; k++) pat[k] = (float)q.pt[k];
-            const TemplateRec t = ws.templates[j];
-            if (!perspective_from_quad(pat, t.width + 2, t.height + 2, m32))
+            const SizeClass sz = ws.sizes[s];
+            if (!perspective_from_quad(pat, sz.width + 2, sz.height + 2, m32))
                 for (int k = 0; k < 9; k++) m32[k] = 0.f;
             double M[9];
             invert_map(m32, M);
-            for (int k = 0; k < 9; k++) sM_dyn[(qi * T + j) * 9 + k] = M[k];
+            for (int k = 0; k < 9; k++) sM_dyn[(qi * NS + s) * 9 + k] = M[k];
         }
         __syncthreads();
         for (int qi = 0; qi < cnt; qi++) {
             const int i = slice + DECODE_SLICES * (base + qi);
-            CandRec* out = ws.cand_recs + ((size_t)f * ws.maxq + i) * MAXT;
+            SquareRec* rec = ws.sq_recs + (size_t)f * ws.maxq + i;
             const int r = s_roi[qi];
             if (r < 0) {  // no quad in the crop: no candidate for this square (opencvar.cpp:704)
-                if (lane < T) out[lane].valid = 0;
+                if (lane == 0) rec->n_match = -1;
                 continue;
             }
             const Roi roi = ws.rois_crop[r];
-            const QuadRec q = ws.quads_crop[s_slot[qi]];
-            float pat[8], pts[8];
-            for (int k = 0; k < 8; k++) {
-                pat[k] = (float)q.pt[k];
-                pts[k] = ws.squares[((size_t)f * ws.maxq + i) * 8 + k];
-            }
+            if (lane < 8) rec->square[lane] = ws.squares[((size_t)f * ws.maxq + i) * 8 + lane];
+            else if (lane < 16) rec->patPoint[lane - 8] = (float)ws.quads_crop[s_slot[qi]].pt[lane - 8];
             const uint8_t* plane = ws.gray + (size_t)roi.frame * gray_plane_bytes(ws.W, ws.H);
             const int pitch = gray_pitch(ws.W);
             auto crop_px = [=](int ix, int iy) -> int { return plane[(size_t)(roi.y0 + iy) * pitch + gray_col(roi.x0 + ix)]; };
-            for (int j = 0; j < T; j++) {   // in order: the orient 2/4 corner rotation leaks into the next template (D4)
-                const TemplateRec t = ws.templates[j];
+            for (int s = 0; s < NS; s++) {
+                const SizeClass sz = ws.sizes[s];
                 double M[9];
-                for (int k = 0; k < 9; k++) M[k] = sM_dyn[(qi * T + j) * 9 + k];
-                const int n = t.width * t.height;     // <= 64 (ocvar_hip_set_templates)
+                for (int k = 0; k < 9; k++) M[k] = sM_dyn[(qi * NS + s) * 9 + k];
+                const int n = sz.width * sz.height;     // <= 64 (ocvar_hip_set_templates)
                 bool v = false;
                 if (lane < n) {
                     const int p = n - 1 - lane;       // position in acArray2DToBit's scan: row p / tw, column tw-1 - p % tw
-                    const int ci = p / t.width, cj = t.width - 1 - p % t.width;
+                    const int ci = p / sz.width, cj = sz.width - 1 - p % sz.width;
                     int cx, cy;
-                    if (code_cell(ci * t.width + cj, t.width, t.height, &cx, &cy))
+                    if (code_cell(ci * sz.width + cj, sz.width, sz.height, &cx, &cy))
                         v = warp_sample_px(crop_px, roi.w, roi.h, M, cx + 1, cy + 1) > 100;
                 }
                 const long long bit = (long long)__ballot(v);
-                const int orient = match_orient(bit, t);
-                if (orient == 4) rot_square(pts, 2);
-                else if (orient == 2) rot_square(pts, 4);
-                if (lane == 0) {
-                    CandRec c;
-                    c.valid = 1;
-                    c.orient = orient;
-                    c.bit = bit;
-                    for (int k = 0; k < 8; k++) {
-                        c.square[k] = pts[k];
-                        c.patPoint[k] = pat[k];
-                    }
-                    out[j] = c;
+                if (lane == 0) s_code[qi * MAX_SIZE_CLASSES + s] = bit;
+            }
+        }
+        __syncthreads();
+        for (int pair = lane; pair < cnt * NS; pair += 64) {
+            const int qi = pair / NS, s = pair - qi * NS;
+            if (s_roi[qi] < 0) continue;
+            const int i = slice + DECODE_SLICES * (base + qi);
+            const long long bit = s_code[qi * MAX_SIZE_CLASSES + s];
+            ws.sq_codes[((size_t)f * ws.maxq + i) * NS + s] = bit;
+            const SizeClass sz = ws.sizes[s];
+            int n;
+            s_lo[qi * MAX_SIZE_CLASSES + s] = lut_find(ws.lut, sz.lut_begin, sz.lut_count, bit, &n);
+            s_cnt[qi * MAX_SIZE_CLASSES + s] = n;
+        }
+        __syncthreads();
+        if (lane < cnt && s_roi[lane] >= 0) {
+            const int i = slice + DECODE_SLICES * (base + lane);
+            int* out = ws.sq_match + ((size_t)f * ws.maxq + i) * ws.max_match;
+            int n = 0;   // <= max_match: at most the longest run of one code per size class
+            for (int s = 0; s < NS; s++) {
+                const int lo = s_lo[lane * MAX_SIZE_CLASSES + s], hi = lo + s_cnt[lane * MAX_SIZE_CLASSES + s];
+                for (int e = lo; e < hi; e++) {   // (runs of different size classes interleave in group order)
+                    const LutEntry le = ws.lut[e];
+                    n = insert_match(out, n, le.group << 2 | (le.orient - 1));
                 }
             }
+            ws.sq_recs[(size_t)f * ws.maxq + i].n_match = n;
         }
         __syncthreads();
     }
 }
 
-// (the tail keeps a frame's candidates in LDS: Workspace::maxc of them, 9 bytes each, sized at launch)
-
+// The elimination in its sparse form (tail_core.h: square_survivor), one wave per frame.  Pass 1: the first square matching
+// each group (LDS atomicMin over the frame's matches); pass 2, one lane per square: its survivor; then the survivors in
+// square order behind the tracked markers.  LDS: n_groups + maxq ints, sized at launch.
 __global__ __launch_bounds__(64) void finalise_kernel(Workspace ws) {
     extern __shared__ int tail_lds[];
-    const int MAXC = ws.maxc;
-    int* s_mid = tail_lds;
-    int* s_tid = tail_lds + MAXC;
-    unsigned char* s_score = reinterpret_cast<unsigned char*>(tail_lds + 2 * MAXC);
-    __shared__ int s_src[MAXM];  // >= 0: candidate index, < 0: -(1 + index into prev)
-    __shared__ int s_nout, s_job;
+    int* s_earliest = tail_lds;                // [n_groups]
+    int* s_surv = tail_lds + ws.n_groups;      // [maxq] template << 1 | score of the square's survivor, -1: none
+    __shared__ int s_src[MAXM];  // >= 0: square index, < 0: -(1 + index into prev)
+    __shared__ int s_first, s_nout, s_job;
     const int f = blockIdx.x;
-    const int T = ws.n_templates;
     const int lane = threadIdx.x;   // one wave per frame
-    // candidates in the reference's order (square-major, template-minor), compacted 64 slots at a time
-    int n = 0;
-    {
-        int nsq = ws.n_squares[f];
-        nsq = nsq < ws.maxq ? nsq : ws.maxq;
-        const int slots = nsq * T;
-        bool overflow = false;
-        for (int base = 0; base < slots; base += 64) {
-            const int s = base + lane;
-            const int i = s / T, j = s - i * T;
-            int orient = 0;
-            bool valid = false;
-            if (s < slots) {
-                const CandRec* c = ws.cand_recs + ((size_t)f * ws.maxq + i) * MAXT + j;
-                valid = c->valid != 0;
-                orient = c->orient;
-            }
-            const unsigned long long m = __ballot(valid);
-            const int at = n + __popcll(m & ((1ull << lane) - 1ull));
-            if (valid) {
-                if (at < MAXC) {
-                    s_mid[at] = i;
-                    s_tid[at] = j;
-                    s_score[at] = orient ? 1 : 0;
-                } else {
-                    overflow = true;
-                }
-            }
-            n += __popcll(m);
-        }
-        if (__ballot(overflow) && lane == 0) atomicOr(ws.counters + CNT_ERR, ERR_QUAD_OVERFLOW);
-        n = n < MAXC ? n : MAXC;
+    int nsq = ws.n_squares[f];
+    nsq = nsq < ws.maxq ? nsq : ws.maxq;
+    const SquareRec* recs = ws.sq_recs + (size_t)f * ws.maxq;
+    const int MM = ws.max_match;
+    const int* match = ws.sq_match + (size_t)f * ws.maxq * MM;
+    for (int g = lane; g < ws.n_groups; g += 64) s_earliest[g] = NO_SQUARE;
+    if (lane == 0) s_first = NO_SQUARE;
+    __syncthreads();
+    for (int i = lane; i < nsq; i += 64) {
+        const int n = recs[i].n_match;
+        if (n >= 0) atomicMin(&s_first, i);
+        for (int k = 0; k < n; k++) atomicMin(&s_earliest[match_group(match[(size_t)i * MM + k])], i);
     }
     __syncthreads();
-    // opencvar.cpp:780-792, the order-dependent `||` elimination: for a, for b < a: if same square or same template, the
-    // lower score (ties: a) gets markerId -1.  The inner loop is replayed 64 values of b at a time: until a itself is
-    // eliminated -- at the first b it loses to -- every matching b with a lower score is eliminated; from there on
-    // markerId[a] is -1, which still "matches" eliminated b's (a no-op) and same-template b's.  Same result as the
-    // sequential loop, entry for entry.
-    for (int a = 1; a < n; a++) {
-        const int ma = s_mid[a], ta = s_tid[a];
-        const int sa = s_score[a];
-        bool dead = false;   // wave-uniform: markerId[a] has become -1 inside this inner loop
-        for (int base = 0; base < a; base += 64) {
-            const int b = base + lane;
-            const bool in = b < a;
-            const int mb = in ? s_mid[b] : -2, tb = in ? s_tid[b] : -2, sb = in ? (int)s_score[b] : 0;
-            const bool pre = in && (ma == mb || ta == tb);        // match while markerId[a] is still ma
-            const bool post = in && (mb == -1 || ta == tb);       // match once markerId[a] is -1
-            const bool wins = sa > sb;
-            unsigned long long lose = dead ? 0ull : __ballot(pre && !wins);
-            const int bstar = lose ? __ffsll((long long)lose) - 1 : 64;
-            const bool kill = wins && (dead ? post : (lane < bstar ? pre : (lane > bstar ? post : false)));
-            if (kill) s_mid[b] = -1;
-            dead = dead || lose != 0;
+    for (int i = lane; i < nsq; i += 64) {
+        const int n = recs[i].n_match;
+        int v = -1;
+        if (n >= 0) {
+            int score;
+            const int t = square_survivor(i, i == s_first, n, match + (size_t)i * MM, s_earliest, ws.group_off, ws.group_members, &score);
+            if (t >= 0) v = t << 1 | score;
         }
-        if (dead && lane == 0) s_mid[a] = -1;
-        __syncthreads();
+        s_surv[i] = v;
     }
+    __syncthreads();
     if (lane == 0) {
         int nout = 0, total = 0;
         const int nr = ws.n_reserve[f];
@@ -188,9 +168,9 @@ __global__ __launch_bounds__(64) void finalise_kernel(Workspace ws) {
             if (k < MAXM && nout < MAXM) s_src[nout++] = -(1 + ws.reserve[(size_t)f * MAXM + k]);
             total++;
         }
-        for (int a = 0; a < n; a++)
-            if (s_mid[a] >= 0) {
-                if (nout < MAXM) s_src[nout++] = a;
+        for (int i = 0; i < nsq; i++)
+            if (s_surv[i] >= 0) {
+                if (nout < MAXM) s_src[nout++] = i;
                 total++;
             }
         s_nout = nout;
@@ -208,14 +188,16 @@ __global__ __launch_bounds__(64) void finalise_kernel(Workspace ws) {
         if (src < 0) {
             *m = ws.prev[(size_t)f * MAXM + (-src - 1)];  // square already updated by the tracking step
         } else {
-            const int i = s_mid[src], j = s_tid[src];
-            const CandRec* c = ws.cand_recs + ((size_t)f * ws.maxq + i) * MAXT + j;
-            const TemplateRec t = ws.templates[j];
-            m->templateId = j;
+            const int i = src, t = s_surv[i] >> 1;
+            const int sh = prefix_shift(match + (size_t)i * MM, recs[i].n_match, ws.group_off, ws.group_members, t);
+            float sq[8];
+            for (int q = 0; q < 8; q++) sq[q] = recs[i].square[q];
+            const TemplateRec tp = ws.templates[t];
+            m->templateId = t;
             m->markerId = i;
-            m->score = c->orient ? 1.0 : 0.0;
-            for (int q = 0; q < 8; q++) m->square[q] = c->square[q];
-            m->aspectRatio = (double)t.width / t.height;
+            m->score = (s_surv[i] & 1) ? 1.0 : 0.0;
+            shift_square(sq, sh, m->square);
+            m->aspectRatio = (double)tp.width / tp.height;
         }
         ws.pose_jobs[s_job + k] = f * MAXM + k;
     }
@@ -243,11 +225,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 
 void launch_decode(const Workspace& ws, hipStream_t stream) {
     if (ws.n_frames > 0)
-        hipLaunchKernelGGL(decode_kernel, dim3(ws.n_frames * DECODE_SLICES), dim3(64), (size_t)DECODE_CHUNK * ws.n_templates * 9 * sizeof(double), stream, ws);
+        hipLaunchKernelGGL(decode_kernel, dim3(ws.n_frames * DECODE_SLICES), dim3(64), (size_t)DECODE_CHUNK * ws.n_sizes * 9 * sizeof(double), stream, ws);
 }
 void launch_finalise(const Workspace& ws, hipStream_t stream) {
     if (ws.n_frames <= 0) return;
-    hipLaunchKernelGGL(finalise_kernel, dim3(ws.n_frames), dim3(64), (size_t)ws.maxc * 9 + 16, stream, ws);
+    hipLaunchKernelGGL(finalise_kernel, dim3(ws.n_frames), dim3(64), (size_t)(ws.n_groups + ws.maxq) * sizeof(int), stream, ws);
     // a stateless frame keeps at most one marker per template: a grid of one wave per 8 frames takes a batch's poses in one
     // pass; stateful batches with many tracked markers per frame loop (grid-stride)
     const int blocks = ws.n_frames / 8 + 1;

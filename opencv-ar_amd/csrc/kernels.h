@@ -36,11 +36,11 @@ enum { ERR_CAND_OVERFLOW = 1, ERR_POOL_OVERFLOW = 2, ERR_QUAD_OVERFLOW = 4, ERR_
 
 struct TileDesc { int roi, x0, y0; };   // binarise work unit of the crop pass: x0 = strip index, y0 = first row
 
-struct CandRec {   // pre-dedupe candidate, slot [frame][quad][template]
-    int valid, orient;
-    long long bit;
-    float square[8];
-    float patPoint[8];
+struct SquareRec {   // decode's record of one square, slot [frame][quad]; its codes and matches live beside it (Workspace)
+    float square[8];    // the square's corners before any orient 2/4 rotation (a candidate's are shift_square of these)
+    float patPoint[8];  // the crop quad
+    int n_match;        // -1: no quad in the crop (no candidates), else the number of matches in sq_match
+    int pad;
 };
 
 // counters block (device ints), zeroed at the start of every batch
@@ -55,11 +55,11 @@ struct Workspace {
     // limits
     int max_w, max_h, max_batch;
     int maxq;               // frame-pass quads kept per frame (ocvar_hip_create: OCVAR_MAX_QUADS; ocvar_hip_create_ex: caller's choice)
-    int maxc;               // pre-dedupe candidates per frame the tail can replay = maxq * n_templates, bounded by its LDS
     int cap_frame_cands, cap_crop_cands, cap_crop_rois, cap_crop_tiles, cap_crop_quads;
     long long cap_pool_ints, cap_crop_pixels;
     // per batch geometry
     int W, H, sw, sh, ns, n_frames, n_templates;   // ns: row stride of a neighbour-mask plane = sw rounded up to 4
+    int n_sizes, n_groups, max_match;        // the library (library_core.h): size classes, groups, most matches per square
     int crop_phases;                         // 2: crop tier 2 in two launches (earliest starts first, then the rest behind exact pruning); 1: one launch (few frames: the shorter chain)
     int mid_steps, mid_blocks, long_blocks;  // tuning (env OCVAR_MID_STEPS / OCVAR_MID_BLOCKS / OCVAR_LONG_BLOCKS): tier-2 step budget and grid, tier-3 grid
     int max_mid_blocks, max_long_blocks;     // slabs allocated at create (scaled with max_batch)
@@ -93,7 +93,9 @@ struct Workspace {
     int* ring_frame;        // [B] 1: the frame's own frame border is the rectangle ring_quads_kernel has published (tier 1 drops its start)
     int* ring_crop;         // [cap_crop_rois] the same for a crop
     int* crop_min_rest;     // [cap_crop_rois] smallest start position among a crop's tier-2 starts off the crop's frame (tier 2 walks these first)
-    CandRec* cand_recs;     // [B][maxq][MAXT]
+    SquareRec* sq_recs;     // [B][maxq]
+    long long* sq_codes;    // [B][maxq][n_sizes] the code read for each size class
+    int* sq_match;          // [B][maxq][max_match] matched groups (group << 2 | orient - 1), ascending
     MarkerRec* prev;        // [B][MAXM]
     int* n_prev;            // [B]
     int* reserve;           // [B][MAXM] tracked marker indices
@@ -102,6 +104,10 @@ struct Workspace {
     MarkerRec* markers;     // [B][MAXM] output
     int* n_markers;         // [B]
     TemplateRec* templates; // [MAXT]
+    SizeClass* sizes;       // [MAX_SIZE_CLASSES]
+    LutEntry* lut;          // [4 * MAXT] per size class, sorted by (code, group)
+    int* group_off;         // [MAXT + 1] into group_members
+    int* group_members;     // [MAXT]
     CameraRec* camera;
     int* counters;          // [CNT_COUNT]
 };

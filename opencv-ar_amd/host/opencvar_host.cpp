@@ -574,7 +574,7 @@ int cvarArMultRegistration(IplImage* image, vector<CvarMarker>* markers, vector<
     std::lock_guard<std::mutex> lk(g_mu);
     if (!image_ok(image) || !camera || templates.empty() || templates.size() > OCVAR_MAX_TEMPLATES) {
         std::fprintf(stderr, "opencvar: cvarArMultRegistration: unsupported arguments (need 8UC3 image >= 16x16, 1..%d templates)\n",
-                     OCVAR_MAX_TEMPLATES);
+                     (int)OCVAR_MAX_TEMPLATES);
         markers->clear();
         return 0;
     }
@@ -614,7 +614,7 @@ int cvarArMultRegistration(IplImage* image, vector<CvarMarker>* markers, vector<
         rc = ocvar_hip_detect_host(ctx, (uint8_t*)image->imageData, image->width, image->height, image->widthStep,
                                    (size_t)image->widthStep * image->height, 1, 1, n_prev ? prev.data() : nullptr,
                                    n_prev ? &n_prev : nullptr, out.data(), &count, OCVAR_MAX_MARKERS);
-        // The reference's square list is unbounded (opencvar.cpp:187-214).  A frame with more squares (or candidates) than
+        // The reference's square list is unbounded (opencvar.cpp:187-214).  A frame with more squares than
         // the context has room for fails before the caller's image is touched; it is run again on a larger context
         // (256 -> 1024 -> OCVAR_MAX_QUADS_EX squares), which is then kept.
         if (rc != OCVAR_E_CAPACITY || !(ocvar_hip_capacity_flags(ctx) & 4) || g_maxq >= OCVAR_MAX_QUADS_EX) break;

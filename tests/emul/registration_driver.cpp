@@ -1,0 +1,43 @@
+// registration_driver.cpp -- calls cvarArMultRegistration of libopencv-ar.so once, as an application built on the reference
+// would, for tests/test_gpu_template_library.py.  TEST ONLY.
+//   registration_driver <in> <out>
+//   in:  int width, height, n_templates; CvarTemplate[n]; CvarCamera; BGR bytes (width * 3 per row)
+//   out: int count, n_out; CvarMarker[n_out]
+#include "opencvar/opencvar.h"
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+int main(int argc, char** argv) {
+    if (argc != 3) return 2;
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f) return 2;
+    int hdr[3];
+    if (std::fread(hdr, sizeof hdr, 1, f) != 1) return 2;
+    vector<CvarTemplate> templates(hdr[2]);
+    CvarCamera camera;
+    std::vector<char> bgr((size_t)hdr[0] * hdr[1] * 3);
+    if ((hdr[2] && std::fread(templates.data(), sizeof(CvarTemplate), hdr[2], f) != (size_t)hdr[2]) ||
+        std::fread(&camera, sizeof camera, 1, f) != 1 || std::fread(bgr.data(), 1, bgr.size(), f) != bgr.size())
+        return 2;
+    std::fclose(f);
+    IplImage img;
+    std::memset(&img, 0, sizeof img);
+    img.nSize = sizeof img;
+    img.nChannels = 3;
+    img.depth = IPL_DEPTH_8U;
+    img.width = hdr[0];
+    img.height = hdr[1];
+    img.widthStep = hdr[0] * 3;
+    img.imageSize = img.widthStep * img.height;
+    img.imageData = img.imageDataOrigin = bgr.data();
+    vector<CvarMarker> markers;
+    const int count = cvarArMultRegistration(&img, &markers, templates, &camera);
+    FILE* o = std::fopen(argv[2], "wb");
+    if (!o) return 2;
+    const int out[2] = {count, (int)markers.size()};
+    std::fwrite(out, sizeof out, 1, o);
+    if (!markers.empty()) std::fwrite(markers.data(), sizeof(CvarMarker), markers.size(), o);
+    std::fclose(o);
+    return 0;
+}
