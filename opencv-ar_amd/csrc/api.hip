@@ -121,10 +121,12 @@ extern "C" int ocvar_hip_create_ex(OcvarHip** out, int device, int max_width, in
     // only tier-2 borders with more corner points than a lane slab holds land here; the fixed part lets a small context take
     // a pathological frame (full-frame noise: thousands of long ragged borders)
     w.cap_pool_ints = (long long)B * (1 << 18) + (1 << 24);
-    w.cap_crop_pixels = (long long)(2 * B * (size_t)(max_width + 16) * (max_height + 8));
+    // (bytes of the crops' bit planes: a crop's plane is at most half the bytes of its neighbour-mask byte plane, ns x (sh
+    // rounded up to 8), which this pool was sized for at 2 B (W + 16) (H + 8) bytes)
+    w.cap_crop_pixels = (long long)(B * (size_t)(max_width + 16) * (max_height + 8));
     int rc;
     if ((rc = dev_alloc(c, &w.gray, B * (size_t)gray_plane_bytes(max_width, max_height)))) return rc;   // (panels: hd.h::gray_col)
-    if ((rc = dev_alloc(c, &w.nbr_frame, B * (size_t)(max_width + 16) * (max_height + 8)))) return rc;
+    if ((rc = dev_alloc(c, &w.nbr_frame, B * (size_t)nbr_plane_bytes(((max_width & ~1) + 15) & ~15, max_height & ~1)))) return rc;
     if ((rc = dev_alloc(c, &w.nbr_crop, (size_t)w.cap_crop_pixels))) return rc;
     if ((rc = dev_alloc(c, &w.cands_frame, (size_t)w.cap_frame_cands))) return rc;
     if ((rc = dev_alloc(c, &w.cands_crop, (size_t)w.cap_crop_cands))) return rc;
@@ -426,7 +428,7 @@ static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int 
         const long long min_units = tuned(c, OCVAR_TUNE_MIN_UNITS, "OCVAR_MIN_UNITS", c->gate ? 16384 : 65536);
         while (chunks > 1 && (long long)w.frame_strips * (chunks / 2) * n_frames >= min_units) chunks /= 2;
         int rows = (w.sh + chunks - 1) / chunks;
-        rows = (rows + 7) & ~7;   // whole mask tiles (8 rows) per work unit: binarise.hip writes the mask plane tile by tile
+        rows = (rows + NBR_TILE_H - 1) / NBR_TILE_H * NBR_TILE_H;   // whole tile rows (14) per work unit: binarise.hip writes the bit plane tile by tile
         w.frame_chunk_rows = rows;
         w.frame_chunks = (w.sh + rows - 1) / rows;
     }
@@ -901,9 +903,9 @@ extern "C" int ocvar_hip_debug_binary(OcvarHip* c, int frame, uint8_t* h) {
     const size_t bytes = (size_t)nbr_plane_bytes(ns, sh);
     std::vector<uint8_t> nbr(bytes);
     HIP_TRY(c, hipMemcpy(nbr.data(), c->ws.nbr_frame + (size_t)frame * bytes, bytes, hipMemcpyDeviceToHost));
-    // pixel (x,y) is the west neighbour (bit 4) of (x+1,y); the 1-px frame is zero as cvFindContours makes it
+    // the bit plane holds the binary image itself; the 1-px frame is zero as cvFindContours makes it
     for (int y = 0; y < sh; y++)
-        for (int x = 0; x < sw; x++) h[(size_t)y * sw + x] = (x + 1 < sw && ((nbr[(size_t)nbr_addr(x + 1, y, ns)] >> 4) & 1)) ? 255 : 0;
+        for (int x = 0; x < sw; x++) h[(size_t)y * sw + x] = nbr_bit(nbr.data(), x, y, ns) ? 255 : 0;
     return OCVAR_OK;
 }
 
@@ -915,7 +917,7 @@ extern "C" int ocvar_hip_debug_masks(OcvarHip* c, int frame, uint8_t* h) {
     std::vector<uint8_t> nbr(bytes);
     HIP_TRY(c, hipMemcpy(nbr.data(), c->ws.nbr_frame + (size_t)frame * bytes, bytes, hipMemcpyDeviceToHost));
     for (int y = 0; y < sh; y++)
-        for (int x = 0; x < sw; x++) h[(size_t)y * sw + x] = nbr[(size_t)nbr_addr(x, y, ns)];
+        for (int x = 0; x < sw; x++) h[(size_t)y * sw + x] = (uint8_t)nbr_of(nbr.data(), x, y, ns);   // (expanded from the bit plane)
     return OCVAR_OK;
 }
 

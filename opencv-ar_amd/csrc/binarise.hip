@@ -3,22 +3,23 @@
 // Replaces the image stages of cvarFindSquares (/root/reference/src/opencvar.cpp:156-184): cvCloneImage,
 // cvPyrDown(5x5), cvPyrUp, cvCvtColor(BGR2GRAY), cvAdaptiveThreshold(GAUSSIAN_C, 7x7, delta 8) -- in frame mode
 // also the BGR2GRAY of cvarArMultRegistration (opencvar.cpp:624-627) -- and the local part of cvFindContours
-// (opencvar.cpp:183-184): zeroing the 1-px frame and spotting where a border can begin.
+// (opencvar.cpp:183-184): zeroing the 1-px frame and spotting where a border can begin.  The binary image goes out as a bit
+// plane in 16x14-pixel tiles with a one-pixel apron (hd.h::nbr_win_off), from which the followers read 8-neighbour masks.
 //
 // "Wave march": one 64-lane wavefront (a workgroup of its own) owns a strip of 256 columns (4 pixels per lane: 240 output
 // columns + an 8-column halo on each side) and walks down a chunk of rows.  Everything vertical lives in registers and nothing
 // is a window that is shifted: the vertical pyrDown is two accumulators, the vertical pyrUp two running sums (times four, so a
 // finished pixel is the high byte of its sum), the last 8 pyrUp rows a ring of bytes in two registers per pixel that swap names
-// every four rows, the table outputs of the last two threshold rows three registers; everything horizontal is a 4-pixel packed
+// every four rows, the start nibbles of the last threshold row a register; everything horizontal is a 4-pixel packed
 // word handed to the neighbour lane with a DPP wave shift.  One (unaligned) buffer load per lane and row, reflected columns
 // included, two rows under way beyond the current one; rows are addressed through buffer resources (scalar row offset,
 // loop-invariant lane offset, stores masked by range).  The image itself never goes through LDS, which only holds a 128-entry
-// table (threshold-bit window -> neighbour-mask contributions and border-start nibbles), 8 mask rows per wave on their way to
-// whole 16x8 tiles, and the staged border starts.  The grey plane is stored in 256-byte panels, one per strip (hd.h::gray_col):
+// table (threshold-bit window -> border-start nibbles), a ring of 16 threshold rows per wave (a nibble per lane) on their way to
+// whole 16x14 bit tiles, and the staged border starts.  The grey plane is stored in 256-byte panels, one per strip (hd.h::gray_col):
 // every store of the kernel is whole 64-byte sectors.  The row body exists in several instances (steady rows in groups of four
 // with the ring's position known, strips away from the image edges) so that the hot loop carries no range tests; the filters'
 // border rules at the image edges are per-lane byte selectors.
-// HBM traffic per pixel: 3 B read + 1 B grey + 1 B mask (frame mode).
+// HBM traffic per pixel: 3 B read + 1 B grey + 2/7 B of bit plane (frame mode).
 // The arithmetic is the integer arithmetic of the definition, so the output is bit-identical:
 //   pyrDown  [1 4 6 4 1]^2, (v+128)>>8, BORDER_REFLECT_101        pyrUp  [1 6 1]/[4 4], (v+32)>>6, borders -1->1, n->n-1
 //   Gaussian [8 28 56 72 56 28 8]^2, (v+32768)>>16, BORDER_REPLICATE    threshold  src - mean > -8
@@ -112,26 +113,20 @@ __device__ __forceinline__ void first_bit(unsigned& nib, unsigned S, unsigned w)
     if constexpr (B == 3) asm("v_cmp_lt_i32_sdwa vcc, sext(%1), %2 src0_sel:WORD_1 src1_sel:BYTE_3\n\tv_cndmask_b32_e64 %0, 0, 1, vcc" : "=v"(nib) : "v"(S), "v"(w) : "vcc");
 }
 
-// ---- neighbour masks and border starts by table ---------------------------------------------------------------------
+// ---- border starts by table ----------------------------------------------------------------------------------------
 // A lane's 4 threshold bits of one row plus the bits next to them form a 7-bit window: bit 0 = column c0-1 (the left
 // lane's pixel 3), bits 1..4 = the lane's pixels 0..3, bits 5, 6 = columns c0+4, c0+5 (the right lane's pixels 0, 1).
-// What a row contributes to the 8-neighbour masks of the 4 pixels -- as the row above (NE N NW), the pixels' own row
-// (E W) and the row below (SW S SE) -- and to the border-start tests depends on that window only, so it is read from a
-// 128-entry table in LDS (one ds_read_b128 per lane and row) instead of being spread out with multiplications:
-//   x: mask bytes of the 4 pixels contributed as the row above      y: ... as their own row      z: ... as the row below
-//   w: start nibbles (bit p = pixel p).  Low half, the row as the pixels' own row:  [0] centre & ~W   [1] E   [2] W & ~centre
-//      [3] ~E.  High half, the row as the row above:  [4] ~(NW | N | NE)   [5] the pixel above E's east neighbour
-//      [6] N   [7] ~NE.  With t = low(own row) & high(row above), t & ~(t >> 4) has the outer starts in nibble 0
-//      (centre & ~W & ~NW & ~N & ~NE & ~(E & NEE)) and the hole starts in nibble 2 (W & ~centre & N & (E | NE)):
-//      the necessary local conditions for being the raster-first pixel of a region (see march_unit).
-__device__ __forceinline__ uint4 mask_table_entry(unsigned w) {
-    uint4 t = make_uint4(0u, 0u, 0u, 0u);
+// What a row contributes to the border-start tests of the 4 pixels depends on that window only, so it is read from a
+// 128-entry table in LDS (one ds_read_b32 per lane and row) instead of being spread out bit by bit.  Start nibbles (bit p =
+// pixel p).  Low half, the row as the pixels' own row:  [0] centre & ~W   [1] E   [2] W & ~centre   [3] ~E.  High half, the
+// row as the row above:  [4] ~(NW | N | NE)   [5] the pixel above E's east neighbour   [6] N   [7] ~NE.  With t = low(own row)
+// & high(row above), t & ~(t >> 4) has the outer starts in nibble 0 (centre & ~W & ~NW & ~N & ~NE & ~(E & NEE)) and the hole
+// starts in nibble 2 (W & ~centre & N & (E | NE)): the necessary local conditions for being the raster-first pixel of a
+// region (see march_unit).
+__device__ __forceinline__ unsigned start_table_entry(unsigned w) {
     unsigned mA = 0, mB = 0, mC = 0, uA = 0, uB = 0, uC = 0, uD = 0;
     for (unsigned p = 0; p < 4; p++) {
         const unsigned xm = (w >> p) & 1u, x0 = (w >> (p + 1)) & 1u, xp = (w >> (p + 2)) & 1u, xpp = (w >> (p + 3)) & 1u;
-        t.x |= ((xp << 1) | (x0 << 2) | (xm << 3)) << (8 * p);   // NE N NW
-        t.y |= (xp | (xm << 4)) << (8 * p);                      // E W
-        t.z |= ((xm << 5) | (x0 << 6) | (xp << 7)) << (8 * p);   // SW S SE
         mA |= (x0 & ~xm & 1u) << p;
         mB |= xp << p;
         mC |= (xm & ~x0 & 1u) << p;
@@ -140,8 +135,7 @@ __device__ __forceinline__ uint4 mask_table_entry(unsigned w) {
         uC |= x0 << p;
         uD |= xp << p;
     }
-    t.w = mA | (mB << 4) | (mC << 8) | ((~mB & 15u) << 12) | (uA << 16) | (uB << 20) | (uC << 24) | ((~uD & 15u) << 28);
-    return t;
+    return mA | (mB << 4) | (mC << 8) | ((~mB & 15u) << 12) | (uA << 16) | (uB << 20) | (uC << 24) | ((~uD & 15u) << 28);
 }
 
 // table index (march_unit: bits 0..3 own pixels, bit 4 the left lane's pixel 3, bits 5, 6 the right lane's pixels 0, 1) -> window
@@ -150,7 +144,7 @@ __device__ __forceinline__ unsigned table_window(unsigned i) { return ((i >> 4) 
 struct MarchOut {
     uint8_t* gray;          // frame mode: grey plane of this frame (stride gray_stride), else null
     long long gray_stride;
-    uint8_t* nbr;           // neighbour-mask plane of this ROI, stride ns
+    uint8_t* nbr;           // bit plane of this ROI (hd.h::nbr_win_off), ns columns
     int ns;
     int roi;
     StartCand* cands;
@@ -164,7 +158,7 @@ struct MarchOut {
 // filters and their lane masks are compiled out -- six of a 1080p frame's eight strips; a crop's strips always touch an edge.
 template <bool BGR, bool EDGE>
 __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /* crops: the ROI's first column in the frame's grey plane */, int sw, int sh, int strip, int Y0, int Y1, const MarchOut& o,
-                           unsigned* stage, unsigned* rowbuf /* LDS, 8 rows x 64 lanes */, const uint4* tab /* LDS, mask_table_entry */) {
+                           unsigned* stage, uint8_t* rowbuf /* LDS, 16 rows x 64 lanes */, const unsigned* tab /* LDS, start_table_entry */) {
     const int lane = threadIdx.x & 63;
     const int XS = strip * SV - 4 * HL;
     const int c0 = XS + 4 * lane;
@@ -229,9 +223,9 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     // the grey plane's panel of this strip (hd.h::gray_col): all 64 lanes store, 256 contiguous bytes at a 256-byte boundary -- the
     // halo lanes' bytes are the neighbouring strips' columns again (same values), or columns outside the image (never read)
     const unsigned out_off = (unsigned)(strip * GRAY_PANEL_BYTES + 4 * lane);
-    const unsigned rmask4 = lane == 63 - HR ? 0x10u : 0x30u;   // the last output lane's x+2 bit (row above) is not computed
-    unsigned bit7;   // (a constant in a register, opaque to the compiler: then the AND below folds into the DPP move -- DPP operands cannot be literals)
-    asm("v_mov_b32 %0, 0x80" : "=v"(bit7));
+    const unsigned rmask2 = lane == 63 - HR ? 0x04u : 0x0cu;   // the last output lane's x+2 bit (row above) is not computed
+    unsigned bit5;   // (a constant in a register, opaque to the compiler: then the AND below folds into the DPP move -- DPP operands cannot be literals)
+    asm("v_mov_b32 %0, 0x20" : "=v"(bit5));
     unsigned colmask = 0;  // which of the lane's 4 columns lie inside cvFindContours' zeroed frame
     for (int j = 0; j < 4; j++) colmask |= (!EDGE || (c0 + j >= 1 && c0 + j <= sw - 2)) ? (1u << j) : 0u;
     // Which pixels may yield border starts: the output lanes' (inside the image).  Strips away from the edges: all four pixels of
@@ -242,38 +236,41 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     if (EDGE)
         for (int j = 0; j < 4; j++) pxsel |= (out_lane && c0 + j < sw) ? (0x101u << j) : 0u;
 
-    // Mask rows are collected in LDS, 8 rows at a time, and written as whole 16x8-pixel tiles (128 contiguous bytes, 32
-    // per lane) -- a row at a time would be 16-byte pieces of 15 different cache lines per wave, and on this hardware a
-    // store issued in every iteration makes the loop-top wait for the prefetched source row wait for that store too
-    // (vmcnt counts loads and stores in order).  Y0 is a multiple of 8 (api.hip / MARCH_CROP_ROWS), so a group of 8 rows
-    // belongs to one work unit; padding rows/columns of the plane (rows up to sh rounded to 8, columns up to ns) may
-    // receive stale values, nothing reads them.
-    // A group of 8 rows is 15 tiles of 128 bytes = 120 pieces of 16 bytes (piece k: row k & 7 of tile k >> 3, at byte 16 k of the
-    // strip's part of the tile row group).  Two store instructions, each writing CONTIGUOUS memory: lane l stores piece l, then
-    // (l < 56) piece 64 + l -- every 64-byte sector is written whole by one instruction.  (Lane = (pair of rows, tile) with both
-    // rows' pieces from one lane made every instruction write 16-byte pieces at a stride of 32: twice the write requests, each
-    // half a sector.)  Piece 64 + l is the same row, eight tiles (32 lanes' dwords) further on: one LDS offset register.
-    const int tile1 = strip * (SV / 16) + (lane >> 3), tile2 = tile1 + 8;
-    const unsigned flush_src = (unsigned)(lane & 7) * 64u + (unsigned)(HL + 4 * (lane >> 3));   // dword index in rowbuf: row l & 7, first lane of tile l >> 3
-    const unsigned flush_dst1 = tile1 * 16 < o.ns ? ((unsigned)tile1 << 7) + (unsigned)(lane & 7) * 16u : OOB;   // byte offsets inside a tile row group
-    const unsigned flush_dst2 = lane < 56 && tile2 * 16 < o.ns ? ((unsigned)tile2 << 7) + (unsigned)(lane & 7) * 16u : OOB;
-    auto flush_rows = [&](int yr_last) {   // yr_last: last row written; its group is complete or the unit ends
+    // The bit plane (hd.h::nbr_win_off) is written a tile row at a time: threshold rows go to a ring of 16 rows in LDS (one byte
+    // per lane and row: its nibble), and when row 14 ty + 14 is in, the 16 rows 14 ty - 1 .. 14 ty + 14 of tile row ty are made
+    // into the strip's 15 tiles -- 960 contiguous bytes, ONE store instruction: lane l (< 60) stores dwords 4 (l & 3) .. 4 (l & 3) + 3
+    // of tile l >> 2, so every 64-byte sector is written whole by four neighbouring lanes.  (A row at a time would be pieces of
+    // 15 sectors per wave, and on this hardware a store issued in every iteration makes the loop-top wait for the prefetched
+    // source row wait for that store too: vmcnt counts loads and stores in order.)  A tile's dword is 18 columns, 16 tx - 1 ..
+    // 16 tx + 16: the nibbles of lanes 4 tx + 1 .. 4 tx + 6 -- the apron columns -1 and 240 of a strip are the threshold bits of
+    // halo lanes 1 and 62, which the wave computes anyway; rows Y0 - 1 and Y1, the apron rows of a unit, are computed for the
+    // start tests.  Y0 is a multiple of 14 (api.hip / MARCH_CROP_ROWS), so a tile row belongs to one work unit; rows outside
+    // [0, Y1] (row -1, rows below the image) are stored as 0.
+    const int tile_s = strip * (SV / NBR_TILE_W) + (lane >> 2);   // the lane's tile in the tile row
+    const unsigned flush_src = (unsigned)(lane < 60 ? lane >> 2 : 14) * 4u;   // byte of lane 4 tx in an LDS row (lanes 60..63: any tile, their store is dropped)
+    const unsigned flush_dst = lane < 60 && tile_s * NBR_TILE_W < o.ns ? (unsigned)tile_s * NBR_TILE_BYTES + (unsigned)(lane & 3) * 16u : OOB;
+    auto flush_tiles = [&](int ty) {   // the rows of tile row ty are in the ring
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         {
-            const uint2* s0 = reinterpret_cast<const uint2*>(rowbuf + flush_src);   // (lanes 56..63 read past the tiles in the second read, inside this wave's rows: their store is dropped)
-            const uint2 a0 = s0[0], a1 = s0[1];       // piece l: 16 bytes
-            const uint2 b0 = s0[16], b1 = s0[17];     // piece 64 + l: 32 dwords further on
-            const unsigned so = (unsigned)wave_uniform(((yr_last >> 3) * (o.ns >> 4)) << 7);
             typedef unsigned v4u __attribute__((ext_vector_type(4)));   // (non-temporal stores: written once, read much later)
-            // The row group's offset is added to the lanes' offsets, the scalar offset field stays 0.  A store of more than 64 bits
+            v4u d;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int r = NBR_TILE_H * ty + 4 * (lane & 3) + i - 1;   // image row of dword 4 (l & 3) + i
+                const unsigned* p = reinterpret_cast<const unsigned*>(rowbuf + (r & 15) * 64 + flush_src);   // nibbles of lanes 4 tx .. 4 tx + 7, a byte each
+                const unsigned p0 = p[0], p1 = p[1];
+                // two nibbles per byte (bytes 0 and 2 of each word), those four bytes into one word: columns 16 tx - 8 .. 16 tx + 23
+                const unsigned w = __builtin_amdgcn_perm(p1 | (p1 >> 4), p0 | (p0 >> 4), 0x06040200u);
+                d[i] = (unsigned)r <= (unsigned)Y1 ? (w >> 7) & 0x3ffffu : 0u;
+            }
+            const unsigned so = (unsigned)wave_uniform((int)nbr_tile_off(0u, (unsigned)ty, o.ns));
+            // The tile row's offset is added to the lanes' offsets, the scalar offset field stays 0.  A store of more than 64 bits
             // must not be followed at once by a vector instruction that writes its data registers; the compiler's hazard
             // recogniser inserts the wait state only for buffer stores WITHOUT a register in the scalar offset field (with one the
             // ISA manual promises no hazard) -- and gfx950 has it all the same: with the offset in an SGPR a register copy the
-            // allocator placed right behind the second store overwrote its first data dword now and then (a selector constant
-            // in the mask plane, first dword of 16-byte pieces, only while the memory system was busy: frames >= 16 of a batch).
-            // (OOB + so < 2^32: dropped all the same.)
-            __builtin_amdgcn_raw_buffer_store_b128((v4u){a0.x, a0.y, a1.x, a1.y}, nbr_rs, (int)(flush_dst1 + so), 0, BUF_NT);
-            __builtin_amdgcn_raw_buffer_store_b128((v4u){b0.x, b0.y, b1.x, b1.y}, nbr_rs, (int)(flush_dst2 + so), 0, BUF_NT);
+            // allocator placed right behind the store overwrote its first data dword now and then (only while the memory system
+            // was busy: frames >= 16 of a batch).  (OOB + so < 2^32: dropped all the same.)
+            __builtin_amdgcn_raw_buffer_store_b128(d, nbr_rs, (int)(flush_dst + so), 0, BUF_NT);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     };
@@ -392,7 +389,7 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     // and coefficients on the scalar unit.  (An 8-row ring without the renaming needs the loop unrolled over 8 rows: with the
     // two instances of this function in one kernel that was 52 KB of code and 30 % slower -- instruction cache.)
     unsigned wa[4] = {0u, 0u, 0u, 0u}, wb[4] = {0u, 0u, 0u, 0u};
-    unsigned m_prev = 0, u_prev = 0, x_prev = 0;   // mask of row y-1 still without its row below; what row y-1 gives to the row below it; its start nibbles
+    unsigned x_prev = 0;   // the start nibbles of row y-1
 
     // One source row.  S ("steady"): v lies where every range test below has a known outcome -- the rows it completes are
     // inside the work unit and away from the image's first and last rows -- so the tests (a scalar compare and branch
@@ -428,7 +425,7 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
             if (S || v + 3 < v_last) nxt4 = fetch(v + 4, S);
         }
         if (EDGE && (S || plan)) g = __builtin_amdgcn_perm(g, g, gsel);   // (gsel: the identity in lanes that hold no reflected columns)
-        // (a 32-bit store reads its data register as it issues: unlike the 128-bit tile stores in flush_rows it may keep the row's
+        // (a 32-bit store reads its data register as it issues: unlike the 128-bit tile stores in flush_tiles it may keep the row's
         // offset in the scalar offset field; test_planes_of_every_frame_of_a_busy_batch compares the grey plane too)
         if (BGR && (S || (v >= Y0 && v < Y1)))   // (BGR: the frame pass, which always has a grey plane) rows [Y0,Y1) are real rows, each loaded exactly once
             __builtin_amdgcn_raw_buffer_store_b32(g, gray_rs, (int)out_off, wave_uniform(v * (int)o.gray_stride), BUF_NT);
@@ -554,26 +551,23 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
                         }
                         if (EDGE || VM < 0) nib &= colmask;   // (strips inside the image: every column counts, and the four tests above left four bits)
                     }
-                    // Row y's window -> table: its share of the masks of rows y-1, y, y+1 and its start nibbles.
-                    // Byte offset of the table entry (16 bytes each; the table is laid out for it): bits 4..7 = own pixels, bit 8 = the left
-                    // lane's pixel 3, bits 9, 10 = the right lane's pixels 0, 1 -- every lane shifts its nibble once, the neighbours'
-                    // parts are an AND on the DPP-shifted value and a shift-or each.
-                    const unsigned n4 = nib << 4;
-                    const unsigned wdw16 = ((down1(n4) & rmask4) << 5) | (((up1(n4) & bit7) << 1) | n4);
-                    const uint4 T = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(tab) + wdw16);
-                    const unsigned nbr4 = m_prev | T.z;        // row y-1: E | NE N NW | W | SW S SE complete
-                    unsigned st;                               // row y's own nibbles (low half of T.w) & row y-1's "row above" nibbles (high half of x_prev)
-                    asm("v_and_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1" : "=v"(st) : "v"(T.w), "v"(x_prev));
-                    m_prev = u_prev | T.y;
-                    u_prev = T.x;
-                    x_prev = T.w;
+                    // Row y's window -> table: its start nibbles.
+                    // Byte offset of the table entry (4 bytes each): bits 2..5 = own pixels, bit 6 = the left lane's pixel 3, bits 7, 8 =
+                    // the right lane's pixels 0, 1 -- every lane shifts its nibble once, the neighbours' parts are an AND on the
+                    // DPP-shifted value and a shift-or each.
+                    const unsigned n2 = nib << 2;
+                    const unsigned wdw4 = ((down1(n2) & rmask2) << 5) | (((up1(n2) & bit5) << 1) | n2);
+                    const unsigned Tw = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(tab) + wdw4);
+                    unsigned st;                               // row y's own nibbles (low half of Tw) & row y-1's "row above" nibbles (high half of x_prev)
+                    asm("v_and_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1" : "=v"(st) : "v"(Tw), "v"(x_prev));
+                    x_prev = Tw;
                     st = st & ~(st >> 4);                      // bits 0..3: outer starts, bits 8..11: hole starts of row y (other bits: don't care)
                     if (EDGE) st &= pxsel;
-                    const int yr = y - 1;
-                    if (S || (yr >= Y0 && yr < Y1)) {
-                        rowbuf[(yr & 7) * 64 + lane] = nbr4;
-                        if ((yr & 7) == 7 || (!S && yr == Y1 - 1)) flush_rows(yr);
-                    }
+                    // row y into the ring (here y >= max(Y0 - 1, 0) and y <= Y1); a tile row is complete with its row 14 ty + 14, the
+                    // unit's last one (only at the image's bottom, where Y1 = sh need not be a multiple of 14) with row Y1
+                    rowbuf[(y & 15) * 64 + lane] = (uint8_t)nib;
+                    if (y % NBR_TILE_H == 0 && y >= Y0 + NBR_TILE_H) flush_tiles(y / NBR_TILE_H - 1);
+                    else if (!S && y == Y1 && Y1 % NBR_TILE_H != 0) flush_tiles(Y1 / NBR_TILE_H);
                     // Plausible border starts of row y (sparse): necessary local conditions for being the raster-first pixel of
                     // a region.  Outer: foreground pixel whose W, NW, N, NE are background -- and not (E foreground and the pixel
                     // above E's east neighbour foreground: that one belongs to the same 8-connected component and comes earlier).
@@ -640,9 +634,9 @@ constexpr int BW = OCVAR_BIN_WG_WAVES;
 
 __global__ __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(OCVAR_WAVES_F, 8))) void binarise_frames_kernel(Workspace ws, const uint8_t* bgr, int row_stride, size_t frame_stride) {
     __shared__ unsigned stage[BW][MARCH_STAGE];
-    __shared__ __attribute__((aligned(16))) unsigned rowbuf[BW][8 * 64];
-    __shared__ uint4 tab[128];
-    for (unsigned i = threadIdx.x; i < 128u; i += 64u * BW) tab[i] = mask_table_entry(table_window(i));
+    __shared__ __attribute__((aligned(16))) uint8_t rowbuf[BW][16 * 64];
+    __shared__ unsigned tab[128];
+    for (unsigned i = threadIdx.x; i < 128u; i += 64u * BW) tab[i] = start_table_entry(table_window(i));
     __syncthreads();
     const int per_frame = ws.frame_strips * ws.frame_chunks;
     // XCD-aware order.  Consecutive workgroups go round the 8 XCDs, each with its own L2; in launch order the workgroups of one
@@ -716,9 +710,9 @@ __global__ __launch_bounds__(256) void grey_writeback_kernel(Workspace ws, uint8
 
 __global__ __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(OCVAR_WAVES_C, 8))) void binarise_crops_kernel(Workspace ws) {
     __shared__ unsigned stage[BW][MARCH_STAGE];
-    __shared__ __attribute__((aligned(16))) unsigned rowbuf[BW][8 * 64];
-    __shared__ uint4 tab[128];
-    for (unsigned i = threadIdx.x; i < 128u; i += 64u * BW) tab[i] = mask_table_entry(table_window(i));
+    __shared__ __attribute__((aligned(16))) uint8_t rowbuf[BW][16 * 64];
+    __shared__ unsigned tab[128];
+    for (unsigned i = threadIdx.x; i < 128u; i += 64u * BW) tab[i] = start_table_entry(table_window(i));
     __syncthreads();
     int n_units = ws.counters[CNT_CROP_TILES];
     if (n_units > ws.cap_crop_tiles) n_units = ws.cap_crop_tiles;

@@ -418,58 +418,7 @@ __device__ __forceinline__ bool wave_finish_packed(const Workspace& ws, const St
     return true;
 }
 
-// trace_core.h::run_has_earlier_pixel on the tiled mask plane: the masks of the run's pixels lie next to each other in a
-// tile row, so the 16 pixels from the start on come with two 16-byte loads (the tile row the start is in and the same
-// row of the next tile) instead of one byte load per pixel -- a quarter of the requests for twice the look-ahead, which
-// matters on shallow staircases, where the row above reaches over the run only after more than 8 pixels.  The per-pixel
-// tests become byte-parallel bit scans.  Same decision rule: pixel k's row above is looked at before its E neighbour; a
-// run that is still going on after the look-ahead (or at the plane's edge) is given the benefit of the doubt.
-__device__ __forceinline__ bool run_has_earlier_pixel_rows(const uint8_t* nbr, int ns, int cpos, int is_hole) {
-    const int x = cpos % ns, y = cpos / ns;
-    const int xa = x & ~15;
-    const uint8_t* row = nbr + nbr_addr(xa, y, ns);   // 16 masks of tile row (xa .. xa+15, y): 16-byte aligned
-    const uint4 A = *reinterpret_cast<const uint4*>(row);
-    uint4 B = make_uint4(0u, 0u, 0u, 0u);
-    if (xa + 16 < ns) B = *reinterpret_cast<const uint4*>(row + 128);   // the next tile of the same tile row
-    // the 16 masks from pixel x on: bytes (x & 15) .. of A:B
-    const unsigned w[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
-    const int ds = (x & 15) >> 2;
-    const unsigned bs = (unsigned)(x & 3);
-    unsigned m[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        unsigned lo = 0, hi = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {   // ds is 0..3: select without dynamic indexing
-            lo = ds == j ? w[i + j] : lo;
-            hi = ds == j ? w[i + j + 1 < 8 ? i + j + 1 : 7] : hi;
-        }
-        m[i] = __builtin_amdgcn_alignbyte(hi, lo, bs);
-    }
-    int lim = ns - x < 16 ? ns - x : 16;   // pixels that exist
-    unsigned long long bad, end;
-    const unsigned long long m0 = ((unsigned long long)m[1] << 32) | m[0], m1 = ((unsigned long long)m[3] << 32) | m[2];
-    for (int half = 0; half < 2; half++) {
-        const unsigned long long v = half ? m1 : m0;
-        const int n = lim - 8 * half;
-        if (n <= 0) return false;
-        const unsigned long long keep = n >= 8 ? ~0ull : ((1ull << (8 * n)) - 1ull);
-        if (is_hole) {
-            bad = ~v & 0x0404040404040404ull & keep;   // background directly above a pixel of the background run
-            end = v & 0x0101010101010101ull & keep;    // E is foreground: the run ends here
-        } else {
-            bad = v & 0x0e0e0e0e0e0e0e0eull & keep;    // NE, N or NW of a pixel of the foreground run is foreground
-            end = ~v & 0x0101010101010101ull & keep;   // E is background: the run ends here
-        }
-        if (bad | end) {
-            const int kb = bad ? __builtin_ctzll(bad) >> 3 : 64, ke = end ? __builtin_ctzll(end) >> 3 : 64;
-            return kb <= ke;
-        }
-    }
-    return false;
-}
-
-// Tier 1, one lane per start, mask bytes read from global memory (one memory latency per step, 64 starts per wave in
+// Tier 1, one lane per start, masks read from the bit plane in global memory (one memory latency per step, 64 starts per wave in
 // flight).  It sees every plausible start, and most of them drop out within a few steps (noise, staircase false
 // starts).  Returns the route: 0 = dead, 1 = tier 2, 2 = straight to tier 3.
 template <bool CROP>
@@ -603,7 +552,7 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_kernel(Workspace ws) {
                 // (the ROI's own frame border -- the outer start at pixel (1, 1) -- is a rectangle when the ROI's ring of pixels next to
                 // its zeroed frame is all set; ring_quads_kernel has then published what the walk would find: nothing to follow)
                 const bool ring_done = !cc.is_hole && cc.pos == pl.ns + 1 && (CROP ? ws.ring_crop : ws.ring_frame)[cc.roi] != 0;
-                if (!ring_done && cc.pos > 0 && cc.pos < pl.plane && !run_has_earlier_pixel_rows(pl.nbr, pl.ns, cc.pos, cc.is_hole))
+                if (!ring_done && cc.pos > 0 && cc.pos < pl.plane && !run_has_earlier_pixel_bits(pl.nbr, pl.ns, cc.pos, cc.is_hole))
                     alive = trace_flat(pl.nbr, pl.ns, pl.plane, cc.pos, cc.is_hole, nullptr, 0, PRE_STEPS).status == TRACE_OVERRUN;
             }
             const unsigned long long mask = __ballot(alive);
@@ -638,9 +587,8 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_kernel(Workspace ws) {
 // the longest dependent chain of the whole call.  If the ring of pixels next to the zeroed frame (rows 1 and sh-2, columns 1 and sw-2)
 // is all set, that border is exactly the rectangle (1,1) (1,sh-2) (sw-2,sh-2) (sw-2,1) -- the follower keeps the zeroed frame on one
 // side and the next ring pixel is always there, whatever lies inside -- with these four corner points in this order (the walk runs
-// down the left side first).  One wave per ROI checks the ring on the mask plane (bit 4 of a mask byte = the pixel to the west is set,
-// bit 0 = the pixel to the east): a handful of independent loads instead of a dependent chain; lane 0 then runs the same
-// approximation and filter on the four points as on any stored border and publishes the quad if it is one.  ring[roi] tells tier 1
+// down the left side first).  One wave per ROI checks the ring on the bit plane: a handful of independent loads instead of a
+// dependent chain; lane 0 then runs the same approximation and filter on the four points as on any stored border and publishes the quad if it is one.  ring[roi] tells tier 1
 // to drop the start.  A ring with a hole in it: ring[roi] = 0, the border is walked as before.
 template <bool CROP>
 __global__ __launch_bounds__(64) void ring_quads_kernel(Workspace ws) {
@@ -653,23 +601,21 @@ __global__ __launch_bounds__(64) void ring_quads_kernel(Workspace ws) {
         const int ns = uni(pl.ns), sh = uni(pl.sh), sw = uni(pl.img_w) & ~1;
         bool bad = sw < 8 || sh < 8;
         if (!bad) {
-            // rows 1 and sh-2: pixel x in [1, sw-2] is bit 4 of mask byte x+1
+            // rows 1 and sh-2: pixel x in [1, sw-2] is bit x % 16 + 1 of its row's dword in tile x >> 4: the ring's rows are runs of
+            // set bits, one dword per tile
             const int tiles = ns >> 4;
             for (int i = lane; i < 2 * tiles; i += 64) {
                 const int y = i < tiles ? 1 : sh - 2, xt = i < tiles ? i : i - tiles;
-                const uint4 v = *reinterpret_cast<const uint4*>(pl.nbr + nbr_addr(xt << 4, y, ns));
-                const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int xb = (xt << 4) + k;   // mask byte of pixel xb: its west neighbour is pixel xb-1
-                    if (xb >= 2 && xb <= sw - 1 && !((w[k >> 2] >> (8 * (k & 3) + 4)) & 1u)) bad = true;
+                const unsigned v = *reinterpret_cast<const unsigned*>(pl.nbr + nbr_win_off(xt << 4, y, ns) + 4);
+                const int lo = (xt << 4) > 1 ? (xt << 4) : 1, hi = (xt << 4) + 15 < sw - 2 ? (xt << 4) + 15 : sw - 2;   // columns of the ring in this tile
+                if (lo <= hi) {
+                    const unsigned need = ((2u << (hi - lo)) - 1u) << (lo - (xt << 4) + 1);
+                    if ((v & need) != need) bad = true;
                 }
             }
-            // columns 1 and sw-2, rows 1 .. sh-2: bit 4 of mask(2, y), bit 0 of mask(sw-3, y)
-            for (int y = 1 + lane; y <= sh - 2; y += 64) {
-                const unsigned a = pl.nbr[nbr_addr(2, y, ns)], b = pl.nbr[nbr_addr(sw - 3, y, ns)];
-                if (!((a >> 4) & 1u) || !(b & 1u)) bad = true;
-            }
+            // columns 1 and sw-2, rows 1 .. sh-2
+            for (int y = 1 + lane; y <= sh - 2; y += 64)
+                if (!nbr_bit(pl.nbr, 1, y, ns) || !nbr_bit(pl.nbr, sw - 2, y, ns)) bad = true;
         }
         const bool clean = __ballot(bad) == 0;
         if (lane == 0) {
@@ -738,7 +684,7 @@ __device__ __forceinline__ void lean_begin(LeanWalk& w, const uint8_t* nbr, int 
     w.xy1 = 0;
     w.pe = 0;
     w.from = 0;
-    w.m = nbr[nbr_addr(x, y, ns)];
+    w.m = nbr_of(nbr, x, y, ns);
     if (w.m == 0) {   // single-pixel domain (only reachable for outer borders)
         w.status = TRACE_SINGLE;
         w.npts = 1;
@@ -751,7 +697,7 @@ __device__ __forceinline__ void lean_begin(LeanWalk& w, const uint8_t* nbr, int 
 }
 
 // One step of a running walk.  tab: the 64-entry table in LDS; base / nt / last: the walk's plane (its first byte, tiles per
-// tile row = ns >> 4, its last byte offset); park(xy): the caller parks the pixel being left (every step; only a corner point
+// tile row = ns >> 4, the offset of its last 12-byte window); park(xy): the caller parks the pixel being left (every step; only a corner point
 // advances npts afterwards).
 template <class Park>
 __device__ __forceinline__ void lean_step(LeanWalk& w, const unsigned* tab, const uint8_t* base, unsigned nt, unsigned last, Park&& park) {
@@ -764,14 +710,13 @@ __device__ __forceinline__ void lean_step(LeanWalk& w, const unsigned* tab, cons
     const bool closes = (nxy == w.xy0) & (w.xy == w.xy1);
     const unsigned e = ent & LW_EXIT;
     const bool emit = e != w.pe;
-    // tiled address of the next pixel (hd.h::nbr_addr on the packed point).  A consistent plane never sends a walk outside
-    // itself; should one be inconsistent the offset is clamped (no access outside the plane), the walk runs into its budget and
-    // the wave tier, which checks every coordinate, reports it.
-    unsigned off = __umul24(nxy >> 19, nt) + ((nxy >> 4) & 0xfffu);
-    off = (off << 7) | (nxy & 15u);
-    off |= (nxy >> 12) & 0x70u;
+    // the next pixel's 3x3 window in the bit plane (hd.h::nbr_win_off_xy on the packed point) and its mask (hd.h::nbr_mask9).  A
+    // consistent plane never sends a walk outside itself; should one be inconsistent the offset is clamped (no access outside the
+    // plane), the walk runs into its budget and the wave tier, which checks every coordinate, reports it.
+    unsigned off = nbr_win_off_xy(nxy, nt);
     off = off < last ? off : last;
-    const unsigned m4 = base[off];
+    const unsigned* win = reinterpret_cast<const unsigned*>(base + off);
+    const unsigned m4 = nbr_mask9(win[0], win[1], win[2], nxy & 15u);
     park(w.xy);
     w.npts += emit ? 1 : 0;
     w.status = (int)nf < 0 ? (int)TRACE_NOT_FIRST : closes ? (int)TRACE_OK : m4 == 0u ? (int)TRACE_OVERRUN : -1;
@@ -783,7 +728,7 @@ __device__ __forceinline__ void lean_step(LeanWalk& w, const unsigned* tab, cons
 }
 
 // ---- Tier 2: one lane per surviving border, 64 independent walks per wave, lanes refilled as they finish -------------
-// A walk is a chain of dependent byte loads, so a wave's time is its longest walk; with one batch of 64 starts per wave
+// A walk is a chain of dependent loads, so a wave's time is its longest walk; with one batch of 64 starts per wave
 // most lanes would sit idle behind the longest border (a crop holds a ~900-step border next to 100-step ones).  Here a
 // lane whose walk has ended is retired every MID_BLOCK steps -- routed on, or approximated by the whole wave from its
 // slab -- and takes the next start from the list, so the lanes stay busy until the list is empty.
@@ -839,7 +784,7 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
     w.xy = w.m = w.from = w.pe = w.xy0 = w.xy1 = w.cxy = 0u;
     w.npts = w.step = 0;
     w.status = TRACE_NOT_FIRST;
-    unsigned pl_nt = 1u, pl_last = 0u;   // tiles per tile row and last byte offset of the lane's plane
+    unsigned pl_nt = 1u, pl_last = 0u;   // tiles per tile row and offset of the last 12-byte window of the lane's plane
     // every round hands out at least one start or retires at least one walk after <= budget / MID_BLOCK rounds of stepping
     long long guard = ((long long)n + 64) * (budget / MID_BLOCK + 5) + 64;
     PROF_DECL();
@@ -878,7 +823,7 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
                     if (take && c.pos > 0 && c.pos < pl.plane) {
                         lean_begin(w, pl.nbr, pl.ns, c.pos, c.is_hole);
                         pl_nt = (unsigned)(pl.ns >> 4);
-                        pl_last = (unsigned)nbr_plane_bytes(pl.ns, pl.sh) - 1u;
+                        pl_last = (unsigned)nbr_plane_bytes(pl.ns, pl.sh) - 12u;
                         have = true;
                         flushed = 0;
                     }
@@ -1008,38 +953,61 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
 }
 
 // ---- Phase B: one wave per long border, walking inside an LDS tile cache -------------------------------------
-// The follower's step needs the neighbour mask of the pixel it just moved to: a dependent byte load, i.e. one
-// HBM/L2 latency per step when done from global memory.  Here the wave cooperatively copies a TILE x TILE window
-// of the mask plane around the current pixel into LDS (each lane one row, 16-byte loads) and all lanes walk the
-// same border redundantly (wave-uniform control flow), so a step costs an LDS read; the window is re-centred when
-// the walk leaves it.  Same stepping rules as trace_core.h::trace_border.
+// The follower's step needs the neighbour mask of the pixel it just moved to: a dependent load, i.e. one HBM/L2 latency
+// per step when done from global memory.  Here the wave cooperatively copies a window of TILE_TX x TILE_TY tiles of the bit
+// plane around the current pixel into LDS (16-byte loads, one per lane and quarter tile) and all lanes walk the same border
+// redundantly (wave-uniform control flow), so a step costs an LDS read of the pixel's 3x3 window; the window is re-centred
+// when the walk leaves it.  Same stepping rules as trace_core.h::trace_border.
+// In LDS the window is stored by column block: block i (columns tx0 + 16 i - 1 .. tx0 + 16 i + 16, a tile's 18 bits) holds the
+// rows ty0 - 1 .. ty0 + TILE_H in TILE_SLOTS consecutive dwords, so a pixel's 3x3 window is dwords ly .. ly + 2 of its block --
+// no division by the tile height on the step's chain.  Dword d of window tile (i, j) is slot 14 j + d: a tile's apron rows land
+// on the slots of the neighbouring tiles' rows, which they equal.
+constexpr int TILE_SLOTS = TILE_H + 2;
 struct TileCache {
-    uint8_t* lds;          // TILE*TILE bytes of this wave
+    unsigned* lds;         // TILE_TX x TILE_SLOTS dwords of this wave
     const uint8_t* nbr;
     int ns, sh;            // ns is a multiple of 16, the plane base is 16-byte aligned
-    int tx0, ty0;          // window origin (tx0 multiple of 16, may be negative); wave-uniform
+    int tx0, ty0;          // window origin (tx0 a multiple of 16, ty0 of 14, either may be negative); wave-uniform
 };
 
 // (bx,by): direction of travel; the window is pushed ahead so that a straight run re-centres as rarely as possible
 __device__ __forceinline__ void tile_load(TileCache& t, int x, int y, int bx = 0, int by = 0) {
     const int lane = threadIdx.x & 63;
-    t.tx0 = (x + 20 * bx - TILE / 2 + 8) & ~15;   // keeps x-20..x+27 inside for bx = 0, up to 55 pixels ahead otherwise
-    t.ty0 = y + 28 * by - TILE / 2;
-    const int row = t.ty0 + lane;
-    uint4* dst = reinterpret_cast<uint4*>(t.lds + lane * TILE);
+    t.tx0 = (x + 20 * bx - TILE_W / 2 + 8) & ~15;   // keeps x-20..x+27 inside for bx = 0, up to 55 pixels ahead otherwise
+    // rows: y - ty0 in [28, 42) for by = 0 (28 rows either side), [4, 18) going down, [52, 66) going up (ty0 a whole tile row;
+    // the offset keeps the division's operand positive)
+    t.ty0 = (int)div14((unsigned)(y + 24 * by - 28 + 4 * NBR_TILE_H)) * NBR_TILE_H - 4 * NBR_TILE_H;
+    const int tx = (t.tx0 >> 4), ty = t.ty0 / NBR_TILE_H, nty = (t.sh + NBR_TILE_H - 1) / NBR_TILE_H;
+    constexpr int NQ = TILE_TX * TILE_TY * 4;   // quarter tiles of the window: lane l takes quarters l and l + 64 (< NQ)
+    static_assert(NQ > 64 && NQ <= 128, "two quarter tiles per lane at most");
+    uint4 v[2];
 #pragma unroll
-    for (int cch = 0; cch < TILE / 16; cch++) {
-        const int cx = t.tx0 + 16 * cch;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (row >= 0 && row < t.sh && cx >= 0 && cx + 16 <= t.ns) v = *reinterpret_cast<const uint4*>(t.nbr + nbr_addr(cx, row, t.ns));
-        dst[cch] = v;
+    for (int h = 0; h < 2; h++) {   // (both loads issued before any LDS store)
+        const int q = lane + 64 * h, i = (q >> 2) % TILE_TX, j = (q >> 2) / TILE_TX;
+        v[h] = make_uint4(0u, 0u, 0u, 0u);
+        if (q < NQ && tx + i >= 0 && (tx + i) * 16 < t.ns && ty + j >= 0 && ty + j < nty)
+            v[h] = *reinterpret_cast<const uint4*>(t.nbr + nbr_tile_off((unsigned)(tx + i), (unsigned)(ty + j), t.ns) + 16 * (q & 3));
+    }
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const int q = lane + 64 * h, i = (q >> 2) % TILE_TX, j = (q >> 2) / TILE_TX;
+        if (q < NQ) {
+            unsigned* d = t.lds + i * TILE_SLOTS + NBR_TILE_H * j + 4 * (q & 3);
+            d[0] = v[h].x; d[1] = v[h].y; d[2] = v[h].z; d[3] = v[h].w;
+        }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
 }
 
+// mask of window pixel (lx, ly), 0 <= lx < TILE_W, 0 <= ly < TILE_H
+__device__ __forceinline__ unsigned tile_mask(const TileCache& t, int lx, int ly) {
+    const unsigned* w = t.lds + ((unsigned)lx >> 4) * TILE_SLOTS + (unsigned)ly;
+    return nbr_mask9(w[0], w[1], w[2], (unsigned)lx & 15u);
+}
+
 __device__ __forceinline__ unsigned tile_get(TileCache& t, int x, int y) {
-    if ((unsigned)(x - t.tx0) >= (unsigned)TILE || (unsigned)(y - t.ty0) >= (unsigned)TILE) tile_load(t, x, y);
-    return uni((unsigned)t.lds[(y - t.ty0) * TILE + (x - t.tx0)]);
+    if ((unsigned)(x - t.tx0) >= (unsigned)TILE_W || (unsigned)(y - t.ty0) >= (unsigned)TILE_H) tile_load(t, x, y);
+    return uni(tile_mask(t, x - t.tx0, y - t.ty0));
 }
 
 // Lean follower on the tile cache.  All 64 lanes walk the same border and the walker's state (position, direction,
@@ -1114,8 +1082,8 @@ __device__ LeanTrace trace_lean_tiled(TileCache& t, int cpos, int is_hole, int* 
                 bool closed = false, bad = false;
                 for (;;) {
                     const int qx = x + (lane + 1) * ddx, qy = y + (lane + 1) * ddy;
-                    const bool in_tile = (unsigned)(qx - t.tx0) < (unsigned)TILE && (unsigned)(qy - t.ty0) < (unsigned)TILE;
-                    const unsigned mq = in_tile ? t.lds[(qy - t.ty0) * TILE + (qx - t.tx0)] : 256u;
+                    const bool in_tile = (unsigned)(qx - t.tx0) < (unsigned)TILE_W && (unsigned)(qy - t.ty0) < (unsigned)TILE_H;
+                    const unsigned mq = in_tile ? tile_mask(t, qx - t.tx0, qy - t.ty0) : 256u;
                     const bool closes = qx == x0 && qy == y0 && qx - ddx == x1 && qy - ddy == y1;
                     const unsigned long long close_mask = __ballot(closes);
                     const unsigned long long stop = close_mask | __ballot(mq != m);
@@ -1180,7 +1148,7 @@ __device__ LeanTrace trace_lean_tiled(TileCache& t, int cpos, int is_hole, int* 
 
 template <bool CROP>
 __global__ __launch_bounds__(FOLLOW_THREADS) void follow_long_kernel(Workspace ws) {
-    __shared__ __attribute__((aligned(16))) uint8_t tiles[FW][TILE * TILE];
+    __shared__ unsigned tiles[FW][TILE_TX * TILE_SLOTS];
     __shared__ WaveScratch scratch[FW];
     __shared__ unsigned staged[FW][LDS_PTS];
     const StartCand* longs = CROP ? ws.long_crop : ws.long_frame;

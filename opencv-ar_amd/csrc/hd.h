@@ -26,41 +26,72 @@ OCVAR_HD int dir_dy(int s) { return (s >= 1 && s <= 3) ? -1 : ((s >= 5 && s <= 7
 
 struct Pt { int x, y; };
 
-// Byte offset of pixel (x,y) in a neighbour-mask plane of row stride ns (a multiple of 16).
-// Product build (OCVAR_NBR_TILED): the plane is stored as 16x8-pixel tiles of 128 contiguous bytes -- one cache
-// line -- because the border follower walks locally in 2-D: with raster rows every vertical step of a border is
-// a new 128-byte line (a fresh HBM/MALL miss on a dependent chain), with tiles a walk stays in a line for ~10 steps.
-// The host-side test build of the cores keeps plain raster planes.
-// (A plane is far smaller than 4 GB; the offset is 32-bit and, on the device, built with the 24-bit multiplier: the
-// followers compute it once per step on a dependent chain.)
-OCVAR_HD unsigned nbr_addr(int x, int y, int ns) {
-#if defined(OCVAR_NBR_TILED)
+// The neighbour plane of a binary image (sw x sh, row stride ns: sw rounded up to a multiple of 16).
+//
+// Host-side test build of the cores: one byte per pixel, raster rows, the 8-neighbour mask (bit s = the neighbour in
+// direction s is set); nbr_at() reads it.
+//
+// Product build (OCVAR_NBR_TILED): a BIT plane with an apron, stored as tiles.  A tile covers 16 columns x 14 rows and is
+// 16 dwords (64 bytes, one sector); dword j holds row 14 ty + j - 1, bit b of it column 16 tx + b - 1 (b = 0..17).  So a
+// pixel's 3x3 neighbourhood is dwords y % 14 .. y % 14 + 2 of its tile -- one aligned 12-byte load -- at bits x % 16 ..
+// x % 16 + 2, and its mask byte follows from those 9 bits (nbr_mask9).  Pixels outside the plane and on cvFindContours'
+// zeroed frame are 0.  The tiles of one tile row are contiguous.  0.29 bytes per pixel instead of 1: the binarise kernels
+// write it in whole sectors, the followers' dependent loads stay inside one sector for ~10 steps as with byte tiles.
+// (A plane is far smaller than 4 GB; offsets are 32-bit and, on the device, built with the 24-bit multiplier: the
+// followers compute one per step on a dependent chain.)
+constexpr int NBR_TILE_W = 16, NBR_TILE_H = 14, NBR_TILE_BYTES = 64;
+OCVAR_HD unsigned umul24(unsigned a, unsigned b) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    const unsigned tile = __umul24((unsigned)(y >> 3), (unsigned)(ns >> 4)) + (unsigned)(x >> 4);
+    return __umul24(a, b);
 #else
-    const unsigned tile = (unsigned)(y >> 3) * (unsigned)(ns >> 4) + (unsigned)(x >> 4);
-#endif
-    return (tile << 7) | ((unsigned)(y & 7) << 4) | (unsigned)(x & 15);
-#else
-    return (unsigned)(y * ns + x);
+    return a * b;
 #endif
 }
-// the same offset split into its row part (wave-uniform in the row-marching kernels) and its column part (constant per lane)
-OCVAR_HD long long nbr_row_off(int y, int ns) {
+// y / 14 and y % 14 for 0 <= y < 43690 (2^19 / 14 rounded up: exact in that range; images are at most 32767 rows)
+OCVAR_HD unsigned div14(unsigned y) { return umul24(y, 37450u) >> 19; }
+// bytes of a plane: (ns / 16) tiles per tile row, sh rounded up to whole tile rows
+OCVAR_HD long long nbr_plane_bytes(int ns, int sh) {
 #if defined(OCVAR_NBR_TILED)
-    return ((long long)((y >> 3) * (ns >> 4)) << 7) + ((y & 7) << 4);
+    return (long long)(ns >> 4) * NBR_TILE_BYTES * ((sh + NBR_TILE_H - 1) / NBR_TILE_H);
 #else
-    return (long long)y * ns;
+    return (long long)ns * sh;
 #endif
 }
-OCVAR_HD unsigned nbr_col_off(int x) {
+// byte offset of tile (tx, ty); of the 3x3 window of pixel (x, y) (dword y % 14 of its tile: rows y-1, y, y+1 follow)
+OCVAR_HD unsigned nbr_tile_off(unsigned tx, unsigned ty, int ns) { return (umul24(ty, (unsigned)ns >> 4) + tx) * (unsigned)NBR_TILE_BYTES; }
+OCVAR_HD unsigned nbr_win_off(int x, int y, int ns) {
+    const unsigned ty = div14((unsigned)y);
+    return nbr_tile_off((unsigned)x >> 4, ty, ns) + 4u * ((unsigned)y - 14u * ty);
+}
+// the same for a packed point x | y << 16 with nt = ns / 16 (the border followers' position format)
+OCVAR_HD unsigned nbr_win_off_xy(unsigned xy, unsigned nt) {
+    const unsigned y = xy >> 16, ty = div14(y);
+    return (umul24(ty, nt) + ((xy >> 4) & 0xfffu)) * (unsigned)NBR_TILE_BYTES + 4u * (y - 14u * ty);
+}
+// The 8-neighbour mask (E NE N NW W SW S SE = bits 0..7) of the pixel at bit k + 1 of the row words above (a), own (c), below (b).
+// (Bit arithmetic instead of a table: on a follower's dependent chain ten VALU operations are shorter than an LDS round trip.)
+OCVAR_HD unsigned nbr_mask9(unsigned a, unsigned c, unsigned b, unsigned k) {
+    // the row above comes in as NW N NE (bits 0 1 2) and goes to mask bits 3 2 1: a nibble table indexed by the 3 bits
+    constexpr unsigned REV = (0u << 0) | (8u << 4) | (4u << 8) | (12u << 12) | (2u << 16) | (10u << 20) | (6u << 24) | (14u << 28);
+    const unsigned up = (REV >> (((a >> k) & 7u) << 2)) & 15u;
+    const unsigned own = ((c >> (k + 2u)) & 1u) | (((c >> k) & 1u) << 4);
+    return up | own | (((b >> k) & 7u) << 5);
+}
 #if defined(OCVAR_NBR_TILED)
-    return ((unsigned)(x >> 4) << 7) + (unsigned)(x & 15);
-#else
-    return (unsigned)x;
-#endif
+// mask byte of pixel (x, y), 0 <= x < ns, 0 <= y < sh: one 12-byte load
+OCVAR_HD unsigned nbr_of(const uint8_t* plane, int x, int y, int ns) {
+    const unsigned* w = reinterpret_cast<const unsigned*>(plane + nbr_win_off(x, y, ns));
+    return nbr_mask9(w[0], w[1], w[2], (unsigned)x & 15u);
 }
-OCVAR_HD long long nbr_plane_bytes(int ns, int sh) { return (long long)ns * ((sh + 7) & ~7); }
+// the pixel's own binary value (0 / 1)
+OCVAR_HD unsigned nbr_bit(const uint8_t* plane, int x, int y, int ns) {
+    const unsigned* w = reinterpret_cast<const unsigned*>(plane + nbr_win_off(x, y, ns));
+    return (w[1] >> (((unsigned)x & 15u) + 1u)) & 1u;
+}
+OCVAR_HD unsigned nbr_at(const uint8_t* plane, int x, int y, int ns) { return nbr_of(plane, x, y, ns); }
+#else
+OCVAR_HD unsigned nbr_at(const uint8_t* plane, int x, int y, int ns) { return plane[y * ns + x]; }
+#endif
 
 // The grey plane is stored in PANELS: panel p of a row holds columns 240 p - 8 .. 240 p + 247 in 256 bytes -- the 256 columns one
 // wave of the frame binarise kernel converts (its 240 output columns and the 8-column halo on either side), so that every grey
@@ -86,9 +117,9 @@ struct Roi {
     int x0, y0;       // origin inside the frame's gray plane
     int w, h;         // ROI size (img->width/height for the border rule, opencvar.cpp:204-206)
     int sw, sh;       // w & ~1, h & ~1 (opencvar.cpp:158): size of the binary / neighbour plane
-    int ns;           // row stride of the neighbour plane (sw rounded up to a multiple of 4)
+    int ns;           // columns of the neighbour plane (sw rounded up to a multiple of 16)
     int owner;        // frame pass: frame index; crop pass: index of the frame-pass quad it came from
-    long long nbr_off;  // offset of this ROI's neighbour-mask plane in the pass's pool
+    long long nbr_off;  // byte offset of this ROI's neighbour plane (a bit plane on the device) in the pass's pool
 };
 
 // A candidate border start found by the binarise kernel.

@@ -14,7 +14,7 @@ constexpr int MAXT = OCVAR_MAX_TEMPLATES;
 constexpr int MARCH_HALO_L = 2, MARCH_HALO_R = 2;   // halo lanes (4 pixels each) left / right of a strip's output lanes
 constexpr int MARCH_STRIP = 4 * (64 - MARCH_HALO_L - MARCH_HALO_R);   // 240 output columns of one wave's strip in the binarise kernel (256 loaded)
 static_assert(MARCH_STRIP == GRAY_PANEL_COLS && 4 * MARCH_HALO_L == GRAY_PANEL_LEAD && 4 * 64 == GRAY_PANEL_BYTES, "a grey panel is what one wave of the frame kernel converts");
-constexpr int MARCH_CROP_ROWS = 256;       // rows per work unit in the crop pass (even)
+constexpr int MARCH_CROP_ROWS = 252;       // rows per work unit in the crop pass (whole tile rows of the bit plane: a multiple of 14)
 constexpr int MARCH_STAGE = 512;           // border starts a wave stages in LDS between two appends to the global list
 constexpr int BACK_STEPS = 32;             // backward look of an outer start before it follows its border
 constexpr int PRE_STEPS = 8;               // steps every plausible start gets before it may queue for tier 1's full budget
@@ -26,7 +26,8 @@ constexpr int MID_BLOCKS_MAX = 1024;       // tier-2 grid limit (x256 threads, o
 constexpr int SLAB3_PTS = 8192;            // points a tier-3 wave can keep in its slab
 constexpr int SLAB3_STRIDE = SLAB3_PTS + 64;   // dwords per tier-3 wave slab
 constexpr int LONG_BLOCKS_MAX = 1024;      // tier-3 grid limit (x4 waves, one slab each)
-constexpr int TILE = 64;                   // side of the LDS tile the wave-per-border follower walks in
+constexpr int TILE_TX = 4, TILE_TY = 5;    // the window of the bit plane (in 16x14 tiles) the wave-per-border follower walks in
+constexpr int TILE_W = TILE_TX * NBR_TILE_W, TILE_H = TILE_TY * NBR_TILE_H;   // 64 x 70 pixels
 
 // error bits accumulated in Workspace::err[0]
 enum { ERR_CAND_OVERFLOW = 1, ERR_POOL_OVERFLOW = 2, ERR_QUAD_OVERFLOW = 4, ERR_TRACE_OVERRUN = 8, ERR_CROP_OVERFLOW = 16,
@@ -58,7 +59,7 @@ struct Workspace {
     int cap_frame_cands, cap_crop_cands, cap_crop_rois, cap_crop_tiles, cap_crop_quads;
     long long cap_pool_ints, cap_crop_pixels;
     // per batch geometry
-    int W, H, sw, sh, ns, n_frames, n_templates;   // ns: row stride of a neighbour-mask plane = sw rounded up to 4
+    int W, H, sw, sh, ns, n_frames, n_templates;   // ns: columns of a neighbour plane = sw rounded up to 16
     int n_sizes, n_groups, max_match;        // the library (library_core.h): size classes, groups, most matches per square
     int crop_phases;                         // 2: crop tier 2 in two launches (earliest starts first, then the rest behind exact pruning); 1: one launch (few frames: the shorter chain)
     int mid_steps, mid_blocks, long_blocks;  // tuning (env OCVAR_MID_STEPS / OCVAR_MID_BLOCKS / OCVAR_LONG_BLOCKS): tier-2 step budget and grid, tier-3 grid

@@ -70,7 +70,7 @@ OCVAR_HD TraceStats trace_border(const uint8_t* nbr, int sw, int plane, int cpos
     st.steps = 0;
     const int i0 = cpos - is_hole;
     int x = i0 % sw, y = i0 / sw;
-    unsigned m = nbr[nbr_addr(x, y, sw)];
+    unsigned m = nbr_at(nbr, x, y, sw);
     if (m == 0) {  // single-pixel domain (only reachable for outer borders)
         st.status = TRACE_SINGLE;
         st.npts = 1;
@@ -131,7 +131,7 @@ OCVAR_HD TraceStats trace_border(const uint8_t* nbr, int sw, int plane, int cpos
             st.status = TRACE_OVERRUN;
             return st;
         }
-        unsigned m4 = nbr[nbr_addr(x, y, sw)];
+        unsigned m4 = nbr_at(nbr, x, y, sw);
         if (m4 == 0) {
             st.status = TRACE_OVERRUN;
             return st;
@@ -148,8 +148,9 @@ OCVAR_HD TraceStats trace_border(const uint8_t* nbr, int sw, int plane, int cpos
                 unsigned long long ahead = 0;
                 for (int t = 1; t <= 8; t++) {
                     const int qi = p + t * d;
-                    const bool ok = qi >= 0 && qi < plane;   // (x,y) is the position of p here
-                    ahead |= (unsigned long long)(ok ? nbr[nbr_addr(x + t * ddx, y + t * ddy, sw)] : 0) << (8 * (t - 1));
+                    const bool ok = qi >= 0 && qi < plane && (unsigned)(x + t * ddx) < (unsigned)sw;   // (x,y) is the position of p here; the run
+                    // ends at a foreground pixel inside the zeroed frame, so masks beyond the plane's columns are never compared
+                    ahead |= (unsigned long long)(ok ? nbr_at(nbr, x + t * ddx, y + t * ddy, sw) : 0) << (8 * (t - 1));
                 }
                 for (int t = 1; t <= 8; t++) {
                     // p carries mask m and leaves in direction s: its scan positions, then the step p -> q
@@ -221,7 +222,7 @@ OCVAR_HD LeanTrace trace_lean(const uint8_t* nbr, int ns, int plane, int cpos, i
     r.steps = 0;
     const int i0 = cpos - is_hole;
     int x = i0 % ns, y = i0 / ns;
-    unsigned m = nbr[nbr_addr(x, y, ns)];
+    unsigned m = nbr_at(nbr, x, y, ns);
     if (m == 0) {
         r.status = TRACE_SINGLE;
         r.npts = 1;
@@ -271,7 +272,7 @@ OCVAR_HD LeanTrace trace_lean(const uint8_t* nbr, int ns, int plane, int cpos, i
         // (non-points go to a scratch slot behind the last point): memory operations retire in order, so the wait for
         // the mask must be able to leave exactly these two younger stores in flight -- which the compiler can only
         // count when they are on the straight-line path.
-        m = nbr[nbr_addr(x, y, ns)];
+        m = nbr_at(nbr, x, y, ns);
         if (max_pts > 0) {
             const int slot = (emit && r.npts < max_pts) ? r.npts : max_pts;
             out[2 * slot] = ex;
@@ -311,7 +312,7 @@ OCVAR_HD void flat_begin(FlatWalk& w, const uint8_t* nbr, int ns, int cpos, int 
     w.npts = 0;
     w.step = 0;
     w.status = -1;
-    w.m = nbr[nbr_addr(w.x, w.y, ns)];
+    w.m = nbr_at(nbr, w.x, w.y, ns);
     w.s = 0;
     w.prev_s = 0;
     w.i1 = 0;
@@ -351,7 +352,8 @@ OCVAR_HD void flat_step_t(FlatWalk& w, const uint8_t* nbr, int ns, int plane, in
     // except for a border that closes, whose last corner point is exactly this pixel (emit as for any other step).
     const bool emit = !budget & (e != w.prev_s);          // CHAIN_APPROX_SIMPLE: a point wherever the direction changes
     const int lx = w.x + dx, ly = w.y + dy;
-    const unsigned m4 = nbr[oob ? 0u : nbr_addr(lx, ly, ns)];
+    const bool off_plane = oob | ((unsigned)lx >= (unsigned)ns);   // (the column too: a bit plane has no raster wrap-around)
+    const unsigned m4 = nbr_at(nbr, off_plane ? 0 : lx, off_plane ? 0 : ly, ns);
     store(emit, w.x, w.y);
     w.npts += emit ? 1 : 0;
     w.status = budget ? (int)TRACE_OVERRUN : nf ? (int)TRACE_NOT_FIRST : closes ? (int)TRACE_OK : (oob | (m4 == 0u)) ? (int)TRACE_OVERRUN : -1;
@@ -432,7 +434,7 @@ OCVAR_HD TraceStats stats_of_points(const int* pts, int n) {
 OCVAR_HD bool earlier_start_behind(const uint8_t* nbr, int sw, int plane, int cpos, int is_hole, int max_back) {
     const int i0 = cpos - is_hole;
     int x = i0 % sw, y = i0 / sw;
-    unsigned m = nbr[nbr_addr(x, y, sw)];
+    unsigned m = nbr_at(nbr, x, y, sw);
     if (m == 0) return false;
     const int b0 = first_cw(m, (is_hole ? 0 : 4) - 1);
     int q = i0 + dir_dy(b0) * sw + dir_dx(b0);
@@ -441,7 +443,7 @@ OCVAR_HD bool earlier_start_behind(const uint8_t* nbr, int sw, int plane, int cp
     int s = (b0 + 4) & 7;  // exit direction at q (towards the pixel we came from)
     for (int k = 0; k < max_back; k++) {
         if ((unsigned)q >= (unsigned)plane) return false;
-        m = nbr[nbr_addr(x, y, sw)];
+        m = nbr_at(nbr, x, y, sw);
         if (m == 0) return false;
         const int b = first_cw(m, s - 1);
         if (q == i0 && b == b0) return false;  // back at the start visit: whole lap, nothing earlier
@@ -464,12 +466,12 @@ OCVAR_HD bool earlier_start_behind(const uint8_t* nbr, int sw, int plane, int cp
 // goes on), the loads are independent (one memory latency, usually one cache line), and on marker frames ~80 % of the
 // plausible starts (stair corners of slanted edges) end here.  The binarise kernel's local test is the first pixel of
 // this one.  max_run (<= 16) bounds the look-ahead; a run that is still going on after max_run pixels is given the benefit
-// of the doubt.  (The device reads the 16 masks with two 16-byte loads: follow.hip::run_has_earlier_pixel_rows.)
+// of the doubt.  (The device scans the two rows of the bit plane instead: run_has_earlier_pixel_bits below.)
 OCVAR_HD bool run_has_earlier_pixel(const uint8_t* nbr, int ns, int cpos, int is_hole, int max_run) {
     const int x = cpos % ns, y = cpos / ns;
     unsigned m[16];
     const int n = max_run < 16 ? max_run : 16;
-    for (int k = 0; k < 16; k++) m[k] = (k < n && x + k < ns) ? nbr[nbr_addr(x + k, y, ns)] : 0u;
+    for (int k = 0; k < 16; k++) m[k] = (k < n && x + k < ns) ? nbr_at(nbr, x + k, y, ns) : 0u;
     for (int k = 0; k < n && x + k < ns; k++) {
         if (is_hole) {
             if (!(m[k] & 0x04u)) return true;       // background directly above a pixel of the background run
@@ -483,6 +485,42 @@ OCVAR_HD bool run_has_earlier_pixel(const uint8_t* nbr, int ns, int cpos, int is
 }
 
 struct DpSlice { int start, end; };
+
+#if defined(OCVAR_NBR_TILED)
+// run_has_earlier_pixel on the bit plane (product build; follow.hip's tier 1) for max_run = 16: the run's row and the row
+// above it are two dwords of a tile, so the pixels x .. x+15 come with two 8-byte loads (the tile x is in and the next tile
+// of the same tile row) -- and the per-pixel tests become bit scans of the two rows.  Same decision rule: pixel k's row above is looked at before its E neighbour; a run
+// that is still going on after the look-ahead (or at the plane's edge) is given the benefit of the doubt.
+OCVAR_HD bool run_has_earlier_pixel_bits(const uint8_t* nbr, int ns, int cpos, int is_hole) {
+    const int x = cpos % ns, y = cpos / ns;
+    const uint8_t* win = nbr + nbr_win_off(x & ~15, y, ns);   // dwords: row y-1, row y of tile x >> 4
+    const unsigned* a = reinterpret_cast<const unsigned*>(win);
+    const unsigned a0 = a[0], a1 = a[1];
+    unsigned b0 = 0, b1 = 0;
+    if ((x | 15) + 1 < ns) {   // the next tile of the same tile row
+        b0 = a[NBR_TILE_BYTES / 4];
+        b1 = a[NBR_TILE_BYTES / 4 + 1];
+    }
+    // columns (x & ~15) - 1 .. (x & ~15) + 32 at bits 0 .. 33: the first tile's 18 bits, then the next tile's columns 17 .. 32
+    const unsigned long long up = (unsigned long long)(a0 & 0x3ffffu) | ((unsigned long long)((b0 >> 2) & 0xffffu) << 18);
+    const unsigned long long own = (unsigned long long)(a1 & 0x3ffffu) | ((unsigned long long)((b1 >> 2) & 0xffffu) << 18);
+    const unsigned sh = (unsigned)(x & 15);   // pixel x + k is then bit k + 1 of (row >> sh)
+    const unsigned long long va = up >> sh, vc = own >> sh;
+    const int lim = ns - x < 16 ? ns - x : 16;   // pixels that exist
+    const unsigned long long keep = (1ull << lim) - 1ull;
+    unsigned long long bad, end;
+    if (is_hole) {
+        bad = ~(va >> 1) & keep;                   // background directly above a pixel of the background run
+        end = (vc >> 2) & keep;                    // E is foreground: the run ends here
+    } else {
+        bad = (va | (va >> 1) | (va >> 2)) & keep; // NW, N or NE of a pixel of the foreground run is foreground
+        end = ~(vc >> 2) & keep;                   // E is background: the run ends here
+    }
+    if (!(bad | end)) return false;
+    const int kb = bad ? __builtin_ctzll(bad) : 64, ke = end ? __builtin_ctzll(end) : 64;
+    return kb <= ke;
+}
+#endif
 
 // cvApproxPoly(CV_POLY_APPROX_DP) on a closed integer contour of count >= 1 points (x,y pairs in src).
 // dst must hold DP_MAX_OUT+1 points, stack DP_STACK slices.  Returns the vertex count after the
