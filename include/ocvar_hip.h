@@ -89,8 +89,27 @@ int ocvar_hip_set_gate(OcvarHip* ctx, OcvarGate* gate);
 int ocvar_hip_set_templates(OcvarHip* ctx, const OcvarTemplate* templates, int n);
 int ocvar_hip_set_camera(OcvarHip* ctx, const OcvarCamera* camera);
 
+/* Input formats: what the frames handed to the detection entry points hold (d_bgr / h_bgr below keep their names).  8-bit
+ * interleaved pixels of 3, 3, 4, 4 and 1 bytes; row_stride must be at least that many bytes times width (else OCVAR_E_ARG).
+ * Parity: a frame in format F gives exactly what the reference gives on the BGR frame with the same colours --
+ *   OCVAR_FMT_GRAY  B = G = R = g (the reference's BGR2GRAY of such a pixel is g)
+ *   OCVAR_FMT_RGB   the channels reversed
+ *   OCVAR_FMT_BGRA / OCVAR_FMT_RGBA  the fourth byte is ignored
+ * grey_in_place writes the grey value into bytes 0..2 of every pixel (a four-channel pixel's byte 3 is left as it is); in
+ * OCVAR_FMT_GRAY it does nothing (no kernel, and ocvar_hip_detect_host copies nothing back).
+ * YUV sources (NV12, I420): OCVAR_FMT_GRAY on the luma plane -- row_stride = the plane's pitch, frame_stride = the whole
+ * YUV frame's size (pitch * height * 3 / 2 for NV12 and I420 with a common pitch); the chroma bytes are never read.  The result
+ * is the reference on the luma image; it is NOT the reference on a BT.601 conversion of the YUV frame to BGR. */
+enum { OCVAR_FMT_BGR = 0, OCVAR_FMT_RGB = 1, OCVAR_FMT_BGRA = 2, OCVAR_FMT_RGBA = 3, OCVAR_FMT_GRAY = 4 };
+/* Context state like the result limit and the camera: read when a batch is enqueued, by every entry point that takes frames
+ * (detect_device, enqueue, enqueue_tracked, detect_host).  Default OCVAR_FMT_BGR.  OCVAR_E_ARG for an unknown format, or
+ * while the context has a batch that has not been collected.  ocvar_hip_find_squares takes a grey image whatever the
+ * format. */
+int ocvar_hip_set_input_format(OcvarHip* ctx, int format);
+
 /* Batch detection on frames already resident in device memory.
- *   d_bgr        8UC3 interleaved BGR, frame f starts at d_bgr + f*frame_stride, rows row_stride bytes apart
+ *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
+ *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart
  *   grey_in_place non-zero: overwrite each frame with its grey version (the reference's side effect,
  *                opencvar.cpp:624-627)
  *   prev / prev_counts  host arrays [n_frames][OCVAR_MAX_MARKERS] and [n_frames] of the previous call's
@@ -190,8 +209,12 @@ int ocvar_hip_pipe_submit(OcvarPipe* pipe, uint8_t* d_bgr, int width, int height
 int ocvar_hip_pipe_collect(OcvarPipe* pipe, long long* tag, OcvarMarker* markers, int* counts, int max_per_frame);
 int ocvar_hip_pipe_in_flight(const OcvarPipe* pipe);
 int ocvar_hip_pipe_set_result_limit(OcvarPipe* pipe, int max_per_frame);
+/* The input format of every context of the pipe (ocvar_hip_set_input_format), for detect_device, submit and track_device.
+ * OCVAR_E_ARG for an unknown format or while a submitted chunk is in flight. */
+int ocvar_hip_pipe_set_input_format(OcvarPipe* pipe, int format);
 
-/* Same, frames in host memory (copied over PCIe first; greyed frames are copied back when requested). */
+/* Same, frames in host memory, h_bgr in the context's input format (copied over PCIe first; greyed frames are copied back
+ * when requested -- never in OCVAR_FMT_GRAY, where the frames are their own grey). */
 int ocvar_hip_detect_host(OcvarHip* ctx, uint8_t* h_bgr, int width, int height, int row_stride, size_t frame_stride,
                           int n_frames, int grey_in_place, const OcvarMarker* prev, const int* prev_counts,
                           OcvarMarker* markers, int* counts, int max_per_frame);

@@ -24,6 +24,9 @@ extern "C" {
 
 typedef struct OcvarMulti OcvarMulti;
 
+/* ocvar_multi_set_input_format: frames in grey, RGB or four-channel formats (ocvar_hip.h, OCVAR_FMT_*) */
+#include "ocvar_multi_format.h"
+
 enum { OCVAR_E_RCCL = -5 };   /* an RCCL call failed; see ocvar_multi_last_error */
 
 /* devices: n_devices HIP device indices (NULL: 0 .. n_devices-1); the first one is the gather root.
@@ -36,7 +39,8 @@ int ocvar_multi_devices(const OcvarMulti* m);
 int ocvar_multi_set_templates(OcvarMulti* m, const OcvarTemplate* templates, int n);
 int ocvar_multi_set_camera(OcvarMulti* m, const OcvarCamera* camera);
 
-/* Stateless detection of n_frames (<= n_devices * max_frames_per_device) frames in host memory; frame f runs on device
+/* Stateless detection of n_frames (<= n_devices * max_frames_per_device) frames in host memory (h_bgr / d_bgr: frames in the
+ * input format, ocvar_multi_set_input_format; BGR by default); frame f runs on device
  * f mod n_devices.  markers [n_frames][max_per_frame] and counts [n_frames] are host outputs in caller order
  * (cvarArMultRegistration's result per frame). */
 int ocvar_multi_detect_host(OcvarMulti* m, const uint8_t* h_bgr, int width, int height, int row_stride, size_t frame_stride,

@@ -23,11 +23,36 @@ MAX_TEMPLATES, MAX_TEMPLATE_SIZES, MAX_QUADS, MAX_MARKERS = 4096, 16, 256, 64
 HIP_SYMBOLS = [
     "ocvar_hip_create", "ocvar_hip_create_ex", "ocvar_hip_capacity_flags", "ocvar_hip_gate_create", "ocvar_hip_gate_destroy", "ocvar_hip_set_gate", "ocvar_hip_ready", "ocvar_hip_set_result_limit",
     "ocvar_hip_pipe_create", "ocvar_hip_pipe_destroy", "ocvar_hip_pipe_last_error", "ocvar_hip_pipe_set_templates", "ocvar_hip_pipe_set_camera",
-    "ocvar_hip_pipe_detect_device", "ocvar_hip_pipe_track_device", "ocvar_hip_pipe_submit", "ocvar_hip_pipe_collect", "ocvar_hip_pipe_in_flight", "ocvar_hip_pipe_set_result_limit", "ocvar_hip_enqueue_tracked", "ocvar_hip_build_info", "ocvar_hip_set_tuning", "ocvar_hip_destroy", "ocvar_hip_last_error", "ocvar_hip_set_templates", "ocvar_hip_set_camera",
+    "ocvar_hip_pipe_detect_device", "ocvar_hip_pipe_track_device", "ocvar_hip_pipe_submit", "ocvar_hip_pipe_collect", "ocvar_hip_pipe_in_flight", "ocvar_hip_pipe_set_result_limit", "ocvar_hip_set_input_format", "ocvar_hip_pipe_set_input_format", "ocvar_hip_enqueue_tracked", "ocvar_hip_build_info", "ocvar_hip_set_tuning", "ocvar_hip_destroy", "ocvar_hip_last_error", "ocvar_hip_set_templates", "ocvar_hip_set_camera",
     "ocvar_hip_detect_device", "ocvar_hip_enqueue", "ocvar_hip_collect", "ocvar_hip_detect_host", "ocvar_hip_find_squares",
     "ocvar_hip_debug_gray", "ocvar_hip_debug_binary", "ocvar_hip_debug_masks", "ocvar_hip_debug_frame_quads", "ocvar_hip_debug_candidates",
     "ocvar_hip_stage_ms", "ocvar_hip_stream", "ocvar_hip_stage_stamps", "ocvar_hip_counters", "ocvar_hip_results_to_device", "ocvar_hip_results_to_device_ex", "ocvar_hip_debug_calibrate",
 ]
+# input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
+INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
+FORMAT_BPP = {0: 3, 1: 3, 2: 4, 3: 4, 4: 1}
+
+
+def input_format_code(fmt):
+    """'bgr' | 'rgb' | 'bgra' | 'rgba' | 'gray' (or the OCVAR_FMT_* value) -> the OCVAR_FMT_* value"""
+    if isinstance(fmt, str) and fmt.lower() in INPUT_FORMATS:
+        return INPUT_FORMATS[fmt.lower()]
+    if isinstance(fmt, int) and not isinstance(fmt, bool) and fmt in FORMAT_BPP:
+        return fmt
+    raise ValueError(f"unknown input format {fmt!r}: one of {sorted(INPUT_FORMATS)}")
+
+
+def frame_shape_bpp(shape, fmt):
+    """(n, h, w) of a host frame array [n, H, W] (gray) or [n, H, W, bpp] in format fmt; ValueError if the shape does not fit"""
+    bpp = FORMAT_BPP[input_format_code(fmt)]
+    if bpp == 1:
+        if len(shape) != 3:
+            raise ValueError(f"gray frames are [n, H, W], got {tuple(shape)}")
+    elif len(shape) != 4 or shape[3] != bpp:
+        raise ValueError(f"frames in this format are [n, H, W, {bpp}], got {tuple(shape)}")
+    return shape[0], shape[1], shape[2]
+
+
 STAGE_NAMES = ["binarise_frames", "follow1_frames", "follow2_frames", "follow3_frames", "order_crops", "binarise_crops",
                "follow1_crops", "follow2_crops", "follow3_crops", "decode", "dedupe_pose", "batch_total"]
 
@@ -99,6 +124,8 @@ def hip_lib():
         lib.ocvar_hip_pipe_collect.argtypes = [vp, C.POINTER(C.c_longlong), vp, vp, i]
         lib.ocvar_hip_pipe_in_flight.argtypes = [vp]
         lib.ocvar_hip_pipe_set_result_limit.argtypes = [vp, i]
+        lib.ocvar_hip_pipe_set_input_format.argtypes = [vp, i]
+        lib.ocvar_hip_set_input_format.argtypes = [vp, i]
         lib.ocvar_hip_enqueue_tracked.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, vp]
         lib.ocvar_hip_set_tuning.argtypes = [vp, i, i]
         lib.ocvar_hip_build_info.argtypes = []
@@ -195,6 +222,8 @@ class Pipe:
     """Several contexts on one GPU as one detector (include/ocvar_hip.h: ocvar_hip_pipe_*): device-resident frames, any number
     of them, detected chunk by chunk with one chunk in flight per context."""
 
+    input_format = INPUT_FORMATS["bgr"]   # (set_input_format)
+
     def __init__(self, max_width, max_height, chunk_frames=2048, n_contexts=4, gate_width=2, device=0):
         self._lib = hip_lib()
         self._p = C.c_void_p()
@@ -227,8 +256,14 @@ class Pipe:
     def set_camera(self, camera):
         self._check(self._lib.ocvar_hip_pipe_set_camera(self._p, C.byref(camera)), "pipe_set_camera")
 
+    def set_input_format(self, fmt):
+        """what the frames of detect_device / submit / track_device hold: 'bgr' (default), 'rgb', 'bgra', 'rgba' or 'gray'"""
+        code = input_format_code(fmt)
+        self._check(self._lib.ocvar_hip_pipe_set_input_format(self._p, code), "pipe_set_input_format")
+        self.input_format = code
+
     def detect_device(self, d_ptr, width, height, n_frames, row_stride=None, frame_stride=None, grey_in_place=False, max_per_frame=MAX_MARKERS):
-        row_stride = row_stride or 3 * width
+        row_stride = row_stride or FORMAT_BPP[self.input_format] * width
         frame_stride = frame_stride or row_stride * height
         markers = np.zeros((n_frames, max_per_frame), MARKER_DTYPE)
         counts = np.zeros(n_frames, np.int32)
@@ -238,7 +273,7 @@ class Pipe:
 
     def submit(self, d_ptr, width, height, n_frames, tag=0, row_stride=None, frame_stride=None, grey_in_place=False):
         """streaming form: hand the next chunk to the next context; False when every context already has one in flight"""
-        row_stride = row_stride or 3 * width
+        row_stride = row_stride or FORMAT_BPP[self.input_format] * width
         frame_stride = frame_stride or row_stride * height
         rc = self._lib.ocvar_hip_pipe_submit(self._p, d_ptr, width, height, row_stride, frame_stride, n_frames, int(grey_in_place), tag)
         if rc == -6:
@@ -270,7 +305,7 @@ class Pipe:
     def track_device(self, d_ptr, width, height, n_streams, reset=False, row_stride=None, frame_stride=None, grey_in_place=False,
                      max_per_frame=MAX_MARKERS):
         """one time step of n_streams video streams (frame s = stream s); the streams' markers of the previous step stay on the device"""
-        row_stride = row_stride or 3 * width
+        row_stride = row_stride or FORMAT_BPP[self.input_format] * width
         frame_stride = frame_stride or row_stride * height
         markers = np.zeros((n_streams, max_per_frame), MARKER_DTYPE)
         counts = np.zeros(n_streams, np.int32)
@@ -286,6 +321,8 @@ def build_info():
 
 class Detector:
     """A device context: batches of frames -> CvarMarker arrays (cvarArMultRegistration semantics per frame)."""
+
+    input_format = INPUT_FORMATS["bgr"]   # what the frames hold (set_input_format)
 
     def __init__(self, max_width, max_height, max_batch=1, device=0):
         self._lib = hip_lib()
@@ -337,7 +374,7 @@ class Detector:
 
     def enqueue_device(self, d_ptr, width, height, n_frames, row_stride=None, frame_stride=None, grey_in_place=False,
                        prev=None, stream=None):
-        row_stride = row_stride or 3 * width
+        row_stride = row_stride or FORMAT_BPP[self.input_format] * width
         frame_stride = frame_stride or row_stride * height
         pm, pc = self._prev_arrays(prev, n_frames)
         self._keep = (pm, pc)
@@ -363,6 +400,13 @@ class Detector:
         """marker records per frame a batch brings to the host (default MAX_MARKERS); counts stay the full counts"""
         self._check(self._lib.ocvar_hip_set_result_limit(self._ctx, max_per_frame), "set_result_limit")
 
+    def set_input_format(self, fmt):
+        """what the frames of later batches hold: 'bgr' (default), 'rgb', 'bgra', 'rgba' or 'gray' (include/ocvar_hip.h:
+        the results are the reference's on the BGR frame of the same colours)"""
+        code = input_format_code(fmt)
+        self._check(self._lib.ocvar_hip_set_input_format(self._ctx, code), "set_input_format")
+        self.input_format = code
+
     TUNE = {"crop_phases": 1, "mid_steps": 2, "mid_blocks": 3, "long_blocks": 4, "short_blocks": 5, "min_units": 6, "hp_mask": 7, "gate_mode": 8}
 
     def set_tuning(self, **kw):
@@ -386,13 +430,15 @@ class Detector:
         return self.collect(max_per_frame)
 
     def detect_host(self, frames, grey_in_place=False, prev=None, max_per_frame=MAX_MARKERS):
-        """frames: uint8 array [n, H, W, 3] (C-contiguous).  Greyed in place when asked (reference side effect)."""
-        assert frames.dtype == np.uint8 and frames.ndim == 4 and frames.shape[3] == 3 and frames.flags.c_contiguous
-        n, h, w, _ = frames.shape
+        """frames: uint8 array (C-contiguous) [n, H, W, 3] (bgr, rgb), [n, H, W, 4] (bgra, rgba) or [n, H, W] (gray), as the
+        input format says.  Greyed in place when asked (reference side effect; a gray frame is left as it is)."""
+        assert frames.dtype == np.uint8 and frames.flags.c_contiguous
+        n, h, w = frame_shape_bpp(frames.shape, self.input_format)
+        bpp = FORMAT_BPP[self.input_format]
         markers = np.zeros((n, max_per_frame), MARKER_DTYPE)
         counts = np.zeros(n, np.int32)
         pm, pc = self._prev_arrays(prev, n)
-        self._check(self._lib.ocvar_hip_detect_host(self._ctx, _ptr(frames), w, h, 3 * w, 3 * w * h, n, int(grey_in_place),
+        self._check(self._lib.ocvar_hip_detect_host(self._ctx, _ptr(frames), w, h, bpp * w, bpp * w * h, n, int(grey_in_place),
                                                     _ptr(pm), _ptr(pc), _ptr(markers), _ptr(counts), max_per_frame),
                     "detect_host")
         self._n = n

@@ -34,6 +34,7 @@ struct OcvarHip {
     int device = 0;
     OcvarGate* gate = nullptr;
     int result_limit = OCVAR_MAX_MARKERS;   // marker records per frame copied to the host (ocvar_hip_set_result_limit)
+    int input_format = OCVAR_FMT_BGR;       // what the frames of the next batch hold (ocvar_hip_set_input_format)
     int tune[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // ocvar_hip_set_tuning: 0 = default
     Workspace ws{};
     hipStream_t stream = nullptr;
@@ -372,10 +373,11 @@ static bool trace_launches() {
 
 static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride, int n_frames,
                         int grey_in_place, const OcvarMarker* prev, const int* prev_counts, hipStream_t s, int stages,
-                        bool prev_on_device = false) {
+                        int format, bool prev_on_device = false) {
     Workspace& w = c->ws;
     if (!d_bgr || width < 16 || height < 16 || width > w.max_w || height > w.max_h || n_frames < 1 || n_frames > w.max_batch ||
-        (size_t)width * height > (size_t)w.max_w * w.max_h || row_stride < 3 * width)
+        (size_t)width * height > (size_t)w.max_w * w.max_h || input_format_bpp(format) == 0 ||
+        (long long)row_stride < (long long)input_format_bpp(format) * width)
         return OCVAR_E_ARG;
     if (c->pending) {
         c->err = "the previous batch of this context has not been collected";
@@ -474,7 +476,7 @@ static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int 
     const int gate_mode = (int)tuned(c, OCVAR_TUNE_GATE_MODE, "OCVAR_GATE_MODE", 0);   // which binarise kernels the gate covers: 0 both, 1 the frames kernel only, 2 the crops kernel only
     if (gate_mode != 2) HIP_TRY(c, gate_enter(c->gate, s));   // (before the first timing event: a wait at the gate is not binarise time)
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
-    launch_binarise_frames(w, d_bgr, row_stride, frame_stride, grey_in_place, s);
+    launch_binarise_frames(w, d_bgr, row_stride, frame_stride, grey_in_place, format, s);
     if (gate_mode != 2) HIP_TRY(c, gate_leave(c->gate, s));
     TRACE_LAUNCH("binarise_frames", s);
     // Timing experiments (results are then incomplete or wrong): compiled into profiling builds only (-DOCVAR_PROF, `make prof`)
@@ -579,14 +581,14 @@ extern "C" int ocvar_hip_enqueue(OcvarHip* c, uint8_t* d_bgr, int width, int hei
                                  int n_frames, int grey_in_place, const OcvarMarker* prev, const int* prev_counts, void* stream) {
     if (!c) return OCVAR_E_ARG;
     return enqueue_impl(c, d_bgr, width, height, row_stride, frame_stride, n_frames, grey_in_place, prev, prev_counts,
-                        stream ? (hipStream_t)stream : c->stream, 3);
+                        stream ? (hipStream_t)stream : c->stream, 3, c->input_format);
 }
 
 extern "C" int ocvar_hip_enqueue_tracked(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride,
                                          int n_frames, int grey_in_place, const OcvarMarker* d_prev, const int* d_prev_counts, void* stream) {
     if (!c || !d_prev || !d_prev_counts) return OCVAR_E_ARG;
     return enqueue_impl(c, d_bgr, width, height, row_stride, frame_stride, n_frames, grey_in_place, d_prev, d_prev_counts,
-                        stream ? (hipStream_t)stream : c->stream, 3, true);
+                        stream ? (hipStream_t)stream : c->stream, 3, c->input_format, true);
 }
 
 extern "C" int ocvar_hip_results_to_device(OcvarHip* c, OcvarMarker* d_markers, int* d_counts, void* stream) {
@@ -639,6 +641,20 @@ extern "C" int ocvar_hip_ready(OcvarHip* c) {
 extern "C" int ocvar_hip_set_result_limit(OcvarHip* c, int max_per_frame) {
     if (!c || c->pending || max_per_frame < 1 || max_per_frame > MAXM) return OCVAR_E_ARG;
     c->result_limit = max_per_frame;
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_set_input_format(OcvarHip* c, int format) {
+    if (!c) return OCVAR_E_ARG;
+    if (input_format_bpp(format) == 0) {
+        c->err = "unknown input format";
+        return OCVAR_E_ARG;
+    }
+    if (c->pending) {
+        c->err = "the previous batch of this context has not been collected";
+        return OCVAR_E_ARG;
+    }
+    c->input_format = format;
     return OCVAR_OK;
 }
 
@@ -749,6 +765,9 @@ extern "C" int ocvar_hip_detect_host(OcvarHip* c, uint8_t* h_bgr, int width, int
                                      int n_frames, int grey_in_place, const OcvarMarker* prev, const int* prev_counts,
                                      OcvarMarker* markers, int* counts, int max_per_frame) {
     if (!c || !h_bgr || n_frames < 1 || height < 1 || row_stride < 1) return OCVAR_E_ARG;
+    if ((long long)row_stride < (long long)input_format_bpp(c->input_format) * width) return OCVAR_E_ARG;
+    // a grey frame is its own grey: no write-back kernel, no copy back, no page-locked buffers for it
+    grey_in_place = grey_in_place && c->input_format != OCVAR_FMT_GRAY;
     if (n_frames > 1 && frame_stride < (size_t)height * row_stride) return OCVAR_E_ARG;
     if (!counts || max_per_frame < 0 || (max_per_frame > 0 && !markers)) return OCVAR_E_ARG;
     if (c->pending) {
@@ -840,7 +859,8 @@ extern "C" int ocvar_hip_detect_host(OcvarHip* c, uint8_t* h_bgr, int width, int
         uint8_t* d_slot = c->d_frames + (size_t)(k & 1) * slot_bytes;
         HIP_TRY_HOST(hipStreamWaitEvent(c->stream, c->h2d_done[k & 1], 0));
         rc = enqueue_impl(c, d_slot, width, height, row_stride, frame_stride, cnt, grey_in_place,
-                          prev ? prev + (size_t)k * sub * MAXM : nullptr, prev_counts ? prev_counts + k * sub : nullptr, c->stream, 3);
+                          prev ? prev + (size_t)k * sub * MAXM : nullptr, prev_counts ? prev_counts + k * sub : nullptr, c->stream, 3,
+                          c->input_format);
         if (rc) return fail(rc);
         // while sub-batch k computes: bring sub-batch k-1's grey home, then stage sub-batch k+1 into the slot it leaves
         if (k > 0 && grey_in_place) HIP_TRY_HOST(grey_home(k - 1));
@@ -870,7 +890,8 @@ extern "C" int ocvar_hip_find_squares(OcvarHip* c, const uint8_t* h_gray, int wi
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = stage_frames(c, bgr.data(), height, width * 3, (size_t)width * height * 3, 1);
     if (rc) return rc;
-    rc = enqueue_impl(c, c->d_frames, width, height, width * 3, (size_t)width * height * 3, 1, 0, nullptr, nullptr, c->stream, 2);
+    rc = enqueue_impl(c, c->d_frames, width, height, width * 3, (size_t)width * height * 3, 1, 0, nullptr, nullptr, c->stream, 2,
+                      OCVAR_FMT_BGR);   // (the expanded image, whatever the context's input format)
     if (rc) return rc;
     rc = wait_impl(c);
     if (rc) return rc;

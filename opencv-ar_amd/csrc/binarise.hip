@@ -19,7 +19,7 @@
 // every store of the kernel is whole 64-byte sectors.  The row body exists in several instances (steady rows in groups of four
 // with the ring's position known, strips away from the image edges) so that the hot loop carries no range tests; the filters'
 // border rules at the image edges are per-lane byte selectors.
-// HBM traffic per pixel: 3 B read + 1 B grey + 2/7 B of bit plane (frame mode).
+// HBM traffic per pixel: 3 B read (4 B from a four-channel source, 1 B from a grey one) + 1 B grey + 2/7 B of bit plane (frame mode).
 // The arithmetic is the integer arithmetic of the definition, so the output is bit-identical:
 //   pyrDown  [1 4 6 4 1]^2, (v+128)>>8, BORDER_REFLECT_101        pyrUp  [1 6 1]/[4 4], (v+32)>>6, borders -1->1, n->n-1
 //   Gaussian [8 28 56 72 56 28 8]^2, (v+32768)>>16, BORDER_REPLICATE    threshold  src - mean > -8
@@ -32,6 +32,9 @@
 #endif
 #ifndef OCVAR_ROWS_AHEAD_F
 #define OCVAR_ROWS_AHEAD_F 2   // source rows a wave of the frame kernel has under way beyond the one it works on (1 .. 3)
+#endif
+#ifndef OCVAR_ROWS_AHEAD_F4
+#define OCVAR_ROWS_AHEAD_F4 1   // ... with a four-channel source: 16 bytes per lane and row; with two rows ahead its steady loop spills
 #endif
 #ifndef OCVAR_BIN_WG_WAVES
 #define OCVAR_BIN_WG_WAVES 1   // waves per workgroup of the two binarise kernels (1: a wave can take any SIMD with room for it)
@@ -153,12 +156,22 @@ struct MarchOut {
     int* err;
 };
 
+// Sources of march_unit: the caller's frame in one of the formats of include/ocvar_hip.h (OCVAR_FMT_*: frame mode, which
+// also writes the grey plane), or SRC_CROP, a crop of the frame's panelled grey plane (hd.h::gray_col).
+constexpr int SRC_CROP = 5;
+constexpr int src_bpp(int src) { return src == OCVAR_FMT_BGR || src == OCVAR_FMT_RGB ? 3 : src == OCVAR_FMT_BGRA || src == OCVAR_FMT_RGBA ? 4 : 1; }
+
 // One work unit: strip `strip` of an (sw x sh) ROI, output rows [Y0, Y1).
+// SRC: what `src` holds (above).  BGR / RGB: one 12-byte load per lane and row; BGRA / RGBA: one 16-byte load (four whole
+// pixels); GRAY and crops: one 4-byte load.
 // EDGE = false: the strip lies strictly inside the image (no lane holds a column < 0 or >= sw), so the border rules of the
 // filters and their lane masks are compiled out -- six of a 1080p frame's eight strips; a crop's strips always touch an edge.
-template <bool BGR, bool EDGE>
+template <int SRC, bool EDGE>
 __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /* crops: the ROI's first column in the frame's grey plane */, int sw, int sh, int strip, int Y0, int Y1, const MarchOut& o,
                            unsigned* stage, uint8_t* rowbuf /* LDS, 16 rows x 64 lanes */, const unsigned* tab /* LDS, start_table_entry */) {
+    constexpr bool FRAME = SRC != SRC_CROP;
+    constexpr int BPP = src_bpp(SRC);   // bytes per source pixel
+    constexpr bool FOUR = BPP == 4;
     const int lane = threadIdx.x & 63;
     const int XS = strip * SV - 4 * HL;
     const int c0 = XS + 4 * lane;
@@ -167,7 +180,7 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     const bool out_lane = lane >= HL && lane < 64 - HR && (!EDGE || c0 < sw);
     const bool needed = !EDGE || (c0 + 3 >= -16 && c0 < sw + 16);  // beyond every halo: never consumed
     const bool fast = !EDGE || (c0 >= 0 && c0 + 3 < sw);
-    const bool aligned = BGR ? ((src_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0) : true;
+    const bool aligned = FRAME ? ((src_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0) : true;
     // (wave-uniform flags as scalars: left as they are the compiler keeps them as lane masks and re-derives their negations with
     // vector instructions in every row)
     // The filters' border rules at the image's left and right edge are byte selections in the one or two lanes that hold the edge
@@ -184,9 +197,9 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     const unsigned selL = EDGE && c0 == 0 ? 0x05040504u : SEL_ID;
     const unsigned selB = EDGE && c0 + 2 == sw ? 0x07060706u : SEL_ID;
     const unsigned selR = EDGE && c0 < sw && c0 + 4 >= sw ? 0x07060706u : SEL_ID;
-    // byte offset of source column c (0 <= c < sw) in its row: 3 c in a BGR frame; in the panelled grey plane (hd.h::gray_col) the
-    // crop's column c is the frame's column x_org + c (up to 9 consecutive columns follow contiguously from any column)
-    auto col_off = [&](int c) -> unsigned { return BGR ? (unsigned)(3 * c) : gray_col(x_org + c); };
+    // byte offset of source column c (0 <= c < sw) in its row: BPP c in a frame (3 c BGR); in the panelled grey plane (hd.h::gray_col)
+    // the crop's column c is the frame's column x_org + c (up to 9 consecutive columns follow contiguously from any column)
+    auto col_off = [&](int c) -> unsigned { return FRAME ? (unsigned)(BPP * c) : gray_col(x_org + c); };
     // reflected source columns of the lanes that straddle an image edge (BORDER_REFLECT_101)
     unsigned xr0 = 0, xr1 = 0, xr2 = 0, xr3 = 0;
     if (needed && !fast) {
@@ -195,7 +208,7 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
         xr2 = col_off(reflect101(c0 + 2, sw));
         xr3 = col_off(reflect101(c0 + 3, sw));
     }
-    // Load plan: every lane loads its 4 pixels with ONE (unaligned) load per row -- 4 bytes grey, 12 bytes BGR -- also the
+    // Load plan: every lane loads its 4 pixels with ONE (unaligned) load per row -- 4 bytes grey, 12 bytes BGR, 16 BGRA -- also the
     // lanes that hold reflected columns, whose 4 (grey) bytes are then permuted.  With BORDER_REFLECT_101 a lane left of
     // column 0 holds columns -c0 .. -c0-3, a lane right of column sw-1 holds 2sw-2-c0 .. 2sw-5-c0: four contiguous source
     // pixels in reverse order; the lane that straddles the right edge (sw - c0 == 2: sw is even, c0 a multiple of 4) holds
@@ -300,28 +313,35 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
         staged = 0;
     };
 
-    // raw source words of virtual row v (3 dwords BGR / 1 dword grey for fast lanes, 4 pixels for edge lanes)
-    struct Raw { unsigned d0, d1, d2; };
+    // raw source words of virtual row v (3 dwords BGR / 4 dwords BGRA / 1 dword grey for fast lanes, 4 pixels for edge lanes)
+    struct Raw3 { unsigned d0, d1, d2; };
+    struct Raw4 { unsigned d0, d1, d2, d3; };
+    using Raw = typename std::conditional<FOUR, Raw4, Raw3>::type;
     auto fetch = [&](int v, bool inside /* 0 <= v < sh is known; only asked for when the load plan holds (steady rows) */) -> Raw {
         Raw r = {0u, 0u, 0u};
         const int rv = inside ? v : reflect101(v, sh);
         if (inside || plan) {
             const int so = wave_uniform(rv * (int)src_stride);   // (< 2^31: a frame, or rows of the grey plane from the crop's origin on)
-            if (BGR) {   // one (unaligned) buffer_load_dwordx3.  Not non-temporal: with the hint the kernel is 7 % slower alone on the GPU
+            if constexpr (BPP == 3) {   // one (unaligned) buffer_load_dwordx3.  Not non-temporal: with the hint the kernel is 7 % slower alone on the GPU
                          // (5.8 against 5.4 ms per 2048 frames: the halo columns two strips share stop hitting in the L2); the grey
                          // and mask STORES carry it (+2 % with four contexts, round 3)
                 typedef unsigned v3u __attribute__((ext_vector_type(3)));
                 const v3u d = __builtin_amdgcn_raw_buffer_load_b96(src_rs, (int)goff, so, 0);
                 r.d0 = d.x; r.d1 = d.y; r.d2 = d.z;
-            } else {     // crops: ordinary loads -- the two concentric quads of a marker give two crops over nearly the same pixels
+            } else if constexpr (FOUR) {   // one buffer_load_dwordx4: four whole pixels, a dword each
+                typedef unsigned v4u __attribute__((ext_vector_type(4)));
+                const v4u d = __builtin_amdgcn_raw_buffer_load_b128(src_rs, (int)goff, so, 0);
+                r.d0 = d.x; r.d1 = d.y; r.d2 = d.z; r.d3 = d.w;
+            } else {     // grey frames, and crops: ordinary loads -- the two concentric quads of a marker give two crops over nearly the same pixels
                 r.d0 = __builtin_amdgcn_raw_buffer_load_b32(src_rs, (int)goff, so, 0);
             }
             return r;
         }
         const uint8_t* row = src + wave_uniform64((long long)rv * src_stride);
         if (!needed) return r;
+        auto bytes4 = [](const uint8_t* p) -> unsigned { return p[0] | (p[1] << 8) | (p[2] << 16) | ((unsigned)p[3] << 24); };
         if (fast) {
-            if (BGR) {
+            if constexpr (BPP == 3) {
                 if (aligned) {
                     const unsigned* p = reinterpret_cast<const unsigned*>(row + src_off);
                     r.d0 = p[0]; r.d1 = p[1]; r.d2 = p[2];
@@ -331,27 +351,55 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
                     r.d1 = p[4] | (p[5] << 8) | (p[6] << 16) | ((unsigned)p[7] << 24);
                     r.d2 = p[8] | (p[9] << 8) | (p[10] << 16) | ((unsigned)p[11] << 24);
                 }
+            } else if constexpr (FOUR) {
+                const uint8_t* p = row + src_off;
+                if (aligned) {
+                    const unsigned* q = reinterpret_cast<const unsigned*>(p);
+                    r.d0 = q[0]; r.d1 = q[1]; r.d2 = q[2]; r.d3 = q[3];
+                } else {
+                    r.d0 = bytes4(p); r.d1 = bytes4(p + 4); r.d2 = bytes4(p + 8); r.d3 = bytes4(p + 12);
+                }
+            } else if constexpr (FRAME) {   // a grey frame: nothing beyond the lane's 4 bytes is read (the row may end there)
+                const uint8_t* p = row + src_off;
+                r.d0 = aligned ? *reinterpret_cast<const unsigned*>(p) : bytes4(p);
             } else {
                 const uintptr_t a = reinterpret_cast<uintptr_t>(row + src_off);
                 const unsigned* p = reinterpret_cast<const unsigned*>(a & ~(uintptr_t)3);
                 r.d0 = alignb(p[1], p[0], (unsigned)(a & 3));
             }
-        } else if (BGR) {  // pack the 4 reflected pixels into the same 12-byte layout
+        } else if constexpr (BPP == 3) {  // pack the 4 reflected pixels into the same 12-byte layout
             const uint8_t *p0 = row + xr0, *p1 = row + xr1, *p2 = row + xr2, *p3 = row + xr3;
             r.d0 = p0[0] | (p0[1] << 8) | (p0[2] << 16) | ((unsigned)p1[0] << 24);
             r.d1 = p1[1] | (p1[2] << 8) | (p2[0] << 16) | ((unsigned)p2[1] << 24);
             r.d2 = p2[2] | (p3[0] << 8) | (p3[1] << 16) | ((unsigned)p3[2] << 24);
+        } else if constexpr (FOUR) {      // a dword per pixel (the fourth byte is not read: its coefficient is 0)
+            const uint8_t *p0 = row + xr0, *p1 = row + xr1, *p2 = row + xr2, *p3 = row + xr3;
+            r.d0 = p0[0] | (p0[1] << 8) | (p0[2] << 16);
+            r.d1 = p1[0] | (p1[1] << 8) | (p1[2] << 16);
+            r.d2 = p2[0] | (p2[1] << 8) | (p2[2] << 16);
+            r.d3 = p3[0] | (p3[1] << 8) | (p3[2] << 16);
         } else {
             r.d0 = row[xr0] | (row[xr1] << 8) | (row[xr2] << 16) | ((unsigned)row[xr3] << 24);
         }
         return r;
     };
     auto to_grey = [&](const Raw& r) -> unsigned {
-        if (!BGR) return r.d0;
+        if constexpr (BPP == 1) return r.d0;   // (grey frames: BGR2GRAY of B = G = R = g is g)
         // (1868 B + 9617 G + 4899 R + 8192) >> 14 with everything times four: (7472 B + 38468 G + 19596 R + 32768) >> 16 -- the
         // grey value is then BYTE 2 of the sum (< 2^24), which a byte permute picks: no shift per pixel.  Coefficient halves for
-        // v_dot4_u32_u8: 7472 = 29*256+48, 38468 = 150*256+68, 19596 = 76*256+140.
-        const unsigned KH = 29u | (150u << 8) | (76u << 16), KL = 48u | (68u << 8) | (140u << 16);
+        // v_dot4_u32_u8 (hd.h::GREY_KH_BGR ...): 7472 = 29*256+48, 38468 = 150*256+68, 19596 = 76*256+140; in reverse byte order
+        // for RGB sources; 0 on byte 3 (a four-channel pixel's alpha).
+        constexpr bool REV = SRC == OCVAR_FMT_RGB || SRC == OCVAR_FMT_RGBA;
+        const unsigned KH = REV ? GREY_KH_RGB : GREY_KH_BGR, KL = REV ? GREY_KL_RGB : GREY_KL_BGR;
+        if constexpr (FOUR) {   // a dword per pixel: one dot4 pair each, no byte alignment
+            const unsigned s0 = (dot4(r.d0, KH, 0u) << 8) + dot4(r.d0, KL, 32768u);
+            const unsigned s1 = (dot4(r.d1, KH, 0u) << 8) + dot4(r.d1, KL, 32768u);
+            const unsigned s2 = (dot4(r.d2, KH, 0u) << 8) + dot4(r.d2, KL, 32768u);
+            const unsigned s3 = (dot4(r.d3, KH, 0u) << 8) + dot4(r.d3, KL, 32768u);
+            const unsigned g01 = __builtin_amdgcn_perm(s1, s0, 0x0c0c0602u);
+            const unsigned g23 = __builtin_amdgcn_perm(s3, s2, 0x0c0c0602u);
+            return g01 | (g23 << 16);
+        }
         const unsigned s0 = (dot4(r.d0, KH, 0u) << 8) + dot4(r.d0, KL, 32768u);                          // bytes b0 g0 r0 (x)
         const unsigned w1 = alignb(r.d1, r.d0, 3), w2 = alignb(r.d2, r.d1, 2);
         const unsigned s1 = (dot4(w1, KH, 0u) << 8) + dot4(w1, KL, 32768u);                              // b1 g1 r1 (x)
@@ -398,7 +446,7 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     // ~6 K resident waves have 4.7 MB in flight, which at the latency of a loaded memory system caps the frame kernel near 4 TB/s;
     // and when other contexts' kernels hold half of the wave slots the frame kernel's waves must each keep more in flight to
     // keep the memory system busy.
-    constexpr int AHEAD = BGR ? OCVAR_ROWS_AHEAD_F : OCVAR_ROWS_AHEAD_C;
+    constexpr int AHEAD = !FRAME ? OCVAR_ROWS_AHEAD_C : FOUR ? OCVAR_ROWS_AHEAD_F4 : OCVAR_ROWS_AHEAD_F;
     Raw nxt = fetch(v_first, false), nxt2 = fetch(v_first + 1, false), nxt3 = {0u, 0u, 0u}, nxt4 = {0u, 0u, 0u};
     if (AHEAD >= 2) nxt3 = fetch(v_first + 2, false);
     if (AHEAD >= 3) nxt4 = fetch(v_first + 3, false);
@@ -411,7 +459,7 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
         // requested as soon as they have been turned into grey -- into the registers they leave, so the two sets swap names
         // every row and nothing is copied (loaded before, a third set was live and the sets rotated through moves).
         unsigned g = to_grey(nxt);
-        if (BGR) asm volatile("" : "+v"(g) : : "memory");   // (keeps the load below this point, and the conversion above it)
+        if (FRAME) asm volatile("" : "+v"(g) : : "memory");   // (keeps the load below this point, and the conversion above it)
         else asm volatile("" : : : "memory");
         // (the request goes into the registers the converted row leaves: the sets swap names, nothing is copied in the unrolled loop)
         if (AHEAD == 1) {
@@ -427,7 +475,7 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
         if (EDGE && (S || plan)) g = __builtin_amdgcn_perm(g, g, gsel);   // (gsel: the identity in lanes that hold no reflected columns)
         // (a 32-bit store reads its data register as it issues: unlike the 128-bit tile stores in flush_tiles it may keep the row's
         // offset in the scalar offset field; test_planes_of_every_frame_of_a_busy_batch compares the grey plane too)
-        if (BGR && (S || (v >= Y0 && v < Y1)))   // (BGR: the frame pass, which always has a grey plane) rows [Y0,Y1) are real rows, each loaded exactly once
+        if (FRAME && (S || (v >= Y0 && v < Y1)))   // (the frame pass, which always has a grey plane) rows [Y0,Y1) are real rows, each loaded exactly once
             __builtin_amdgcn_raw_buffer_store_b32(g, gray_rs, (int)out_off, wave_uniform(v * (int)o.gray_stride), BUF_NT);
         us2 hsum;
         {   // horizontal [1 4 6 4 1] at the lane's two even columns c0 and c0+2
@@ -632,6 +680,8 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
 // a CU holds a whole workgroup less.  A one-wave workgroup takes any SIMD with 96 free registers and 6 KB of LDS.
 constexpr int BW = OCVAR_BIN_WG_WAVES;
 
+// One instance per source format (FMT: OCVAR_FMT_*); they differ in the row loads and the grey conversion only.
+template <int FMT>
 __global__ __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(OCVAR_WAVES_F, 8))) void binarise_frames_kernel(Workspace ws, const uint8_t* bgr, int row_stride, size_t frame_stride) {
     __shared__ unsigned stage[BW][MARCH_STAGE];
     __shared__ __attribute__((aligned(16))) uint8_t rowbuf[BW][16 * 64];
@@ -670,13 +720,20 @@ __global__ __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(OCVAR_W
     o.err = ws.counters + CNT_ERR;
     const int w4 = wave_uniform((int)(threadIdx.x >> 6));
     const bool edge = strip == 0 || ((ws.sw - 1 - (strip * MARCH_STRIP - 4 * MARCH_HALO_L)) >> 2) <= 63;   // march_unit's left_edge || right_edge
-    if (edge) march_unit<true, true>(bgr + (size_t)f * frame_stride, row_stride, 0, ws.sw, ws.sh, strip, Y0, Y1, o, stage[w4], rowbuf[w4], tab);
-    else march_unit<true, false>(bgr + (size_t)f * frame_stride, row_stride, 0, ws.sw, ws.sh, strip, Y0, Y1, o, stage[w4], rowbuf[w4], tab);
+    if (edge) march_unit<FMT, true>(bgr + (size_t)f * frame_stride, row_stride, 0, ws.sw, ws.sh, strip, Y0, Y1, o, stage[w4], rowbuf[w4], tab);
+    else march_unit<FMT, false>(bgr + (size_t)f * frame_stride, row_stride, 0, ws.sw, ws.sh, strip, Y0, Y1, o, stage[w4], rowbuf[w4], tab);
+}
+
+// grey of the source pixel at p in format fmt (OCVAR_FMT_*)
+__device__ __forceinline__ uint8_t grey_at(const uint8_t* p, int fmt) {
+    if (fmt == OCVAR_FMT_GRAY) return p[0];
+    const bool rev = fmt == OCVAR_FMT_RGB || fmt == OCVAR_FMT_RGBA;
+    return (uint8_t)grey_of(p[rev ? 2 : 0], p[1], p[rev ? 0 : 2]);
 }
 
 // Odd width / height: the last column / row lies outside the even working size (opencvar.cpp:158) but is still
 // greyed by cvarArMultRegistration's BGR2GRAY.
-__global__ __launch_bounds__(256) void grey_edges_kernel(Workspace ws, const uint8_t* bgr, int row_stride, size_t frame_stride) {
+__global__ __launch_bounds__(256) void grey_edges_kernel(Workspace ws, const uint8_t* bgr, int row_stride, size_t frame_stride, int fmt) {
     const int f = blockIdx.y;
     const uint8_t* src = bgr + (size_t)f * frame_stride;
     uint8_t* g = ws.gray + (size_t)f * gray_plane_bytes(ws.W, ws.H);
@@ -684,8 +741,8 @@ __global__ __launch_bounds__(256) void grey_edges_kernel(Workspace ws, const uin
     const int n_col = ws.W > ws.sw ? ws.H : 0, n_row = ws.H > ws.sh ? ws.W : 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_col + n_row; i += gridDim.x * blockDim.x) {
         const int x = i < n_col ? ws.sw : i - n_col, y = i < n_col ? i : ws.sh;
-        const uint8_t* p = src + (long long)y * row_stride + 3 * x;
-        const uint8_t v = (uint8_t)grey_of(p[0], p[1], p[2]);
+        const uint8_t* p = src + (long long)y * row_stride + src_bpp(fmt) * x;
+        const uint8_t v = grey_at(p, fmt);
         g[(long long)y * pitch + gray_col(x)] = v;
         // (a column within 8 of a panel's start is also kept at the end of the panel before: readers take the panel of a run's first column)
         if (x >= GRAY_PANEL_COLS && x % GRAY_PANEL_COLS < GRAY_PANEL_LEAD) g[(long long)y * pitch + gray_col(x - GRAY_PANEL_LEAD) + GRAY_PANEL_LEAD] = v;
@@ -693,8 +750,9 @@ __global__ __launch_bounds__(256) void grey_edges_kernel(Workspace ws, const uin
 }
 
 // The reference greys the caller's frame in place (opencvar.cpp:624-627).  Done as its own pass over the
-// grey plane so that no wave ever reads a half-written BGR pixel of a neighbouring strip's halo.
-__global__ __launch_bounds__(256) void grey_writeback_kernel(Workspace ws, uint8_t* bgr, int row_stride, size_t frame_stride) {
+// grey plane so that no wave ever reads a half-written BGR pixel of a neighbouring strip's halo.  Bytes 0..2 of a pixel take
+// the grey value, a four-channel pixel's byte 3 is left as it is; a grey frame is its own grey (not launched).
+__global__ __launch_bounds__(256) void grey_writeback_kernel(Workspace ws, uint8_t* bgr, int row_stride, size_t frame_stride, int bpp) {
     const int f = blockIdx.y;
     const uint8_t* g = ws.gray + (size_t)f * gray_plane_bytes(ws.W, ws.H);
     const int pitch = gray_pitch(ws.W);
@@ -703,7 +761,7 @@ __global__ __launch_bounds__(256) void grey_writeback_kernel(Workspace ws, uint8
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int x = (int)(i % ws.W), y = (int)(i / ws.W);
         const uint8_t v = g[(long long)y * pitch + gray_col(x)];
-        uint8_t* q = dst + (long long)y * row_stride + 3 * x;
+        uint8_t* q = dst + (long long)y * row_stride + bpp * x;
         q[0] = q[1] = q[2] = v;
     }
 }
@@ -748,20 +806,29 @@ __global__ __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(OCVAR_W
         o.n_cands = ws.counters + CNT_CROP_CANDS;
         o.cap_cands = ws.cap_crop_cands;
         o.err = ws.counters + CNT_ERR;
-        march_unit<false, true>(src, pitch, r.x0, r.sw, r.sh, td.x0, td.y0, Y1, o, stage[wave], rowbuf[wave], tab);
+        march_unit<SRC_CROP, true>(src, pitch, r.x0, r.sw, r.sh, td.x0, td.y0, Y1, o, stage[wave], rowbuf[wave], tab);
     }
 }
 
+int input_format_bpp(int format) { return format >= OCVAR_FMT_BGR && format <= OCVAR_FMT_GRAY ? src_bpp(format) : 0; }
+
 void launch_binarise_frames(const Workspace& ws, const uint8_t* d_bgr, int row_stride, size_t frame_stride, int grey_in_place,
-                            hipStream_t stream) {
+                            int format, hipStream_t stream) {
     const int units = ws.frame_strips * ws.frame_chunks * ws.n_frames;
     if (units <= 0) return;
-    hipLaunchKernelGGL(binarise_frames_kernel, dim3((units + BW - 1) / BW), dim3(64 * BW), 0, stream, ws, d_bgr, row_stride, frame_stride);
+    const dim3 grid((units + BW - 1) / BW), block(64 * BW);
+    switch (format) {
+    case OCVAR_FMT_RGB: hipLaunchKernelGGL(binarise_frames_kernel<OCVAR_FMT_RGB>, grid, block, 0, stream, ws, d_bgr, row_stride, frame_stride); break;
+    case OCVAR_FMT_BGRA: hipLaunchKernelGGL(binarise_frames_kernel<OCVAR_FMT_BGRA>, grid, block, 0, stream, ws, d_bgr, row_stride, frame_stride); break;
+    case OCVAR_FMT_RGBA: hipLaunchKernelGGL(binarise_frames_kernel<OCVAR_FMT_RGBA>, grid, block, 0, stream, ws, d_bgr, row_stride, frame_stride); break;
+    case OCVAR_FMT_GRAY: hipLaunchKernelGGL(binarise_frames_kernel<OCVAR_FMT_GRAY>, grid, block, 0, stream, ws, d_bgr, row_stride, frame_stride); break;
+    default: hipLaunchKernelGGL(binarise_frames_kernel<OCVAR_FMT_BGR>, grid, block, 0, stream, ws, d_bgr, row_stride, frame_stride); break;
+    }
     if (ws.W > ws.sw || ws.H > ws.sh)
-        hipLaunchKernelGGL(grey_edges_kernel, dim3(8, ws.n_frames), dim3(256), 0, stream, ws, d_bgr, row_stride, frame_stride);
-    if (grey_in_place)
+        hipLaunchKernelGGL(grey_edges_kernel, dim3(8, ws.n_frames), dim3(256), 0, stream, ws, d_bgr, row_stride, frame_stride, format);
+    if (grey_in_place && format != OCVAR_FMT_GRAY)
         hipLaunchKernelGGL(grey_writeback_kernel, dim3(1024, ws.n_frames), dim3(256), 0, stream, ws, const_cast<uint8_t*>(d_bgr),
-                           row_stride, frame_stride);
+                           row_stride, frame_stride, src_bpp(format));
 }
 
 void launch_binarise_crops(const Workspace& ws, hipStream_t stream) {

@@ -26,6 +26,13 @@ OCVAR_HD int dir_dy(int s) { return (s >= 1 && s <= 3) ? -1 : ((s >= 5 && s <= 7
 
 struct Pt { int x, y; };
 
+// BGR2GRAY, (1868 B + 9617 G + 4899 R + 8192) >> 14, as the frame kernel computes it: times four, (7472 B + 38468 G + 19596 R
+// + 32768) >> 16, with each coefficient split into a high and a low byte for v_dot4_u32_u8 -- the grey value is byte 2 of
+// (dot4(pixel, KH) << 8) + dot4(pixel, KL) + 32768.  One word per byte order of the source pixel (B G R x / R G B x); byte 3
+// is 0, so a four-channel pixel's fourth byte does not count.  (tests/test_input_formats_cpu.py checks all 2^24 pixels.)
+constexpr unsigned GREY_KH_BGR = 29u | (150u << 8) | (76u << 16), GREY_KL_BGR = 48u | (68u << 8) | (140u << 16);
+constexpr unsigned GREY_KH_RGB = 76u | (150u << 8) | (29u << 16), GREY_KL_RGB = 140u | (68u << 8) | (48u << 16);
+
 // The neighbour plane of a binary image (sw x sh, row stride ns: sw rounded up to a multiple of 16).
 //
 // Host-side test build of the cores: one byte per pixel, raster rows, the 8-neighbour mask (bit s = the neighbour in

@@ -113,9 +113,13 @@ struct Workspace {
     int* counters;          // [CNT_COUNT]
 };
 
+// bytes per pixel of an input format (OCVAR_FMT_*: 3, 3, 4, 4, 1), 0 for anything else
+int input_format_bpp(int format);
+
 // launchers (each enqueues on `stream`, no synchronisation)
+// d_bgr holds frames in `format` (OCVAR_FMT_*); grey_in_place is not launched for OCVAR_FMT_GRAY (nothing to write)
 void launch_binarise_frames(const Workspace& ws, const uint8_t* d_bgr, int row_stride, size_t frame_stride, int grey_in_place,
-                            hipStream_t stream);
+                            int format, hipStream_t stream);
 void launch_binarise_crops(const Workspace& ws, hipStream_t stream);
 void launch_ring_quads_frames(const Workspace& ws, hipStream_t stream);   // the ROIs' own frame borders without a walk (before tier 1)
 void launch_ring_quads_crops(const Workspace& ws, hipStream_t stream);

@@ -231,6 +231,17 @@ extern "C" int ocvar_hip_pipe_collect(OcvarPipe* p, long long* tag, OcvarMarker*
     return p->counts_in_flight[i];
 }
 
+extern "C" int ocvar_hip_pipe_set_input_format(OcvarPipe* p, int format) {
+    if (!p) return OCVAR_E_ARG;
+    if (p->head != p->tail) { p->err = "a submitted chunk is in flight: collect it first"; return OCVAR_E_ARG; }
+    if (format < OCVAR_FMT_BGR || format > OCVAR_FMT_GRAY) { p->err = "unknown input format"; return OCVAR_E_ARG; }
+    for (OcvarHip* c : p->ctx) {
+        const int rc = ocvar_hip_set_input_format(c, format);
+        if (rc) { p->err = ocvar_hip_last_error(c); return rc; }
+    }
+    return OCVAR_OK;
+}
+
 extern "C" int ocvar_hip_pipe_set_result_limit(OcvarPipe* p, int max_per_frame) {
     if (!p || p->head != p->tail || max_per_frame < 1 || max_per_frame > OCVAR_MAX_MARKERS) return OCVAR_E_ARG;
     for (OcvarHip* c : p->ctx) {

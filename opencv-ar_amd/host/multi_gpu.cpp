@@ -14,6 +14,7 @@
 
 struct OcvarMulti {
     int n = 0, max_local = 0;
+    int format = OCVAR_FMT_BGR;       // input format of every context (ocvar_multi_set_input_format)
     std::vector<int> dev;
     std::vector<OcvarHip*> ctx;
     std::vector<ncclComm_t> comm;
@@ -138,6 +139,17 @@ extern "C" int ocvar_multi_set_camera(OcvarMulti* m, const OcvarCamera* cam) {
         const int rc = ocvar_hip_set_camera(m->ctx[d], cam);
         if (rc) { m->err = ocvar_hip_last_error(m->ctx[d]); return rc; }
     }
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_multi_set_input_format(OcvarMulti* m, int format) {
+    if (!m) return OCVAR_E_ARG;
+    if (format < OCVAR_FMT_BGR || format > OCVAR_FMT_GRAY) { m->err = "unknown input format"; return OCVAR_E_ARG; }
+    for (int d = 0; d < m->n; d++) {
+        const int rc = ocvar_hip_set_input_format(m->ctx[d], format);
+        if (rc) { m->err = ocvar_hip_last_error(m->ctx[d]); return rc; }
+    }
+    m->format = format;
     return OCVAR_OK;
 }
 
@@ -277,7 +289,9 @@ extern "C" int ocvar_multi_track_host(OcvarMulti* m, const uint8_t* h_bgr, int w
 // each device's stream
 static int multi_stage_host(OcvarMulti* m, const uint8_t* h_bgr, int width, int height, int row_stride, size_t frame_stride, int n_frames,
                             std::vector<int>& n_local_out) {
-    if (!m || !h_bgr || n_frames < 1 || n_frames > m->n * m->max_local || height < 1 || row_stride < 3 * width) return OCVAR_E_ARG;
+    if (!m || !h_bgr || n_frames < 1 || n_frames > m->n * m->max_local || height < 1) return OCVAR_E_ARG;
+    const int bpp = m->format == OCVAR_FMT_GRAY ? 1 : (m->format == OCVAR_FMT_BGRA || m->format == OCVAR_FMT_RGBA ? 4 : 3);
+    if ((long long)row_stride < (long long)bpp * width) return OCVAR_E_ARG;
     if (n_frames > 1 && frame_stride < (size_t)height * row_stride) return OCVAR_E_ARG;
     const int N = m->n;
     const size_t fb = (size_t)height * row_stride;
