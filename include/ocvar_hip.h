@@ -58,7 +58,8 @@ enum {
  * OCVAR_MAX_TEMPLATE_SIZES distinct (width, height) code sizes; ocvar_hip_set_templates returns OCVAR_E_ARG beyond either.
  * Identical templates and rotationally symmetric codes are allowed, as in the reference. */
 enum { OCVAR_MAX_TEMPLATES = 4096, OCVAR_MAX_TEMPLATE_SIZES = 16, OCVAR_MAX_QUADS = 256, OCVAR_MAX_MARKERS = 64,
-       OCVAR_MAX_QUADS_EX = 1792 /* most squares per frame a context can be created for (ocvar_hip_create_ex) */ };
+       OCVAR_MAX_QUADS_EX = 1792 /* most squares per frame a context can be created for (ocvar_hip_create_ex) */,
+       OCVAR_MAX_QUADS_DENSE = 16384, OCVAR_MAX_MARKERS_DENSE = 4096 /* limits of ocvar_hip_create_dense */ };
 
 /* Creates a context on `device` with workspace for batches of up to max_batch frames of up to
  * max_width x max_height pixels. */
@@ -67,10 +68,26 @@ int ocvar_hip_create(OcvarHip** ctx, int device, int max_width, int max_height, 
  * reference's square list is unbounded (opencvar.cpp:187-214); a caller that gets OCVAR_E_CAPACITY with flag 4 (squares)
  * repeats the frame on such a context (the host mirror of cvarArMultRegistration / cvarFindSquares does). */
 int ocvar_hip_create_ex(OcvarHip** ctx, int device, int max_width, int max_height, int max_batch, int max_quads);
+/* A dense context: room for max_quads (1 .. OCVAR_MAX_QUADS_DENSE) frame-pass squares and max_markers (1 ..
+ * OCVAR_MAX_MARKERS_DENSE) markers per frame, tracked plus new -- the reference bounds neither (opencvar.cpp:187-214, 619-807).
+ * OCVAR_E_ARG outside those ranges, checked before any device call.  The per-frame tail runs in scalable kernels (a sort of
+ * the squares in place of an O(n^2) rank, a sparse replay of the tracking loop, global workspace in place of LDS); results are
+ * those of any other context.  The marker stride M of every [n][M] array below is max_markers (ocvar_hip_max_markers).
+ * Footprint per frame of max_batch, with W x H = max_width x max_height, Q = max_quads, M = max_markers: device ~480 Q bytes
+ * (square lists, crop records, the dense tail's sort / grid / replay arrays) + 380 M bytes (prev, reserve, markers, pose jobs)
+ * + a crop pool of 4 (W + 16) (H + 8) bytes (four times a default context's: crops of neighbouring squares overlap) + W H / 128
+ * bytes (tracking grid) + the per-square decode tables of ocvar_hip_set_templates (8 bytes per template size class and 4 per
+ * match of the library, per square); pinned host 368 M bytes (result and `prev` staging).  At 4K with Q = 16384, M = 4096:
+ * ~43 MB of device memory and 1.5 MB pinned per frame, besides the frame planes every context holds. */
+int ocvar_hip_create_dense(OcvarHip** ctx, int device, int max_width, int max_height, int max_batch, int max_quads, int max_markers);
+/* The context's marker stride M: max_markers of ocvar_hip_create_dense, OCVAR_MAX_MARKERS on a context made by
+ * ocvar_hip_create / ocvar_hip_create_ex.  OCVAR_E_ARG for NULL. */
+int ocvar_hip_max_markers(const OcvarHip* ctx);
 void ocvar_hip_destroy(OcvarHip* ctx);
 const char* ocvar_hip_last_error(const OcvarHip* ctx);
 /* Flag word of the last call that failed with OCVAR_E_CAPACITY: 1 start lists, 2 point pool, 4 squares / candidates per
- * frame, 8 trace overrun, 16 crops, 32 crop tiles, 64 work-queue runaway, 128 markers per frame.  0 after a good call. */
+ * frame, 8 trace overrun, 16 crops, 32 crop tiles, 64 work-queue runaway, 128 markers per frame (more than the context's
+ * M = ocvar_hip_max_markers).  0 after a good call. */
 int ocvar_hip_capacity_flags(const OcvarHip* ctx);
 
 /* Several contexts in flight on one GPU (each with its own stream) overlap the latency-bound border followers of one batch
@@ -112,8 +129,8 @@ int ocvar_hip_set_input_format(OcvarHip* ctx, int format);
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart
  *   grey_in_place non-zero: overwrite each frame with its grey version (the reference's side effect,
  *                opencvar.cpp:624-627)
- *   prev / prev_counts  host arrays [n_frames][OCVAR_MAX_MARKERS] and [n_frames] of the previous call's
- *                markers per stream, or NULL for stateless detection
+ *   prev / prev_counts  host arrays [n_frames][M] (M = ocvar_hip_max_markers(ctx): OCVAR_MAX_MARKERS unless the context
+ *                is dense) and [n_frames] of the previous call's markers per stream, or NULL for stateless detection
  *   markers / counts    host outputs [n_frames][max_per_frame] and [n_frames]; counts[f] is the reference's
  *                return value for frame f (may exceed max_per_frame; only the first max_per_frame are stored)
  * ocvar_hip_detect_device = enqueue + wait + copy-out.  The enqueue/collect pair lets a caller time or
@@ -124,8 +141,8 @@ int ocvar_hip_detect_device(OcvarHip* ctx, uint8_t* d_bgr, int width, int height
 int ocvar_hip_enqueue(OcvarHip* ctx, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride,
                       int n_frames, int grey_in_place, const OcvarMarker* prev, const int* prev_counts, void* stream);
 int ocvar_hip_collect(OcvarHip* ctx, OcvarMarker* markers, int* counts, int max_per_frame);
-/* ocvar_hip_enqueue with the previous markers in DEVICE memory: d_prev [n_frames][OCVAR_MAX_MARKERS], d_prev_counts [n_frames]
- * (counts above OCVAR_MAX_MARKERS are read as OCVAR_MAX_MARKERS), e.g. the block ocvar_hip_results_to_device wrote for the
+/* ocvar_hip_enqueue with the previous markers in DEVICE memory: d_prev [n_frames][M], d_prev_counts [n_frames]
+ * (M = ocvar_hip_max_markers(ctx); counts above M are read as M), e.g. the block ocvar_hip_results_to_device wrote for the
  * same streams one time step earlier -- the tracking state of a block of video streams (the caller-owned `markers` vector of
  * cvarArMultRegistration, /root/reference/src/opencvar.cpp:635-668, samples/ARTest.cpp:57) then never leaves the device.
  * The copy into the context is stream-ordered: the arrays may be overwritten by ocvar_hip_results_to_device of the same
@@ -135,7 +152,7 @@ int ocvar_hip_enqueue_tracked(OcvarHip* ctx, uint8_t* d_bgr, int width, int heig
 /* 1 if the enqueued batch has finished (ocvar_hip_collect will not wait), 0 if it is still running, < 0 on error or when
  * nothing is enqueued.  A caller with several contexts in flight collects the one that is ready first. */
 int ocvar_hip_ready(OcvarHip* ctx);
-/* How many marker records per frame a batch brings to the host (1 .. OCVAR_MAX_MARKERS, the default): the copy-out of a
+/* How many marker records per frame a batch brings to the host (1 .. M = ocvar_hip_max_markers(ctx), the default): the copy-out of a
  * 2048-frame batch is 24 MB at 64 records per frame, 3 MB at 8.  ocvar_hip_collect returns at most this many per frame;
  * the counts are always the frames' full counts. */
 int ocvar_hip_set_result_limit(OcvarHip* ctx, int max_per_frame);
@@ -162,10 +179,10 @@ const char* ocvar_hip_build_info(void);
 void* ocvar_hip_stream(const OcvarHip* ctx);
 
 /* After ocvar_hip_enqueue: stream-ordered device-to-device copy of the batch's results into caller-owned device
- * buffers, d_markers [n_frames][OCVAR_MAX_MARKERS] and d_counts [n_frames] -- for callers that gather results
+ * buffers, d_markers [n_frames][M] (M = ocvar_hip_max_markers(ctx)) and d_counts [n_frames] -- for callers that gather results
  * across GPUs (RCCL) before any host copy.  Does not wait; ocvar_hip_collect must still be called. */
 int ocvar_hip_results_to_device(OcvarHip* ctx, OcvarMarker* d_markers, int* d_counts, void* stream);
-/* Same with a narrower block: d_markers [n_frames][max_per_frame] (1 <= max_per_frame <= OCVAR_MAX_MARKERS) holds the first
+/* Same with a narrower block: d_markers [n_frames][max_per_frame] (1 <= max_per_frame <= M) holds the first
  * max_per_frame records of every frame; d_counts still carries the frames' full counts, so a frame with more markers than
  * the block keeps is visible to the receiver.  A gather of 8 records per frame moves 1/8 of the bytes over xGMI. */
 int ocvar_hip_results_to_device_ex(OcvarHip* ctx, OcvarMarker* d_markers, int* d_counts, int max_per_frame, void* stream);

@@ -18,10 +18,11 @@ SYNTH_LIB = os.path.join(LIB_DIR, "libocvar_synth.so")
 HOST_LIB = os.path.join(LIB_DIR, "libopencv-ar.so.1.0.0")
 
 MAX_TEMPLATES, MAX_TEMPLATE_SIZES, MAX_QUADS, MAX_MARKERS = 4096, 16, 256, 64
+MAX_QUADS_EX, MAX_QUADS_DENSE, MAX_MARKERS_DENSE = 1792, 16384, 4096   # ocvar_hip_create_ex / ocvar_hip_create_dense limits
 
 # every symbol include/ocvar_hip.h declares
 HIP_SYMBOLS = [
-    "ocvar_hip_create", "ocvar_hip_create_ex", "ocvar_hip_capacity_flags", "ocvar_hip_gate_create", "ocvar_hip_gate_destroy", "ocvar_hip_set_gate", "ocvar_hip_ready", "ocvar_hip_set_result_limit",
+    "ocvar_hip_create", "ocvar_hip_create_ex", "ocvar_hip_create_dense", "ocvar_hip_max_markers", "ocvar_hip_capacity_flags", "ocvar_hip_gate_create", "ocvar_hip_gate_destroy", "ocvar_hip_set_gate", "ocvar_hip_ready", "ocvar_hip_set_result_limit",
     "ocvar_hip_pipe_create", "ocvar_hip_pipe_destroy", "ocvar_hip_pipe_last_error", "ocvar_hip_pipe_set_templates", "ocvar_hip_pipe_set_camera",
     "ocvar_hip_pipe_detect_device", "ocvar_hip_pipe_track_device", "ocvar_hip_pipe_submit", "ocvar_hip_pipe_collect", "ocvar_hip_pipe_in_flight", "ocvar_hip_pipe_set_result_limit", "ocvar_hip_set_input_format", "ocvar_hip_pipe_set_input_format", "ocvar_hip_enqueue_tracked", "ocvar_hip_build_info", "ocvar_hip_set_tuning", "ocvar_hip_destroy", "ocvar_hip_last_error", "ocvar_hip_set_templates", "ocvar_hip_set_camera",
     "ocvar_hip_detect_device", "ocvar_hip_enqueue", "ocvar_hip_collect", "ocvar_hip_detect_host", "ocvar_hip_find_squares",
@@ -104,6 +105,8 @@ def hip_lib():
         lib = C.CDLL(HIP_LIB)
         vp, i, sz = C.c_void_p, C.c_int, C.c_size_t
         lib.ocvar_hip_create.argtypes = [C.POINTER(vp), i, i, i, i]
+        lib.ocvar_hip_create_dense.argtypes = [C.POINTER(vp), i, i, i, i, i, i]
+        lib.ocvar_hip_max_markers.argtypes = [vp]
         lib.ocvar_hip_destroy.argtypes = [vp]
         lib.ocvar_hip_gate_create.argtypes = [C.POINTER(vp), i, i]
         lib.ocvar_hip_gate_destroy.argtypes = [vp]
@@ -320,20 +323,35 @@ def build_info():
 
 
 class Detector:
-    """A device context: batches of frames -> CvarMarker arrays (cvarArMultRegistration semantics per frame)."""
+    """A device context: batches of frames -> CvarMarker arrays (cvarArMultRegistration semantics per frame).
+
+    max_quads / max_markers (either one): a dense context (ocvar_hip_create_dense) with room for that many frame-pass squares
+    (1 .. MAX_QUADS_DENSE, default MAX_QUADS) and markers (1 .. MAX_MARKERS_DENSE, default MAX_MARKERS) per frame.  Result
+    arrays and `prev` blocks are [n, det.max_markers]."""
 
     input_format = INPUT_FORMATS["bgr"]   # what the frames hold (set_input_format)
+    max_markers = MAX_MARKERS             # the context's marker stride M (ocvar_hip_max_markers)
+    max_quads = MAX_QUADS                 # squares per frame find_squares / debug_frame_quads bring back
 
-    def __init__(self, max_width, max_height, max_batch=1, device=0):
+    def __init__(self, max_width, max_height, max_batch=1, device=0, max_quads=None, max_markers=None):
         self._lib = hip_lib()
         self._ctx = C.c_void_p()
-        rc = self._lib.ocvar_hip_create(C.byref(self._ctx), device, max_width, max_height, max_batch)
+        dense = max_quads is not None or max_markers is not None
+        if dense:
+            q = MAX_QUADS if max_quads is None else int(max_quads)
+            m = MAX_MARKERS if max_markers is None else int(max_markers)
+            rc = self._lib.ocvar_hip_create_dense(C.byref(self._ctx), device, max_width, max_height, max_batch, q, m)
+        else:
+            rc = self._lib.ocvar_hip_create(C.byref(self._ctx), device, max_width, max_height, max_batch)
         if rc != 0:
-            msg = self._lib.ocvar_hip_last_error(self._ctx).decode() if self._ctx else "no gfx950 device"
+            msg = self._lib.ocvar_hip_last_error(self._ctx).decode() if self._ctx else "no gfx950 device or bad arguments"
             if self._ctx:
                 self._lib.ocvar_hip_destroy(self._ctx)
                 self._ctx = C.c_void_p()
-            raise OcvarError(f"ocvar_hip_create failed ({rc}): {msg}")
+            raise OcvarError(f"{'ocvar_hip_create_dense' if dense else 'ocvar_hip_create'} failed ({rc}): {msg}")
+        if dense:
+            self.max_quads = q
+            self.max_markers = self._lib.ocvar_hip_max_markers(self._ctx)
         self.max_batch = max_batch
         self.n_templates = 0
 
@@ -360,14 +378,14 @@ class Detector:
     def set_camera(self, camera):
         self._check(self._lib.ocvar_hip_set_camera(self._ctx, C.byref(camera)), "set_camera")
 
-    @staticmethod
-    def _prev_arrays(prev, n_frames):
+    def _prev_arrays(self, prev, n_frames):
         if prev is None:
             return None, None
-        pm = np.zeros((n_frames, MAX_MARKERS), MARKER_DTYPE)
+        M = self.max_markers
+        pm = np.zeros((n_frames, M), MARKER_DTYPE)
         pc = np.zeros(n_frames, np.int32)
         for f, lst in enumerate(prev):
-            pc[f] = min(len(lst), MAX_MARKERS)
+            pc[f] = min(len(lst), M)
             for k in range(pc[f]):
                 pm[f, k] = lst[k]
         return pm, pc
@@ -382,7 +400,18 @@ class Detector:
                                                 int(grey_in_place), _ptr(pm), _ptr(pc), stream), "enqueue")
         self._n = n_frames
 
-    def collect(self, max_per_frame=MAX_MARKERS):
+    def enqueue_tracked(self, d_ptr, width, height, n_frames, d_prev_ptr, d_prev_counts_ptr, row_stride=None, frame_stride=None,
+                        grey_in_place=False, stream=None):
+        """enqueue with the previous markers in device memory: d_prev [n_frames, max_markers] records, d_prev_counts [n_frames]
+        (ocvar_hip_enqueue_tracked); collect() as after enqueue_device"""
+        row_stride = row_stride or FORMAT_BPP[self.input_format] * width
+        frame_stride = frame_stride or row_stride * height
+        self._check(self._lib.ocvar_hip_enqueue_tracked(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames,
+                                                        int(grey_in_place), d_prev_ptr, d_prev_counts_ptr, stream), "enqueue_tracked")
+        self._n = n_frames
+
+    def collect(self, max_per_frame=None):
+        max_per_frame = self.max_markers if max_per_frame is None else max_per_frame
         n = self._n
         markers = np.zeros((n, max_per_frame), MARKER_DTYPE)
         counts = np.zeros(n, np.int32)
@@ -397,7 +426,7 @@ class Detector:
         return rc == 1
 
     def set_result_limit(self, max_per_frame):
-        """marker records per frame a batch brings to the host (default MAX_MARKERS); counts stay the full counts"""
+        """marker records per frame a batch brings to the host (1 .. max_markers, the default); counts stay the full counts"""
         self._check(self._lib.ocvar_hip_set_result_limit(self._ctx, max_per_frame), "set_result_limit")
 
     def set_input_format(self, fmt):
@@ -419,20 +448,23 @@ class Detector:
         self._check(self._lib.ocvar_hip_set_gate(self._ctx, gate._g if gate is not None else None), "set_gate")
         self._gate = gate
 
-    def results_to_device(self, d_markers_ptr, d_counts_ptr, stream=None, per_frame=MAX_MARKERS):
+    def results_to_device(self, d_markers_ptr, d_counts_ptr, stream=None, per_frame=None):
         """Copies the enqueued batch's [n][per_frame] marker records (the first per_frame of every frame) and [n] full counts
-        into caller-owned device buffers (stream-ordered), e.g. torch tensors handed to an RCCL gather."""
+        into caller-owned device buffers (stream-ordered), e.g. torch tensors handed to an RCCL gather (default per_frame:
+        max_markers)."""
+        per_frame = self.max_markers if per_frame is None else per_frame
         self._check(self._lib.ocvar_hip_results_to_device_ex(self._ctx, d_markers_ptr, d_counts_ptr, per_frame, stream), "results_to_device")
 
     def detect_device(self, d_ptr, width, height, n_frames, **kw):
-        max_per_frame = kw.pop("max_per_frame", MAX_MARKERS)
+        max_per_frame = kw.pop("max_per_frame", None)
         self.enqueue_device(d_ptr, width, height, n_frames, **kw)
         return self.collect(max_per_frame)
 
-    def detect_host(self, frames, grey_in_place=False, prev=None, max_per_frame=MAX_MARKERS):
+    def detect_host(self, frames, grey_in_place=False, prev=None, max_per_frame=None):
         """frames: uint8 array (C-contiguous) [n, H, W, 3] (bgr, rgb), [n, H, W, 4] (bgra, rgba) or [n, H, W] (gray), as the
         input format says.  Greyed in place when asked (reference side effect; a gray frame is left as it is)."""
         assert frames.dtype == np.uint8 and frames.flags.c_contiguous
+        max_per_frame = self.max_markers if max_per_frame is None else max_per_frame
         n, h, w = frame_shape_bpp(frames.shape, self.input_format)
         bpp = FORMAT_BPP[self.input_format]
         markers = np.zeros((n, max_per_frame), MARKER_DTYPE)
@@ -447,11 +479,12 @@ class Detector:
     def find_squares(self, gray):
         g = np.ascontiguousarray(gray, dtype=np.uint8)
         h, w = g.shape
-        quads = np.zeros((MAX_QUADS, 4, 2), np.int32)
+        mq = self.max_quads
+        quads = np.zeros((mq, 4, 2), np.int32)
         n = C.c_int(0)
-        self._check(self._lib.ocvar_hip_find_squares(self._ctx, _ptr(g), w, h, w, _ptr(quads), MAX_QUADS, C.byref(n)),
+        self._check(self._lib.ocvar_hip_find_squares(self._ctx, _ptr(g), w, h, w, _ptr(quads), mq, C.byref(n)),
                     "find_squares")
-        return quads[:min(n.value, MAX_QUADS)].copy(), n.value
+        return quads[:min(n.value, mq)].copy(), n.value
 
     # parity hooks
     def debug_gray(self, frame, width, height):

@@ -82,14 +82,32 @@ static int dev_alloc(OcvarHip* c, T** p, size_t n) {
     return OCVAR_OK;
 }
 
+static int create_impl(OcvarHip** out, int device, int max_width, int max_height, int max_batch, int max_quads, int max_markers,
+                       bool dense);
+
 extern "C" int ocvar_hip_create(OcvarHip** out, int device, int max_width, int max_height, int max_batch) {
     return ocvar_hip_create_ex(out, device, max_width, max_height, max_batch, OCVAR_MAX_QUADS);
 }
 
 extern "C" int ocvar_hip_create_ex(OcvarHip** out, int device, int max_width, int max_height, int max_batch, int max_quads) {
+    if (max_quads < 1 || max_quads > OCVAR_MAX_QUADS_EX) return OCVAR_E_ARG;
+    return create_impl(out, device, max_width, max_height, max_batch, max_quads, OCVAR_MAX_MARKERS, false);
+}
+
+extern "C" int ocvar_hip_create_dense(OcvarHip** out, int device, int max_width, int max_height, int max_batch, int max_quads,
+                                      int max_markers) {
+    // (the arguments are checked before any device call)
+    if (max_quads < 1 || max_quads > OCVAR_MAX_QUADS_DENSE || max_markers < 1 || max_markers > OCVAR_MAX_MARKERS_DENSE) return OCVAR_E_ARG;
+    return create_impl(out, device, max_width, max_height, max_batch, max_quads, max_markers, true);
+}
+
+extern "C" int ocvar_hip_max_markers(const OcvarHip* c) { return c ? c->ws.maxm : OCVAR_E_ARG; }
+
+static int create_impl(OcvarHip** out, int device, int max_width, int max_height, int max_batch, int max_quads, int max_markers,
+                       bool dense) {
     // (corner points travel packed as x | y << 16 through the follower tiers: coordinates stay below 2^15)
     if (!out || max_width < 16 || max_height < 16 || max_width > 32767 || max_height > 32767 || max_batch < 1 || max_quads < 1 ||
-        max_quads > OCVAR_MAX_QUADS_EX)
+        max_markers < 1)
         return OCVAR_E_ARG;
     *out = nullptr;
     int ndev = 0;
@@ -112,12 +130,16 @@ extern "C" int ocvar_hip_create_ex(OcvarHip** out, int device, int max_width, in
     w.max_h = max_height;
     w.max_batch = max_batch;
     w.maxq = max_quads;
-    const size_t B = (size_t)max_batch, WH = (size_t)max_width * max_height;
+    w.maxm = max_markers;
+    w.dense = dense ? 1 : 0;
+    c->result_limit = max_markers;
+    const size_t B = (size_t)max_batch, WH = (size_t)max_width * max_height, M = (size_t)max_markers;
     size_t per_frame_cands = WH / 16 < 16384 ? 16384 : WH / 16;
     w.cap_frame_cands = (int)std::min<size_t>(B * per_frame_cands, (size_t)1 << 30);
     w.cap_crop_cands = w.cap_frame_cands;
     w.cap_crop_rois = (int)(B * max_quads);
-    w.cap_crop_tiles = (int)std::min<size_t>(B * 4096, (size_t)1 << 30);
+    // (dense contexts: a crop of a marker-sized square is one or two work units; room for four per square)
+    w.cap_crop_tiles = (int)std::min<size_t>(B * (dense ? std::max<size_t>(4096, 4 * (size_t)max_quads) : 4096), (size_t)1 << 30);
     w.cap_crop_quads = (int)(B * max_quads * 4);
     // only tier-2 borders with more corner points than a lane slab holds land here; the fixed part lets a small context take
     // a pathological frame (full-frame noise: thousands of long ragged borders)
@@ -125,6 +147,9 @@ extern "C" int ocvar_hip_create_ex(OcvarHip** out, int device, int max_width, in
     // (bytes of the crops' bit planes: a crop's plane is at most half the bytes of its neighbour-mask byte plane, ns x (sh
     // rounded up to 8), which this pool was sized for at 2 B (W + 16) (H + 8) bytes)
     w.cap_crop_pixels = (long long)(B * (size_t)(max_width + 16) * (max_height + 8));
+    // (a dense grid of squares covers the frame with crops that overlap their neighbours' -- each crop reaches 5 px past its
+    // square and rounds up to whole 16 x 14 tiles: room for four times the frame's plane)
+    if (dense) w.cap_crop_pixels *= 4;
     int rc;
     if ((rc = dev_alloc(c, &w.gray, B * (size_t)gray_plane_bytes(max_width, max_height)))) return rc;   // (panels: hd.h::gray_col)
     if ((rc = dev_alloc(c, &w.nbr_frame, B * (size_t)nbr_plane_bytes(((max_width & ~1) + 15) & ~15, max_height & ~1)))) return rc;
@@ -157,12 +182,25 @@ extern "C" int ocvar_hip_create_ex(OcvarHip** out, int device, int max_width, in
     if ((rc = dev_alloc(c, &w.ring_frame, B))) return rc;
     if ((rc = dev_alloc(c, &w.ring_crop, (size_t)w.cap_crop_rois))) return rc;
     if ((rc = dev_alloc(c, &w.sq_recs, B * max_quads))) return rc;   // (sq_codes, sq_match: ocvar_hip_set_templates)
-    if ((rc = dev_alloc(c, &w.prev, B * MAXM))) return rc;
+    if ((rc = dev_alloc(c, &w.prev, B * M))) return rc;
     if ((rc = dev_alloc(c, &w.n_prev, B))) return rc;
-    if ((rc = dev_alloc(c, &w.reserve, B * MAXM))) return rc;
+    if ((rc = dev_alloc(c, &w.reserve, B * M))) return rc;
     if ((rc = dev_alloc(c, &w.n_reserve, B))) return rc;
-    if ((rc = dev_alloc(c, &w.markers, B * MAXM))) return rc;
-    if ((rc = dev_alloc(c, &w.pose_jobs, B * MAXM))) return rc;
+    if ((rc = dev_alloc(c, &w.markers, B * M))) return rc;
+    if ((rc = dev_alloc(c, &w.pose_jobs, B * M))) return rc;
+    if (dense) {   // the scalable tail (follow.hip: order_sort .. crops_kernel; decode.hip: finalise_kernel<true>)
+        const int nc = track_grid_cells(max_width, max_height, &w.track_gw, &w.track_gh);
+        w.decode_slices = std::max(4, std::min(64, max_quads / 64));   // (4: decode.hip DECODE_SLICES)
+        for (w.order_chunk = 2; w.order_chunk < max_quads && w.order_chunk < ORDER_CHUNK;) w.order_chunk <<= 1;
+        if ((rc = dev_alloc(c, &w.sorted_starts, B * max_quads))) return rc;
+        if ((rc = dev_alloc(c, &w.sq_tmp, B * max_quads * 8))) return rc;
+        if ((rc = dev_alloc(c, &w.trk_cells, B * (nc + 1)))) return rc;
+        if ((rc = dev_alloc(c, &w.trk_fill, B * nc))) return rc;
+        if ((rc = dev_alloc(c, &w.trk_items, B * 4 * max_quads))) return rc;
+        if ((rc = dev_alloc(c, &w.trk_next, B * (max_quads + 1)))) return rc;
+        if ((rc = dev_alloc(c, &w.surv, B * max_quads))) return rc;
+        if ((rc = dev_alloc(c, &w.src, B * M))) return rc;
+    }
     if ((rc = dev_alloc(c, &w.n_markers, B))) return rc;
     if ((rc = dev_alloc(c, &w.templates, (size_t)MAXT))) return rc;
     if ((rc = dev_alloc(c, &w.sizes, (size_t)MAX_SIZE_CLASSES))) return rc;
@@ -175,9 +213,9 @@ extern "C" int ocvar_hip_create_ex(OcvarHip** out, int device, int max_width, in
     w.crop_pixels = reinterpret_cast<unsigned long long*>(w.counters + CNT_CROP_PIXELS);
     HIP_TRY(c, hipMemset(w.n_prev, 0, B * sizeof(int)));
     HIP_TRY(c, hipMemset(w.counters, 0, CNT_COUNT * sizeof(int)));
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_markers, B * MAXM * sizeof(MarkerRec)));
+    HIP_TRY(c, hipHostMalloc((void**)&c->h_markers, B * M * sizeof(MarkerRec)));
     HIP_TRY(c, hipHostMalloc((void**)&c->h_counts, B * sizeof(int)));
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_prev, B * MAXM * sizeof(MarkerRec)));
+    HIP_TRY(c, hipHostMalloc((void**)&c->h_prev, B * M * sizeof(MarkerRec)));
     HIP_TRY(c, hipHostMalloc((void**)&c->h_prev_counts, B * sizeof(int)));
     HIP_TRY(c, hipHostMalloc((void**)&c->h_counters, CNT_COUNT * sizeof(int)));
     return OCVAR_OK;
@@ -438,14 +476,14 @@ static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int 
     HIP_TRY(c, hipMemsetAsync(w.n_quads_frame, 0, n_frames * sizeof(int), s));
     if (prev && prev_counts && prev_on_device) {
         // the previous step's markers never left the device (ocvar_hip_enqueue_tracked: streams of a tracker)
-        HIP_TRY(c, hipMemcpyAsync(w.prev, prev, (size_t)n_frames * MAXM * sizeof(MarkerRec), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(w.prev, prev, (size_t)n_frames * w.maxm * sizeof(MarkerRec), hipMemcpyDeviceToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(w.n_prev, prev_counts, n_frames * sizeof(int), hipMemcpyDeviceToDevice, s));
     } else if (prev && prev_counts) {
         // through the context's page-locked buffers: the device never touches the caller's (pageable, possibly tiny) arrays.
         // (A batch is collected before the next one is enqueued on a context, so the buffers are free again by then.)
-        std::memcpy(c->h_prev, prev, (size_t)n_frames * MAXM * sizeof(MarkerRec));
+        std::memcpy(c->h_prev, prev, (size_t)n_frames * w.maxm * sizeof(MarkerRec));
         std::memcpy(c->h_prev_counts, prev_counts, n_frames * sizeof(int));
-        HIP_TRY(c, hipMemcpyAsync(w.prev, c->h_prev, (size_t)n_frames * MAXM * sizeof(MarkerRec), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(w.prev, c->h_prev, (size_t)n_frames * w.maxm * sizeof(MarkerRec), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(w.n_prev, c->h_prev_counts, n_frames * sizeof(int), hipMemcpyHostToDevice, s));
     } else {
         HIP_TRY(c, hipMemsetAsync(w.n_prev, 0, n_frames * sizeof(int), s));
@@ -541,10 +579,10 @@ static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int 
         TRACE_LAUNCH("finalise", cur);
         HIP_TRY(c, stage(11, -1));
         HIP_TRY(c, hipMemcpyAsync(c->h_counts, w.n_markers, n_frames * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (c->result_limit >= MAXM)
-            HIP_TRY(c, hipMemcpyAsync(c->h_markers, w.markers, (size_t)n_frames * MAXM * sizeof(MarkerRec), hipMemcpyDeviceToHost, s));
+        if (c->result_limit >= w.maxm)
+            HIP_TRY(c, hipMemcpyAsync(c->h_markers, w.markers, (size_t)n_frames * w.maxm * sizeof(MarkerRec), hipMemcpyDeviceToHost, s));
         else   // the first result_limit records of every frame, at their usual places in the host block
-            HIP_TRY(c, hipMemcpy2DAsync(c->h_markers, (size_t)MAXM * sizeof(MarkerRec), w.markers, (size_t)MAXM * sizeof(MarkerRec),
+            HIP_TRY(c, hipMemcpy2DAsync(c->h_markers, (size_t)w.maxm * sizeof(MarkerRec), w.markers, (size_t)w.maxm * sizeof(MarkerRec),
                                         (size_t)c->result_limit * sizeof(MarkerRec), (size_t)n_frames, hipMemcpyDeviceToHost, s));
     } else {
         HIP_TRY(c, stage(5, -1));
@@ -592,21 +630,21 @@ extern "C" int ocvar_hip_enqueue_tracked(OcvarHip* c, uint8_t* d_bgr, int width,
 }
 
 extern "C" int ocvar_hip_results_to_device(OcvarHip* c, OcvarMarker* d_markers, int* d_counts, void* stream) {
-    return ocvar_hip_results_to_device_ex(c, d_markers, d_counts, MAXM, stream);
+    return ocvar_hip_results_to_device_ex(c, d_markers, d_counts, c ? c->ws.maxm : MAXM, stream);
 }
 
 extern "C" int ocvar_hip_results_to_device_ex(OcvarHip* c, OcvarMarker* d_markers, int* d_counts, int max_per_frame, void* stream) {
-    if (!c || !d_markers || !d_counts || !c->pending || max_per_frame < 1 || max_per_frame > MAXM) return OCVAR_E_ARG;
+    if (!c || !d_markers || !d_counts || !c->pending || max_per_frame < 1 || max_per_frame > c->ws.maxm) return OCVAR_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->last_stream;
     if (s != c->last_stream) {  // order behind the batch
         HIP_TRY(c, hipStreamWaitEvent(s, c->ev[12], 0));
     }
-    const int n = c->ws.n_frames;
-    if (max_per_frame == MAXM)
-        HIP_TRY(c, hipMemcpyAsync(d_markers, c->ws.markers, (size_t)n * MAXM * sizeof(MarkerRec), hipMemcpyDeviceToDevice, s));
+    const int n = c->ws.n_frames, M = c->ws.maxm;
+    if (max_per_frame == M)
+        HIP_TRY(c, hipMemcpyAsync(d_markers, c->ws.markers, (size_t)n * M * sizeof(MarkerRec), hipMemcpyDeviceToDevice, s));
     else   // the first max_per_frame records of every frame: a strided copy
-        HIP_TRY(c, hipMemcpy2DAsync(d_markers, (size_t)max_per_frame * sizeof(MarkerRec), c->ws.markers, (size_t)MAXM * sizeof(MarkerRec),
+        HIP_TRY(c, hipMemcpy2DAsync(d_markers, (size_t)max_per_frame * sizeof(MarkerRec), c->ws.markers, (size_t)M * sizeof(MarkerRec),
                                     (size_t)max_per_frame * sizeof(MarkerRec), (size_t)n, hipMemcpyDeviceToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d_counts, c->ws.n_markers, n * sizeof(int), hipMemcpyDeviceToDevice, s));
     return OCVAR_OK;
@@ -621,7 +659,7 @@ extern "C" int ocvar_hip_collect(OcvarHip* c, OcvarMarker* markers, int* counts,
         counts[f] = c->h_counts[f];
         int k = counts[f] < max_per_frame ? counts[f] : max_per_frame;
         if (k > c->result_limit) k = c->result_limit;
-        if (k > 0) std::memcpy(markers + (size_t)f * max_per_frame, c->h_markers + (size_t)f * MAXM, k * sizeof(OcvarMarker));
+        if (k > 0) std::memcpy(markers + (size_t)f * max_per_frame, c->h_markers + (size_t)f * c->ws.maxm, k * sizeof(OcvarMarker));
     }
     return OCVAR_OK;
 }
@@ -639,7 +677,7 @@ extern "C" int ocvar_hip_ready(OcvarHip* c) {
 }
 
 extern "C" int ocvar_hip_set_result_limit(OcvarHip* c, int max_per_frame) {
-    if (!c || c->pending || max_per_frame < 1 || max_per_frame > MAXM) return OCVAR_E_ARG;
+    if (!c || c->pending || max_per_frame < 1 || max_per_frame > c->ws.maxm) return OCVAR_E_ARG;
     c->result_limit = max_per_frame;
     return OCVAR_OK;
 }
@@ -859,7 +897,7 @@ extern "C" int ocvar_hip_detect_host(OcvarHip* c, uint8_t* h_bgr, int width, int
         uint8_t* d_slot = c->d_frames + (size_t)(k & 1) * slot_bytes;
         HIP_TRY_HOST(hipStreamWaitEvent(c->stream, c->h2d_done[k & 1], 0));
         rc = enqueue_impl(c, d_slot, width, height, row_stride, frame_stride, cnt, grey_in_place,
-                          prev ? prev + (size_t)k * sub * MAXM : nullptr, prev_counts ? prev_counts + k * sub : nullptr, c->stream, 3,
+                          prev ? prev + (size_t)k * sub * c->ws.maxm : nullptr, prev_counts ? prev_counts + k * sub : nullptr, c->stream, 3,
                           c->input_format);
         if (rc) return fail(rc);
         // while sub-batch k computes: bring sub-batch k-1's grey home, then stage sub-batch k+1 into the slot it leaves

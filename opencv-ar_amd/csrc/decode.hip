@@ -27,22 +27,25 @@ namespace ocvar {
 constexpr int DECODE_SLICES = 4;   // waves per frame: quad i belongs to slice i % 4
 constexpr int DECODE_CHUNK = 8;    // quads of a slice per round (x size classes <= 128 lanes of phases 1 and 3)
 
+template <bool DENSE>
 __global__ __launch_bounds__(64) void decode_kernel(Workspace ws) {
     extern __shared__ double sM_dyn[];   // [DECODE_CHUNK][n_sizes][9]
     __shared__ int s_roi[DECODE_CHUNK];        // crop ROI of the chunk's quad, -1: no quad in its crop
     __shared__ unsigned s_slot[DECODE_CHUNK];  // quads_crop slot of the crop's quad
     __shared__ long long s_code[DECODE_CHUNK * MAX_SIZE_CLASSES];
     __shared__ int s_lo[DECODE_CHUNK * MAX_SIZE_CLASSES], s_cnt[DECODE_CHUNK * MAX_SIZE_CLASSES];
-    const int f = blockIdx.x / DECODE_SLICES, slice = blockIdx.x % DECODE_SLICES;
+    // (dense contexts: more waves per frame, ws.decode_slices -- thousands of squares would queue behind four)
+    const int SLICES = DENSE ? ws.decode_slices : DECODE_SLICES;
+    const int f = blockIdx.x / SLICES, slice = blockIdx.x % SLICES;
     const int lane = threadIdx.x;
     const int NS = ws.n_sizes;
     int nsq = ws.n_squares[f];
     nsq = nsq < ws.maxq ? nsq : ws.maxq;
-    const int mine = (nsq - slice + DECODE_SLICES - 1) / DECODE_SLICES;   // quads slice, slice + 4, ... < nsq
+    const int mine = (nsq - slice + SLICES - 1) / SLICES;   // quads slice, slice + SLICES, ... < nsq
     for (int base = 0; base < mine; base += DECODE_CHUNK) {
         const int cnt = mine - base < DECODE_CHUNK ? mine - base : DECODE_CHUNK;
         if (lane < cnt) {
-            const int i = slice + DECODE_SLICES * (base + lane);
+            const int i = slice + SLICES * (base + lane);
             const int r = ws.crop_of[(size_t)f * ws.maxq + i];
             unsigned long long best = ~0ull;
             if (r >= 0) best = ws.best_crop[r];
@@ -65,7 +68,7 @@ __global__ __launch_bounds__(64) void decode_kernel(Workspace ws) {
         }
         __syncthreads();
         for (int qi = 0; qi < cnt; qi++) {
-            const int i = slice + DECODE_SLICES * (base + qi);
+            const int i = slice + SLICES * (base + qi);
             SquareRec* rec = ws.sq_recs + (size_t)f * ws.maxq + i;
             const int r = s_roi[qi];
             if (r < 0) {  // no quad in the crop: no candidate for this square (opencvar.cpp:704)
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(64) void decode_kernel(Workspace ws) {
         for (int pair = lane; pair < cnt * NS; pair += 64) {
             const int qi = pair / NS, s = pair - qi * NS;
             if (s_roi[qi] < 0) continue;
-            const int i = slice + DECODE_SLICES * (base + qi);
+            const int i = slice + SLICES * (base + qi);
             const long long bit = s_code[qi * MAX_SIZE_CLASSES + s];
             ws.sq_codes[((size_t)f * ws.maxq + i) * NS + s] = bit;
             const SizeClass sz = ws.sizes[s];
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(64) void decode_kernel(Workspace ws) {
         }
         __syncthreads();
         if (lane < cnt && s_roi[lane] >= 0) {
-            const int i = slice + DECODE_SLICES * (base + lane);
+            const int i = slice + SLICES * (base + lane);
             int* out = ws.sq_match + ((size_t)f * ws.maxq + i) * ws.max_match;
             int n = 0;   // <= max_match: at most the longest run of one code per size class
             for (int s = 0; s < NS; s++) {
@@ -128,13 +131,18 @@ __global__ __launch_bounds__(64) void decode_kernel(Workspace ws) {
 // The elimination in its sparse form (tail_core.h: square_survivor), one wave per frame.  Pass 1: the first square matching
 // each group (LDS atomicMin over the frame's matches); pass 2, one lane per square: its survivor; then the survivors in
 // square order behind the tracked markers.  LDS: n_groups + maxq ints, sized at launch.
+// Dense contexts (DENSE): s_surv and s_src live in global workspace (ws.surv, ws.src), the LDS holds n_groups ints only.
+template <bool DENSE>
 __global__ __launch_bounds__(64) void finalise_kernel(Workspace ws) {
     extern __shared__ int tail_lds[];
-    int* s_earliest = tail_lds;                // [n_groups]
-    int* s_surv = tail_lds + ws.n_groups;      // [maxq] template << 1 | score of the square's survivor, -1: none
-    __shared__ int s_src[MAXM];  // >= 0: square index, < 0: -(1 + index into prev)
-    __shared__ int s_first, s_nout, s_job;
+    __shared__ int s_src_lds[DENSE ? 1 : MAXM];
     const int f = blockIdx.x;
+    const int MM_OUT = DENSE ? ws.maxm : MAXM;   // marker records per frame
+    int* s_earliest = tail_lds;                // [n_groups]
+    // [maxq] template << 1 | score of the square's survivor, -1: none
+    int* s_surv = DENSE ? ws.surv + (size_t)f * ws.maxq : tail_lds + ws.n_groups;
+    int* s_src = DENSE ? ws.src + (size_t)f * ws.maxm : s_src_lds;   // >= 0: square index, < 0: -(1 + index into prev)
+    __shared__ int s_first, s_nout, s_job;
     const int lane = threadIdx.x;   // one wave per frame
     int nsq = ws.n_squares[f];
     nsq = nsq < ws.maxq ? nsq : ws.maxq;
@@ -161,32 +169,52 @@ __global__ __launch_bounds__(64) void finalise_kernel(Workspace ws) {
         s_surv[i] = v;
     }
     __syncthreads();
-    if (lane == 0) {
+    if (DENSE) {
+        // the same list, compacted by the whole wave (ballot + prefix count) instead of one lane walking thousands of squares
+        const int nr = ws.n_reserve[f];
+        for (int k = lane; k < nr && k < MM_OUT; k += 64) s_src[k] = -(1 + ws.reserve[(size_t)f * MM_OUT + k]);
+        int total = nr;
+        for (int base = 0; base < nsq; base += 64) {
+            const int i = base + lane;
+            const bool v = i < nsq && s_surv[i] >= 0;
+            const unsigned long long b = __ballot(v);
+            const int pos = total + __popcll(b & ((1ull << lane) - 1ull));
+            if (v && pos < MM_OUT) s_src[pos] = i;
+            total += __popcll(b);
+        }
+        if (lane == 0) {
+            const int nout = total < MM_OUT ? total : MM_OUT;
+            s_nout = nout;
+            if (total > MM_OUT) atomicOr(ws.counters + CNT_ERR, ERR_MARKER_OVERFLOW);
+            ws.n_markers[f] = total;
+            s_job = nout > 0 ? atomicAdd(ws.counters + CNT_POSE_JOBS, nout) : 0;
+        }
+    } else if (lane == 0) {
         int nout = 0, total = 0;
         const int nr = ws.n_reserve[f];
         for (int k = 0; k < nr; k++) {  // tracked markers first (662-668)
-            if (k < MAXM && nout < MAXM) s_src[nout++] = -(1 + ws.reserve[(size_t)f * MAXM + k]);
+            if (k < MM_OUT && nout < MM_OUT) s_src[nout++] = -(1 + ws.reserve[(size_t)f * MM_OUT + k]);
             total++;
         }
         for (int i = 0; i < nsq; i++)
             if (s_surv[i] >= 0) {
-                if (nout < MAXM) s_src[nout++] = i;
+                if (nout < MM_OUT) s_src[nout++] = i;
                 total++;
             }
         s_nout = nout;
         // more markers than a frame's output block holds (tracking keeps duplicates, opencvar.cpp:662-668): the next frame's
         // `prev` would be cut short and its tracking would diverge from the reference -- fail loudly instead
-        if (total > MAXM) atomicOr(ws.counters + CNT_ERR, ERR_MARKER_OVERFLOW);
+        if (total > MM_OUT) atomicOr(ws.counters + CNT_ERR, ERR_MARKER_OVERFLOW);
         ws.n_markers[f] = total;
         s_job = nout > 0 ? atomicAdd(ws.counters + CNT_POSE_JOBS, nout) : 0;   // one list append per frame
     }
     __syncthreads();
     // the surviving markers' records, all but the pose; one pose job per marker for pose_kernel
     for (int k = threadIdx.x; k < s_nout; k += blockDim.x) {
-        MarkerRec* m = ws.markers + (size_t)f * MAXM + k;
+        MarkerRec* m = ws.markers + (size_t)f * MM_OUT + k;
         const int src = s_src[k];
         if (src < 0) {
-            *m = ws.prev[(size_t)f * MAXM + (-src - 1)];  // square already updated by the tracking step
+            *m = ws.prev[(size_t)f * MM_OUT + (-src - 1)];  // square already updated by the tracking step
         } else {
             const int i = src, t = s_surv[i] >> 1;
             const int sh = prefix_shift(match + (size_t)i * MM, recs[i].n_match, ws.group_off, ws.group_members, t);
@@ -199,7 +227,7 @@ __global__ __launch_bounds__(64) void finalise_kernel(Workspace ws) {
             shift_square(sq, sh, m->square);
             m->aspectRatio = (double)tp.width / tp.height;
         }
-        ws.pose_jobs[s_job + k] = f * MAXM + k;
+        ws.pose_jobs[s_job + k] = f * MM_OUT + k;
     }
 }
 
@@ -210,7 +238,7 @@ __global__ __launch_bounds__(64) void finalise_kernel(Workspace ws) {
 // constant indices, the seeding homography in closed form: pose_core.h) and the kernel is as long as one solve.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void pose_kernel(Workspace ws) {
     int n = ws.counters[CNT_POSE_JOBS];
-    const int cap = ws.n_frames * MAXM;
+    const int cap = ws.n_frames * ws.maxm;
     if (n > cap) n = cap;
     const CameraRec cam = *ws.camera;
     for (int j = blockIdx.x * 64 + threadIdx.x; j < n; j += gridDim.x * 64) {
@@ -224,15 +252,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 }
 
 void launch_decode(const Workspace& ws, hipStream_t stream) {
-    if (ws.n_frames > 0)
-        hipLaunchKernelGGL(decode_kernel, dim3(ws.n_frames * DECODE_SLICES), dim3(64), (size_t)DECODE_CHUNK * ws.n_sizes * 9 * sizeof(double), stream, ws);
+    if (ws.n_frames <= 0) return;
+    const size_t lds = (size_t)DECODE_CHUNK * ws.n_sizes * 9 * sizeof(double);
+    if (ws.dense) hipLaunchKernelGGL(decode_kernel<true>, dim3(ws.n_frames * ws.decode_slices), dim3(64), lds, stream, ws);
+    else hipLaunchKernelGGL(decode_kernel<false>, dim3(ws.n_frames * DECODE_SLICES), dim3(64), lds, stream, ws);
 }
 void launch_finalise(const Workspace& ws, hipStream_t stream) {
     if (ws.n_frames <= 0) return;
-    hipLaunchKernelGGL(finalise_kernel, dim3(ws.n_frames), dim3(64), (size_t)(ws.n_groups + ws.maxq) * sizeof(int), stream, ws);
     // a stateless frame keeps at most one marker per template: a grid of one wave per 8 frames takes a batch's poses in one
-    // pass; stateful batches with many tracked markers per frame loop (grid-stride)
-    const int blocks = ws.n_frames / 8 + 1;
+    // pass; stateful batches with many tracked markers per frame loop (grid-stride).  A dense context sizes the grid for its
+    // marker records (one lane each, up to 2048 waves)
+    int blocks = ws.n_frames / 8 + 1;
+    if (ws.dense) {
+        hipLaunchKernelGGL(finalise_kernel<true>, dim3(ws.n_frames), dim3(64), (size_t)ws.n_groups * sizeof(int), stream, ws);
+        const long long want = ((long long)ws.n_frames * ws.maxm + 63) / 64;
+        blocks = (int)(want < 2048 ? (want > blocks ? want : blocks) : 2048);
+    } else {
+        hipLaunchKernelGGL(finalise_kernel<false>, dim3(ws.n_frames), dim3(64), (size_t)(ws.n_groups + ws.maxq) * sizeof(int), stream, ws);
+    }
     hipLaunchKernelGGL(pose_kernel, dim3(blocks), dim3(64), 0, stream, ws);
 }
 

@@ -9,7 +9,7 @@
 namespace ocvar {
 
 constexpr int MAXQ_DEFAULT = OCVAR_MAX_QUADS;   // frame-pass quads kept per frame unless the context was created for more (Workspace::maxq)
-constexpr int MAXM = OCVAR_MAX_MARKERS;    // markers kept per frame (tracked + new)
+constexpr int MAXM = OCVAR_MAX_MARKERS;    // markers kept per frame (tracked + new) unless the context was created for more (Workspace::maxm)
 constexpr int MAXT = OCVAR_MAX_TEMPLATES;
 constexpr int MARCH_HALO_L = 2, MARCH_HALO_R = 2;   // halo lanes (4 pixels each) left / right of a strip's output lanes
 constexpr int MARCH_STRIP = 4 * (64 - MARCH_HALO_L - MARCH_HALO_R);   // 240 output columns of one wave's strip in the binarise kernel (256 loaded)
@@ -33,7 +33,7 @@ constexpr int TILE_W = TILE_TX * NBR_TILE_W, TILE_H = TILE_TY * NBR_TILE_H;   //
 enum { ERR_CAND_OVERFLOW = 1, ERR_POOL_OVERFLOW = 2, ERR_QUAD_OVERFLOW = 4, ERR_TRACE_OVERRUN = 8, ERR_CROP_OVERFLOW = 16,
        ERR_TILE_OVERFLOW = 32,
        ERR_TICKET_RUNAWAY = 64,     // a work-queue loop ran more iterations than its list can account for (control flow broken)
-       ERR_MARKER_OVERFLOW = 128 }; // more than OCVAR_MAX_MARKERS markers in one frame
+       ERR_MARKER_OVERFLOW = 128 }; // more than Workspace::maxm markers in one frame
 
 struct TileDesc { int roi, x0, y0; };   // binarise work unit of the crop pass: x0 = strip index, y0 = first row
 
@@ -55,7 +55,12 @@ enum { CNT_FRAME_CANDS = 0, CNT_CROP_ROIS = 1, CNT_CROP_TILES = 2, CNT_CROP_CAND
 struct Workspace {
     // limits
     int max_w, max_h, max_batch;
-    int maxq;               // frame-pass quads kept per frame (ocvar_hip_create: OCVAR_MAX_QUADS; ocvar_hip_create_ex: caller's choice)
+    int maxq;               // frame-pass quads kept per frame (ocvar_hip_create: OCVAR_MAX_QUADS; ocvar_hip_create_ex/_dense: caller's choice)
+    int maxm;               // marker records per frame: MAXM, or the caller's choice on a dense context (ocvar_hip_create_dense)
+    int dense;              // 1: made by ocvar_hip_create_dense -- the per-frame tail runs the scalable kernels (follow.hip, decode.hip)
+    int track_gw, track_gh; // dense: corner grid of the sparse tracking replay (tail_core.h), cells of TRACK_CELL px over max_w x max_h
+    int decode_slices;      // dense: waves of decode_kernel per frame (DECODE_SLICES on the other contexts)
+    int order_chunk;        // dense: squares per sorted chunk of the ordering (ORDER_CHUNK, or maxq rounded up to a power of two)
     int cap_frame_cands, cap_crop_cands, cap_crop_rois, cap_crop_tiles, cap_crop_quads;
     long long cap_pool_ints, cap_crop_pixels;
     // per batch geometry
@@ -97,12 +102,21 @@ struct Workspace {
     SquareRec* sq_recs;     // [B][maxq]
     long long* sq_codes;    // [B][maxq][n_sizes] the code read for each size class
     int* sq_match;          // [B][maxq][max_match] matched groups (group << 2 | orient - 1), ascending
-    MarkerRec* prev;        // [B][MAXM]
+    MarkerRec* prev;        // [B][maxm]
     int* n_prev;            // [B]
-    int* reserve;           // [B][MAXM] tracked marker indices
+    int* reserve;           // [B][maxm] tracked marker indices
     int* n_reserve;         // [B]
-    int* pose_jobs;         // [B][MAXM] frame * MAXM + slot of every output marker (counter CNT_POSE_JOBS): pose_kernel's work list
-    MarkerRec* markers;     // [B][MAXM] output
+    int* pose_jobs;         // [B][maxm] frame * maxm + slot of every output marker (counter CNT_POSE_JOBS): pose_kernel's work list
+    MarkerRec* markers;     // [B][maxm] output
+    // dense contexts only (nullptr elsewhere)
+    int* sorted_starts;     // [B][maxq] the frame's discovery positions, sorted in chunks of ORDER_CHUNK
+    float* sq_tmp;          // [B][maxq][8] squares in sequence order before tracking
+    int* trk_cells;         // [B][track_gw * track_gh + 1] corner grid: first entry of each cell
+    int* trk_fill;          // [B][track_gw * track_gh] fill cursors of the grid build
+    int* trk_items;         // [B][4 maxq] square index of each corner entry
+    int* trk_next;          // [B][maxq + 1] "next square still in the list" forest of the replay
+    int* surv;              // [B][maxq] finalise: the square's survivor (template << 1 | score), -1: none
+    int* src;               // [B][maxm] finalise: source of each output record
     int* n_markers;         // [B]
     TemplateRec* templates; // [MAXT]
     SizeClass* sizes;       // [MAX_SIZE_CLASSES]
@@ -129,7 +143,7 @@ void launch_follow_mid_frames(const Workspace& ws, hipStream_t stream);
 void launch_follow_mid_crops(const Workspace& ws, hipStream_t stream);   // both phases
 void launch_follow_long_frames(const Workspace& ws, hipStream_t stream);
 void launch_follow_long_crops(const Workspace& ws, hipStream_t stream);
-void launch_order_and_crops(const Workspace& ws, hipStream_t stream);
+void launch_order_and_crops(const Workspace& ws, hipStream_t stream);   // (dense contexts: the sort, replay and crop kernels)
 void launch_decode(const Workspace& ws, hipStream_t stream);
 void launch_finalise(const Workspace& ws, hipStream_t stream);
 

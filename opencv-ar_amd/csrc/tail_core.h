@@ -63,6 +63,131 @@ OCVAR_HD int track_markers(MarkerRec* markers, int n_markers, float* squares, in
     return n_quads;
 }
 
+// ---- the tracking loop in sparse form (dense contexts: up to 4096 markers x 16384 squares per frame) ----
+// Same result as track_markers, bit for bit, without its O(markers x squares) scan and O(squares) shift per match.
+// track_square(m, q) can only succeed when m's corner 0 lies within 20 px of a corner of q (|dx|, |dy| < 20), so the squares a
+// marker can take are found in the 3 x 3 cells of TRACK_CELL px around its corner 0 in a grid of all squares' corners.  The
+// loop's order rules, restated on the ORIGINAL list indices of the squares:
+//   - marker i examines the squares still in the list in list order; the first one it matches is the lowest index >= pos that
+//     matches with its current corners (a failed track_square changes nothing), wherever it lies in the grid;
+//   - a match erases that square and the loop index is not corrected: the next square still in the list is skipped, the marker
+//     goes on behind it (pos = that square + 1), with its updated corners.
+// Erased squares are skipped with a "next square still in the list" forest (next[i] == i: i is in the list; erasing i sets
+// next[i] = i + 1; path halving).  The caller compacts the list afterwards (next[i] == i, in index order).
+constexpr int TRACK_CELL = 32;   // >= 20: a point within 20 px of another lies in the same or a neighbouring cell
+
+// grid cell of one coordinate, clamped to [0, n) -- monotone and 1-Lipschitz in cells, so the 3 x 3 rule survives clamping
+// (negative and NaN coordinates go to cell 0: a NaN corner never matches anyway)
+OCVAR_HD int track_cell(float v, int n) {
+    if (!(v >= 0.f)) return 0;
+    const float c = v / (float)TRACK_CELL;   // (exact: a power of two)
+    if (c >= (float)(n - 1)) return n - 1;
+    return (int)c;
+}
+
+// cells of a grid covering [0, w) x [0, h) px
+OCVAR_HD int track_grid_cells(int w, int h, int* gw, int* gh) {
+    *gw = (w + TRACK_CELL - 1) / TRACK_CELL > 0 ? (w + TRACK_CELL - 1) / TRACK_CELL : 1;
+    *gh = (h + TRACK_CELL - 1) / TRACK_CELL > 0 ? (h + TRACK_CELL - 1) / TRACK_CELL : 1;
+    return *gw * *gh;
+}
+
+// The grid by counting sort, sequentially: cell_start [gw*gh + 1], items [4 n] (one entry per corner; a square can appear
+// more than once in a neighbourhood).  The device builds the same lists in parallel, in another order within a cell: the
+// replay takes the lowest matching index, so it does not depend on that order.
+OCVAR_HD void track_grid_build(const float* squares, int n, int gw, int gh, int* cell_start, int* items) {
+    const int nc = gw * gh;
+    for (int c = 0; c <= nc; c++) cell_start[c] = 0;
+    for (int j = 0; j < 4 * n; j++) cell_start[track_cell(squares[2 * j + 1], gh) * gw + track_cell(squares[2 * j], gw) + 1]++;
+    for (int c = 0; c < nc; c++) cell_start[c + 1] += cell_start[c];
+    for (int j = 0; j < 4 * n; j++) {
+        const int c = track_cell(squares[2 * j + 1], gh) * gw + track_cell(squares[2 * j], gw);
+        items[cell_start[c]++] = j >> 2;
+    }
+    for (int c = nc; c > 0; c--) cell_start[c] = cell_start[c - 1];
+    cell_start[0] = 0;
+}
+
+OCVAR_HD int track_next_alive(int* next, int i) {
+    while (next[i] != i) {
+        next[i] = next[next[i]];
+        i = next[i];
+    }
+    return i;
+}
+
+// would track_square(m, q) succeed? (m unchanged)
+OCVAR_HD bool track_test(const float* m, const float* q) {
+    float t[8];
+    for (int k = 0; k < 8; k++) t[k] = m[k];
+    return track_square(t, q) != 0;
+}
+
+// The lowest square index >= pos still in the list that marker corners m match (n: none).
+OCVAR_HD int track_first_match(const float* m, const float* squares, int n, int pos, const int* cell_start, const int* items, int gw,
+                               int gh, const int* next) {
+    const int cx = track_cell(m[0], gw), cy = track_cell(m[1], gh);
+    int best = n;
+    for (int y = cy > 0 ? cy - 1 : 0; y <= cy + 1 && y < gh; y++)
+        for (int x = cx > 0 ? cx - 1 : 0; x <= cx + 1 && x < gw; x++)
+            for (int e = cell_start[y * gw + x]; e < cell_start[y * gw + x + 1]; e++) {
+                const int j = items[e];
+                if (j >= pos && j < best && next[j] == j && track_test(m, squares + 8 * j)) best = j;
+            }
+    return best;
+}
+
+// One frame: squares [n][8] (read only), next [n + 1] (scratch, set here), the grid of track_grid_build.  Returns the number
+// of squares left in the list (those with next[i] == i, i < n).
+OCVAR_HD int track_markers_sparse(MarkerRec* markers, int n_markers, const float* squares, int n_quads, const int* cell_start,
+                                  const int* items, int gw, int gh, int* next, int* reserve, int max_reserve, int* n_reserve) {
+    for (int j = 0; j <= n_quads; j++) next[j] = j;
+    int nr = 0, left = n_quads;
+    for (int i = 0; i < n_markers; i++) {
+        int pos = 0;
+        for (;;) {
+            const int j = track_first_match(markers[i].square, squares, n_quads, pos, cell_start, items, gw, gh, next);
+            if (j >= n_quads) break;
+            track_square(markers[i].square, squares + 8 * j);
+            if (nr < max_reserve) reserve[nr] = i;
+            nr++;
+            next[j] = j + 1;
+            left--;
+            const int skipped = track_next_alive(next, j + 1);
+            if (skipped >= n_quads) break;
+            pos = skipped + 1;
+        }
+    }
+    *n_reserve = nr;
+    return left;
+}
+
+// The order of cvarFindSquares (opencvar.cpp:187-214): square i of a frame goes to slot "number of squares with a larger
+// discovery position".  Dense contexts count it with binary searches in sorted chunks of the frame's starts (sorted: one
+// chunk of starts in ascending order, len of them): squares of the chunk whose start is larger than `start`.
+constexpr int ORDER_CHUNK = 2048;   // starts sorted per workgroup in LDS (follow.hip: order_sort_kernel), a power of two
+
+// One compare-exchange of the bitonic network that sorts a chunk ascending (stage k = 2, 4, .. len, step j = k / 2, .. 1; len / 2
+// threads tid, each one pair per step).
+OCVAR_HD void bitonic_step(int* key, int k, int j, int tid) {
+    const int i = 2 * tid - (tid & (j - 1)), p = i + j;   // pair (i, i + j), bit j of i clear
+    const int a = key[i], b = key[p];
+    if ((a > b) == ((i & k) == 0)) {
+        key[i] = b;
+        key[p] = a;
+    }
+}
+
+OCVAR_HD int count_greater_sorted(const int* sorted, int len, int start) {
+    int lo = 0, hi = len;   // first element > start
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sorted[mid] > start) hi = mid;
+        else lo = mid + 1;
+    }
+    return len - lo;
+}
+
 // Greedy elimination (opencvar.cpp:780-792): markerId[i] = -1 marks a loser.
 OCVAR_HD void dedupe(int* markerId, const int* templateId, const double* score, int n) {
     for (int i = 0; i < n; i++)

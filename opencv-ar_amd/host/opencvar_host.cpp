@@ -71,6 +71,14 @@ std::mutex g_mu;
 OcvarHip* g_ctx = nullptr;
 int g_w = 0, g_h = 0;
 int g_maxq = OCVAR_MAX_QUADS;   // squares per frame the current context has room for (grows when a frame needs more)
+int g_maxm = OCVAR_MAX_MARKERS; // markers per frame the same (grows on flag 128 or with the markers carried in)
+
+// The next rung of the ladders a failing frame climbs: squares 256 -> 1024 -> 1792 (ocvar_hip_create_ex) -> 4096 -> 16384,
+// markers 64 -> 512 -> 4096 (ocvar_hip_create_dense); 0 at the top.
+int next_quads(int q) {
+    return q < 1024 ? 1024 : q < OCVAR_MAX_QUADS_EX ? OCVAR_MAX_QUADS_EX : q < 4096 ? 4096 : q < OCVAR_MAX_QUADS_DENSE ? OCVAR_MAX_QUADS_DENSE : 0;
+}
+int next_markers(int m) { return m < 512 ? 512 : m < OCVAR_MAX_MARKERS_DENSE ? OCVAR_MAX_MARKERS_DENSE : 0; }
 // Sequences handed out by cvarFindSquares, per CvMemStorage* the caller passed.  In the reference a sequence lives in the
 // caller's storage until that storage is cleared or released (opencvar.cpp:168, 621-630, 803-804).  OpenCV is not part of
 // this build, so the storage is an opaque key here: a key's sequences stay alive until cvarReleaseSquares(key) -- the
@@ -83,19 +91,25 @@ std::vector<CvarTemplate> g_templates;        // what the context currently hold
 CvarCamera g_camera;
 bool g_have_camera = false;
 
-OcvarHip* context_for(int w, int h, int maxq = 0) {
+OcvarHip* context_for(int w, int h, int maxq = 0, int maxm = 0) {
     if (maxq <= 0) maxq = g_maxq;
-    if (g_ctx && w <= g_w && h <= g_h && maxq <= g_maxq) return g_ctx;
+    if (maxm <= 0) maxm = g_maxm;
+    if (g_ctx && w <= g_w && h <= g_h && maxq <= g_maxq && maxm <= g_maxm) return g_ctx;
     if (g_ctx) {   // keep what the old context had room for
         w = w > g_w ? w : g_w;
         h = h > g_h ? h : g_h;
+        maxq = maxq > g_maxq ? maxq : g_maxq;
+        maxm = maxm > g_maxm ? maxm : g_maxm;
     }
     if (g_ctx) ocvar_hip_destroy(g_ctx);
     g_ctx = nullptr;
     g_templates.clear();
     g_have_camera = false;
     const int dev = std::getenv("OCVAR_DEVICE") ? std::atoi(std::getenv("OCVAR_DEVICE")) : 0;
-    int rc = ocvar_hip_create_ex(&g_ctx, dev, w < 64 ? 64 : w, h < 64 ? 64 : h, 1, maxq);
+    // (past the limits of ocvar_hip_create_ex: a dense context)
+    int rc = maxq > OCVAR_MAX_QUADS_EX || maxm > OCVAR_MAX_MARKERS
+                 ? ocvar_hip_create_dense(&g_ctx, dev, w < 64 ? 64 : w, h < 64 ? 64 : h, 1, maxq, maxm)
+                 : ocvar_hip_create_ex(&g_ctx, dev, w < 64 ? 64 : w, h < 64 ? 64 : h, 1, maxq);
     if (rc != OCVAR_OK) {
         std::fprintf(stderr, "opencvar: no MI355X context (%d): %s\n", rc, g_ctx ? ocvar_hip_last_error(g_ctx) : "no gfx950 device");
         if (g_ctx) ocvar_hip_destroy(g_ctx);
@@ -105,6 +119,7 @@ OcvarHip* context_for(int w, int h, int maxq = 0) {
     g_w = w < 64 ? 64 : w;
     g_h = h < 64 ? 64 : h;
     g_maxq = maxq;
+    g_maxm = maxm;
     return g_ctx;
 }
 
@@ -442,14 +457,14 @@ CvSeq* cvarFindSquares(IplImage* img, CvMemStorage* storage) {
                 std::fprintf(stderr, "opencvar: cvarFindSquares: colour image greyed before the pyramid filter (the reference filters per channel)\n");
             }
             // the reference's square list is unbounded (opencvar.cpp:187-214): an image with more squares than the context has
-            // room for is run again on a larger one (256 -> 1024 -> OCVAR_MAX_QUADS_EX); beyond that the failure is reported
+            // room for is run again on a larger one (256 -> 1024 -> 1792 -> 4096 -> 16384); beyond that the failure is reported
             std::vector<int> quads;
             int n = 0, rc = OCVAR_OK;
             for (;;) {
                 quads.assign((size_t)g_maxq * 8, 0);
                 rc = ocvar_hip_find_squares(ctx, gray.data(), img->width, img->height, img->width, quads.data(), g_maxq, &n);
-                if (rc != OCVAR_E_CAPACITY || !(ocvar_hip_capacity_flags(ctx) & 4) || g_maxq >= OCVAR_MAX_QUADS_EX) break;
-                ctx = context_for(img->width, img->height, g_maxq * 4 < OCVAR_MAX_QUADS_EX ? g_maxq * 4 : OCVAR_MAX_QUADS_EX);
+                if (rc != OCVAR_E_CAPACITY || !(ocvar_hip_capacity_flags(ctx) & 4) || !next_quads(g_maxq)) break;
+                ctx = context_for(img->width, img->height, next_quads(g_maxq));
                 if (!ctx) break;
             }
             if (!ctx) rc = OCVAR_E_HIP;
@@ -578,23 +593,29 @@ int cvarArMultRegistration(IplImage* image, vector<CvarMarker>* markers, vector<
         markers->clear();
         return 0;
     }
-    if (markers->size() > OCVAR_MAX_MARKERS) {
+    if (markers->size() > OCVAR_MAX_MARKERS_DENSE) {
         std::fprintf(stderr, "opencvar: cvarArMultRegistration: %zu markers carried in, this build tracks at most %d per frame\n",
-                     markers->size(), OCVAR_MAX_MARKERS);
+                     markers->size(), (int)OCVAR_MAX_MARKERS_DENSE);
         markers->clear();
         return 0;
     }
-    std::vector<OcvarMarker> prev(OCVAR_MAX_MARKERS);
-    int n_prev = (int)markers->size();
-    if (n_prev) std::memcpy(prev.data(), markers->data(), n_prev * sizeof(OcvarMarker));
-    std::vector<OcvarMarker> out(OCVAR_MAX_MARKERS);
+    const int n_prev = (int)markers->size();
+    // a context whose marker stride holds the markers carried in (64 -> 512 -> 4096)
+    int need_m = g_maxm;
+    while (need_m < n_prev) need_m = next_markers(need_m);
+    std::vector<OcvarMarker> prev, out;
     int count = 0, rc = OCVAR_OK;
-    OcvarHip* ctx = context_for(image->width, image->height);
+    OcvarHip* ctx = context_for(image->width, image->height, 0, need_m);
     for (;;) {
         if (!ctx) {
             markers->clear();
             return 0;
         }
+        const int M = ocvar_hip_max_markers(ctx);   // ([1][M] blocks: prev in, markers out)
+        prev.assign(M, OcvarMarker{});
+        out.assign(M, OcvarMarker{});
+        int n_in = n_prev;
+        if (n_prev) std::memcpy(prev.data(), markers->data(), n_prev * sizeof(OcvarMarker));
         // templates and camera are uploaded only when they differ from what the context holds (a caller passes the same
         // ones frame after frame, ARTest.cpp:57)
         const bool same_t = g_templates.size() == templates.size() &&
@@ -613,19 +634,23 @@ int cvarArMultRegistration(IplImage* image, vector<CvarMarker>* markers, vector<
         g_have_camera = true;
         rc = ocvar_hip_detect_host(ctx, (uint8_t*)image->imageData, image->width, image->height, image->widthStep,
                                    (size_t)image->widthStep * image->height, 1, 1, n_prev ? prev.data() : nullptr,
-                                   n_prev ? &n_prev : nullptr, out.data(), &count, OCVAR_MAX_MARKERS);
-        // The reference's square list is unbounded (opencvar.cpp:187-214).  A frame with more squares than
-        // the context has room for fails before the caller's image is touched; it is run again on a larger context
-        // (256 -> 1024 -> OCVAR_MAX_QUADS_EX squares), which is then kept.
-        if (rc != OCVAR_E_CAPACITY || !(ocvar_hip_capacity_flags(ctx) & 4) || g_maxq >= OCVAR_MAX_QUADS_EX) break;
-        ctx = context_for(image->width, image->height, g_maxq * 4 < OCVAR_MAX_QUADS_EX ? g_maxq * 4 : OCVAR_MAX_QUADS_EX);
+                                   n_prev ? &n_in : nullptr, out.data(), &count, M);
+        // The reference's square list and marker vector are unbounded (opencvar.cpp:187-214, 619-807).  A frame with more
+        // squares (flag 4) or markers (flag 128) than the context has room for fails before the caller's image is touched; it is
+        // run again on a larger context (squares 256 -> 1024 -> 1792 -> 4096 -> 16384, markers 64 -> 512 -> 4096), which is then
+        // kept.
+        if (rc != OCVAR_E_CAPACITY) break;
+        const int flags = ocvar_hip_capacity_flags(ctx);
+        const int q = (flags & 4) ? next_quads(g_maxq) : g_maxq, m = (flags & 128) ? next_markers(g_maxm) : g_maxm;
+        if (!(flags & (4 | 128)) || q == 0 || m == 0 || (q == g_maxq && m == g_maxm)) break;
+        ctx = context_for(image->width, image->height, q, m);
     }
     markers->clear();
     if (rc != OCVAR_OK) {
         std::fprintf(stderr, "opencvar: detection failed (%d): %s\n", rc, ocvar_hip_last_error(ctx));
         return 0;
     }
-    markers->resize(count);   // (more than OCVAR_MAX_MARKERS would have failed above with OCVAR_E_CAPACITY)
+    markers->resize(count);   // (more than M would have failed above with OCVAR_E_CAPACITY)
     if (count) std::memcpy(markers->data(), out.data(), count * sizeof(OcvarMarker));
     return (int)markers->size();
 }

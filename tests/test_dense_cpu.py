@@ -1,0 +1,185 @@
+"""CPU tests of dense contexts (ocvar_hip_create_dense): the sparse tracking replay and the chunked square order of the dense
+per-frame tail (opencv-ar_amd/csrc/tail_core.h, built for the host from tests/emul/dense_emul.cpp) against the literal loops
+they replace, and the new entry points' argument checks, which run before any device call."""
+import ctypes as C
+import itertools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+from helpers import P
+
+CSRC = os.path.join(H.PKG, "csrc")
+
+
+@pytest.fixture(scope="module")
+def lib(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("dense_emul") / "libdense_emul.so")
+    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + CSRC,
+                           "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so,
+                           os.path.join(H.ROOT, "tests", "emul", "dense_emul.cpp")])
+    L = C.CDLL(so)
+    L.dense_track_literal.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.dense_track_sparse.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p]
+    L.dense_order_rank.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.dense_order_sorted.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.dense_track_exhaustive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.dense_track_exhaustive.restype = C.c_longlong
+    return L
+
+
+def both(L, marker_squares, squares, w, h):
+    """(reserve, n_squares, compacted squares, updated marker squares) of the literal loop and of the sparse replay"""
+    out = []
+    nm, n = len(marker_squares), len(squares)
+    for sparse in (False, True):
+        m = (H.Marker * max(nm, 1))()
+        for i, s in enumerate(marker_squares):
+            m[i].square[:] = [float(v) for v in s]
+            m[i].markerId = i
+        sq = np.ascontiguousarray(np.asarray(squares, np.float32).reshape(-1, 8)) if n else np.zeros((1, 8), np.float32)
+        res = np.full(max(nm * n, 1), -7, np.int32)
+        nr = C.c_int(0)
+        if sparse:
+            dst = np.zeros_like(sq)
+            left = L.dense_track_sparse(m, nm, P(sq), n, w, h, P(dst), P(res), len(res), C.byref(nr))
+            assert left >= 0
+            lst = dst[:left]
+        else:
+            left = L.dense_track_literal(m, nm, P(sq), n, P(res), len(res), C.byref(nr))
+            lst = sq[:left]
+        out.append((res[:nr.value].tolist(), left, lst.copy(), np.array([list(m[i].square) for i in range(nm)], np.float32)))
+    return out
+
+
+def assert_same(a, b):
+    assert a[0] == b[0]
+    assert a[1] == b[1]
+    assert np.array_equal(a[2].view(np.uint32), b[2].view(np.uint32))
+    assert np.array_equal(a[3].view(np.uint32), b[3].view(np.uint32))
+
+
+def square_at(x, y, side=30.0, shift=0):
+    c = [(x, y), (x + side, y), (x + side, y + side), (x, y + side)]
+    c = c[shift:] + c[:shift]
+    return [v for p in c for v in p]
+
+
+def test_sparse_replay_equals_literal_loop_exhaustive_small(lib):
+    """Every list of 0..4 markers x 0..6 squares (with repetition) over small pools around one position: squares on and just
+    inside / outside the 20 px boundary, in different cyclic shifts, one within reach only after the marker has moved (15 px
+    steps), and equal squares back to back (a match directly followed by a square that would match too: the skip)."""
+    b = (100.0, 100.0)
+    squares = [square_at(b[0], b[1]), square_at(b[0] + 15, b[1], shift=1), square_at(b[0] + 30, b[1], shift=3),
+               square_at(b[0] + 19.99, b[1] - 0.5, shift=2), square_at(b[0] + 20.0, b[1])]
+    marks = [square_at(b[0], b[1]), square_at(b[0] + 5, b[1] + 5, shift=2)]
+    pool_s = np.ascontiguousarray(np.array(squares, np.float32))
+    pool_m = np.ascontiguousarray(np.array(marks, np.float32))
+    cases = C.c_longlong(0)
+    bad = lib.dense_track_exhaustive(P(pool_m), len(marks), 4, P(pool_s), len(squares), 6, 320, 240, C.byref(cases))
+    assert cases.value == sum(2 ** m for m in range(5)) * sum(5 ** n for n in range(7))
+    assert bad == 0
+    # the skip, spelled out: marker 0 matches squares 0 and 1 equally; the literal loop takes 0 and skips 1
+    ms = [square_at(100, 100)]
+    sq = [square_at(101, 100), square_at(102, 100), square_at(300, 200), square_at(103, 100)]
+    a, c = both(lib, ms, sq, 640, 480)
+    assert_same(a, c)
+    assert a[0] == [0, 0] and a[1] == 2   # squares 0 and 3 taken, 1 skipped, 2 out of reach
+    # updated corners: the marker walks along a row of squares 15 px apart, one step per match
+    ms = [square_at(100, 100)]
+    sq = [square_at(100 + 15 * k, 100) for k in (1, 0, 2, 4, 3, 5)]
+    a, c = both(lib, ms, sq, 640, 480)
+    assert_same(a, c)
+
+
+@pytest.mark.parametrize("nm,n,w,h", [(64, 256, 640, 480), (300, 1800, 1920, 1080), (1300, 5000, 3840, 2160),
+                                      (4096, 16384, 3840, 2160)])
+def test_sparse_replay_equals_literal_loop_random_frames(lib, nm, n, w, h):
+    """random frames up to 4096 markers x 16384 squares: squares on a jittered grid with repeats and strays (some off the frame),
+    markers near some of them in random cyclic order"""
+    rng = np.random.default_rng(nm + n)
+    centres = rng.uniform([-30, -30], [w + 30, h + 30], (max(n // 3, 1), 2))
+    sq = []
+    for k in range(n):
+        cx, cy = centres[rng.integers(0, len(centres))] + rng.normal(0, 6, 2)
+        side = rng.uniform(20, 60)
+        sq.append(square_at(float(np.float32(cx)), float(np.float32(cy)), float(np.float32(side)), int(rng.integers(0, 4))))
+    ms = []
+    for k in range(nm):
+        s = np.array(sq[rng.integers(0, n)], np.float64).reshape(4, 2) + rng.normal(0, 8, (4, 2))
+        s = np.roll(s, int(rng.integers(0, 4)), axis=0)
+        ms.append(s.reshape(-1).tolist())
+    a, b = both(lib, ms, sq, w, h)
+    assert_same(a, b)
+    assert len(a[0]) > 0 and a[1] < n   # (the case does exercise matches)
+
+
+def test_sparse_replay_ignores_non_finite_marker_corners(lib):
+    ms = [[float("nan")] * 8, [float("inf")] * 8, square_at(100, 100)]
+    sq = [square_at(100, 100), square_at(1e30, -1e30)]
+    a, b = both(lib, ms, sq, 640, 480)
+    assert_same(a, b)
+
+
+@pytest.mark.parametrize("n,chunk", [(0, 2048), (1, 2048), (2, 2), (7, 8), (200, 256), (2047, 2048), (2048, 2048), (2049, 2048),
+                                     (5000, 2048), (16384, 2048), (1000, 64)])
+def test_chunked_order_equals_rank_rule(lib, n, chunk):
+    rng = np.random.default_rng(n)
+    starts = np.ascontiguousarray(rng.choice(3840 * 2160, size=n, replace=False).astype(np.int32)) if n else np.zeros(1, np.int32)
+    a = np.zeros(max(n, 1), np.int32)
+    b = np.full(max(n, 1), -1, np.int32)
+    lib.dense_order_rank(P(starts), n, P(a))
+    lib.dense_order_sorted(P(starts), n, chunk, P(b))
+    assert np.array_equal(a[:n], b[:n])
+    if n:
+        assert sorted(a[:n].tolist()) == list(range(n))   # a permutation: last discovered first
+
+
+def test_chunked_order_equals_rank_rule_with_repeated_starts(lib):
+    """the rank rule sends equal starts to the same slot; the chunked count does the same"""
+    rng = np.random.default_rng(5)
+    starts = np.ascontiguousarray(rng.integers(0, 3000, 6000).astype(np.int32))
+    a = np.zeros(6000, np.int32)
+    b = np.zeros(6000, np.int32)
+    lib.dense_order_rank(P(starts), 6000, P(a))
+    lib.dense_order_sorted(P(starts), 6000, 2048, P(b))
+    assert np.array_equal(a, b)
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import __graft_entry__ as g
+    g.build()
+    import opencv_ar_amd
+    return opencv_ar_amd
+
+
+def test_dense_entry_points_declared_and_exported(pkg):
+    header = open(os.path.join(H.ROOT, "include", "ocvar_hip.h")).read()
+    for name in ("ocvar_hip_create_dense", "ocvar_hip_max_markers"):
+        assert name + "(" in header and name in pkg.HIP_SYMBOLS
+        assert hasattr(pkg.hip_lib(), name)
+    assert "OCVAR_MAX_QUADS_DENSE = 16384" in header and "OCVAR_MAX_MARKERS_DENSE = 4096" in header
+
+
+@pytest.mark.parametrize("q,m", [(0, 64), (16385, 64), (256, 0), (256, 4097), (-1, -1)])
+def test_create_dense_rejects_out_of_range_limits(pkg, q, m):
+    """OCVAR_E_ARG (-2) for squares outside 1..16384 or markers outside 1..4096, decided before any device call (no GPU here)"""
+    lib = pkg.hip_lib()
+    ctx = C.c_void_p()
+    assert lib.ocvar_hip_create_dense(C.byref(ctx), 0, 1920, 1080, 1, q, m) == -2
+    assert not ctx
+    assert lib.ocvar_hip_max_markers(None) == -2
+    with pytest.raises(pkg.OcvarError):
+        pkg.Detector(1920, 1080, 1, max_quads=q, max_markers=m)
+
+
+def test_detectors_made_without_init_keep_the_default_stride(pkg):
+    det = pkg.Detector.__new__(pkg.Detector)
+    assert det.max_markers == pkg.MAX_MARKERS == 64 and det.max_quads == pkg.MAX_QUADS
+    pm, pc = det._prev_arrays([list(np.zeros(3, pkg.MARKER_DTYPE))], 1)
+    assert pm.shape == (1, 64) and pc.tolist() == [3]
