@@ -57,9 +57,14 @@ extern "C" int orc_registration(uint8_t* bgr, int w, int h, int stride, OrcMarke
             p[0] = p[1] = p[2] = g;
         }
     // B. frame pass (630-632)
-    std::vector<int> quads(8 * 4096);
-    int nq = orc_find_squares(gray.data(), w, h, w, quads.data(), 4096);
-    if (nq < 0) nq = 0;
+    // (the reference's square list is unbounded: a frame with more squares than the buffer holds is run again on a larger one,
+    // not taken as a frame without squares)
+    std::vector<int> quads;
+    int nq = -1;
+    for (int cap = 4096; nq < 0; cap *= 4) {
+        quads.assign(8 * (size_t)cap, 0);
+        nq = orc_find_squares(gray.data(), w, h, w, quads.data(), cap);
+    }
     std::vector<OrcPoint2f> squares((size_t)nq * 4);
     for (int i = 0; i < nq * 4; i++) {
         squares[i].x = (float)quads[2 * i];

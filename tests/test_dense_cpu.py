@@ -183,3 +183,67 @@ def test_detectors_made_without_init_keep_the_default_stride(pkg):
     assert det.max_markers == pkg.MAX_MARKERS == 64 and det.max_quads == pkg.MAX_QUADS
     pm, pc = det._prev_arrays([list(np.zeros(3, pkg.MARKER_DTYPE))], 1)
     assert pm.shape == (1, 64) and pc.tolist() == [3]
+
+
+# ---- the frame builders of tests/test_gpu_dense_limits.py hit their exact oracle counts ----
+
+LIMIT_QS = [1, 63, 64, 65, 255, 256, 2047, 2048, 2049, 4097, 16384]
+LIMIT_MS = [1, 7, 64, 65]
+
+
+def test_squares_frame_hits_every_exact_count_of_the_limit_tests():
+    import dense_synth as D
+    for n in sorted({n for q in LIMIT_QS for n in (q - 1, q, q + 1)}):
+        g = D.squares_frame(n)   # (asserts the oracle's count itself)
+        assert len(D.oracle_squares(g)) == n and g.shape[::-1] == D.frame_size_for(n)
+    for w, h in ((3839, 2157), (1001, 999)):   # (frame sides that are not multiples of 32, squares up to 4 px from the border)
+        n = len(D.square_slots(w, h, margin=4))
+        assert len(D.oracle_squares(D.squares_frame(n, w, h, margin=4))) == n
+    with pytest.raises(AssertionError):
+        D.squares_frame(len(D.square_slots(640, 480)) + 1, 640, 480)
+
+
+def test_squares_frame_around_a_marker_strip():
+    import dense_synth as D
+    names = D.library(3)
+    strip = D.marker_strip(1, names)
+    have = D.strip_squares(strip, 3840, 2160)
+    assert have >= 1
+    for n in (have + 4095, have + 4096):
+        g = D.squares_frame(n, 3840, 2160, marker_strip=strip)
+        assert len(D.oracle_squares(g)) == n and np.array_equal(g[:100, :100], strip)
+    tpls, cam = H.oracle_templates(names), H.oracle_camera(3840, 2160)
+    m, _, _ = H.oracle_registration(np.repeat(g[:, :, None], 3, axis=2), tpls, cam, max_markers=20000, max_cands=100000)
+    assert len(m) == 1 and m[0].templateId == 0   # (the strip's marker decodes; the solid squares give no candidate)
+
+
+def test_marker_frame_hits_every_exact_marker_count():
+    import dense_synth as D
+    names = D.library(66, seed=11)
+    tpls, cam = H.oracle_templates(names), H.oracle_camera(1920, 1080)
+    for k in sorted({k for m in LIMIT_MS for k in (m - 1, m, m + 1)}):
+        m, _, _ = H.oracle_registration(D.marker_frame(k, names), tpls, cam, max_markers=20000, max_cands=100000)
+        assert len(m) == k, (k, len(m))
+        assert sorted(r.templateId for r in m) == list(range(k))
+
+
+def test_concentric_frame_squares_nest():
+    import dense_synth as D
+    g = D.concentric_frame(3840, 2160)
+    sq = D.oracle_squares(g)
+    targets = len(range(20, 2160 - 120 - 20, 150)) * len(range(20, 3840 - 120 - 20, 150))
+    assert len(sq) >= 3 * targets
+
+
+def test_oracle_registration_sees_more_than_4096_squares():
+    """the reference's square list is unbounded: a frame past the oracle's first buffer is not a frame without squares"""
+    import dense_synth as D
+    g = D.squares_frame(4097)
+    sq = D.oracle_squares(g)
+    prev = (H.Marker * 1)()
+    prev[0].square[:] = [float(v) for v in sq[-1].reshape(-1)]
+    prev[0].aspectRatio = 1.0
+    h, w = g.shape
+    m, _, _ = H.oracle_registration(np.repeat(g[:, :, None], 3, axis=2), H.oracle_templates(), H.oracle_camera(w, h),
+                                    prev=list(prev), max_markers=16, max_cands=16)
+    assert len(m) >= 1 and list(m[0].square) == [float(v) for v in sq[-1].reshape(-1)]   # (tracked: the first record)
