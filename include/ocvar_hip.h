@@ -124,6 +124,19 @@ enum { OCVAR_FMT_BGR = 0, OCVAR_FMT_RGB = 1, OCVAR_FMT_BGRA = 2, OCVAR_FMT_RGBA 
  * format. */
 int ocvar_hip_set_input_format(OcvarHip* ctx, int format);
 
+/* Sub-pixel corner refinement (off by default): every marker record a batch writes, tracked or new, gets its four square
+ * corners refined on that frame's grey image with the equations of OpenCV's cornerSubPix (opencv-ar_amd/csrc/refine_core.h),
+ * and its glMatrix is solved from the refined corners.  Frame quads, crop quads, candidates, and which markers come out with
+ * which ids, templates and scores do not change.  With tracking, the refined squares a caller hands back as `prev` are what
+ * the next frame's 20-px rule compares.
+ *   half_win  0 (off) .. OCVAR_MAX_REFINE_HALF_WIN: the window is (2 half_win + 1)^2 px around the corner
+ *   max_iter  1 .. 100 steps per corner
+ *   eps       >= 0 px: a corner stops once a step moves it by at most eps
+ * ArUco's typical setting is 5 / 30 / 0.1.  OCVAR_E_ARG outside those ranges, before any device call.  Applies from the next
+ * enqueue (a batch in flight keeps the setting it was enqueued with). */
+enum { OCVAR_MAX_REFINE_HALF_WIN = 15 };
+int ocvar_hip_set_corner_refine(OcvarHip* ctx, int half_win, int max_iter, float eps);
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart
@@ -229,6 +242,9 @@ int ocvar_hip_pipe_set_result_limit(OcvarPipe* pipe, int max_per_frame);
 /* The input format of every context of the pipe (ocvar_hip_set_input_format), for detect_device, submit and track_device.
  * OCVAR_E_ARG for an unknown format or while a submitted chunk is in flight. */
 int ocvar_hip_pipe_set_input_format(OcvarPipe* pipe, int format);
+/* ocvar_hip_set_corner_refine on every context of the pipe.  OCVAR_E_ARG outside its ranges or while a submitted chunk is in
+ * flight. */
+int ocvar_hip_pipe_set_corner_refine(OcvarPipe* pipe, int half_win, int max_iter, float eps);
 
 /* Same, frames in host memory, h_bgr in the context's input format (copied over PCIe first; greyed frames are copied back
  * when requested -- never in OCVAR_FMT_GRAY, where the frames are their own grey). */

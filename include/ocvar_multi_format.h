@@ -17,6 +17,8 @@ typedef struct OcvarMulti OcvarMulti;
  * calls hold (OCVAR_FMT_*, default OCVAR_FMT_BGR; row_stride at least bytes per pixel times width).  OCVAR_E_ARG for an unknown
  * format. */
 int ocvar_multi_set_input_format(OcvarMulti* m, int format);
+/* ocvar_hip_set_corner_refine on every device's context (half_win 0 = off, the default).  OCVAR_E_ARG outside its ranges. */
+int ocvar_multi_set_corner_refine(OcvarMulti* m, int half_win, int max_iter, float eps);
 
 #ifdef __cplusplus
 }

@@ -91,4 +91,10 @@ int cvarArMultRegistration(IplImage* image, vector<CvarMarker>* markers, vector<
  * its oldest goes).  Call it where the reference's caller clears or releases the storage. */
 AC_DLL void cvarReleaseSquares(CvMemStorage* storage);
 
+/* EXTENSION (not in the reference's header): sub-pixel refinement of the corners cvarArMultRegistration returns, with the
+ * equations of OpenCV's cornerSubPix on the greyed frame (include/ocvar_hip.h: ocvar_hip_set_corner_refine).  Process-wide:
+ * applies to every later registration.  half_win 0 (the default) turns it off; 1..15 with max_iter 1..100 and eps >= 0 turn it
+ * on (5 / 30 / 0.1 is ArUco's typical setting).  Arguments outside those ranges are ignored (the setting stays as it was). */
+AC_DLL void cvarSetCornerRefine(int half_win, int max_iter, double eps);
+
 }  // extern "C"

@@ -24,7 +24,7 @@ MAX_QUADS_EX, MAX_QUADS_DENSE, MAX_MARKERS_DENSE = 1792, 16384, 4096   # ocvar_h
 HIP_SYMBOLS = [
     "ocvar_hip_create", "ocvar_hip_create_ex", "ocvar_hip_create_dense", "ocvar_hip_max_markers", "ocvar_hip_capacity_flags", "ocvar_hip_gate_create", "ocvar_hip_gate_destroy", "ocvar_hip_set_gate", "ocvar_hip_ready", "ocvar_hip_set_result_limit",
     "ocvar_hip_pipe_create", "ocvar_hip_pipe_destroy", "ocvar_hip_pipe_last_error", "ocvar_hip_pipe_set_templates", "ocvar_hip_pipe_set_camera",
-    "ocvar_hip_pipe_detect_device", "ocvar_hip_pipe_track_device", "ocvar_hip_pipe_submit", "ocvar_hip_pipe_collect", "ocvar_hip_pipe_in_flight", "ocvar_hip_pipe_set_result_limit", "ocvar_hip_set_input_format", "ocvar_hip_pipe_set_input_format", "ocvar_hip_enqueue_tracked", "ocvar_hip_build_info", "ocvar_hip_set_tuning", "ocvar_hip_destroy", "ocvar_hip_last_error", "ocvar_hip_set_templates", "ocvar_hip_set_camera",
+    "ocvar_hip_pipe_detect_device", "ocvar_hip_pipe_track_device", "ocvar_hip_pipe_submit", "ocvar_hip_pipe_collect", "ocvar_hip_pipe_in_flight", "ocvar_hip_pipe_set_result_limit", "ocvar_hip_set_input_format", "ocvar_hip_pipe_set_input_format", "ocvar_hip_set_corner_refine", "ocvar_hip_pipe_set_corner_refine", "ocvar_hip_enqueue_tracked", "ocvar_hip_build_info", "ocvar_hip_set_tuning", "ocvar_hip_destroy", "ocvar_hip_last_error", "ocvar_hip_set_templates", "ocvar_hip_set_camera",
     "ocvar_hip_detect_device", "ocvar_hip_enqueue", "ocvar_hip_collect", "ocvar_hip_detect_host", "ocvar_hip_find_squares",
     "ocvar_hip_debug_gray", "ocvar_hip_debug_binary", "ocvar_hip_debug_masks", "ocvar_hip_debug_frame_quads", "ocvar_hip_debug_candidates",
     "ocvar_hip_stage_ms", "ocvar_hip_stream", "ocvar_hip_stage_stamps", "ocvar_hip_counters", "ocvar_hip_results_to_device", "ocvar_hip_results_to_device_ex", "ocvar_hip_debug_calibrate",
@@ -52,6 +52,24 @@ def frame_shape_bpp(shape, fmt):
     elif len(shape) != 4 or shape[3] != bpp:
         raise ValueError(f"frames in this format are [n, H, W, {bpp}], got {tuple(shape)}")
     return shape[0], shape[1], shape[2]
+
+
+MAX_REFINE_HALF_WIN = 15   # include/ocvar_hip.h: OCVAR_MAX_REFINE_HALF_WIN
+
+
+def corner_refine_args(half_win, max_iter, eps):
+    """(half_win, max_iter, eps) of a corner refinement setting, checked: ValueError outside half_win 0..15 (0: off),
+    max_iter 1..100, eps >= 0"""
+    for name, v in (("half_win", half_win), ("max_iter", max_iter)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an int, got {v!r}")
+    if not 0 <= half_win <= MAX_REFINE_HALF_WIN:
+        raise ValueError(f"half_win must be 0 .. {MAX_REFINE_HALF_WIN}, got {half_win}")
+    if not 1 <= max_iter <= 100:
+        raise ValueError(f"max_iter must be 1 .. 100, got {max_iter}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not 0 <= float(eps) < 1e30:
+        raise ValueError(f"eps must be a number >= 0, got {eps!r}")
+    return int(half_win), int(max_iter), float(eps)
 
 
 STAGE_NAMES = ["binarise_frames", "follow1_frames", "follow2_frames", "follow3_frames", "order_crops", "binarise_crops",
@@ -129,6 +147,8 @@ def hip_lib():
         lib.ocvar_hip_pipe_set_result_limit.argtypes = [vp, i]
         lib.ocvar_hip_pipe_set_input_format.argtypes = [vp, i]
         lib.ocvar_hip_set_input_format.argtypes = [vp, i]
+        lib.ocvar_hip_set_corner_refine.argtypes = [vp, i, i, C.c_float]
+        lib.ocvar_hip_pipe_set_corner_refine.argtypes = [vp, i, i, C.c_float]
         lib.ocvar_hip_enqueue_tracked.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, vp]
         lib.ocvar_hip_set_tuning.argtypes = [vp, i, i]
         lib.ocvar_hip_build_info.argtypes = []
@@ -264,6 +284,12 @@ class Pipe:
         code = input_format_code(fmt)
         self._check(self._lib.ocvar_hip_pipe_set_input_format(self._p, code), "pipe_set_input_format")
         self.input_format = code
+
+    def set_corner_refine(self, half_win=5, max_iter=30, eps=0.1):
+        """sub-pixel corner refinement of every context (Detector.set_corner_refine); half_win=0 turns it off.  OcvarError while a
+        submitted chunk is in flight"""
+        w, it, e = corner_refine_args(half_win, max_iter, eps)
+        self._check(self._lib.ocvar_hip_pipe_set_corner_refine(self._p, w, it, e), "pipe_set_corner_refine")
 
     def detect_device(self, d_ptr, width, height, n_frames, row_stride=None, frame_stride=None, grey_in_place=False, max_per_frame=MAX_MARKERS):
         row_stride = row_stride or FORMAT_BPP[self.input_format] * width
@@ -435,6 +461,13 @@ class Detector:
         code = input_format_code(fmt)
         self._check(self._lib.ocvar_hip_set_input_format(self._ctx, code), "set_input_format")
         self.input_format = code
+
+    def set_corner_refine(self, half_win=5, max_iter=30, eps=0.1):
+        """sub-pixel refinement of the output markers' corners on the grey frame (OpenCV's cornerSubPix equations:
+        include/ocvar_hip.h, ocvar_hip_set_corner_refine), and poses solved from the refined corners, from the next batch on.
+        half_win 0 (the default of a new detector) turns it off; 5 / 30 / 0.1 is ArUco's typical setting."""
+        w, it, e = corner_refine_args(half_win, max_iter, eps)
+        self._check(self._lib.ocvar_hip_set_corner_refine(self._ctx, w, it, e), "set_corner_refine")
 
     TUNE = {"crop_phases": 1, "mid_steps": 2, "mid_blocks": 3, "long_blocks": 4, "short_blocks": 5, "min_units": 6, "hp_mask": 7, "gate_mode": 8}
 

@@ -35,6 +35,7 @@ struct OcvarHip {
     OcvarGate* gate = nullptr;
     int result_limit = OCVAR_MAX_MARKERS;   // marker records per frame copied to the host (ocvar_hip_set_result_limit)
     int input_format = OCVAR_FMT_BGR;       // what the frames of the next batch hold (ocvar_hip_set_input_format)
+    RefineArgs refine{};                    // corner refinement of the next batch (ocvar_hip_set_corner_refine): half_win 0 = off
     int tune[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // ocvar_hip_set_tuning: 0 = default
     Workspace ws{};
     hipStream_t stream = nullptr;
@@ -575,7 +576,7 @@ static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int 
         launch_decode(w, cur);
         TRACE_LAUNCH("decode", cur);
         HIP_TRY(c, stage(10, 8));
-        launch_finalise(w, cur);
+        launch_finalise(w, c->refine, cur);
         TRACE_LAUNCH("finalise", cur);
         HIP_TRY(c, stage(11, -1));
         HIP_TRY(c, hipMemcpyAsync(c->h_counts, w.n_markers, n_frames * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -693,6 +694,17 @@ extern "C" int ocvar_hip_set_input_format(OcvarHip* c, int format) {
         return OCVAR_E_ARG;
     }
     c->input_format = format;
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_set_corner_refine(OcvarHip* c, int half_win, int max_iter, float eps) {
+    if (!c) return OCVAR_E_ARG;
+    if (half_win < 0 || half_win > OCVAR_MAX_REFINE_HALF_WIN || max_iter < 1 || max_iter > 100 || !(eps >= 0.0f) || eps > 3.0e38f) {
+        c->err = "corner refinement: half_win 0..15, max_iter 1..100, eps >= 0";
+        return OCVAR_E_ARG;
+    }
+    // (the batch in flight, if any, took its own copy into its launch arguments)
+    c->refine = refine_args_make(half_win, max_iter, eps);
     return OCVAR_OK;
 }
 

@@ -257,7 +257,7 @@ void launch_decode(const Workspace& ws, hipStream_t stream) {
     if (ws.dense) hipLaunchKernelGGL(decode_kernel<true>, dim3(ws.n_frames * ws.decode_slices), dim3(64), lds, stream, ws);
     else hipLaunchKernelGGL(decode_kernel<false>, dim3(ws.n_frames * DECODE_SLICES), dim3(64), lds, stream, ws);
 }
-void launch_finalise(const Workspace& ws, hipStream_t stream) {
+void launch_finalise(const Workspace& ws, const RefineArgs& refine, hipStream_t stream) {
     if (ws.n_frames <= 0) return;
     // a stateless frame keeps at most one marker per template: a grid of one wave per 8 frames takes a batch's poses in one
     // pass; stateful batches with many tracked markers per frame loop (grid-stride).  A dense context sizes the grid for its
@@ -270,6 +270,7 @@ void launch_finalise(const Workspace& ws, hipStream_t stream) {
     } else {
         hipLaunchKernelGGL(finalise_kernel<false>, dim3(ws.n_frames), dim3(64), (size_t)(ws.n_groups + ws.maxq) * sizeof(int), stream, ws);
     }
+    if (refine.half_win > 0) launch_refine_corners(ws, refine, stream);
     hipLaunchKernelGGL(pose_kernel, dim3(blocks), dim3(64), 0, stream, ws);
 }
 

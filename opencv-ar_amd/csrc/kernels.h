@@ -4,6 +4,7 @@
 #include "decode_core.h"
 #include "pose_core.h"
 #include "tail_core.h"
+#include "refine_core.h"
 #include "ocvar_hip.h"
 
 namespace ocvar {
@@ -145,6 +146,8 @@ void launch_follow_long_frames(const Workspace& ws, hipStream_t stream);
 void launch_follow_long_crops(const Workspace& ws, hipStream_t stream);
 void launch_order_and_crops(const Workspace& ws, hipStream_t stream);   // (dense contexts: the sort, replay and crop kernels)
 void launch_decode(const Workspace& ws, hipStream_t stream);
-void launch_finalise(const Workspace& ws, hipStream_t stream);
+// (refine.half_win > 0: refine_corners_kernel between the marker records and the poses, refine.hip)
+void launch_finalise(const Workspace& ws, const RefineArgs& refine, hipStream_t stream);
+void launch_refine_corners(const Workspace& ws, const RefineArgs& refine, hipStream_t stream);
 
 }  // namespace ocvar

@@ -242,6 +242,16 @@ extern "C" int ocvar_hip_pipe_set_input_format(OcvarPipe* p, int format) {
     return OCVAR_OK;
 }
 
+extern "C" int ocvar_hip_pipe_set_corner_refine(OcvarPipe* p, int half_win, int max_iter, float eps) {
+    if (!p) return OCVAR_E_ARG;
+    if (p->head != p->tail) { p->err = "a submitted chunk is in flight: collect it first"; return OCVAR_E_ARG; }
+    for (OcvarHip* c : p->ctx) {
+        const int rc = ocvar_hip_set_corner_refine(c, half_win, max_iter, eps);
+        if (rc) { p->err = ocvar_hip_last_error(c); return rc; }
+    }
+    return OCVAR_OK;
+}
+
 extern "C" int ocvar_hip_pipe_set_result_limit(OcvarPipe* p, int max_per_frame) {
     if (!p || p->head != p->tail || max_per_frame < 1 || max_per_frame > OCVAR_MAX_MARKERS) return OCVAR_E_ARG;
     for (OcvarHip* c : p->ctx) {

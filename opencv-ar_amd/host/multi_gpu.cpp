@@ -153,6 +153,15 @@ extern "C" int ocvar_multi_set_input_format(OcvarMulti* m, int format) {
     return OCVAR_OK;
 }
 
+extern "C" int ocvar_multi_set_corner_refine(OcvarMulti* m, int half_win, int max_iter, float eps) {
+    if (!m) return OCVAR_E_ARG;
+    for (int d = 0; d < m->n; d++) {
+        const int rc = ocvar_hip_set_corner_refine(m->ctx[d], half_win, max_iter, eps);
+        if (rc) { m->err = ocvar_hip_last_error(m->ctx[d]); return rc; }
+    }
+    return OCVAR_OK;
+}
+
 // tracked: every device takes its frames' previous markers from its device-resident state (stream s = local slot s / N of
 // device s mod N) and leaves the new ones there, behind the kernels on its own stream.
 static int multi_run(OcvarMulti* m, uint8_t* const* d_bgr, int width, int height, int row_stride, size_t frame_stride,

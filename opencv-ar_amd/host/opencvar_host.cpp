@@ -90,6 +90,8 @@ std::map<const void*, std::deque<std::unique_ptr<OwnedSeq>>> g_seqs;
 std::vector<CvarTemplate> g_templates;        // what the context currently holds: unchanged arguments are not uploaded again
 CvarCamera g_camera;
 bool g_have_camera = false;
+int g_refine_w = 0, g_refine_iter = 30;   // cvarSetCornerRefine: applied to g_ctx and to every context made later
+float g_refine_eps = 0.1f;
 
 OcvarHip* context_for(int w, int h, int maxq = 0, int maxm = 0) {
     if (maxq <= 0) maxq = g_maxq;
@@ -116,6 +118,7 @@ OcvarHip* context_for(int w, int h, int maxq = 0, int maxm = 0) {
         g_ctx = nullptr;
         return nullptr;
     }
+    (void)ocvar_hip_set_corner_refine(g_ctx, g_refine_w, g_refine_iter, g_refine_eps);   // (checked when it was set)
     g_w = w < 64 ? 64 : w;
     g_h = h < 64 ? 64 : h;
     g_maxq = maxq;
@@ -429,6 +432,19 @@ int cvarTrack(CvPoint2D32f pt1[4], CvPoint2D32f pt2[4]) { return ocvar::track_sq
 void cvarReleaseSquares(CvMemStorage* storage) {   // extension (not in the reference's header): see g_seqs
     std::lock_guard<std::mutex> lock(g_mu);
     g_seqs.erase(storage);
+}
+
+void cvarSetCornerRefine(int half_win, int max_iter, double eps) {   // extension (not in the reference's header)
+    std::lock_guard<std::mutex> lock(g_mu);
+    if (half_win < 0 || half_win > OCVAR_MAX_REFINE_HALF_WIN || max_iter < 1 || max_iter > 100 || !(eps >= 0.0) || eps > 1e30) {
+        std::fprintf(stderr, "opencvar: cvarSetCornerRefine(%d, %d, %g) ignored: half_win 0..15, max_iter 1..100, eps >= 0\n", half_win,
+                     max_iter, eps);
+        return;
+    }
+    g_refine_w = half_win;
+    g_refine_iter = max_iter;
+    g_refine_eps = (float)eps;
+    if (g_ctx) (void)ocvar_hip_set_corner_refine(g_ctx, g_refine_w, g_refine_iter, g_refine_eps);
 }
 
 CvSeq* cvarFindSquares(IplImage* img, CvMemStorage* storage) {
