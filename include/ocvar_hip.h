@@ -137,6 +137,39 @@ int ocvar_hip_set_input_format(OcvarHip* ctx, int format);
 enum { OCVAR_MAX_REFINE_HALF_WIN = 15 };
 int ocvar_hip_set_corner_refine(OcvarHip* ctx, int half_win, int max_iter, float eps);
 
+/* Planar marker board (off by default): one rigid pose per frame from every board marker the frame's records hold -- ArUco's
+ * estimatePoseBoard, ARToolKit's multi-marker set (opencv-ar_amd/csrc/board_core.h).  An entry names a template and the board
+ * plane (z = 0) coordinates of the marker's corners 0..3.  Corner c is the point the code[0] readout puts at corner c of the
+ * readout's destination rectangle (0,0), (W-1,0), (W-1,H-1), (0,H-1); since templates are loaded flipped vertically, corners 0..3
+ * are the template image's bottom-left, bottom-right, top-right and top-left corners (and corners 0..3 of OcvarSynthMarker.corner
+ * for a marker ocvar_synth_* draws).
+ * Per frame the board takes, of every entry, the first record in output order with score > 0 and the entry's template, reads
+ * that record's code again on the frame's grey image at the record's square (refined when corner refinement is on) to find which
+ * record corner is which board corner (no match: the marker is not used), seeds from the (up to) 4 used markers of largest image
+ * area and refines with Levenberg-Marquardt over all used corners, with the context's camera (intrinsics and distortion).
+ * Entries whose template is absent from the current library, or is not square (width != height), never match.
+ * ocvar_hip_set_board: n = 0 turns the board off; OCVAR_E_ARG, before any device call, for n outside 0..OCVAR_MAX_BOARD_MARKERS,
+ * a template id outside 0..OCVAR_MAX_TEMPLATES-1 or repeated, a coordinate that is not finite, corners that are not a convex quad
+ * of non-zero area, or while the context has a batch that has not been collected.  Applies from the next enqueue.  With no board
+ * nothing changes: no launch, no copy.  Markers and counts never depend on the board. */
+enum { OCVAR_MAX_BOARD_MARKERS = 256 };
+/* one marker of a planar board: its template and the board-plane (z = 0) coordinates of its 4 corners; 72 bytes */
+typedef struct { int templateId; int pad; double corner[8]; } OcvarBoardMarker;
+typedef struct {
+    double glMatrix[16];     /* board frame -> GL modelview, the convention of a marker record (cvarGlMatrix) */
+    double rvec[3], tvec[3]; /* OpenCV convention: X_cam = R(rvec) X_board + tvec, in board units */
+    double rms;              /* RMS reprojection error over the corners used, px */
+    int n_markers;           /* board markers used in this frame */
+    int status;              /* 1 solved, 0 no board marker found, -1 not solvable (degenerate seeds / non-finite) */
+} OcvarBoardPose;            /* 192 bytes */
+int ocvar_hip_set_board(OcvarHip* ctx, const OcvarBoardMarker* markers, int n);
+/* The poses [n_frames] of the last collected batch (all frames of an ocvar_hip_detect_host call); OCVAR_E_ARG when that batch had
+ * no board, or for n_frames outside 1 .. its frame count. */
+int ocvar_hip_board_poses(OcvarHip* ctx, OcvarBoardPose* poses, int n_frames);
+/* After ocvar_hip_enqueue (like ocvar_hip_results_to_device): stream-ordered copy of the batch's poses into d_poses [n_frames]
+ * in device memory.  OCVAR_E_ARG when nothing is enqueued or the batch has no board. */
+int ocvar_hip_board_poses_to_device(OcvarHip* ctx, OcvarBoardPose* d_poses, void* stream);
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart

@@ -40,6 +40,13 @@ void ocvar_synth_config(int config_id /* 1,2,3,5 = BASELINE.json configs */, Ocv
 int ocvar_synth_frame(const OcvarSynthConfig* cfg, uint64_t frame_index, const OcvarSynthTemplate* templates,
                       int n_templates, uint8_t* bgr, int stride, OcvarSynthMarker* truth, int max_truth);
 
+/* Draws n templates at given image quads over the frame the caller has filled (8UC3, equal channels): marker k is
+ * templates[template_index[k]] with the unit square (0,0) (1,0) (1,1) (0,1) at quads[8k .. 8k+7] (corners 0..3, as
+ * OcvarSynthMarker.corner), the same mapping and 4x4 supersampling as ocvar_synth_frame, no quiet zone.  Returns the number
+ * of markers drawn (a degenerate quad or a template index outside 0..n_templates-1 is skipped). */
+int ocvar_synth_draw_quads(uint8_t* bgr, int width, int height, int stride, const OcvarSynthTemplate* templates, int n_templates,
+                           const int* template_index, const double* quads, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_detect_device", "ocvar_hip_enqueue", "ocvar_hip_collect", "ocvar_hip_detect_host", "ocvar_hip_find_squares",
     "ocvar_hip_debug_gray", "ocvar_hip_debug_binary", "ocvar_hip_debug_masks", "ocvar_hip_debug_frame_quads", "ocvar_hip_debug_candidates",
     "ocvar_hip_stage_ms", "ocvar_hip_stream", "ocvar_hip_stage_stamps", "ocvar_hip_counters", "ocvar_hip_results_to_device", "ocvar_hip_results_to_device_ex", "ocvar_hip_debug_calibrate",
+    "ocvar_hip_set_board", "ocvar_hip_board_poses", "ocvar_hip_board_poses_to_device",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -70,6 +71,33 @@ def corner_refine_args(half_win, max_iter, eps):
     if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not 0 <= float(eps) < 1e30:
         raise ValueError(f"eps must be a number >= 0, got {eps!r}")
     return int(half_win), int(max_iter), float(eps)
+
+
+MAX_BOARD_MARKERS = 256   # include/ocvar_hip.h: OCVAR_MAX_BOARD_MARKERS
+
+
+class BoardMarker(C.Structure):  # OcvarBoardMarker: a template and the board-plane (z = 0) coordinates of its corners 0..3
+    _fields_ = [("templateId", C.c_int), ("pad", C.c_int), ("corner", C.c_double * 8)]
+
+
+# OcvarBoardPose: glMatrix (board frame -> GL modelview, as a marker record's), rvec / tvec (OpenCV: X_cam = R(rvec) X_board +
+# tvec), rms (px), n_markers (board markers used), status (1 solved, 0 no board marker, -1 not solvable)
+BOARD_DTYPE = np.dtype([("glMatrix", "<f8", (16,)), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("rms", "<f8"),
+                        ("n_markers", "<i4"), ("status", "<i4")], align=True)
+assert C.sizeof(BoardMarker) == 72 and BOARD_DTYPE.itemsize == 192
+
+
+def grid_board(template_ids, cols, rows, length, separation):
+    """A planar grid board (ArUco's GridBoard): marker k carries template_ids[k] and sits at column k % cols, row k // cols;
+    its corners 0..3 are (x0, y0), (x0 + L, y0), (x0 + L, y0 + L), (x0, y0 + L) with x0 = col (L + s), y0 = row (L + s).
+    Returns [(template_id, 4x2 corners)] for Detector.set_board."""
+    if len(template_ids) > cols * rows:
+        raise ValueError(f"{len(template_ids)} templates for a {cols} x {rows} grid")
+    out = []
+    for k, t in enumerate(template_ids):
+        x0, y0 = (k % cols) * (length + separation), (k // cols) * (length + separation)
+        out.append((int(t), np.array([[x0, y0], [x0 + length, y0], [x0 + length, y0 + length], [x0, y0 + length]], np.float64)))
+    return out
 
 
 STAGE_NAMES = ["binarise_frames", "follow1_frames", "follow2_frames", "follow3_frames", "order_crops", "binarise_crops",
@@ -176,6 +204,9 @@ def hip_lib():
         lib.ocvar_hip_results_to_device.argtypes = [vp, vp, vp, vp]
         lib.ocvar_hip_results_to_device_ex.argtypes = [vp, vp, vp, i, vp]
         lib.ocvar_hip_debug_calibrate.argtypes = [vp, sz]
+        lib.ocvar_hip_set_board.argtypes = [vp, vp, i]
+        lib.ocvar_hip_board_poses.argtypes = [vp, vp, i]
+        lib.ocvar_hip_board_poses_to_device.argtypes = [vp, vp, vp]
         _hip = lib
     return _hip
 
@@ -468,6 +499,30 @@ class Detector:
         half_win 0 (the default of a new detector) turns it off; 5 / 30 / 0.1 is ArUco's typical setting."""
         w, it, e = corner_refine_args(half_win, max_iter, eps)
         self._check(self._lib.ocvar_hip_set_corner_refine(self._ctx, w, it, e), "set_corner_refine")
+
+    def set_board(self, entries):
+        """A planar marker board, from the next batch on: entries = [(template_id, 4x2 board-plane corners)] (grid_board makes
+        them; corners 0..3 as include/ocvar_hip.h defines them), up to MAX_BOARD_MARKERS; None or [] turns it off (the default).
+        Every collected batch then has one pose per frame: board_poses()."""
+        entries = [] if entries is None else list(entries)
+        arr = (BoardMarker * max(len(entries), 1))()
+        for k, (t, corners) in enumerate(entries):
+            c = np.asarray(corners, np.float64)
+            if c.shape != (4, 2):
+                raise ValueError(f"board entry {k}: corners must be 4 x 2, got {c.shape}")
+            arr[k].templateId = int(t)
+            arr[k].corner[:] = c.reshape(8).tolist()
+        self._check(self._lib.ocvar_hip_set_board(self._ctx, arr, len(entries)), "set_board")
+
+    def board_poses(self):
+        """[n] BOARD_DTYPE: the board pose of every frame of the last collected batch (all frames of a detect_host call)"""
+        out = np.zeros(self._n, BOARD_DTYPE)
+        self._check(self._lib.ocvar_hip_board_poses(self._ctx, _ptr(out), self._n), "board_poses")
+        return out
+
+    def board_poses_to_device(self, d_poses_ptr, stream=None):
+        """after enqueue: stream-ordered copy of the batch's [n] board poses (192 bytes each) into caller-owned device memory"""
+        self._check(self._lib.ocvar_hip_board_poses_to_device(self._ctx, d_poses_ptr, stream), "board_poses_to_device")
 
     TUNE = {"crop_phases": 1, "mid_steps": 2, "mid_blocks": 3, "long_blocks": 4, "short_blocks": 5, "min_units": 6, "hp_mask": 7, "gate_mode": 8}
 

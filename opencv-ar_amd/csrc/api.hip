@@ -20,6 +20,8 @@ static_assert(sizeof(TemplateRec) == sizeof(OcvarTemplate) && sizeof(TemplateRec
 static_assert(MAX_SIZE_CLASSES == OCVAR_MAX_TEMPLATE_SIZES, "size classes");
 static_assert(sizeof(CameraRec) == sizeof(OcvarCamera) && sizeof(CameraRec) == 248, "CvarCamera layout");
 static_assert(sizeof(MarkerRec) == sizeof(OcvarMarker) && sizeof(MarkerRec) == 184, "CvarMarker layout");
+static_assert(sizeof(BoardEntry) == sizeof(OcvarBoardMarker) && sizeof(BoardEntry) == 72, "OcvarBoardMarker layout");
+static_assert(sizeof(BoardPose) == sizeof(OcvarBoardPose) && sizeof(BoardPose) == 192, "OcvarBoardPose layout");
 
 // At most `width` binarise kernels of the contexts that share the gate run at once: launch n waits (on its stream) for the
 // event recorded behind launch n - width.  Host side only keeps the ring of events.
@@ -62,6 +64,16 @@ struct OcvarHip {
     Library lib;              // the templates' table as uploaded (ocvar_hip_debug_candidates expands a square with it)
     size_t sq_codes_bytes = 0, sq_match_bytes = 0;   // allocations of ws.sq_codes / ws.sq_match (they grow with the library)
     int capacity_flags = 0;   // flag word of the last batch that failed with OCVAR_E_CAPACITY
+    // planar board (ocvar_hip_set_board): the device table is allocated by the first board set
+    int board_n = 0;                        // entries of the next batch's board, 0: off
+    BoardEntry* d_board = nullptr;          // [OCVAR_MAX_BOARD_MARKERS]
+    int* d_board_map = nullptr;             // [MAXT] templateId -> board index, -1
+    BoardPose* d_board_poses = nullptr;     // [max_batch]
+    BoardPose* h_board_poses = nullptr;     // pinned [max_batch]
+    bool batch_board = false;               // the enqueued batch runs the board kernel
+    std::vector<BoardPose> board_out;       // the poses of the last collected batch (ocvar_hip_board_poses)
+    bool board_out_valid = false;
+    int board_out_off = 0;                  // where collect puts a batch's poses in board_out (detect_host's sub-batches)
     std::string err;
 };
 
@@ -239,6 +251,7 @@ extern "C" void ocvar_hip_destroy(OcvarHip* c) {
     if (c->h_prev) (void)hipHostFree(c->h_prev);
     if (c->h_prev_counts) (void)hipHostFree(c->h_prev_counts);
     if (c->h_counters) (void)hipHostFree(c->h_counters);
+    if (c->h_board_poses) (void)hipHostFree(c->h_board_poses);
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : c->h2d_done) (void)hipEventDestroy(e);
@@ -427,6 +440,7 @@ static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int 
         return OCVAR_E_ARG;
     }
     HIP_TRY(c, hipSetDevice(c->device));
+    c->batch_board = false;
     w.W = width;
     w.H = height;
     w.sw = width & ~1;
@@ -579,6 +593,12 @@ static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int 
         launch_finalise(w, c->refine, cur);
         TRACE_LAUNCH("finalise", cur);
         HIP_TRY(c, stage(11, -1));
+        if (c->board_n > 0) {   // (no board: no launch, no copy)
+            launch_board_poses(w, BoardArgs{c->board_n, c->d_board, c->d_board_map, c->d_board_poses}, s);
+            TRACE_LAUNCH("board", s);
+            HIP_TRY(c, hipMemcpyAsync(c->h_board_poses, c->d_board_poses, n_frames * sizeof(BoardPose), hipMemcpyDeviceToHost, s));
+            c->batch_board = true;
+        }
         HIP_TRY(c, hipMemcpyAsync(c->h_counts, w.n_markers, n_frames * sizeof(int), hipMemcpyDeviceToHost, s));
         if (c->result_limit >= w.maxm)
             HIP_TRY(c, hipMemcpyAsync(c->h_markers, w.markers, (size_t)n_frames * w.maxm * sizeof(MarkerRec), hipMemcpyDeviceToHost, s));
@@ -653,9 +673,20 @@ extern "C" int ocvar_hip_results_to_device_ex(OcvarHip* c, OcvarMarker* d_marker
 
 extern "C" int ocvar_hip_collect(OcvarHip* c, OcvarMarker* markers, int* counts, int max_per_frame) {
     if (!c || !counts || max_per_frame < 0 || (max_per_frame > 0 && !markers)) return OCVAR_E_ARG;
+    if (c->board_out_off == 0) c->board_out_valid = false;
     int rc = wait_impl(c);
     if (rc) return rc;
     const int n = c->ws.n_frames;
+    if (c->batch_board) {   // (a detect_host call gathers the poses of all its sub-batches)
+        const size_t off = (size_t)c->board_out_off;
+        if (off == 0 || c->board_out_valid) {
+            c->board_out.resize(off + n);
+            std::memcpy(c->board_out.data() + off, c->h_board_poses, n * sizeof(BoardPose));
+            c->board_out_valid = true;
+        }
+    } else {
+        c->board_out_valid = false;
+    }
     for (int f = 0; f < n; f++) {
         counts[f] = c->h_counts[f];
         int k = counts[f] < max_per_frame ? counts[f] : max_per_frame;
@@ -705,6 +736,64 @@ extern "C" int ocvar_hip_set_corner_refine(OcvarHip* c, int half_win, int max_it
     }
     // (the batch in flight, if any, took its own copy into its launch arguments)
     c->refine = refine_args_make(half_win, max_iter, eps);
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_set_board(OcvarHip* c, const OcvarBoardMarker* markers, int n) {
+    if (!c) return OCVAR_E_ARG;
+    if (n < 0 || n > OCVAR_MAX_BOARD_MARKERS || (n > 0 && !markers)) {
+        c->err = "ocvar_hip_set_board: n is 0 .. 256";
+        return OCVAR_E_ARG;
+    }
+    const BoardEntry* e = reinterpret_cast<const BoardEntry*>(markers);
+    const int bad = board_first_bad(e, n);
+    if (bad >= 0) {
+        c->err = "ocvar_hip_set_board: entry " + std::to_string(bad) +
+                 ": template id outside 0..4095 or repeated, or corners not a finite convex quad of non-zero area";
+        return OCVAR_E_ARG;
+    }
+    if (c->pending) {
+        c->err = "the previous batch of this context has not been collected";
+        return OCVAR_E_ARG;
+    }
+    if (n == 0) {
+        c->board_n = 0;
+        return OCVAR_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->h_board_poses) {   // (the pinned block last: its presence says that all four exist)
+        int rc = dev_alloc(c, &c->d_board, BOARD_MAX);
+        if (!rc) rc = dev_alloc(c, &c->d_board_map, MAXT);
+        if (!rc) rc = dev_alloc(c, &c->d_board_poses, (size_t)c->ws.max_batch);
+        if (rc) return rc;
+        HIP_TRY(c, hipHostMalloc((void**)&c->h_board_poses, (size_t)c->ws.max_batch * sizeof(BoardPose)));
+    }
+    std::vector<int> map(MAXT, -1);
+    for (int i = 0; i < n; i++) map[e[i].templateId] = i;
+    // (no batch is in flight: the kernel that read the old table has finished)
+    HIP_TRY(c, hipMemcpy(c->d_board, e, n * sizeof(BoardEntry), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_board_map, map.data(), MAXT * sizeof(int), hipMemcpyHostToDevice));
+    c->board_n = n;
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_board_poses(OcvarHip* c, OcvarBoardPose* poses, int n_frames) {
+    if (!c || !poses) return OCVAR_E_ARG;
+    if (!c->board_out_valid) {
+        c->err = "ocvar_hip_board_poses: the last collected batch had no board";
+        return OCVAR_E_ARG;
+    }
+    if (n_frames < 1 || (size_t)n_frames > c->board_out.size()) return OCVAR_E_ARG;
+    std::memcpy(poses, c->board_out.data(), (size_t)n_frames * sizeof(BoardPose));
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_board_poses_to_device(OcvarHip* c, OcvarBoardPose* d_poses, void* stream) {
+    if (!c || !d_poses || !c->pending || !c->batch_board) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->last_stream;
+    if (s != c->last_stream) HIP_TRY(c, hipStreamWaitEvent(s, c->ev[12], 0));   // order behind the batch
+    HIP_TRY(c, hipMemcpyAsync(d_poses, c->d_board_poses, (size_t)c->ws.n_frames * sizeof(BoardPose), hipMemcpyDeviceToDevice, s));
     return OCVAR_OK;
 }
 
@@ -856,6 +945,8 @@ extern "C" int ocvar_hip_detect_host(OcvarHip* c, uint8_t* h_bgr, int width, int
         (void)hipStreamSynchronize(c->stream);
         if (copier_ref && copier_ref->joinable()) copier_ref->join();
         c->pending = false;
+        c->board_out_off = 0;
+        c->board_out_valid = false;
         return code;
     };
 #define HIP_TRY_HOST(expr)                                            \
@@ -915,7 +1006,9 @@ extern "C" int ocvar_hip_detect_host(OcvarHip* c, uint8_t* h_bgr, int width, int
         // while sub-batch k computes: bring sub-batch k-1's grey home, then stage sub-batch k+1 into the slot it leaves
         if (k > 0 && grey_in_place) HIP_TRY_HOST(grey_home(k - 1));
         if (k + 1 < n_sub) HIP_TRY_HOST(upload(k + 1));
+        c->board_out_off = k * sub;
         rc = ocvar_hip_collect(c, markers ? markers + (size_t)k * sub * max_per_frame : nullptr, counts + k * sub, max_per_frame);
+        c->board_out_off = 0;
         if (rc) return fail(rc);
         if (grey_in_place)   // (the kernels of sub-batch k have finished: collect waited for them)
             // (slot k & 1 last held sub-batch k - 2, whose copy-back thread was joined when sub-batch k - 1's was started)

@@ -5,6 +5,7 @@
 #include "pose_core.h"
 #include "tail_core.h"
 #include "refine_core.h"
+#include "board_core.h"
 #include "ocvar_hip.h"
 
 namespace ocvar {
@@ -149,5 +150,16 @@ void launch_decode(const Workspace& ws, hipStream_t stream);
 // (refine.half_win > 0: refine_corners_kernel between the marker records and the poses, refine.hip)
 void launch_finalise(const Workspace& ws, const RefineArgs& refine, hipStream_t stream);
 void launch_refine_corners(const Workspace& ws, const RefineArgs& refine, hipStream_t stream);
+
+// A batch's board (ocvar_hip_set_board), passed by value in the launch arguments: n entries (0: off) and the context's device
+// table -- entries [OCVAR_MAX_BOARD_MARKERS], templateId -> board index map [MAXT] (-1: not on the board), poses [max_batch].
+struct BoardArgs {
+    int n;
+    const BoardEntry* entries;
+    const int* map;
+    BoardPose* poses;
+};
+// (board.n > 0: board_pose_kernel, one wave per frame, after launch_finalise; board.hip)
+void launch_board_poses(const Workspace& ws, const BoardArgs& board, hipStream_t stream);
 
 }  // namespace ocvar

@@ -105,6 +105,64 @@ inline int sample(const MarkerDraw& m, double px, double py) {
 
 }  // namespace
 
+// one marker's pixels inside [bx0, bx1) x [by0, by1): flat cells keep their class, edge pixels are averaged over 4x4 samples
+static void draw_marker(const MarkerDraw& md, uint8_t* bgr, int stride, int bx0, int bx1, int by0, int by1) {
+    for (int y = by0; y < by1; y++) {
+        uint8_t* row = bgr + (size_t)y * stride;
+        for (int x = bx0; x < bx1; x++) {
+            int c00 = sample(md, x + 0.0625, y + 0.0625), c10 = sample(md, x + 0.9375, y + 0.0625);
+            int c01 = sample(md, x + 0.0625, y + 0.9375), c11 = sample(md, x + 0.9375, y + 0.9375);
+            int bg = row[3 * x];
+            int val;
+            if (c00 == c10 && c00 == c01 && c00 == c11) {
+                val = c00 < 0 ? bg : c00;
+            } else {
+                int sum = 0;
+                for (int sy = 0; sy < 4; sy++)
+                    for (int sx = 0; sx < 4; sx++) {
+                        int c = sample(md, x + (sx + 0.5) * 0.25, y + (sy + 0.5) * 0.25);
+                        sum += c < 0 ? bg : c;
+                    }
+                val = (sum + 8) >> 4;
+            }
+            row[3 * x] = row[3 * x + 1] = row[3 * x + 2] = (uint8_t)val;
+        }
+    }
+}
+
+extern "C" int ocvar_synth_draw_quads(uint8_t* bgr, int W, int H, int stride, const OcvarSynthTemplate* templates, int n_templates,
+                                      const int* template_index, const double* quads, int n) {
+    int drawn = 0;
+    for (int k = 0; k < n; k++) {
+        const double* quad = quads + 8 * k;
+        const int ti = template_index[k];
+        if (ti < 0 || ti >= n_templates) continue;
+        MarkerDraw md;
+        double Hm[9];
+        if (!square_to_quad(quad, Hm) || !invert3(Hm, md.Hinv)) continue;
+        md.tpl = &templates[ti];
+        md.quiet = 0.0;
+        md.occl_corner = -1;
+        md.occl_size = 0.0;
+        double x0 = quad[0], x1 = quad[0], y0 = quad[1], y1 = quad[1];
+        for (int c = 1; c < 4; c++) {
+            x0 = fmin(x0, quad[2 * c]);
+            x1 = fmax(x1, quad[2 * c]);
+            y0 = fmin(y0, quad[2 * c + 1]);
+            y1 = fmax(y1, quad[2 * c + 1]);
+        }
+        int bx0 = (int)floor(x0) - 1, bx1 = (int)ceil(x1) + 1, by0 = (int)floor(y0) - 1, by1 = (int)ceil(y1) + 1;
+        bx0 = bx0 < 0 ? 0 : bx0;
+        by0 = by0 < 0 ? 0 : by0;
+        bx1 = bx1 > W ? W : bx1;
+        by1 = by1 > H ? H : by1;
+        if (bx0 >= bx1 || by0 >= by1) continue;
+        draw_marker(md, bgr, stride, bx0, bx1, by0, by1);
+        drawn++;
+    }
+    return drawn;
+}
+
 extern "C" void ocvar_synth_config(int id, OcvarSynthConfig* c) {
     memset(c, 0, sizeof *c);
     switch (id) {
@@ -200,27 +258,7 @@ extern "C" int ocvar_synth_frame(const OcvarSynthConfig* cfg, uint64_t frame_ind
             if (by0 < 0) by0 = 0;
             if (bx1 > W) bx1 = W;
             if (by1 > H) by1 = H;
-            for (int y = by0; y < by1; y++) {
-                uint8_t* row = bgr + (size_t)y * stride;
-                for (int x = bx0; x < bx1; x++) {
-                    int c00 = sample(md, x + 0.0625, y + 0.0625), c10 = sample(md, x + 0.9375, y + 0.0625);
-                    int c01 = sample(md, x + 0.0625, y + 0.9375), c11 = sample(md, x + 0.9375, y + 0.9375);
-                    int bg = row[3 * x];
-                    int val;
-                    if (c00 == c10 && c00 == c01 && c00 == c11) {
-                        val = c00 < 0 ? bg : c00;
-                    } else {
-                        int sum = 0;
-                        for (int sy = 0; sy < 4; sy++)
-                            for (int sx = 0; sx < 4; sx++) {
-                                int c = sample(md, x + (sx + 0.5) * 0.25, y + (sy + 0.5) * 0.25);
-                                sum += c < 0 ? bg : c;
-                            }
-                        val = (sum + 8) >> 4;
-                    }
-                    row[3 * x] = row[3 * x + 1] = row[3 * x + 2] = (uint8_t)val;
-                }
-            }
+            draw_marker(md, bgr, stride, bx0, bx1, by0, by1);
             if (truth && n < max_truth) {
                 memcpy(truth[n].corner, quad, sizeof quad);
                 truth[n].template_index = ti;
