@@ -205,7 +205,11 @@ def truth_shift(square, truth_quad):
 
 def pose_errors(pose, R, t):
     """(rotation error in degrees, translation error relative to the distance) of a solved pose against the truth"""
-    Rs = rodrigues(np.array(pose.rvec))
+    return rt_errors(rodrigues(np.array(pose.rvec)), np.array(pose.tvec), R, t)
+
+
+def rt_errors(Rs, ts, R, t):
+    """pose_errors of a solved rotation matrix and translation"""
     dR = Rs @ R.T
     ang = math.degrees(math.acos(max(-1.0, min(1.0, (np.trace(dR) - 1) / 2))))
-    return ang, np.linalg.norm(np.array(pose.tvec) - t) / np.linalg.norm(t)
+    return ang, np.linalg.norm(ts - t) / np.linalg.norm(t)
