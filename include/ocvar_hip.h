@@ -90,17 +90,33 @@ const char* ocvar_hip_last_error(const OcvarHip* ctx);
  * M = ocvar_hip_max_markers).  0 after a good call. */
 int ocvar_hip_capacity_flags(const OcvarHip* ctx);
 
-/* Several contexts in flight on one GPU (each with its own stream) overlap the latency-bound border followers of one batch
- * with the streaming binarise kernels of another -- but left alone they drift: a quarter of the time none of them is in a
- * binarise kernel and a sixth of the time three are (rocprofv3 trace of bench.py).  A gate shared by the
- * contexts lets at most `width` binarise kernels run at once (stream-ordered: the n-th binarise launch waits for the
- * (n - width)-th to finish; nothing blocks on the host), so that more contexts can be kept in flight to always have one
- * ready.  No counterpart in the reference (it processes one frame per call). */
+/* Several contexts in flight on one GPU overlap the latency-bound border followers of one batch with the streaming binarise
+ * kernels of another -- but left alone they drift: a quarter of the time none of them is in a binarise kernel and a sixth of
+ * the time three are (rocprofv3 trace of bench.py).  A gate shared by the contexts lets at most `width`
+ * binarise kernels run at once (stream-ordered: the n-th binarise launch waits for the (n - width)-th to finish; nothing
+ * blocks on the host), so that more contexts can be kept in flight to always have one ready.
+ *
+ * The gate is also the scheduler of its contexts' batches.  Streams that share a hardware queue run one after the other, and
+ * a process has few queues (GPU_MAX_HW_QUEUES, four by default; the library reads the variable and never sets it).  So the
+ * gate owns one stream per queue -- a "lane"; at most 8, created together so that they land on distinct queues -- and a
+ * batch enqueued with stream == NULL on a context of the gate runs on the lane with the least outstanding work at that moment
+ * (ties: the lane whose newest batch is oldest), not on the context's own stream.  More contexts than lanes is the intended
+ * use: the batch queued behind another keeps its lane busy while the host collects and re-enqueues.  Create the gate before
+ * the contexts (and before other streams) where queues are scarce: streams made earlier have taken their queues by then.
+ * A context without a gate, and every call that names a stream, are untouched by this.
+ * No counterpart in the reference (it processes one frame per call). */
 typedef struct OcvarGate OcvarGate;
 int ocvar_hip_gate_create(OcvarGate** gate, int device, int width);
+/* The same with the number of lanes chosen by the caller (1..8; 0: from the queue count as above) -- for experiments and
+ * tests; results do not depend on it. */
+int ocvar_hip_gate_create_lanes(OcvarGate** gate, int device, int width, int lanes);
+int ocvar_hip_gate_lanes(const OcvarGate* gate);
+/* Waits for the work on the gate's lanes.  Contexts still attached are detached (they go on without a gate; a batch one of
+ * them has in flight is complete by then and is collected as usual). */
 void ocvar_hip_gate_destroy(OcvarGate* gate);
-/* gate may be NULL (no gate: the default).  The gate must outlive the batches enqueued under it; it keeps its order on the
- * host without locks, so the contexts that share one are enqueued from one host thread. */
+/* gate may be NULL (no gate: the default).  The gate keeps the order of its gated launches on the host without locks, so the
+ * contexts that share one are enqueued from one host thread; they may be collected and destroyed from other threads (the lanes'
+ * bookkeeping is locked).  Changing the gate of a context whose batch runs on a lane of the old gate waits for that batch. */
 int ocvar_hip_set_gate(OcvarHip* ctx, OcvarGate* gate);
 
 int ocvar_hip_set_templates(OcvarHip* ctx, const OcvarTemplate* templates, int n);
@@ -220,8 +236,15 @@ int ocvar_hip_set_tuning(OcvarHip* ctx, int knob, int value);
 /* How the library was built: "... product(...)" or "... OCVAR_PROF(...)" -- bench.py prints it with its number. */
 const char* ocvar_hip_build_info(void);
 
-/* The context's own HIP stream (hipStream_t; what ocvar_hip_enqueue uses when its `stream` argument is NULL), for callers that
- * order their own work or events against a batch. */
+/* The context's own HIP stream (hipStream_t), for callers that order their own work or events against a batch.  It is what
+ * ocvar_hip_enqueue uses when its `stream` argument is NULL and the context has no gate.  With a gate the batch runs on one of
+ * the gate's lanes, and the stream keeps these promises: work that is on it when ocvar_hip_enqueue is called (a kernel that
+ * writes the frames, a wait for an event) precedes the batch; ocvar_hip_results_to_device / ocvar_hip_board_poses_to_device
+ * that name it follow the batch -- they run on the batch's lane, like those that name no stream --, and ocvar_hip_collect
+ * returns only when such a copy has arrived (a gather may read the block right after collect).  Other work put on the stream
+ * after the enqueue is NOT ordered behind the batch or those copies (that would take a wait in a hardware queue the stream
+ * shares with a lane): wait for ocvar_hip_collect, or name a stream in ocvar_hip_enqueue.  ocvar_hip_collect does not wait for
+ * whatever else is on the lane that carried the batch. */
 void* ocvar_hip_stream(const OcvarHip* ctx);
 
 /* After ocvar_hip_enqueue: stream-ordered device-to-device copy of the batch's results into caller-owned device

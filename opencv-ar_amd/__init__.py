@@ -22,7 +22,7 @@ MAX_QUADS_EX, MAX_QUADS_DENSE, MAX_MARKERS_DENSE = 1792, 16384, 4096   # ocvar_h
 
 # every symbol include/ocvar_hip.h declares
 HIP_SYMBOLS = [
-    "ocvar_hip_create", "ocvar_hip_create_ex", "ocvar_hip_create_dense", "ocvar_hip_max_markers", "ocvar_hip_capacity_flags", "ocvar_hip_gate_create", "ocvar_hip_gate_destroy", "ocvar_hip_set_gate", "ocvar_hip_ready", "ocvar_hip_set_result_limit",
+    "ocvar_hip_create", "ocvar_hip_create_ex", "ocvar_hip_create_dense", "ocvar_hip_max_markers", "ocvar_hip_capacity_flags", "ocvar_hip_gate_create", "ocvar_hip_gate_create_lanes", "ocvar_hip_gate_lanes", "ocvar_hip_gate_destroy", "ocvar_hip_set_gate", "ocvar_hip_ready", "ocvar_hip_set_result_limit",
     "ocvar_hip_pipe_create", "ocvar_hip_pipe_destroy", "ocvar_hip_pipe_last_error", "ocvar_hip_pipe_set_templates", "ocvar_hip_pipe_set_camera",
     "ocvar_hip_pipe_detect_device", "ocvar_hip_pipe_track_device", "ocvar_hip_pipe_submit", "ocvar_hip_pipe_collect", "ocvar_hip_pipe_in_flight", "ocvar_hip_pipe_set_result_limit", "ocvar_hip_set_input_format", "ocvar_hip_pipe_set_input_format", "ocvar_hip_set_corner_refine", "ocvar_hip_pipe_set_corner_refine", "ocvar_hip_enqueue_tracked", "ocvar_hip_build_info", "ocvar_hip_set_tuning", "ocvar_hip_destroy", "ocvar_hip_last_error", "ocvar_hip_set_templates", "ocvar_hip_set_camera",
     "ocvar_hip_detect_device", "ocvar_hip_enqueue", "ocvar_hip_collect", "ocvar_hip_detect_host", "ocvar_hip_find_squares",
@@ -155,6 +155,8 @@ def hip_lib():
         lib.ocvar_hip_max_markers.argtypes = [vp]
         lib.ocvar_hip_destroy.argtypes = [vp]
         lib.ocvar_hip_gate_create.argtypes = [C.POINTER(vp), i, i]
+        lib.ocvar_hip_gate_create_lanes.argtypes = [C.POINTER(vp), i, i, i]
+        lib.ocvar_hip_gate_lanes.argtypes = [vp]
         lib.ocvar_hip_gate_destroy.argtypes = [vp]
         lib.ocvar_hip_gate_destroy.restype = None
         lib.ocvar_hip_set_gate.argtypes = [vp, vp]
@@ -257,14 +259,19 @@ def _ptr(a):
 
 
 class Gate:
-    """At most `width` binarise kernels of the detectors that share the gate run at once (include/ocvar_hip.h)."""
+    """At most `width` binarise kernels of the detectors that share the gate run at once, and their batches are placed on the
+    gate's `lanes` streams (0: one per hardware queue of the process; include/ocvar_hip.h)."""
 
-    def __init__(self, width=2, device=0):
+    def __init__(self, width=2, device=0, lanes=0):
         self._lib = hip_lib()
         self._g = C.c_void_p()
-        rc = self._lib.ocvar_hip_gate_create(C.byref(self._g), device, width)
+        rc = self._lib.ocvar_hip_gate_create_lanes(C.byref(self._g), device, width, lanes)
         if rc != 0:
-            raise OcvarError(f"ocvar_hip_gate_create failed ({rc})")
+            raise OcvarError(f"ocvar_hip_gate_create_lanes failed ({rc})")
+
+    @property
+    def lanes(self):
+        return self._lib.ocvar_hip_gate_lanes(self._g)
 
     def __del__(self):
         if getattr(self, "_g", None):

@@ -6,9 +6,12 @@
 //   follow.hip), 3 (crops) -> decode -> finalise
 // There is deliberately no CPU path here: if the device or the code object is missing, create() fails.
 #include "kernels.h"
+#include "lanes_core.h"
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <new>
 #include <string>
 #include <thread>
@@ -24,12 +27,16 @@ static_assert(sizeof(BoardEntry) == sizeof(OcvarBoardMarker) && sizeof(BoardEntr
 static_assert(sizeof(BoardPose) == sizeof(OcvarBoardPose) && sizeof(BoardPose) == 192, "OcvarBoardPose layout");
 
 // At most `width` binarise kernels of the contexts that share the gate run at once: launch n waits (on its stream) for the
-// event recorded behind launch n - width.  Host side only keeps the ring of events.
+// event recorded behind launch n - width.  The gate also owns the lanes: the streams on which the batches of its contexts run
+// when the caller names none (lanes_core.h has the policy; here are the streams, the events and the contexts' bookkeeping).
 struct OcvarGate {
     int device = 0;
-    int width = 2;
-    unsigned long long issued = 0;
+    std::mutex mu;                  // the lanes' bookkeeping: contexts may be collected and destroyed from other threads than the
+                                    // one that enqueues (sched's lane counts, `attached`, the contexts' `lane`)
+    LaneSched sched;                // placement of batches on lanes, tickets of the gated launches
     std::vector<hipEvent_t> ring;   // far more slots than launches can be in flight (contexts x 2)
+    std::vector<hipStream_t> lanes;
+    std::vector<OcvarHip*> attached;   // the contexts that have this gate (ocvar_hip_set_gate)
 };
 
 struct OcvarHip {
@@ -43,7 +50,14 @@ struct OcvarHip {
     hipStream_t stream = nullptr;
     hipStream_t hp_stream = nullptr;   // high-priority stream for the kernels OCVAR_TUNE_HP_MASK names (created on first use)
     hipStream_t last_stream = nullptr;
+    int lane = -1;                     // the gate's lane that carries the batch in flight and still counts it, -1: none
+    bool on_lane = false;              // the batch in flight runs on a lane (which may carry other contexts' batches)
     hipEvent_t ev[13]{};   // 12 intervals: see ocvar_hip_stage_ms
+    hipEvent_t ordered = nullptr;      // orders a lane behind the caller's work on `stream` (created on first use)
+    // A batch on a lane: collect waits for events, not for a stream.  `copied` lies behind the results copies made with stream
+    // NULL or on the context's own stream -- collect used to cover both, they were the batch's stream then.
+    hipEvent_t copied = nullptr;   // (created on first use)
+    bool copy_pending = false;
     std::vector<void*> allocs;
     uint8_t* d_frames = nullptr;  // staging for the host-buffer entry points
     size_t d_frames_bytes = 0;
@@ -234,9 +248,12 @@ static int create_impl(OcvarHip** out, int device, int max_width, int max_height
     return OCVAR_OK;
 }
 
+static void gate_detach(OcvarHip* c);
+
 extern "C" void ocvar_hip_destroy(OcvarHip* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
+    gate_detach(c);   // (waits for a batch on a lane of the gate)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->ws.sq_codes) (void)hipFree(c->ws.sq_codes);
@@ -256,6 +273,8 @@ extern "C" void ocvar_hip_destroy(OcvarHip* c) {
         if (e) (void)hipEventDestroy(e);
     for (auto& e : c->h2d_done) (void)hipEventDestroy(e);
     if (c->computed) (void)hipEventDestroy(c->computed);
+    if (c->ordered) (void)hipEventDestroy(c->ordered);
+    if (c->copied) (void)hipEventDestroy(c->copied);
     if (c->h2d_stream) (void)hipStreamDestroy(c->h2d_stream);
     if (c->d2h_stream) (void)hipStreamDestroy(c->d2h_stream);
     if (c->hp_stream) (void)hipStreamDestroy(c->hp_stream);
@@ -263,29 +282,81 @@ extern "C" void ocvar_hip_destroy(OcvarHip* c) {
     delete c;
 }
 
-extern "C" int ocvar_hip_gate_create(OcvarGate** out, int device, int width) {
-    if (!out || width < 1 || width > 64) return OCVAR_E_ARG;
+// The hardware queues this process runs with are the host's setting: read, never set.
+static int lanes_of_this_process(int forced) {
+    return lanes_for_queues(parse_queue_count(std::getenv("GPU_MAX_HW_QUEUES")), forced);
+}
+
+extern "C" int ocvar_hip_gate_create(OcvarGate** out, int device, int width) { return ocvar_hip_gate_create_lanes(out, device, width, 0); }
+
+extern "C" int ocvar_hip_gate_create_lanes(OcvarGate** out, int device, int width, int lanes) {
+    if (!out || width < 1 || width > 64 || lanes < 0 || lanes > LANES_MAX) return OCVAR_E_ARG;
     *out = nullptr;
     if (hipSetDevice(device) != hipSuccess) return OCVAR_E_NO_DEVICE;
     OcvarGate* g = new (std::nothrow) OcvarGate();
     if (!g) return OCVAR_E_HIP;
     g->device = device;
-    g->width = width;
+    lane_sched_init(&g->sched, lanes_of_this_process(lanes), width);
     g->ring.resize(256);
-    for (auto& e : g->ring)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-            for (auto& d : g->ring)
-                if (d) (void)hipEventDestroy(d);
-            delete g;
-            return OCVAR_E_HIP;
-        }
+    bool ok = true;
+    // the lanes back to back: the runtime deals streams onto hardware queues in the order they are created
+    g->lanes.assign((size_t)g->sched.n_lanes, nullptr);
+    for (auto& l : g->lanes) ok = ok && hipStreamCreateWithFlags(&l, hipStreamNonBlocking) == hipSuccess;
+    for (auto& e : g->ring) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        ocvar_hip_gate_destroy(g);
+        return OCVAR_E_HIP;
+    }
     *out = g;
     return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_gate_lanes(const OcvarGate* g) { return g ? g->sched.n_lanes : OCVAR_E_ARG; }
+
+// the context's batch no longer counts on its lane (it has been seen complete)
+static void lane_release(OcvarHip* c) {
+    OcvarGate* g = c->gate;
+    if (!g) return;
+    std::lock_guard<std::mutex> lock(g->mu);
+    if (c->lane >= 0) lane_retire(&g->sched, c->lane);
+    c->lane = -1;
+}
+
+// Waits for the batch in flight as collect does: on a lane for its own last event and for the results copies made on the lane
+// or on the context's own stream (the lane may carry the next context's batch by now); elsewhere for the batch's stream.
+static hipError_t batch_wait(OcvarHip* c) {
+    if (!c->on_lane) return hipStreamSynchronize(c->last_stream);
+    return hipEventSynchronize(c->copy_pending ? c->copied : c->ev[12]);   // (`copied` is behind ev[12] on the lane)
+}
+
+// The context leaves its gate.  A batch it has on a lane is waited for first and then belongs to the context's own stream (the
+// lane may be destroyed with the gate; a results copy with stream NULL made from here on goes where collect will wait).
+static void gate_detach(OcvarHip* c) {
+    OcvarGate* g = c->gate;
+    if (!g) return;
+    if (c->pending && c->on_lane) {
+        (void)batch_wait(c);
+        c->on_lane = false;
+        c->copy_pending = false;
+        c->last_stream = c->stream;
+    }
+    lane_release(c);
+    {
+        std::lock_guard<std::mutex> lock(g->mu);
+        auto& a = g->attached;
+        a.erase(std::remove(a.begin(), a.end(), c), a.end());
+    }
+    c->gate = nullptr;
 }
 
 extern "C" void ocvar_hip_gate_destroy(OcvarGate* g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
+    for (auto& l : g->lanes)   // (a batch of a context that is still attached may be on a lane)
+        if (l) (void)hipStreamSynchronize(l);
+    while (!g->attached.empty()) gate_detach(g->attached.back());
+    for (auto& l : g->lanes)
+        if (l) (void)hipStreamDestroy(l);
     for (auto& e : g->ring)
         if (e) (void)hipEventDestroy(e);
     delete g;
@@ -293,19 +364,44 @@ extern "C" void ocvar_hip_gate_destroy(OcvarGate* g) {
 
 extern "C" int ocvar_hip_set_gate(OcvarHip* c, OcvarGate* g) {
     if (!c || (g && g->device != c->device)) return OCVAR_E_ARG;
+    if (g == c->gate) return OCVAR_OK;
+    (void)hipSetDevice(c->device);
+    gate_detach(c);   // (waits for a batch on a lane of the old gate; it is collected as usual)
     c->gate = g;
+    if (g) {
+        std::lock_guard<std::mutex> lock(g->mu);
+        g->attached.push_back(c);
+    }
     return OCVAR_OK;
 }
 
-// before / after a gated launch on stream s
+// The lane for the next batch of a context of the gate (lanes_core.h: lane_place), booked.  "Finished" is a query of the
+// batch's last event.
+static int lane_batch_done(void* user, int i) {
+    OcvarHip* o = (*static_cast<std::vector<OcvarHip*>*>(user))[(size_t)i];
+    if (hipEventQuery(o->ev[12]) == hipSuccess) return 1;
+    (void)hipGetLastError();   // (not ready: no error)
+    return 0;
+}
+static int gate_place(OcvarGate* g) {
+    std::lock_guard<std::mutex> lock(g->mu);
+    int* lane_of[64];
+    const int n = (int)std::min<size_t>(g->attached.size(), 64);
+    for (int i = 0; i < n; i++) lane_of[i] = &g->attached[(size_t)i]->lane;
+    return lane_place(&g->sched, lane_of, n, lane_batch_done, &g->attached);
+}
+
+// before / after a gated launch on stream s: the ticket is taken once the launch and its event are in the stream
 static hipError_t gate_enter(OcvarGate* g, hipStream_t s) {
-    if (!g || g->issued < (unsigned long long)g->width) return hipSuccess;
-    return hipStreamWaitEvent(s, g->ring[(g->issued - g->width) % g->ring.size()], 0);
+    if (!g) return hipSuccess;
+    const long long wait_for = gate_wait_for(&g->sched);
+    if (wait_for < 0) return hipSuccess;
+    return hipStreamWaitEvent(s, g->ring[(size_t)wait_for % g->ring.size()], 0);
 }
 static hipError_t gate_leave(OcvarGate* g, hipStream_t s) {
     if (!g) return hipSuccess;
-    const hipError_t e = hipEventRecord(g->ring[g->issued % g->ring.size()], s);
-    g->issued++;
+    const hipError_t e = hipEventRecord(g->ring[(size_t)g->sched.issued % g->ring.size()], s);
+    (void)gate_ticket(&g->sched);
     return e;
 }
 
@@ -345,7 +441,7 @@ extern "C" int ocvar_hip_set_templates(OcvarHip* c, const OcvarTemplate* t, int 
         return OCVAR_E_ARG;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->pending) HIP_TRY(c, hipStreamSynchronize(c->last_stream));   // (the batch in flight reads the tables)
+    if (c->pending) HIP_TRY(c, batch_wait(c));   // (the batch in flight reads the tables)
     Workspace& w = c->ws;
     const size_t squares = (size_t)w.max_batch * w.maxq;
     c->have_templates = false;   // (until the tables below are all in place)
@@ -425,7 +521,7 @@ static bool trace_launches() {
 
 static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride, int n_frames,
                         int grey_in_place, const OcvarMarker* prev, const int* prev_counts, hipStream_t s, int stages,
-                        int format, bool prev_on_device = false) {
+                        int format, bool prev_on_device = false, hipStream_t after = nullptr) {
     Workspace& w = c->ws;
     if (!d_bgr || width < 16 || height < 16 || width > w.max_w || height > w.max_h || n_frames < 1 || n_frames > w.max_batch ||
         (size_t)width * height > (size_t)w.max_w * w.max_h || input_format_bpp(format) == 0 ||
@@ -486,6 +582,15 @@ static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int 
         rows = (rows + NBR_TILE_H - 1) / NBR_TILE_H * NBR_TILE_H;   // whole tile rows (14) per work unit: binarise.hip writes the bit plane tile by tile
         w.frame_chunk_rows = rows;
         w.frame_chunks = (w.sh + rows - 1) / rows;
+    }
+    if (after && after != s && hipStreamQuery(after) != hipSuccess) {
+        // The batch runs on a lane, and the caller has work in flight on the context's stream (frames being written, a wait for
+        // an event of theirs, the last batch's results on their way out): the batch follows it.  An idle stream asks for
+        // nothing, and nothing is put into its hardware queue -- a record there would queue up behind the lane that shares it.
+        (void)hipGetLastError();   // (not ready: no error)
+        if (!c->ordered) HIP_TRY(c, hipEventCreateWithFlags(&c->ordered, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->ordered, after));
+        HIP_TRY(c, hipStreamWaitEvent(s, c->ordered, 0));
     }
     HIP_TRY(c, hipMemsetAsync(w.counters, 0, CNT_COUNT * sizeof(int), s));
     HIP_TRY(c, hipMemsetAsync(w.n_quads_frame, 0, n_frames * sizeof(int), s));
@@ -613,8 +718,27 @@ static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int 
     HIP_TRY(c, hipEventRecord(c->ev[12], s));
     HIP_TRY(c, hipGetLastError());
     c->last_stream = s;
+    c->copy_pending = false;
     c->pending = true;
     return OCVAR_OK;
+}
+
+// ocvar_hip_enqueue / _tracked: the stream the caller names; else, for a context of a gate, the gate's lane with the least
+// outstanding work; else the context's own stream.
+static int enqueue_placed(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride, int n_frames,
+                          int grey_in_place, const OcvarMarker* prev, const int* prev_counts, void* stream, bool prev_on_device) {
+    OcvarGate* g = c->gate;
+    if (stream || !g || c->pending)   // (pending: enqueue_impl refuses)
+        return enqueue_impl(c, d_bgr, width, height, row_stride, frame_stride, n_frames, grey_in_place, prev, prev_counts,
+                            stream ? (hipStream_t)stream : c->stream, 3, c->input_format, prev_on_device);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int lane = gate_place(g);   // (booked: the context's `lane` must name it before anybody looks)
+    c->lane = lane;
+    const int rc = enqueue_impl(c, d_bgr, width, height, row_stride, frame_stride, n_frames, grey_in_place, prev, prev_counts,
+                                g->lanes[lane], 3, c->input_format, prev_on_device, c->stream);
+    if (rc == OCVAR_OK) c->on_lane = true;
+    else lane_release(c);
+    return rc;
 }
 
 static int wait_impl(OcvarHip* c) {
@@ -623,8 +747,10 @@ static int wait_impl(OcvarHip* c) {
         return OCVAR_E_ARG;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->last_stream));
+    HIP_TRY(c, batch_wait(c));
     c->pending = false;
+    c->on_lane = false;
+    lane_release(c);
     const int e = c->h_counters[CNT_ERR];
     c->capacity_flags = e;
     if (e) {
@@ -639,15 +765,34 @@ static int wait_impl(OcvarHip* c) {
 extern "C" int ocvar_hip_enqueue(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride,
                                  int n_frames, int grey_in_place, const OcvarMarker* prev, const int* prev_counts, void* stream) {
     if (!c) return OCVAR_E_ARG;
-    return enqueue_impl(c, d_bgr, width, height, row_stride, frame_stride, n_frames, grey_in_place, prev, prev_counts,
-                        stream ? (hipStream_t)stream : c->stream, 3, c->input_format);
+    return enqueue_placed(c, d_bgr, width, height, row_stride, frame_stride, n_frames, grey_in_place, prev, prev_counts, stream, false);
 }
 
 extern "C" int ocvar_hip_enqueue_tracked(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride,
                                          int n_frames, int grey_in_place, const OcvarMarker* d_prev, const int* d_prev_counts, void* stream) {
     if (!c || !d_prev || !d_prev_counts) return OCVAR_E_ARG;
-    return enqueue_impl(c, d_bgr, width, height, row_stride, frame_stride, n_frames, grey_in_place, d_prev, d_prev_counts,
-                        stream ? (hipStream_t)stream : c->stream, 3, c->input_format, true);
+    return enqueue_placed(c, d_bgr, width, height, row_stride, frame_stride, n_frames, grey_in_place, d_prev, d_prev_counts, stream, true);
+}
+
+// Where a results copy of the batch in flight goes.  For a batch on a lane the context's own stream means the lane, as NULL
+// does: that is where the batch is, and there the copy follows it without a wait.  (On the context's stream it would need a
+// wait for the batch's last event -- a barrier in a hardware queue that stream shares with a lane, which holds up the other
+// contexts' batches queued there until this one has finished: bench.py's multi-rank path lost a sixth of its rate to it.)
+static hipStream_t copy_stream(const OcvarHip* c, void* stream) {
+    if (!stream || (c->on_lane && (hipStream_t)stream == c->stream)) return c->last_stream;
+    return (hipStream_t)stream;
+}
+
+// Behind a results copy on a lane: collect waits for it too (it waits for events there; in front of the lanes collect's wait
+// for the batch's stream covered the copy, and bench.py's gather reads the block right after collect).
+static hipError_t tail_behind_copy(OcvarHip* c, hipStream_t s) {
+    if (!c->on_lane || s != c->last_stream) return hipSuccess;
+    if (!c->copied) {
+        const hipError_t e = hipEventCreateWithFlags(&c->copied, hipEventDisableTiming);
+        if (e != hipSuccess) return e;
+    }
+    c->copy_pending = true;
+    return hipEventRecord(c->copied, s);
 }
 
 extern "C" int ocvar_hip_results_to_device(OcvarHip* c, OcvarMarker* d_markers, int* d_counts, void* stream) {
@@ -657,7 +802,7 @@ extern "C" int ocvar_hip_results_to_device(OcvarHip* c, OcvarMarker* d_markers, 
 extern "C" int ocvar_hip_results_to_device_ex(OcvarHip* c, OcvarMarker* d_markers, int* d_counts, int max_per_frame, void* stream) {
     if (!c || !d_markers || !d_counts || !c->pending || max_per_frame < 1 || max_per_frame > c->ws.maxm) return OCVAR_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->last_stream;
+    hipStream_t s = copy_stream(c, stream);
     if (s != c->last_stream) {  // order behind the batch
         HIP_TRY(c, hipStreamWaitEvent(s, c->ev[12], 0));
     }
@@ -668,6 +813,7 @@ extern "C" int ocvar_hip_results_to_device_ex(OcvarHip* c, OcvarMarker* d_marker
         HIP_TRY(c, hipMemcpy2DAsync(d_markers, (size_t)max_per_frame * sizeof(MarkerRec), c->ws.markers, (size_t)M * sizeof(MarkerRec),
                                     (size_t)max_per_frame * sizeof(MarkerRec), (size_t)n, hipMemcpyDeviceToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d_counts, c->ws.n_markers, n * sizeof(int), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, tail_behind_copy(c, s));
     return OCVAR_OK;
 }
 
@@ -698,7 +844,7 @@ extern "C" int ocvar_hip_collect(OcvarHip* c, OcvarMarker* markers, int* counts,
 
 extern "C" int ocvar_hip_ready(OcvarHip* c) {
     if (!c || !c->pending) return OCVAR_E_ARG;
-    const hipError_t e = hipEventQuery(c->ev[12]);
+    const hipError_t e = hipEventQuery(c->on_lane && c->copy_pending ? c->copied : c->ev[12]);
     if (e == hipSuccess) return 1;
     if (e == hipErrorNotReady) {
         (void)hipGetLastError();
@@ -791,9 +937,10 @@ extern "C" int ocvar_hip_board_poses(OcvarHip* c, OcvarBoardPose* poses, int n_f
 extern "C" int ocvar_hip_board_poses_to_device(OcvarHip* c, OcvarBoardPose* d_poses, void* stream) {
     if (!c || !d_poses || !c->pending || !c->batch_board) return OCVAR_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->last_stream;
+    hipStream_t s = copy_stream(c, stream);
     if (s != c->last_stream) HIP_TRY(c, hipStreamWaitEvent(s, c->ev[12], 0));   // order behind the batch
     HIP_TRY(c, hipMemcpyAsync(d_poses, c->d_board_poses, (size_t)c->ws.n_frames * sizeof(BoardPose), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, tail_behind_copy(c, s));
     return OCVAR_OK;
 }
 
