@@ -186,6 +186,47 @@ int ocvar_hip_board_poses(OcvarHip* ctx, OcvarBoardPose* poses, int n_frames);
  * in device memory.  OCVAR_E_ARG when nothing is enqueued or the batch has no board. */
 int ocvar_hip_board_poses_to_device(OcvarHip* ctx, OcvarBoardPose* d_poses, void* stream);
 
+/* Overlays (none by default): an RGBA image per template, warped into the quad of every marker record and blended into frames
+ * that stay in device memory -- what the reference's caller does with its records (samples/ARTest.cpp draws on every marker),
+ * without GL.  The definition, bit for bit, is opencv-ar_amd/csrc/overlay_core.h: the map perspective_from_quad(record.square)
+ * from frame pixels to texels in float32, texel coordinates in 1/32, plain bilinear sampling (no mipmaps, no anti-aliased
+ * edges), straight alpha, out = (c a + d (255 - a) + 127) / 255 per colour channel; alpha 0 leaves the pixel untouched; byte 3
+ * of a four-channel pixel is never written; OCVAR_FMT_GRAY takes the library's grey of the colour.  Of a frame's records the
+ * first min(count, stride) are drawn in output order, later over earlier, each with score > 0 whose template has an overlay
+ * (or the default overlay) and whose four corners are finite and a strictly convex quad.
+ * Which way up: the overlay's top-left, top-right, bottom-right and bottom-left texels land on record corners 0, 1, 2, 3.  For a
+ * marker decoded at orient 1, 2 or 4 those are the template image's bottom-left, bottom-right, top-right and top-left corners
+ * however the marker is turned in the frame (templates are loaded flipped vertically, see ocvar_hip_set_board below): the overlay
+ * lies on the marker as its printed pattern does, the image's top row along the template image's bottom row.  A marker decoded
+ * at orient 3 (turned by 180 degrees against orient 1) keeps its corners as found, as in the reference (opencvar.cpp:753-760
+ * rotates for orient 2 and 4 only): its record, its glMatrix and its overlay are turned by 180 degrees on it.
+ *
+ * ocvar_hip_set_overlay: h_rgba is a host image of width x height texels (2 .. OCVAR_MAX_OVERLAY_SIDE each), 4 bytes R G B A per
+ * texel, rows row_stride >= 4 width bytes apart; it is copied to device memory.  template_id 0 .. OCVAR_MAX_TEMPLATES-1, or -1:
+ * the default overlay, used for every template without one of its own.  h_rgba == NULL removes that overlay.  At most
+ * OCVAR_MAX_OVERLAYS per context, the default included.  OCVAR_E_ARG, before any device call, for a size outside the range, a
+ * row_stride below 4 width, a bad id, one overlay more than OCVAR_MAX_OVERLAYS, or while the context has a batch that has not
+ * been collected.  The first overlay allocates the drawing workspace (64 bytes per marker record of max_batch frames); a
+ * context without overlays allocates and launches nothing.  Markers, counts and board poses never depend on overlays. */
+enum { OCVAR_MAX_OVERLAYS = 64, OCVAR_MAX_OVERLAY_SIDE = 1024 };
+int ocvar_hip_set_overlay(OcvarHip* ctx, int template_id, const uint8_t* h_rgba, int width, int height, int row_stride);
+/* After ocvar_hip_enqueue and before ocvar_hip_collect (like ocvar_hip_results_to_device, with the same promises about streams,
+ * lanes and collect on a context of a gate): draws the enqueued batch's own records onto d_frames -- the frames that were
+ * detected (after grey_in_place, if that was asked for) or any other buffer of the batch's frame count and size -- in `format`
+ * (OCVAR_FMT_*; it need not be the input format).  Stream-ordered behind the batch; does not wait.  OCVAR_E_ARG when nothing is
+ * enqueued, no overlay is set, width or height differ from the batch's, the format is unknown or row_stride is below the
+ * format's bytes per pixel times width. */
+int ocvar_hip_render(OcvarHip* ctx, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int format,
+                     void* stream);
+/* The same on records the caller supplies in device memory, d_markers [n_frames][records_per_frame] and d_counts [n_frames]
+ * (1 <= records_per_frame <= M = ocvar_hip_max_markers(ctx); a count above records_per_frame is read as records_per_frame) --
+ * gathered, filtered or smoothed records, say.  Needs no batch; frames of up to the context's max_width x max_height; any
+ * n_frames >= 1 (more than max_batch go through the workspace in chunks, in stream order).  stream NULL: the context's own
+ * stream.  Does not wait.  OCVAR_E_ARG for a size, stride or format as above or when no overlay is set. */
+int ocvar_hip_render_records(OcvarHip* ctx, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride,
+                             int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
+                             void* stream);
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart

@@ -29,6 +29,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_debug_gray", "ocvar_hip_debug_binary", "ocvar_hip_debug_masks", "ocvar_hip_debug_frame_quads", "ocvar_hip_debug_candidates",
     "ocvar_hip_stage_ms", "ocvar_hip_stream", "ocvar_hip_stage_stamps", "ocvar_hip_counters", "ocvar_hip_results_to_device", "ocvar_hip_results_to_device_ex", "ocvar_hip_debug_calibrate",
     "ocvar_hip_set_board", "ocvar_hip_board_poses", "ocvar_hip_board_poses_to_device",
+    "ocvar_hip_set_overlay", "ocvar_hip_render", "ocvar_hip_render_records",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -74,6 +75,7 @@ def corner_refine_args(half_win, max_iter, eps):
 
 
 MAX_BOARD_MARKERS = 256   # include/ocvar_hip.h: OCVAR_MAX_BOARD_MARKERS
+MAX_OVERLAYS, MAX_OVERLAY_SIDE = 64, 1024   # include/ocvar_hip.h: OCVAR_MAX_OVERLAYS, OCVAR_MAX_OVERLAY_SIDE
 
 
 class BoardMarker(C.Structure):  # OcvarBoardMarker: a template and the board-plane (z = 0) coordinates of its corners 0..3
@@ -209,6 +211,9 @@ def hip_lib():
         lib.ocvar_hip_set_board.argtypes = [vp, vp, i]
         lib.ocvar_hip_board_poses.argtypes = [vp, vp, i]
         lib.ocvar_hip_board_poses_to_device.argtypes = [vp, vp, vp]
+        lib.ocvar_hip_set_overlay.argtypes = [vp, i, vp, i, i, i]
+        lib.ocvar_hip_render.argtypes = [vp, vp, i, i, i, sz, i, vp]
+        lib.ocvar_hip_render_records.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, i, vp]
         _hip = lib
     return _hip
 
@@ -530,6 +535,40 @@ class Detector:
     def board_poses_to_device(self, d_poses_ptr, stream=None):
         """after enqueue: stream-ordered copy of the batch's [n] board poses (192 bytes each) into caller-owned device memory"""
         self._check(self._lib.ocvar_hip_board_poses_to_device(self._ctx, d_poses_ptr, stream), "board_poses_to_device")
+
+    def set_overlay(self, template_id, rgba):
+        """The overlay image drawn on every marker of template template_id (-1: the default overlay, for every template without
+        one of its own): an H x W x 4 uint8 array, straight-alpha R G B A, 2 .. MAX_OVERLAY_SIDE texels each way; None removes it.
+        Row 0 of the array lands along the edge between record corners 0 and 1 (include/ocvar_hip.h says which way up that is).
+        At most MAX_OVERLAYS per detector.  OcvarError while a batch is in flight."""
+        if rgba is None:
+            self._check(self._lib.ocvar_hip_set_overlay(self._ctx, int(template_id), None, 0, 0, 0), "set_overlay")
+            return
+        a = np.asarray(rgba)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError(f"an overlay is an H x W x 4 uint8 array, got {a.dtype} {a.shape}")
+        a = np.ascontiguousarray(a)
+        self._check(self._lib.ocvar_hip_set_overlay(self._ctx, int(template_id), _ptr(a), a.shape[1], a.shape[0], 4 * a.shape[1]), "set_overlay")
+
+    def render(self, d_ptr, width, height, fmt=None, row_stride=None, frame_stride=None, stream=None):
+        """between enqueue and collect: draws the overlays onto the enqueued batch's markers in the device frames at d_ptr (the
+        frames detected, or another buffer of the batch's frame count and size) in format fmt (default: the input format);
+        stream-ordered behind the batch, does not wait"""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        row_stride = row_stride or FORMAT_BPP[code] * width
+        frame_stride = frame_stride or row_stride * height
+        self._check(self._lib.ocvar_hip_render(self._ctx, d_ptr, width, height, row_stride, frame_stride, code, stream), "render")
+
+    def render_records(self, d_ptr, width, height, n_frames, d_markers_ptr, d_counts_ptr, per_frame=None, fmt=None, row_stride=None,
+                       frame_stride=None, stream=None):
+        """draws the overlays onto n_frames device frames under caller-supplied device records [n_frames, per_frame] (default
+        per_frame: max_markers) and counts [n_frames]; needs no batch, does not wait (stream None: the detector's own stream)"""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        per_frame = self.max_markers if per_frame is None else per_frame
+        row_stride = row_stride or FORMAT_BPP[code] * width
+        frame_stride = frame_stride or row_stride * height
+        self._check(self._lib.ocvar_hip_render_records(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames, code,
+                                                       d_markers_ptr, d_counts_ptr, per_frame, stream), "render_records")
 
     TUNE = {"crop_phases": 1, "mid_steps": 2, "mid_blocks": 3, "long_blocks": 4, "short_blocks": 5, "min_units": 6, "hp_mask": 7, "gate_mode": 8}
 

@@ -88,6 +88,15 @@ struct OcvarHip {
     std::vector<BoardPose> board_out;       // the poses of the last collected batch (ocvar_hip_board_poses)
     bool board_out_valid = false;
     int board_out_off = 0;                  // where collect puts a batch's poses in board_out (detect_host's sub-batches)
+    // overlays (ocvar_hip_set_overlay): table and drawing workspace are allocated by the first overlay set
+    OverlayTable* h_overlays = nullptr;     // the table as uploaded (device pointers inside)
+    OverlayTable* d_overlays = nullptr;
+    OverlayDraw* d_ovl_draws = nullptr;     // [max_batch][maxm]
+    OverlayBox* d_ovl_boxes = nullptr;      // [max_batch][maxm]
+    int n_overlays = 0;
+    hipEvent_t ovl_done = nullptr;          // behind the last use of the workspace, on ovl_stream
+    hipStream_t ovl_stream = nullptr;
+    bool ovl_used = false;
     std::string err;
 };
 
@@ -269,6 +278,13 @@ extern "C" void ocvar_hip_destroy(OcvarHip* c) {
     if (c->h_prev_counts) (void)hipHostFree(c->h_prev_counts);
     if (c->h_counters) (void)hipHostFree(c->h_counters);
     if (c->h_board_poses) (void)hipHostFree(c->h_board_poses);
+    if (c->h_overlays) {
+        if (c->ovl_used) (void)hipEventSynchronize(c->ovl_done);
+        for (auto& t : c->h_overlays->tex)
+            if (t.px) (void)hipFree(const_cast<uint32_t*>(t.px));
+        delete c->h_overlays;
+    }
+    if (c->ovl_done) (void)hipEventDestroy(c->ovl_done);
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : c->h2d_done) (void)hipEventDestroy(e);
@@ -942,6 +958,136 @@ extern "C" int ocvar_hip_board_poses_to_device(OcvarHip* c, OcvarBoardPose* d_po
     HIP_TRY(c, hipMemcpyAsync(d_poses, c->d_board_poses, (size_t)c->ws.n_frames * sizeof(BoardPose), hipMemcpyDeviceToDevice, s));
     HIP_TRY(c, tail_behind_copy(c, s));
     return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_set_overlay(OcvarHip* c, int template_id, const uint8_t* h_rgba, int width, int height, int row_stride) {
+    if (!c) return OCVAR_E_ARG;
+    if (template_id < -1 || template_id >= MAXT) {
+        c->err = "ocvar_hip_set_overlay: template id outside -1 .. 4095";
+        return OCVAR_E_ARG;
+    }
+    if (h_rgba && (width < 2 || height < 2 || width > OVL_MAX_SIDE || height > OVL_MAX_SIDE || (long long)row_stride < 4ll * width)) {
+        c->err = "ocvar_hip_set_overlay: sides 2 .. 1024 texels, row_stride >= 4 width";
+        return OCVAR_E_ARG;
+    }
+    if (c->pending) {
+        c->err = "the previous batch of this context has not been collected";
+        return OCVAR_E_ARG;
+    }
+    OverlayTable* t = c->h_overlays;
+    int slot = !t ? -1 : (template_id < 0 ? t->dflt : t->map[template_id]);
+    if (!h_rgba && slot < 0) return OCVAR_OK;   // (nothing to remove)
+    if (h_rgba && slot < 0 && c->n_overlays >= OVL_MAX) {
+        c->err = "ocvar_hip_set_overlay: the context has OCVAR_MAX_OVERLAYS overlays";
+        return OCVAR_E_ARG;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!t) {   // (the host table last: its presence says that the device blocks exist)
+        const size_t recs = (size_t)c->ws.max_batch * c->ws.maxm;
+        int rc = dev_alloc(c, &c->d_overlays, 1);
+        if (!rc) rc = dev_alloc(c, &c->d_ovl_draws, recs);
+        if (!rc) rc = dev_alloc(c, &c->d_ovl_boxes, recs);
+        if (rc) return rc;
+        HIP_TRY(c, hipEventCreateWithFlags(&c->ovl_done, hipEventDisableTiming));
+        t = new (std::nothrow) OverlayTable();
+        if (!t) return OCVAR_E_HIP;
+        for (auto& x : t->tex) x = OverlayTex{nullptr, 0, 0};
+        t->dflt = -1;
+        for (auto& m : t->map) m = -1;
+        c->h_overlays = t;
+    }
+    if (c->ovl_used) HIP_TRY(c, hipEventSynchronize(c->ovl_done));   // (a render_records in flight reads the table and the images)
+    if (slot >= 0) {   // removed, or replaced below
+        HIP_TRY(c, hipFree(const_cast<uint32_t*>(t->tex[slot].px)));
+        t->tex[slot] = OverlayTex{nullptr, 0, 0};
+        (template_id < 0 ? t->dflt : t->map[template_id]) = -1;
+        c->n_overlays--;
+    }
+    if (h_rgba) {
+        for (slot = 0; slot < OVL_MAX && t->tex[slot].px; slot++) {}
+        void* d = nullptr;
+        HIP_TRY(c, hipMalloc(&d, (size_t)width * height * 4));
+        const hipError_t e = hipMemcpy2D(d, (size_t)width * 4, h_rgba, (size_t)row_stride, (size_t)width * 4, (size_t)height, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            c->err = std::string("ocvar_hip_set_overlay: ") + hipGetErrorString(e);
+            return OCVAR_E_HIP;
+        }
+        t->tex[slot] = OverlayTex{static_cast<const uint32_t*>(d), width, height};
+        (template_id < 0 ? t->dflt : t->map[template_id]) = slot;
+        c->n_overlays++;
+    }
+    HIP_TRY(c, hipMemcpy(c->d_overlays, t, sizeof(OverlayTable), hipMemcpyHostToDevice));
+    return OCVAR_OK;
+}
+
+// setup + draw of n_frames frames (chunks of the workspace's max_batch) on stream s, behind the workspace's last use
+static int overlay_launch(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int n_frames,
+                          int format, const MarkerRec* recs, const int* counts, int stride, hipStream_t s) {
+    if (c->ovl_used && c->ovl_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->ovl_done, 0));
+    const OverlayArgs oa{c->d_overlays, c->d_ovl_draws, c->d_ovl_boxes};
+    const int chunk = std::min(c->ws.max_batch, 32768);   // (frames are the grid's z)
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int n = std::min(chunk, n_frames - f0);
+        launch_overlay(oa, d_frames + (size_t)f0 * frame_stride, width, height, row_stride, (long long)frame_stride, n, format,
+                       recs + (size_t)f0 * stride, counts + f0, stride, s);
+        TRACE_LAUNCH("overlay", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ovl_done, s));
+    c->ovl_stream = s;
+    c->ovl_used = true;
+    return OCVAR_OK;
+}
+
+static bool overlay_frames_ok(OcvarHip* c, const uint8_t* d_frames, int width, int height, int row_stride, int format) {
+    if (!d_frames || input_format_bpp(format) == 0 || (long long)row_stride < (long long)input_format_bpp(format) * width) {
+        c->err = "render: no frames, an unknown format or a row_stride below the format's bytes per pixel times width";
+        return false;
+    }
+    if (c->n_overlays < 1) {
+        c->err = "render: no overlay is set";
+        return false;
+    }
+    (void)height;
+    return true;
+}
+
+extern "C" int ocvar_hip_render(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int format,
+                                void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    if (!c->pending) {
+        c->err = "render: nothing enqueued";
+        return OCVAR_E_ARG;
+    }
+    if (width != c->ws.W || height != c->ws.H) {
+        c->err = "render: the frames are not of the batch's size";
+        return OCVAR_E_ARG;
+    }
+    if (!overlay_frames_ok(c, d_frames, width, height, row_stride, format)) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = copy_stream(c, stream);
+    if (s != c->last_stream) HIP_TRY(c, hipStreamWaitEvent(s, c->ev[12], 0));   // order behind the batch
+    const int rc = overlay_launch(c, d_frames, width, height, row_stride, frame_stride, c->ws.n_frames, format, c->ws.markers,
+                                  c->ws.n_markers, c->ws.maxm, s);
+    if (rc) return rc;
+    HIP_TRY(c, tail_behind_copy(c, s));
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_render_records(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride,
+                                        int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts,
+                                        int records_per_frame, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    if (!d_markers || !d_counts || n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm || width < 1 || height < 1 ||
+        width > c->ws.max_w || height > c->ws.max_h) {
+        c->err = "render_records: frames of 1 .. the context's size, n_frames >= 1, 1 .. M records per frame";
+        return OCVAR_E_ARG;
+    }
+    if (!overlay_frames_ok(c, d_frames, width, height, row_stride, format)) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return overlay_launch(c, d_frames, width, height, row_stride, frame_stride, n_frames, format,
+                          reinterpret_cast<const MarkerRec*>(d_markers), d_counts, records_per_frame, stream ? (hipStream_t)stream : c->stream);
 }
 
 extern "C" int ocvar_hip_detect_device(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride,

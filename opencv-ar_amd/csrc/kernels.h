@@ -6,6 +6,7 @@
 #include "tail_core.h"
 #include "refine_core.h"
 #include "board_core.h"
+#include "overlay_core.h"
 #include "ocvar_hip.h"
 
 namespace ocvar {
@@ -161,5 +162,17 @@ struct BoardArgs {
 };
 // (board.n > 0: board_pose_kernel, one wave per frame, after launch_finalise; board.hip)
 void launch_board_poses(const Workspace& ws, const BoardArgs& board, hipStream_t stream);
+
+// A context's overlays and drawing workspace (ocvar_hip_set_overlay allocates them): the device table, and per record slot of a
+// chunk of frames its OverlayDraw and OverlayBox, [max_batch][maxm].
+struct OverlayArgs {
+    const OverlayTable* table;
+    OverlayDraw* draws;
+    OverlayBox* boxes;
+};
+// overlay_setup_kernel + overlay_draw_kernel (overlay.hip) on n_frames frames in `format` and their records recs [n_frames][stride]
+// (the first min(counts[f], stride) of frame f), all in device memory
+void launch_overlay(const OverlayArgs& oa, uint8_t* frames, int W, int H, long long row_stride, long long frame_stride, int n_frames,
+                    int format, const MarkerRec* recs, const int* counts, int stride, hipStream_t stream);
 
 }  // namespace ocvar
