@@ -124,6 +124,13 @@ int ocvar_hip_set_camera(OcvarHip* ctx, const OcvarCamera* camera);
 
 /* Input formats: what the frames handed to the detection entry points hold (d_bgr / h_bgr below keep their names).  8-bit
  * interleaved pixels of 3, 3, 4, 4 and 1 bytes; row_stride must be at least that many bytes times width (else OCVAR_E_ARG).
+ * The rows of one frame must lie within 2^31 - 1 bytes of its first byte, which is as far as the frame kernel addresses: with
+ * bpp the bytes per pixel,
+ *     ((height & ~1) - 1) * row_stride + bpp * (width & ~1) <= 2147483647
+ * else OCVAR_E_ARG with a text in ocvar_hip_last_error, before any device call and with the frames untouched -- from every
+ * entry point that takes frames (detect_device, enqueue, enqueue_tracked, the pipe calls, detect_host on the caller's host
+ * strides, find_squares on its 3 * width expansion).  It binds views into a large surface (a big row_stride) and frames
+ * above about 26755 x 26755 BGR / 23170 x 23170 BGRA; frame_stride, and so the batch, are not limited by it.
  * Parity: a frame in format F gives exactly what the reference gives on the BGR frame with the same colours --
  *   OCVAR_FMT_GRAY  B = G = R = g (the reference's BGR2GRAY of such a pixel is g)
  *   OCVAR_FMT_RGB   the channels reversed

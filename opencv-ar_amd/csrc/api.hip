@@ -535,6 +535,17 @@ static bool trace_launches() {
         }                                                                                \
     } while (0)
 
+// A frame whose rows reach further from its first byte than the frame binarise kernel addresses (hd.h::frame_src_addressable)
+// is refused: its lower rows would be read somewhere else, or as zeros, and the call would return a plausible, different result.
+static int frame_span_check(OcvarHip* c, int width, int height, int row_stride, int format) {
+    const int bpp = input_format_bpp(format);
+    if (frame_src_addressable(width, height, row_stride, bpp)) return OCVAR_OK;
+    c->err = "the rows of a frame span more than the frame kernel addresses: ((height & ~1) - 1) * row_stride + bytes per pixel * "
+             "(width & ~1) must not exceed 2147483647 (got " +
+             std::to_string(((long long)(height & ~1) - 1) * row_stride + (long long)bpp * (width & ~1)) + ")";
+    return OCVAR_E_ARG;
+}
+
 static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride, int n_frames,
                         int grey_in_place, const OcvarMarker* prev, const int* prev_counts, hipStream_t s, int stages,
                         int format, bool prev_on_device = false, hipStream_t after = nullptr) {
@@ -543,6 +554,7 @@ static int enqueue_impl(OcvarHip* c, uint8_t* d_bgr, int width, int height, int 
         (size_t)width * height > (size_t)w.max_w * w.max_h || input_format_bpp(format) == 0 ||
         (long long)row_stride < (long long)input_format_bpp(format) * width)
         return OCVAR_E_ARG;
+    if (int rc = frame_span_check(c, width, height, row_stride, format)) return rc;
     if (c->pending) {
         c->err = "the previous batch of this context has not been collected";
         return OCVAR_E_ARG;
@@ -1198,6 +1210,9 @@ extern "C" int ocvar_hip_detect_host(OcvarHip* c, uint8_t* h_bgr, int width, int
                                      OcvarMarker* markers, int* counts, int max_per_frame) {
     if (!c || !h_bgr || n_frames < 1 || height < 1 || row_stride < 1) return OCVAR_E_ARG;
     if ((long long)row_stride < (long long)input_format_bpp(c->input_format) * width) return OCVAR_E_ARG;
+    // (the device slots keep the caller's strides, so the frame kernel's addressing limit is the host frames' too: refused here,
+    // before anything is staged, not by the first sub-batch's enqueue after its upload)
+    if (int rc = frame_span_check(c, width, height, row_stride, c->input_format)) return rc;
     // a grey frame is its own grey: no write-back kernel, no copy back, no page-locked buffers for it
     grey_in_place = grey_in_place && c->input_format != OCVAR_FMT_GRAY;
     if (n_frames > 1 && frame_stride < (size_t)height * row_stride) return OCVAR_E_ARG;
@@ -1316,6 +1331,8 @@ extern "C" int ocvar_hip_detect_host(OcvarHip* c, uint8_t* h_bgr, int width, int
 extern "C" int ocvar_hip_find_squares(OcvarHip* c, const uint8_t* h_gray, int width, int height, int row_stride, int* quads,
                                       int max_quads, int* n_quads) {
     if (!c || !h_gray || !quads || !n_quads || width < 16 || height < 16 || row_stride < width) return OCVAR_E_ARG;
+    if (width > c->ws.max_w || height > c->ws.max_h) return OCVAR_E_ARG;   // (before the expanded copy is made, not after)
+    if (int rc = frame_span_check(c, width, height, 3 * width, OCVAR_FMT_BGR)) return rc;
     std::vector<uint8_t> bgr((size_t)width * height * 3);
     for (int y = 0; y < height; y++)
         for (int x = 0; x < width; x++) {

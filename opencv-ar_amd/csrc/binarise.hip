@@ -230,7 +230,7 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     // must not store gets an offset beyond the resource's size: the hardware drops its store, so the grey and mask stores need
     // no EXEC mask and the row body stays one basic block.
     constexpr unsigned OOB = 0x80000000u;   // >= every resource size below (+ 16 does not wrap)
-    const __amdgpu_buffer_rsrc_t src_rs = make_rsrc(src, 0x7fffffffu);
+    const __amdgpu_buffer_rsrc_t src_rs = make_rsrc(src, (unsigned)MARCH_SRC_BYTES);   // (hd.h::frame_src_addressable: what api.hip lets through)
     const __amdgpu_buffer_rsrc_t gray_rs = make_rsrc(o.gray, o.gray ? (unsigned)(o.gray_stride * sh) : 0u);
     const __amdgpu_buffer_rsrc_t nbr_rs = make_rsrc(o.nbr, (unsigned)nbr_plane_bytes(o.ns, sh));
     // the grey plane's panel of this strip (hd.h::gray_col): all 64 lanes store, 256 contiguous bytes at a 256-byte boundary -- the

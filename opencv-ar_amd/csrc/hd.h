@@ -117,6 +117,21 @@ OCVAR_HD unsigned gray_col(int x) {
     return p * (unsigned)(GRAY_PANEL_BYTES - GRAY_PANEL_COLS) + (unsigned)x + (unsigned)GRAY_PANEL_LEAD;
 }
 
+// What the frame binarise kernel can address of a caller's frame.  binarise.hip::march_unit reads source rows through ONE buffer
+// resource of MARCH_SRC_BYTES bytes laid over the frame's first byte: a row's byte offset rv * row_stride travels as a 32-bit
+// signed product in the scalar offset, the lane's column offset (at most bpp * (sw - 4), plus the 4 bpp bytes of its load) in the
+// vector offset.  The furthest byte a lane reads is byte bpp * sw - 1 of row sh - 1 (sw, sh: width and height rounded down to
+// even; the odd last row and column, and the in-place grey, go through 64-bit pointers), so a frame is addressable when
+//     (sh - 1) * row_stride + bpp * sw <= MARCH_SRC_BYTES
+// -- then the product does not overflow an int, and every load ends inside the resource whether or not the hardware counts the
+// scalar offset in its range check.  Beyond it rows would be read at wrapped offsets, or dropped as zeros: a silently different
+// detection.  api.hip refuses such frames (OCVAR_E_ARG) before any device call.
+constexpr long long MARCH_SRC_BYTES = 0x7fffffffLL;
+OCVAR_HD bool frame_src_addressable(int width, int height, long long row_stride, int bpp) {
+    const long long sw = width & ~1, sh = height & ~1;
+    return sh < 1 || (sh - 1) * row_stride + bpp * sw <= MARCH_SRC_BYTES;
+}
+
 // One region of interest handed to the square finder: a whole frame (frame pass) or the clipped
 // bounding box of a frame-pass quad (crop pass, opencvar.cpp:682-693).
 struct Roi {

@@ -195,10 +195,11 @@ def test_grey_plane_panels(emul):
     kernel converts).  The properties the readers rely on: home offsets are distinct and inside the row; from any column the next
     8 columns follow contiguously (a crop lane's 4-byte load, decode's two neighbouring samples); a column within 8 of a panel's
     start is the 8-column tail of the panel before it shifted by one panel (where the frame kernel's halo lanes -- and the
-    odd-column kernel -- keep the second copy)."""
+    odd-column kernel -- keep the second copy).  Up to the widest frame a context can have: 32767 columns, 137 panels, and 32641,
+    whose last column begins the last panel."""
     import ctypes as C
     emul.emul_gray_col.restype = C.c_uint
-    for W in (16, 239, 240, 241, 243, 480, 487, 640, 1001, 1920, 3840):
+    for W in (16, 239, 240, 241, 243, 480, 487, 640, 1001, 1920, 3840, 32641, 32767):
         pitch = emul.emul_gray_pitch(W)
         assert pitch % 256 == 0 and pitch >= ((W + 239) // 240) * 256
         offs = [emul.emul_gray_col(x) for x in range(W)]
@@ -210,6 +211,15 @@ def test_grey_plane_panels(emul):
             assert offs[x] + 8 <= p * 256 + 255
             if x >= 240 and x % 240 < 8:   # second copy: same column, seen from the panel before
                 assert emul.emul_gray_col(x - 8) + 8 == (p - 1) * 256 + 248 + x % 240
+        # any 9 consecutive columns read from the panel of the first one are contiguous bytes of the row -- at every panel seam too,
+        # where columns x + k of the next panel are the first panel's tail (the frame kernel stores them in both)
+        for x in range(W - 8):
+            assert offs[x] + 8 < pitch and (x + 8) // 240 - x // 240 <= 1
+            if (x + 8) // 240 != x // 240:   # the run crosses into panel p + 1: its columns there, seen from panel p
+                p = x // 240
+                for k in range(9):
+                    assert offs[x] + k == p * 256 + 8 + (x + k - 240 * p) <= p * 256 + 255
+    assert emul.emul_gray_pitch(32767) == 137 * 256 and (32641 - 1) % 240 == 0
 
 
 def test_pose_cores_agree_over_aspect_ratios(emul):
