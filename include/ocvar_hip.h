@@ -234,6 +234,41 @@ int ocvar_hip_render_records(OcvarHip* ctx, uint8_t* d_frames, int width, int he
                              int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
                              void* stream);
 
+/* Patches: the upright, perspective-free image of every marker record, cut out of frames that stay in device memory -- the
+ * reference's cvarInvertPerspective(frame, patch, record.square, cvarSquare(patch_w, patch_h, 0)) (opencvar.cpp:510-516), one
+ * dense block for a whole batch.  The definition, bit for bit, is opencv-ar_amd/csrc/patch_core.h: the map
+ * perspective_from_quad(record.square, patch_w, patch_h) in float32, inverted in double, cvWarpPerspective's 1/32-px bilinear
+ * sampling with a constant 0 outside the frame.  Record corners 0, 1, 2, 3 land on patch pixels (0,0), (patch_w-1,0),
+ * (patch_w-1,patch_h-1), (0,patch_h-1).  Every byte of a pixel is warped alike: a patch has the bytes per pixel of `format`
+ * (1, 3 or 4) in the frame's memory order, byte 3 of a four-channel pixel included.
+ *   d_patches  [n_frames][records_per_frame][patch_h][patch_w][bpp] bytes, contiguous, at any address
+ *   d_status   [n_frames][records_per_frame] ints, every entry written; may be NULL
+ * A slot is written (status 1) when its index is below min(count, records_per_frame), all eight coordinates of the square are
+ * finite and at most 1e6 (OCVAR_PATCH_MAX_COORD) in magnitude, the quad has a map (four corners in a line have none) and, with
+ * OCVAR_PATCH_MATCHED_ONLY, score > 0.  Every other slot gets status 0 and none of its patch bytes is touched.  A written patch
+ * wholly outside the frame is all zeros.  Quads that are not convex give whatever the formulas give.
+ * OCVAR_PATCH_FLIP_ROWS stores patch row r at row patch_h-1-r and changes nothing else: templates are loaded flipped vertically
+ * (see ocvar_hip_set_board), so with this flag a marker's patch reads like its template's image file.
+ *
+ * ocvar_hip_patches: after ocvar_hip_enqueue and before ocvar_hip_collect (like ocvar_hip_render, with the same promises about
+ * streams, lanes and collect on a context of a gate), on the enqueued batch's own records, the first records_per_frame (1 .. M =
+ * ocvar_hip_max_markers(ctx)) of every frame.  d_frames: the frames that were detected (greyed, if grey_in_place was asked for)
+ * or any other buffer of the batch's frame count and size, in any `format`; after ocvar_hip_render on the same stream the
+ * patches show the overlays.  Stream-ordered behind the batch; does not wait.
+ * ocvar_hip_patches_records: the same on records the caller supplies in device memory, d_markers [n_frames][records_per_frame]
+ * and d_counts [n_frames] (a count above records_per_frame is read as records_per_frame).  Needs no batch; frames of up to the
+ * context's max_width x max_height; any n_frames >= 1.  stream NULL: the context's own stream.  Does not wait.
+ * Both need no workspace: a context that never asks for patches allocates and launches nothing.  OCVAR_E_ARG, before any device
+ * call and with a text in ocvar_hip_last_error, for NULL frames or patches, an unknown format, a row_stride below the format's
+ * bytes per pixel times width, a patch side outside 2 .. OCVAR_MAX_PATCH_SIDE, unknown flag bits, records_per_frame outside
+ * 1 .. M; ocvar_hip_patches also when nothing is enqueued or width or height differ from the batch's. */
+enum { OCVAR_MAX_PATCH_SIDE = 256, OCVAR_PATCH_FLIP_ROWS = 1, OCVAR_PATCH_MATCHED_ONLY = 2 };
+int ocvar_hip_patches(OcvarHip* ctx, const uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int format,
+                      uint8_t* d_patches, int patch_w, int patch_h, int records_per_frame, int flags, int* d_status, void* stream);
+int ocvar_hip_patches_records(OcvarHip* ctx, const uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride,
+                              int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
+                              uint8_t* d_patches, int patch_w, int patch_h, int flags, int* d_status, void* stream);
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart

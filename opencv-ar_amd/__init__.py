@@ -30,6 +30,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_stage_ms", "ocvar_hip_stream", "ocvar_hip_stage_stamps", "ocvar_hip_counters", "ocvar_hip_results_to_device", "ocvar_hip_results_to_device_ex", "ocvar_hip_debug_calibrate",
     "ocvar_hip_set_board", "ocvar_hip_board_poses", "ocvar_hip_board_poses_to_device",
     "ocvar_hip_set_overlay", "ocvar_hip_render", "ocvar_hip_render_records",
+    "ocvar_hip_patches", "ocvar_hip_patches_records",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -76,6 +77,7 @@ def corner_refine_args(half_win, max_iter, eps):
 
 MAX_BOARD_MARKERS = 256   # include/ocvar_hip.h: OCVAR_MAX_BOARD_MARKERS
 MAX_OVERLAYS, MAX_OVERLAY_SIDE = 64, 1024   # include/ocvar_hip.h: OCVAR_MAX_OVERLAYS, OCVAR_MAX_OVERLAY_SIDE
+MAX_PATCH_SIDE, PATCH_FLIP_ROWS, PATCH_MATCHED_ONLY = 256, 1, 2   # include/ocvar_hip.h: OCVAR_MAX_PATCH_SIDE, OCVAR_PATCH_*
 
 
 class BoardMarker(C.Structure):  # OcvarBoardMarker: a template and the board-plane (z = 0) coordinates of its corners 0..3
@@ -214,6 +216,8 @@ def hip_lib():
         lib.ocvar_hip_set_overlay.argtypes = [vp, i, vp, i, i, i]
         lib.ocvar_hip_render.argtypes = [vp, vp, i, i, i, sz, i, vp]
         lib.ocvar_hip_render_records.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, i, vp]
+        lib.ocvar_hip_patches.argtypes = [vp, vp, i, i, i, sz, i, vp, i, i, i, i, vp, vp]
+        lib.ocvar_hip_patches_records.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, i, vp, i, i, i, vp, vp]
         _hip = lib
     return _hip
 
@@ -569,6 +573,36 @@ class Detector:
         frame_stride = frame_stride or row_stride * height
         self._check(self._lib.ocvar_hip_render_records(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames, code,
                                                        d_markers_ptr, d_counts_ptr, per_frame, stream), "render_records")
+
+    def patches(self, d_ptr, width, height, d_patches_ptr, patch_w, patch_h, per_frame=None, fmt=None, row_stride=None, frame_stride=None,
+                flip_rows=False, matched_only=False, d_status_ptr=None, stream=None):
+        """between enqueue and collect: the rectified patch_h x patch_w image of the first per_frame (default max_markers) records
+        of every frame of the enqueued batch, cut out of the device frames at d_ptr (the frames detected, or another buffer of the
+        batch's frame count and size) in format fmt (default: the input format), into the device block d_patches_ptr
+        [n, per_frame, patch_h, patch_w, bpp] uint8; record corners 0..3 land on the patch's top-left, top-right, bottom-right and
+        bottom-left pixels (flip_rows: rows stored bottom-up, as the template's image file reads).  d_status_ptr: device ints
+        [n, per_frame], 1 where the slot was written; slots that are not written keep their bytes (include/ocvar_hip.h has the
+        rule).  matched_only: records with score > 0 only.  Stream-ordered behind the batch, does not wait."""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        per_frame = self.max_markers if per_frame is None else per_frame
+        row_stride = row_stride or FORMAT_BPP[code] * width
+        frame_stride = frame_stride or row_stride * height
+        flags = (PATCH_FLIP_ROWS if flip_rows else 0) | (PATCH_MATCHED_ONLY if matched_only else 0)
+        self._check(self._lib.ocvar_hip_patches(self._ctx, d_ptr, width, height, row_stride, frame_stride, code, d_patches_ptr, patch_w,
+                                                patch_h, per_frame, flags, d_status_ptr, stream), "patches")
+
+    def patches_records(self, d_ptr, width, height, n_frames, d_markers_ptr, d_counts_ptr, d_patches_ptr, patch_w, patch_h, per_frame=None,
+                        fmt=None, row_stride=None, frame_stride=None, flip_rows=False, matched_only=False, d_status_ptr=None, stream=None):
+        """the same for n_frames device frames under caller-supplied device records [n_frames, per_frame] (default per_frame:
+        max_markers) and counts [n_frames]; needs no batch, does not wait (stream None: the detector's own stream)"""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        per_frame = self.max_markers if per_frame is None else per_frame
+        row_stride = row_stride or FORMAT_BPP[code] * width
+        frame_stride = frame_stride or row_stride * height
+        flags = (PATCH_FLIP_ROWS if flip_rows else 0) | (PATCH_MATCHED_ONLY if matched_only else 0)
+        self._check(self._lib.ocvar_hip_patches_records(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames, code,
+                                                        d_markers_ptr, d_counts_ptr, per_frame, d_patches_ptr, patch_w, patch_h, flags,
+                                                        d_status_ptr, stream), "patches_records")
 
     TUNE = {"crop_phases": 1, "mid_steps": 2, "mid_blocks": 3, "long_blocks": 4, "short_blocks": 5, "min_units": 6, "hp_mask": 7, "gate_mode": 8}
 

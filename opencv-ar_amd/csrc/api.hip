@@ -1102,6 +1102,81 @@ extern "C" int ocvar_hip_render_records(OcvarHip* c, uint8_t* d_frames, int widt
                           reinterpret_cast<const MarkerRec*>(d_markers), d_counts, records_per_frame, stream ? (hipStream_t)stream : c->stream);
 }
 
+// what ocvar_hip_patches and ocvar_hip_patches_records refuse alike
+static bool patch_args_ok(OcvarHip* c, const uint8_t* d_frames, int width, int row_stride, int format, const uint8_t* d_patches, int patch_w,
+                          int patch_h, int records_per_frame, int flags) {
+    if (!d_frames || !d_patches) {
+        c->err = "patches: no frames or no patch buffer";
+    } else if (patch_bpp(format) == 0 || (long long)row_stride < (long long)patch_bpp(format) * width) {
+        c->err = "patches: an unknown format or a row_stride below the format's bytes per pixel times width";
+    } else if (patch_w < 2 || patch_h < 2 || patch_w > PATCH_MAX_SIDE || patch_h > PATCH_MAX_SIDE) {
+        c->err = "patches: patch sides of 2 .. " + std::to_string(PATCH_MAX_SIDE) + " pixels";
+    } else if (flags & ~PATCH_FLAGS) {
+        c->err = "patches: unknown flag bits";
+    } else if (records_per_frame < 1 || records_per_frame > c->ws.maxm) {
+        c->err = "patches: 1 .. M records per frame";
+    } else {
+        return true;
+    }
+    return false;
+}
+
+// n_frames frames on stream s, in chunks of the grid's z
+static int patch_launch(OcvarHip* c, const PatchArgs& all, int n_frames, int format, hipStream_t s) {
+    const int chunk = 32768;
+    const size_t frame_patches = (size_t)all.slots * all.ph * all.pw * patch_bpp(format);
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        PatchArgs a = all;
+        a.frames += (size_t)f0 * a.frame_stride;
+        a.recs += (size_t)f0 * a.rec_stride;
+        a.counts += f0;
+        a.patches += (size_t)f0 * frame_patches;
+        if (a.status) a.status += (size_t)f0 * a.slots;
+        launch_patches(a, std::min(chunk, n_frames - f0), format, s);
+        TRACE_LAUNCH("patches", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_patches(OcvarHip* c, const uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int format,
+                                 uint8_t* d_patches, int patch_w, int patch_h, int records_per_frame, int flags, int* d_status, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    if (!c->pending) {
+        c->err = "patches: nothing enqueued";
+        return OCVAR_E_ARG;
+    }
+    if (width != c->ws.W || height != c->ws.H) {
+        c->err = "patches: the frames are not of the batch's size";
+        return OCVAR_E_ARG;
+    }
+    if (!patch_args_ok(c, d_frames, width, row_stride, format, d_patches, patch_w, patch_h, records_per_frame, flags)) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = copy_stream(c, stream);
+    if (s != c->last_stream) HIP_TRY(c, hipStreamWaitEvent(s, c->ev[12], 0));   // order behind the batch
+    const PatchArgs a{d_frames, width, height, (long long)row_stride, (long long)frame_stride, c->ws.markers, c->ws.n_markers, c->ws.maxm,
+                      d_patches, patch_w, patch_h, records_per_frame, flags, d_status};
+    const int rc = patch_launch(c, a, c->ws.n_frames, format, s);
+    if (rc) return rc;
+    HIP_TRY(c, tail_behind_copy(c, s));
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_patches_records(OcvarHip* c, const uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride,
+                                         int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
+                                         uint8_t* d_patches, int patch_w, int patch_h, int flags, int* d_status, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    if (!d_markers || !d_counts || n_frames < 1 || width < 1 || height < 1 || width > c->ws.max_w || height > c->ws.max_h) {
+        c->err = "patches_records: records and counts, frames of 1 .. the context's size, n_frames >= 1";
+        return OCVAR_E_ARG;
+    }
+    if (!patch_args_ok(c, d_frames, width, row_stride, format, d_patches, patch_w, patch_h, records_per_frame, flags)) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const PatchArgs a{d_frames, width, height, (long long)row_stride, (long long)frame_stride, reinterpret_cast<const MarkerRec*>(d_markers),
+                      d_counts, records_per_frame, d_patches, patch_w, patch_h, records_per_frame, flags, d_status};
+    return patch_launch(c, a, n_frames, format, stream ? (hipStream_t)stream : c->stream);
+}
+
 extern "C" int ocvar_hip_detect_device(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride,
                                        int n_frames, int grey_in_place, const OcvarMarker* prev, const int* prev_counts,
                                        OcvarMarker* markers, int* counts, int max_per_frame) {

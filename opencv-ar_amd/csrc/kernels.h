@@ -7,6 +7,7 @@
 #include "refine_core.h"
 #include "board_core.h"
 #include "overlay_core.h"
+#include "patch_core.h"
 #include "ocvar_hip.h"
 
 namespace ocvar {
@@ -174,5 +175,22 @@ struct OverlayArgs {
 // (the first min(counts[f], stride) of frame f), all in device memory
 void launch_overlay(const OverlayArgs& oa, uint8_t* frames, int W, int H, long long row_stride, long long frame_stride, int n_frames,
                     int format, const MarkerRec* recs, const int* counts, int stride, hipStream_t stream);
+
+// One launch of patch_kernel (patch.hip), all pointers in device memory: frames of W x H pixels; of frame f the records
+// recs[f * rec_stride + k], k < min(counts[f], slots); patches [n_frames][slots][ph][pw][bpp] at any address; status
+// [n_frames][slots] or nullptr; flags OCVAR_PATCH_*.
+struct PatchArgs {
+    const uint8_t* frames;
+    int W, H;
+    long long row_stride, frame_stride;
+    const MarkerRec* recs;
+    const int* counts;
+    int rec_stride;
+    uint8_t* patches;
+    int pw, ph, slots, flags;
+    int* status;
+};
+// n_frames (at most 32768: the grid's z) frames in `format`
+void launch_patches(const PatchArgs& a, int n_frames, int format, hipStream_t stream);
 
 }  // namespace ocvar
