@@ -257,7 +257,7 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     // source row wait for that store too: vmcnt counts loads and stores in order.)  A tile's dword is 18 columns, 16 tx - 1 ..
     // 16 tx + 16: the nibbles of lanes 4 tx + 1 .. 4 tx + 6 -- the apron columns -1 and 240 of a strip are the threshold bits of
     // halo lanes 1 and 62, which the wave computes anyway; rows Y0 - 1 and Y1, the apron rows of a unit, are computed for the
-    // start tests.  Y0 is a multiple of 14 (api.hip / MARCH_CROP_ROWS), so a tile row belongs to one work unit; rows outside
+    // start tests.  Y0 is a multiple of 14 (plan_core.h / MARCH_CROP_ROWS), so a tile row belongs to one work unit; rows outside
     // [0, Y1] (row -1, rows below the image) are stored as 0.
     const int tile_s = strip * (SV / NBR_TILE_W) + (lane >> 2);   // the lane's tile in the tile row
     const unsigned flush_src = (unsigned)(lane < 60 ? lane >> 2 : 14) * 4u;   // byte of lane 4 tx in an LDS row (lanes 60..63: any tile, their store is dropped)

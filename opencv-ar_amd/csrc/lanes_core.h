@@ -1,4 +1,4 @@
-// lanes_core.h -- the gate's scheduling policy, free of HIP calls (api.hip drives it with streams and events, tests/emul with a
+// lanes_core.h -- the gate's scheduling policy, free of HIP calls (gate.hip drives it with streams and events, tests/emul with a
 // simulated timeline): how many lanes a gate opens, which lane a batch goes to, and the tickets of the gated launches.
 //
 // A lane is a stream the gate owns.  The runtime deals streams onto the process's hardware queues, and streams that share a
@@ -72,7 +72,7 @@ inline void lane_retire(LaneSched* s, int lane) {
 
 // Brings the lanes up to date before a placement: a batch that has finished on the device but has not been collected yet is
 // no outstanding work.  *lane_of[i] is the lane that still counts in-flight batch i (-1: none); done(user, i) says whether
-// that batch has finished (api.hip: a query of its last event; the tests: a simulated clock).
+// that batch has finished (gate.hip: a query of its last event; the tests: a simulated clock).
 typedef int (*LaneDoneFn)(void* user, int batch);
 inline void lane_refresh(LaneSched* s, int* const* lane_of, int n, LaneDoneFn done, void* user) {
     for (int i = 0; i < n; i++)

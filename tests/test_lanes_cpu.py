@@ -39,7 +39,7 @@ def lib(tmp_path_factory):
 class Sim:
     """The device side of a gate: every lane runs its segments in order.  A batch is four segments -- frame binarise (gated),
     followers, crop binarise (gated), the rest -- of given lengths; a gated segment starts when the segment in front of it in
-    its lane has ended AND the gated segment its ticket waits for has ended.  The host side is api.hip's: one batch in flight
+    its lane has ended AND the gated segment its ticket waits for has ended.  The host side is gate.hip's: one batch in flight
     per context, placed by lane_place, whose "finished" callback reads the simulated clock."""
 
     def __init__(self, L, n_lanes, width, n_ctx):
@@ -61,7 +61,7 @@ class Sim:
         return (C.c_int * self.n_ctx)(*[int(seg is not None and seg["end"] <= self.now) for seg in self.last_seg])
 
     def enqueue(self, ctx, lengths):
-        """places a batch of context ctx as api.hip does; returns (lane, lanes' outstanding work at the placement)"""
+        """places a batch of context ctx as gate.hip does; returns (lane, lanes' outstanding work at the placement)"""
         assert self.lane_of[ctx] == -1
         # (the two halves of lane_place apart, to see the counts it chose from; test_place_is_refresh_choose_book ties them)
         counted = sum(1 for l in self.lane_of if l >= 0)
@@ -191,7 +191,7 @@ def test_finished_batches_do_not_count_at_a_placement(lib):
 
 
 def test_place_is_refresh_choose_book(lib):
-    """lane_place (what api.hip calls) against its three steps on a copy of the same state"""
+    """lane_place (what gate.hip calls) against its three steps on a copy of the same state"""
     rng = np.random.default_rng(5)
     for _ in range(200):
         n_lanes, n = int(rng.integers(1, 9)), int(rng.integers(1, 9))
