@@ -70,6 +70,9 @@ static int create_impl(OcvarHip** out, int device, int max_width, int max_height
     if ((rc = dev_alloc(c, &w.mid_frame, (size_t)w.cap_long))) return rc;
     if ((rc = dev_alloc(c, &w.mid_crop, (size_t)w.cap_long))) return rc;
     if ((rc = dev_alloc(c, &w.mid_first_crop, (size_t)w.cap_long))) return rc;
+    if ((rc = dev_alloc(c, &w.crop_early, (size_t)w.cap_long))) return rc;
+    if ((rc = dev_alloc(c, &w.crop_rest, (size_t)w.cap_long))) return rc;
+    if ((rc = dev_alloc(c, &w.crop_live, (size_t)w.cap_long))) return rc;
     if ((rc = dev_alloc(c, &w.long_frame, (size_t)w.cap_long))) return rc;
     if ((rc = dev_alloc(c, &w.long_crop, (size_t)w.cap_long))) return rc;
     if ((rc = dev_alloc(c, &w.quads_frame, B * max_quads))) return rc;

@@ -453,10 +453,10 @@ __device__ __forceinline__ int follow_short(const Workspace& ws, const StartCand
 
 // Tier-2 borders with more corner points than a lane's slab holds (rare: > 1024 corners within the step budget):
 // statistics first, then a storing follow into the pool, approximated by the lane itself.  Returns the route (1 = budget
-// exhausted after all, 0 = done).
+// exhausted after all, 0 = done).  max_steps: the walk's budget in tier 2.
 template <bool CROP>
-__device__ int follow_overflow(const Workspace& ws, const StartCand c, const PlaneRef& pl) {
-    const TraceStats st = trace_border<false, false>(pl.nbr, pl.ns, pl.plane, c.pos, c.is_hole, nullptr, 0, ws.mid_steps);
+__device__ int follow_overflow(const Workspace& ws, const StartCand c, const PlaneRef& pl, int max_steps) {
+    const TraceStats st = trace_border<false, false>(pl.nbr, pl.ns, pl.plane, c.pos, c.is_hole, nullptr, 0, max_steps);
     if (st.status == TRACE_OVERRUN) return 1;
     if (!worth_approximating(st)) return 0;
     const int need = 2 * st.npts + 2 * (st.npts + 2);
@@ -466,7 +466,7 @@ __device__ int follow_overflow(const Workspace& ws, const StartCand c, const Pla
         return 0;
     }
     int* pts = ws.pool + off;
-    trace_border<true, false>(pl.nbr, pl.ns, pl.plane, c.pos, c.is_hole, pts, st.npts, ws.mid_steps);
+    trace_border<true, false>(pl.nbr, pl.ns, pl.plane, c.pos, c.is_hole, pts, st.npts, max_steps);
     approximate_and_emit<CROP>(ws, c, pl, pts, st.npts, st.perimeter, reinterpret_cast<DpSlice*>(pts + 2 * st.npts));
     return 0;
 }
@@ -749,6 +749,10 @@ static_assert(FLUSH_W >= MID_BLOCK && 64 % FLUSH_W == 0, "a group of lanes cover
 // valid quad) and each crop's earliest other start (nearly always the marker's outline: the quad that wins); phase 2 takes
 // what is left and skips every start behind its crop's best quad -- the outline's other side, the code cells, and the
 // staircase starts inside them: about half of a crop's steps.  Frames keep all their quads: one launch, phase 0.
+// The phases read lists that hold only what they walk (croplist_core.h; crop_split_kernel / crop_prune_kernel below): a
+// hand-out that reads an entry only to drop it costs an idle lane a ticket and two dependent loads while the wave's other
+// walks stand still.  Phase 1 takes every entry it is handed; phase 2 still tests "behind the best quad" at hand-out, since
+// best_crop keeps improving while it runs.  A crop's walk gets the step budget that fits its crop (crop_walk_budget).
 template <bool CROP>
 __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws, int phase) {
     __shared__ WaveScratch scratch[FW];
@@ -756,9 +760,9 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
     __shared__ unsigned step_tab[64];
     if (threadIdx.x < 64u) step_tab[threadIdx.x] = lean_table_entry(threadIdx.x);
     __syncthreads();
-    const StartCand* cands = CROP ? ws.mid_crop : ws.mid_frame;
+    const StartCand* cands = CROP ? (phase == 1 ? ws.crop_early : phase == 2 ? ws.crop_live : ws.mid_crop) : ws.mid_frame;
     StartCand* longs = CROP ? ws.long_crop : ws.long_frame;
-    int n = ws.counters[CROP ? CNT_MID_C : CNT_MID_F];
+    int n = ws.counters[CROP ? (phase == 1 ? CNT_CROP_EARLY : phase == 2 ? CNT_CROP_LIVE : CNT_MID_C) : CNT_MID_F];
     if (n > ws.cap_long) n = ws.cap_long;
     // crops, phase 1: the starts on the crop frames (the longest walks) come first in the ticket order
     int n_first = (CROP && phase != 2) ? ws.counters[CNT_MID_C_FIRST] : 0;
@@ -774,7 +778,10 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
     unsigned* my_row = parked[wave] + lane * POINT_ROW;
     const unsigned* wave_rows = parked[wave];
     int flushed = 0;     // points of this lane's walk already in its slab
-    const int budget = ws.mid_steps;
+    const int budget = CROP ? ws.crop_steps_cap : ws.mid_steps;   // (crops: the most any walk gets, see the check below)
+    // hand-outs an idle lane gets per round: phase 1's lists hold nothing to skip, phase 2's only what was beaten since the
+    // prune kernel ran, phase 0 on crops reads tier 1's whole list
+    const int max_tries = CROP ? (phase == 1 ? 1 : phase == 2 ? 2 : 4) : 1;
     bool have = false;   // this lane holds a start whose walk has not been retired
     bool more = true;    // wave-uniform: the list may still hold starts
     StartCand c;
@@ -796,9 +803,9 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
         // hand idle lanes the next starts of the list (one ticket fetch for all of them; taking list entries in bulk per wave
         // instead was slower: lanes wait for the next round whenever the wave's range runs out, and the ranges unbalance the tail)
         const unsigned long long pt0 = PROF_NOW();
-        // (crops: a start may be skipped -- not this phase's, or behind its crop's best quad -- so idle lanes get up to four
-        // hand-outs per round; every hand-out consumes list entries, which the guard counts)
-        for (int tries = 0; tries < (CROP ? 4 : 1); tries++) {
+        // (crops: a start behind its crop's best quad is skipped, so idle lanes get up to max_tries hand-outs per round; every
+        // hand-out consumes list entries, which the guard counts)
+        for (int tries = 0; tries < max_tries; tries++) {
             const unsigned long long idle = __ballot(!have);
             if (!(more && idle)) break;
             if (tries > 0) --guard;
@@ -812,13 +819,8 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
                 if (idx < n) {
                     c = (CROP && idx < n_first) ? ws.mid_first_crop[idx] : cands[idx - n_first];
                     bool take = true;
-                    if (CROP) {
-                        const int earliest = ws.crop_min_rest[c.roi];
-                        const bool beaten = (unsigned)(ws.best_crop[c.roi] >> 32) < (unsigned)c.pos;
-                        if (phase == 1) take = idx < n_first || c.pos == earliest;
-                        else if (phase == 2) take = c.pos != earliest && !beaten;
-                        else take = !beaten;   // phase 0 on crops (Workspace::crop_phases == 1): one launch, pruning only by what happens to be finished
-                    }
+                    // (phase 0 on crops -- Workspace::crop_phases == 1 -- is one launch, pruning only by what happens to be finished)
+                    if (CROP && phase != 1) take = !crop_start_beaten(c.pos, ws.best_crop[c.roi]);
                     pl = plane_of<CROP>(ws, c.roi);
                     if (take && c.pos > 0 && c.pos < pl.plane) {
                         lean_begin(w, pl.nbr, pl.ns, c.pos, c.is_hole);
@@ -848,7 +850,7 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
         }
         // the step budget is checked here, once per block, instead of in every step (a walk may overshoot it by up to
         // MID_BLOCK - 1 steps; it is handed to the wave tier either way, which follows the border again from its start)
-        if (have && w.status < 0 && w.step >= budget) w.status = TRACE_OVERRUN;
+        if (have && w.status < 0 && w.step >= (CROP ? crop_walk_budget(pl.img_w & ~1, pl.img_h & ~1, ws.mid_steps, budget) : budget)) w.status = TRACE_OVERRUN;
         const unsigned long long pt2 = PROF_NOW();
         PROF_ADD(1, pt2 - pt1);
         {   // append the parked points to the slabs: every group of FLUSH_W lanes carries one walk's row per store
@@ -889,7 +891,7 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
                 PROF_ADD(8 + 2 * st_, steps_);
             }
             bool useless = false;   // crops: a closed border that starts after the crop's best quad so far
-            if (CROP && done && w.status == TRACE_OK) useless = (unsigned)(ws.best_crop[c.roi] >> 32) < (unsigned)c.pos;
+            if (CROP && done && w.status == TRACE_OK) useless = crop_start_beaten(c.pos, ws.best_crop[c.roi]);
             unsigned us_ = useless ? (unsigned)w.step : 0u;
             for (int o_ = 32; o_ > 0; o_ >>= 1) us_ += (unsigned)__shfl_xor((int)us_, o_, 64);
             PROF_ADD(14, us_);
@@ -903,7 +905,7 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
                     route = 3;   // finished by the whole wave below
                     slab_npts = w.npts;
                 } else {
-                    route = follow_overflow<CROP>(ws, c, pl);
+                    route = follow_overflow<CROP>(ws, c, pl, CROP ? crop_walk_budget(pl.img_w & ~1, pl.img_h & ~1, ws.mid_steps, budget) : budget);
                 }
             }
             have = false;
@@ -951,6 +953,64 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
     }
     PROF_FLUSH(CROP ? 16 : 0);
 }
+
+// ---- the crop pass's lists (croplist_core.h) ------------------------------------------------------------------------------------
+// One lane per entry of the source list, coalesced; a wave takes CL_CHUNK entries at a time, stages what each target list keeps
+// in LDS and appends it with one atomic per list and chunk (as tier 1's append: a single counter sustains ~90 atomics per
+// microsecond).  crop_split_kernel (PRUNE = false): mid_crop -> E (a crop's earliest start) and R (the others), before phase 1.
+// crop_prune_kernel (PRUNE = true): R -> R' (not behind the crop's best quad), between the phases.
+constexpr int CL_CHUNK = 512;
+static_assert(CROP_BUDGET_BLOCK == MID_BLOCK, "a crop's budget is rounded to the unit tier 2 checks it in");
+
+template <bool PRUNE>
+__device__ __forceinline__ void crop_lists(const Workspace& ws) {
+    __shared__ StartCand stage[PRUNE ? 1 : 2][CL_CHUNK];
+    const StartCand* src = PRUNE ? ws.crop_rest : ws.mid_crop;
+    int n = ws.counters[PRUNE ? CNT_CROP_REST : CNT_MID_C];
+    if (n > ws.cap_long) n = ws.cap_long;
+    const int lane = threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int base = (int)blockIdx.x * CL_CHUNK; base < n; base += (int)gridDim.x * CL_CHUNK) {
+        int n0 = 0, n1 = 0;   // wave-uniform fill levels of the two stages
+        const int end = base + CL_CHUNK < n ? base + CL_CHUNK : n;
+        for (int i0 = base; i0 < end; i0 += 64) {
+            const int i = i0 + lane;
+            bool to0 = false, to1 = false;
+            StartCand c;
+            c.roi = 0; c.pos = 0; c.is_hole = 0;
+            if (i < end) {
+                c = src[i];
+                if (PRUNE) {
+                    to0 = !crop_start_beaten(c.pos, ws.best_crop[c.roi]);
+                } else {
+                    to0 = crop_start_earliest(c.pos, ws.crop_min_rest[c.roi]);
+                    to1 = !to0;
+                }
+            }
+            const unsigned long long m0 = __ballot(to0), m1 = __ballot(to1);
+            if (to0) stage[0][n0 + __popcll(m0 & below)] = c;
+            if (!PRUNE && to1) stage[PRUNE ? 0 : 1][n1 + __popcll(m1 & below)] = c;
+            n0 += __popcll(m0);
+            n1 += __popcll(m1);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        for (int t = 0; t < (PRUNE ? 1 : 2); t++) {
+            const int cnt = t == 0 ? n0 : n1;   // <= CL_CHUNK: every entry goes to at most one stage slot
+            StartCand* list = PRUNE ? ws.crop_live : (t == 0 ? ws.crop_early : ws.crop_rest);
+            int* count = ws.counters + (PRUNE ? CNT_CROP_LIVE : (t == 0 ? CNT_CROP_EARLY : CNT_CROP_REST));
+            int qbase = 0;
+            if (lane == 0 && cnt > 0) qbase = atomicAdd(count, cnt);
+            qbase = uni(qbase);
+            for (int k = lane; k < cnt; k += 64) {
+                if (qbase + k < ws.cap_long) list[qbase + k] = stage[t][k];
+                else atomicOr(ws.counters + CNT_ERR, ERR_CAND_OVERFLOW);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // the stages are refilled by the next chunk
+    }
+}
+__global__ __launch_bounds__(64) void crop_split_kernel(Workspace ws) { crop_lists<false>(ws); }
+__global__ __launch_bounds__(64) void crop_prune_kernel(Workspace ws) { crop_lists<true>(ws); }
 
 // ---- Phase B: one wave per long border, walking inside an LDS tile cache -------------------------------------
 // The follower's step needs the neighbour mask of the pixel it just moved to: a dependent load, i.e. one HBM/L2 latency
@@ -1468,7 +1528,11 @@ void launch_follow_mid_crops(const Workspace& ws, hipStream_t stream) {
         hipLaunchKernelGGL(follow_mid_kernel<true>, dim3(ws.mid_blocks * (4 / FW)), dim3(FOLLOW_THREADS), 0, stream, ws, 0);
         return;
     }
+    // (the list kernels: one wave per CL_CHUNK entries at the benchmark's ~250 entries per frame, fewer waves striding beyond)
+    const int list_blocks = ws.n_frames >= 2048 ? 1024 : (ws.n_frames < 32 ? 16 : ws.n_frames / 2);   // 16 .. 1024
+    hipLaunchKernelGGL(crop_split_kernel, dim3(list_blocks), dim3(64), 0, stream, ws);
     hipLaunchKernelGGL(follow_mid_kernel<true>, dim3(ws.mid_blocks * (4 / FW)), dim3(FOLLOW_THREADS), 0, stream, ws, 1);
+    hipLaunchKernelGGL(crop_prune_kernel, dim3(list_blocks), dim3(64), 0, stream, ws);
     hipLaunchKernelGGL(follow_mid_kernel<true>, dim3(ws.mid_blocks * (4 / FW)), dim3(FOLLOW_THREADS), 0, stream, ws, 2);
 }
 void launch_follow_long_frames(const Workspace& ws, hipStream_t stream) {

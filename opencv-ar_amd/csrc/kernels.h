@@ -8,6 +8,7 @@
 #include "board_core.h"
 #include "overlay_core.h"
 #include "patch_core.h"
+#include "croplist_core.h"
 #include "ocvar_hip.h"
 
 namespace ocvar {
@@ -24,6 +25,7 @@ constexpr int BACK_STEPS = 32;             // backward look of an outer start be
 constexpr int PRE_STEPS = 8;               // steps every plausible start gets before it may queue for tier 1's full budget
 constexpr int SHORT_STEPS = 96;            // step budget of follower tier 1 (every plausible start, one lane each)
 constexpr int MID_STEPS = 1536;            // step budget of tier 2 (borders that outlived tier 1, one lane each); the rest: tier 3, one wave each
+constexpr int CROP_STEPS_CAP = 3072;       // most steps a walk of the crop pass gets in tier 2 in a throughput batch (croplist_core.h: crop_walk_budget)
 constexpr int SLAB_PTS = 1024;             // points (packed x | y << 16) a tier-2 lane can keep in its private slab (no second follow needed below that)
 constexpr int SLAB_STRIDE = SLAB_PTS + 4;  // dwords per tier-2 lane slab: the points + the scratch slot of flat_step
 constexpr int MID_BLOCKS_MAX = 1024;       // tier-2 grid limit (x256 threads, one slab each)
@@ -54,7 +56,8 @@ enum { CNT_FRAME_CANDS = 0, CNT_CROP_ROIS = 1, CNT_CROP_TILES = 2, CNT_CROP_CAND
        CNT_CROP_PIXELS = 10 /* 64-bit, uses 10..11 */, CNT_LONG_F = 12, CNT_LONG_C = 13, CNT_TICKET_LF = 14, CNT_TICKET_LC = 15,
        CNT_MID_F = 16, CNT_MID_C = 17, CNT_TICKET_MF = 18, CNT_TICKET_MC = 19, CNT_TICKET_BC = 20, CNT_MID_C_FIRST = 21, CNT_TICKET_MC2 = 22,
        CNT_POSE_JOBS = 23,
-       CNT_PROF = 24 /* 32 64-bit profiling slots, written only by builds with -DOCVAR_PROF (tools/prof_tier2.py) */, CNT_COUNT = 88 };
+       CNT_PROF = 24 /* 32 64-bit profiling slots, written only by builds with -DOCVAR_PROF (tools/prof_tier2.py) */,
+       CNT_CROP_EARLY = 88, CNT_CROP_REST = 89, CNT_CROP_LIVE = 90 /* entries of the crop pass's lists E, R, R' (croplist_core.h) */, CNT_COUNT = 92 };
 
 struct Workspace {
     // limits
@@ -71,6 +74,7 @@ struct Workspace {
     int W, H, sw, sh, ns, n_frames, n_templates;   // ns: columns of a neighbour plane = sw rounded up to 16
     int n_sizes, n_groups, max_match;        // the library (library_core.h): size classes, groups, most matches per square
     int crop_phases;                         // 2: crop tier 2 in two launches (earliest starts first, then the rest behind exact pruning); 1: one launch (few frames: the shorter chain)
+    int crop_steps_cap;                      // most steps a walk of the crop pass gets in tier 2 (plan_core.h; >= mid_steps, which the frames pass keeps)
     int mid_steps, mid_blocks, long_blocks;  // tuning (env OCVAR_MID_STEPS / OCVAR_MID_BLOCKS / OCVAR_LONG_BLOCKS): tier-2 step budget and grid, tier-3 grid
     int max_mid_blocks, max_long_blocks;     // slabs allocated at create (scaled with max_batch)
     int short_blocks, crop_blocks;           // grids of follower tier 1 and of the crop binarise kernel (scaled with the batch)
@@ -84,6 +88,9 @@ struct Workspace {
     StartCand* mid_frame;   // starts whose border exceeded tier 1's step budget
     StartCand* mid_crop;
     StartCand* mid_first_crop;   // crop starts tier 2 takes first (expected longest walks), counter CNT_MID_C_FIRST, capacity cap_long
+    StartCand* crop_early;  // two-phase crop pass, the lists cut from mid_crop (croplist_core.h), capacity cap_long each: E, counter CNT_CROP_EARLY
+    StartCand* crop_rest;   // R, counter CNT_CROP_REST
+    StartCand* crop_live;   // R', counter CNT_CROP_LIVE
     StartCand* long_frame;  // starts whose border exceeded tier 2's step budget
     StartCand* long_crop;
     int cap_long;
@@ -144,7 +151,7 @@ void launch_ring_quads_crops(const Workspace& ws, hipStream_t stream);
 void launch_follow_frames(const Workspace& ws, hipStream_t stream);
 void launch_follow_crops(const Workspace& ws, hipStream_t stream);
 void launch_follow_mid_frames(const Workspace& ws, hipStream_t stream);
-void launch_follow_mid_crops(const Workspace& ws, hipStream_t stream);   // both phases
+void launch_follow_mid_crops(const Workspace& ws, hipStream_t stream);   // both phases and the list kernels in front of them
 void launch_follow_long_frames(const Workspace& ws, hipStream_t stream);
 void launch_follow_long_crops(const Workspace& ws, hipStream_t stream);
 void launch_order_and_crops(const Workspace& ws, hipStream_t stream);   // (dense contexts: the sort, replay and crop kernels)

@@ -81,6 +81,11 @@ inline void plan_batch(Workspace* wp, int width, int height, int n_frames, bool 
     // 2.5 ms).  Large batches keep the long budget: there the one-lane walks are what fills the machine.
     w.mid_steps = (int)knob_or(ov.mid_steps, n_frames <= 8 ? 128 : MID_STEPS);
     if (w.mid_steps < 32) w.mid_steps = 32;
+    // The crop pass's walks get a budget that fits their crop (croplist_core.h: crop_walk_budget), up to this cap: in a
+    // throughput batch the merged frame border of a large quad-less crop (up to ~1900 steps in a 250 px crop) then closes in
+    // tier 2 instead of burning mid_steps there and being walked again by a whole wave of tier 3.  Where the budget is short
+    // on purpose -- the latency plan above, or a caller's own mid_steps -- the cap equals it: no effect.
+    w.crop_steps_cap = (n_frames > 8 && !ov.mid_steps.set) ? (int)plan_max(CROP_STEPS_CAP, w.mid_steps) : w.mid_steps;
     // Crop tier 2 in two phases saves half of its steps but chains two launches: throughput for batches (+1..2 %), 0.1 ms of
     // latency for a one-frame call -- which therefore keeps the single launch.
     w.crop_phases = knob_or(ov.crop_phases, n_frames <= 8 ? 1 : 2) == 1 ? 1 : 2;
