@@ -1,14 +1,13 @@
-// follow.hip -- border following + polygon approximation + quad filter, and the per-frame ordering that turns
-// the surviving quads into the reference's square sequence and into crop work for the second pass (gfx950).
+// follow.hip -- border following + polygon approximation + quad filter (gfx950).
 //
 // follow_kernel (tier 1, a router), follow_mid_kernel (tier 2) and follow_long_kernel (tier 3) replace the contour half
 // of cvarFindSquares (/root/reference/src/opencvar.cpp:183-214) for every ROI of a pass at once: every plausible border
 // start (trace_core.h) is a work item pulled from a ticket counter; tier 1 decides which starts are worth following,
-// tier 2 follows 64 borders per wave (one lane each), tier 3 one image-sized border per wave.
-// order_and_crops_kernel replaces cvarGetAllSquares (564-590), the tracking loop (635-668) and the crop
-// rectangle set-up of the candidate loop (676-693).
+// tier 2 follows 64 borders per wave (one lane each), tier 3 one image-sized border per wave.  Tier 2's step and the
+// arithmetic of tier 3's window live in walk_core.h, where the CPU tests compile them too.  (What becomes of the surviving
+// quads -- ordering, tracking replay, crop set-up -- is order.hip.)
 #include "kernels.h"
-#include "trace_core.h"
+#include "walk_core.h"
 
 namespace ocvar {
 
@@ -634,99 +633,6 @@ __global__ __launch_bounds__(64) void ring_quads_kernel(Workspace ws) {
     }
 }
 
-// ---- the follower's step from a table (tier 2) ------------------------------------------------------------------------------
-// trace_core.h::flat_step_t spends ~70 vector instructions per step: the rotate / count-trailing-zeros / rotate-back that turn
-// (arrival direction, neighbour mask) into (exit direction, neighbours passed on the way), two table extractions for the
-// direction's dx and dy, the scan position y * ns + x carried next to x and y, the tiled address from scratch, and a chain of
-// selects.  The step is rebuilt around three ideas:
-//  * the mask only matters through t = the number of zero neighbours examined before the next border pixel (a byte replicate,
-//    a funnel shift and a find-first-bit), and everything the step decides is a function of (first examined direction, t): 64
-//    states, ONE lookup in a 256-byte LDS table: entry = (dx + 1) | (dy + 1) << 16 | next first direction << 5 | exit
-//    direction << 10 | passed-E << 30 | passed-W << 31.  (A table over (direction, mask) itself -- 8 KB per workgroup -- saved
-//    four more instructions and cost a workgroup of occupancy next to the binarise kernels: slower.)
-//  * the position is the packed point x | y << 16 itself (what is parked and stored anyway): one add3 moves it, and because y
-//    is the major half, packed points compare like scan positions y * ns + x -- the "a position of this border before its
-//    start" tests and the closing test need no scan position at all (passed-W / passed-E sit in the sign bits: an AND with the
-//    signed distance to the start position decides).
-//  * a walk that ends is never stepped again, so nothing is guarded.
-// ~42 vector instructions per step instead of ~70; same states, same points, same status as flat_step_t, step for step
-// (tests/test_gpu_parity.py compares every quad and candidate with the oracle; tools/fuzz_parity.py sweeps).
-constexpr unsigned LW_EXIT = 0x1c00u;        // exit direction << 10
-constexpr unsigned LW_DELTA = 0x00030003u;   // (dx + 1) | (dy + 1) << 16
-
-__device__ __forceinline__ unsigned lean_table_entry(unsigned idx) {   // idx = t << 3 | first examined direction
-    const unsigned from = idx & 7u, t = idx >> 3;
-    const unsigned e = (from + t) & 7u;
-    const unsigned dx = (unsigned)(step_dx((int)e) + 1), dy = (unsigned)(step_dy((int)e) + 1);
-    // the t neighbours from, from + 1, ... were examined and found zero: was W (direction 4) / E (direction 0) among them?
-    const unsigned pw = ((12u - from) & 7u) < t, pe = ((8u - from) & 7u) < t;
-    return dx | (dy << 16) | (((e + 5u) & 7u) << 5) | (e << 10) | (pe << 30) | (pw << 31);
-}
-
-struct LeanWalk {
-    unsigned xy;        // current pixel, x | y << 16
-    unsigned m;         // its neighbour mask
-    unsigned from;      // first direction examined from it = arrival direction + 1 (mod 8)
-    unsigned pe;        // previous exit direction << 10: a corner point wherever the exit direction changes
-    unsigned xy0, xy1;  // the border's first pixel and the pixel the closing step comes from
-    unsigned cxy;       // the start's scan position as a packed point
-    int npts, step, status;   // status: -1 while running, then a TraceStatus
-};
-
-__device__ __forceinline__ void lean_begin(LeanWalk& w, const uint8_t* nbr, int ns, int cpos, int is_hole) {
-    const int i0 = cpos - is_hole;
-    const int x = i0 % ns, y = i0 / ns;
-    w.xy = w.xy0 = (unsigned)x | ((unsigned)y << 16);
-    w.cxy = w.xy0 + (unsigned)is_hole;   // (a hole's start position is the pixel east of its first pixel, same row)
-    w.npts = 0;
-    w.step = 0;
-    w.status = -1;
-    w.xy1 = 0;
-    w.pe = 0;
-    w.from = 0;
-    w.m = nbr_of(nbr, x, y, ns);
-    if (w.m == 0) {   // single-pixel domain (only reachable for outer borders)
-        w.status = TRACE_SINGLE;
-        w.npts = 1;
-        return;
-    }
-    const int s = first_cw(w.m, (is_hole ? 0 : 4) - 1);   // direction of the border's last pixel seen from its first
-    w.xy1 = w.xy0 + (unsigned)(step_dx(s) + 65536 * step_dy(s));
-    w.pe = (unsigned)(s ^ 4) << 10;                        // prev_s = s ^ 4
-    w.from = (unsigned)(s + 1) & 7u;
-}
-
-// One step of a running walk.  tab: the 64-entry table in LDS; base / nt / last: the walk's plane (its first byte, tiles per
-// tile row = ns >> 4, the offset of its last 12-byte window); park(xy): the caller parks the pixel being left (every step; only a corner point
-// advances npts afterwards).
-template <class Park>
-__device__ __forceinline__ void lean_step(LeanWalk& w, const unsigned* tab, const uint8_t* base, unsigned nt, unsigned last, Park&& park) {
-    const unsigned mm = __builtin_amdgcn_perm(w.m, w.m, 0u);                       // the mask in all four bytes
-    const unsigned t = (unsigned)__builtin_ctz(__builtin_amdgcn_alignbit(mm, mm, w.from));   // zero neighbours before the next border pixel
-    const unsigned ent = tab[(t << 3) + w.from];
-    const int d = (int)(w.xy - w.cxy);                             // < 0: this pixel's west side precedes the start
-    const unsigned nf = ((ent << 1) & (unsigned)(d + 1)) | (ent & (unsigned)d);   // sign: an earlier position of this border was passed
-    const unsigned nxy = w.xy + (ent & LW_DELTA) - 0x10001u;
-    const bool closes = (nxy == w.xy0) & (w.xy == w.xy1);
-    const unsigned e = ent & LW_EXIT;
-    const bool emit = e != w.pe;
-    // the next pixel's 3x3 window in the bit plane (hd.h::nbr_win_off_xy on the packed point) and its mask (hd.h::nbr_mask9).  A
-    // consistent plane never sends a walk outside itself; should one be inconsistent the offset is clamped (no access outside the
-    // plane), the walk runs into its budget and the wave tier, which checks every coordinate, reports it.
-    unsigned off = nbr_win_off_xy(nxy, nt);
-    off = off < last ? off : last;
-    const unsigned* win = reinterpret_cast<const unsigned*>(base + off);
-    const unsigned m4 = nbr_mask9(win[0], win[1], win[2], nxy & 15u);
-    park(w.xy);
-    w.npts += emit ? 1 : 0;
-    w.status = (int)nf < 0 ? (int)TRACE_NOT_FIRST : closes ? (int)TRACE_OK : m4 == 0u ? (int)TRACE_OVERRUN : -1;
-    w.step += 1;
-    w.xy = nxy;
-    w.pe = e;
-    w.from = (ent >> 5) & 7u;
-    w.m = m4;
-}
-
 // ---- Tier 2: one lane per surviving border, 64 independent walks per wave, lanes refilled as they finish -------------
 // A walk is a chain of dependent loads, so a wave's time is its longest walk; with one batch of 64 starts per wave
 // most lanes would sit idle behind the longest border (a crop holds a ~900-step border next to 100-step ones).  Here a
@@ -752,7 +658,7 @@ static_assert(FLUSH_W >= MID_BLOCK && 64 % FLUSH_W == 0, "a group of lanes cover
 // The phases read lists that hold only what they walk (croplist_core.h; crop_split_kernel / crop_prune_kernel below): a
 // hand-out that reads an entry only to drop it costs an idle lane a ticket and two dependent loads while the wave's other
 // walks stand still.  Phase 1 takes every entry it is handed; phase 2 still tests "behind the best quad" at hand-out, since
-// best_crop keeps improving while it runs.  A crop's walk gets the step budget that fits its crop (crop_walk_budget).
+// best_crop keeps improving while it runs.  A crop's walk gets the step budget that fits its crop (walk_core.h: lean_budget).
 template <bool CROP>
 __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws, int phase) {
     __shared__ WaveScratch scratch[FW];
@@ -850,7 +756,7 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
         }
         // the step budget is checked here, once per block, instead of in every step (a walk may overshoot it by up to
         // MID_BLOCK - 1 steps; it is handed to the wave tier either way, which follows the border again from its start)
-        if (have && w.status < 0 && w.step >= (CROP ? crop_walk_budget(pl.img_w & ~1, pl.img_h & ~1, ws.mid_steps, budget) : budget)) w.status = TRACE_OVERRUN;
+        if (have && w.status < 0 && w.step >= lean_budget<CROP>(pl.img_w, pl.img_h, ws.mid_steps, budget)) w.status = TRACE_OVERRUN;
         const unsigned long long pt2 = PROF_NOW();
         PROF_ADD(1, pt2 - pt1);
         {   // append the parked points to the slabs: every group of FLUSH_W lanes carries one walk's row per store
@@ -905,7 +811,7 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_mid_kernel(Workspace ws
                     route = 3;   // finished by the whole wave below
                     slab_npts = w.npts;
                 } else {
-                    route = follow_overflow<CROP>(ws, c, pl, CROP ? crop_walk_budget(pl.img_w & ~1, pl.img_h & ~1, ws.mid_steps, budget) : budget);
+                    route = follow_overflow<CROP>(ws, c, pl, lean_budget<CROP>(pl.img_w, pl.img_h, ws.mid_steps, budget));
                 }
             }
             have = false;
@@ -1017,12 +923,12 @@ __global__ __launch_bounds__(64) void crop_prune_kernel(Workspace ws) { crop_lis
 // per step when done from global memory.  Here the wave cooperatively copies a window of TILE_TX x TILE_TY tiles of the bit
 // plane around the current pixel into LDS (16-byte loads, one per lane and quarter tile) and all lanes walk the same border
 // redundantly (wave-uniform control flow), so a step costs an LDS read of the pixel's 3x3 window; the window is re-centred
-// when the walk leaves it.  Same stepping rules as trace_core.h::trace_border.
-// In LDS the window is stored by column block: block i (columns tx0 + 16 i - 1 .. tx0 + 16 i + 16, a tile's 18 bits) holds the
-// rows ty0 - 1 .. ty0 + TILE_H in TILE_SLOTS consecutive dwords, so a pixel's 3x3 window is dwords ly .. ly + 2 of its block --
-// no division by the tile height on the step's chain.  Dword d of window tile (i, j) is slot 14 j + d: a tile's apron rows land
-// on the slots of the neighbouring tiles' rows, which they equal.
-constexpr int TILE_SLOTS = TILE_H + 2;
+// when the walk leaves it.  Same stepping rules as trace_core.h::trace_border: tests/test_follow_tiers_cpu.py walks every
+// plausible start of its images with a host emulation of this wave (tests/emul/follow_emul.cpp: lanes as a loop, LDS as an
+// array) and compares status, corner count and every corner point.  The window's layout in LDS, its origin, the quarter-tile
+// mapping of its load, the mask read and the step decode are walk_core.h's: the kernel and the emulation compile the same
+// functions.  What exists only here is the wave: the loop of trace_lean_tiled with its ballots and its two "an earlier position
+// of this border was passed" tests (the emulation restates them), and the parking of points.
 struct TileCache {
     unsigned* lds;         // TILE_TX x TILE_SLOTS dwords of this wave
     const uint8_t* nbr;
@@ -1033,41 +939,33 @@ struct TileCache {
 // (bx,by): direction of travel; the window is pushed ahead so that a straight run re-centres as rarely as possible
 __device__ __forceinline__ void tile_load(TileCache& t, int x, int y, int bx = 0, int by = 0) {
     const int lane = threadIdx.x & 63;
-    t.tx0 = (x + 20 * bx - TILE_W / 2 + 8) & ~15;   // keeps x-20..x+27 inside for bx = 0, up to 55 pixels ahead otherwise
-    // rows: y - ty0 in [28, 42) for by = 0 (28 rows either side), [4, 18) going down, [52, 66) going up (ty0 a whole tile row;
-    // the offset keeps the division's operand positive)
-    t.ty0 = (int)div14((unsigned)(y + 24 * by - 28 + 4 * NBR_TILE_H)) * NBR_TILE_H - 4 * NBR_TILE_H;
+    t.tx0 = tile_origin_x(x, bx);
+    t.ty0 = tile_origin_y(y, by);
     const int tx = (t.tx0 >> 4), ty = t.ty0 / NBR_TILE_H, nty = (t.sh + NBR_TILE_H - 1) / NBR_TILE_H;
-    constexpr int NQ = TILE_TX * TILE_TY * 4;   // quarter tiles of the window: lane l takes quarters l and l + 64 (< NQ)
+    constexpr int NQ = TILE_QUARTERS;   // quarter tiles of the window: lane l takes quarters l and l + 64 (< NQ)
     static_assert(NQ > 64 && NQ <= 128, "two quarter tiles per lane at most");
     uint4 v[2];
 #pragma unroll
     for (int h = 0; h < 2; h++) {   // (both loads issued before any LDS store)
-        const int q = lane + 64 * h, i = (q >> 2) % TILE_TX, j = (q >> 2) / TILE_TX;
+        const int q = lane + 64 * h;
         v[h] = make_uint4(0u, 0u, 0u, 0u);
-        if (q < NQ && tx + i >= 0 && (tx + i) * 16 < t.ns && ty + j >= 0 && ty + j < nty)
-            v[h] = *reinterpret_cast<const uint4*>(t.nbr + nbr_tile_off((unsigned)(tx + i), (unsigned)(ty + j), t.ns) + 16 * (q & 3));
+        if (q < NQ && tile_quarter_col_in_plane(q, tx, t.ns) && tile_quarter_row_in_plane(q, ty, nty))
+            v[h] = *reinterpret_cast<const uint4*>(tile_quarter_src(t.nbr, q, tx, ty, t.ns));
     }
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-        const int q = lane + 64 * h, i = (q >> 2) % TILE_TX, j = (q >> 2) / TILE_TX;
+        const int q = lane + 64 * h;
         if (q < NQ) {
-            unsigned* d = t.lds + i * TILE_SLOTS + NBR_TILE_H * j + 4 * (q & 3);
+            unsigned* d = tile_quarter_dst(t.lds, q);
             d[0] = v[h].x; d[1] = v[h].y; d[2] = v[h].z; d[3] = v[h].w;
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
 }
 
-// mask of window pixel (lx, ly), 0 <= lx < TILE_W, 0 <= ly < TILE_H
-__device__ __forceinline__ unsigned tile_mask(const TileCache& t, int lx, int ly) {
-    const unsigned* w = t.lds + ((unsigned)lx >> 4) * TILE_SLOTS + (unsigned)ly;
-    return nbr_mask9(w[0], w[1], w[2], (unsigned)lx & 15u);
-}
-
 __device__ __forceinline__ unsigned tile_get(TileCache& t, int x, int y) {
-    if ((unsigned)(x - t.tx0) >= (unsigned)TILE_W || (unsigned)(y - t.ty0) >= (unsigned)TILE_H) tile_load(t, x, y);
-    return uni(tile_mask(t, x - t.tx0, y - t.ty0));
+    if (tile_misses(t.tx0, t.ty0, x, y)) tile_load(t, x, y);
+    return uni(tile_mask(t.lds, x - t.tx0, y - t.ty0));
 }
 
 // Lean follower on the tile cache.  All 64 lanes walk the same border and the walker's state (position, direction,
@@ -1102,10 +1000,9 @@ __device__ LeanTrace trace_lean_tiled(TileCache& t, int cpos, int is_hole, int* 
             r.status = TRACE_OVERRUN;
             break;
         }
-        const int from = (s + 1) & 7;
-        const int tz = __builtin_ctz(((m * 0x101u) >> from) & 0xffu);
-        const int e = (from + tz) & 7;
-        const unsigned passed = ((((1u << tz) - 1u) * 0x101u) << from) >> 8;
+        const TileStep d = tile_step(m, s);
+        const int e = d.e;
+        const unsigned passed = d.passed;
         const int idx = y * ns + x;
         if (((passed & 0x10u) && idx < cpos) || ((passed & 1u) && idx + 1 < cpos)) {
             r.status = TRACE_NOT_FIRST;
@@ -1143,7 +1040,7 @@ __device__ LeanTrace trace_lean_tiled(TileCache& t, int cpos, int is_hole, int* 
                 for (;;) {
                     const int qx = x + (lane + 1) * ddx, qy = y + (lane + 1) * ddy;
                     const bool in_tile = (unsigned)(qx - t.tx0) < (unsigned)TILE_W && (unsigned)(qy - t.ty0) < (unsigned)TILE_H;
-                    const unsigned mq = in_tile ? tile_mask(t, qx - t.tx0, qy - t.ty0) : 256u;
+                    const unsigned mq = in_tile ? tile_mask(t.lds, qx - t.tx0, qy - t.ty0) : 256u;
                     const bool closes = qx == x0 && qy == y0 && qx - ddx == x1 && qy - ddy == y1;
                     const unsigned long long close_mask = __ballot(closes);
                     const unsigned long long stop = close_mask | __ballot(mq != m);
@@ -1283,231 +1180,6 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_long_kernel(Workspace w
     }
 }
 
-// Crop rectangle of square i of frame f (corners sq) and its binarise work units for the second pass (opencvar.cpp:676-693).
-__device__ __forceinline__ void setup_crop(const Workspace& ws, int f, int i, const float* sq) {
-    int quad[8];
-    for (int k = 0; k < 8; k++) quad[k] = (int)sq[k];
-    int x0, y0, cw, ch, roi_index = -1;
-    crop_rect(quad, ws.W, ws.H, &x0, &y0, &cw, &ch);
-    const int sw = cw & ~1, sh = ch & ~1, ns = (sw + 15) & ~15;
-    if (sw >= 2 && sh >= 2) {
-        const int r = atomicAdd(ws.counters + CNT_CROP_ROIS, 1);
-        const long long plane = nbr_plane_bytes(ns, sh);
-        const long long off = (long long)atomicAdd(ws.crop_pixels, (unsigned long long)plane);
-        const int ntx = (sw + MARCH_STRIP - 1) / MARCH_STRIP, nty = (sh + MARCH_CROP_ROWS - 1) / MARCH_CROP_ROWS;
-        if (r >= ws.cap_crop_rois || off + plane > ws.cap_crop_pixels) {
-            atomicOr(ws.counters + CNT_ERR, ERR_CROP_OVERFLOW);
-        } else {
-            const int tbase = atomicAdd(ws.counters + CNT_CROP_TILES, ntx * nty);
-            if (tbase + ntx * nty > ws.cap_crop_tiles) {
-                atomicOr(ws.counters + CNT_ERR, ERR_TILE_OVERFLOW);
-            } else {
-                Roi roi;
-                roi.frame = f; roi.x0 = x0; roi.y0 = y0; roi.w = cw; roi.h = ch; roi.sw = sw; roi.sh = sh; roi.ns = ns;
-                roi.owner = i; roi.nbr_off = off;
-                ws.rois_crop[r] = roi;
-                ws.best_crop[r] = ~0ull;
-                ws.crop_min_rest[r] = 0x7fffffff;
-                ws.ring_crop[r] = 0;   // (ring_quads_kernel sets it where the crop's own frame border needs no walk)
-                for (int t = 0; t < ntx * nty; t++) {
-                    TileDesc td;
-                    td.roi = r; td.x0 = t % ntx; td.y0 = (t / ntx) * MARCH_CROP_ROWS;
-                    ws.tiles_crop[tbase + t] = td;
-                }
-                roi_index = r;
-            }
-        }
-    }
-    ws.crop_of[(size_t)f * ws.maxq + i] = roi_index;
-}
-
-__global__ __launch_bounds__(256) void order_and_crops_kernel(Workspace ws) {
-    extern __shared__ int order_lds[];              // [maxq] discovery positions, then [maxq][8] ordered corners
-    int* s_start = order_lds;
-    float (*s_sq)[8] = reinterpret_cast<float (*)[8]>(order_lds + ws.maxq);
-    __shared__ int s_n;
-    const int f = blockIdx.x;
-    const int tid = threadIdx.x;
-    int n = ws.n_quads_frame[f];
-    if (n > ws.maxq) n = ws.maxq;
-    const QuadRec* q = ws.quads_frame + (size_t)f * ws.maxq;
-    for (int i = tid; i < n; i += blockDim.x) s_start[i] = q[i].start;
-    __syncthreads();
-    // sequence order of cvarFindSquares: contours come out last-discovered first (opencvar.cpp:187-214)
-    for (int i = tid; i < n; i += blockDim.x) {
-        const int mine = s_start[i];
-        int rank = 0;
-        for (int u = 0; u < n; u++) rank += s_start[u] > mine;
-        for (int k = 0; k < 8; k++) s_sq[rank][k] = (float)q[i].pt[k];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int nr = 0, nn = n;
-        const int np = ws.n_prev[f];
-        if (np > 0)
-            nn = track_markers(ws.prev + (size_t)f * MAXM, np < MAXM ? np : MAXM, &s_sq[0][0], n, ws.reserve + (size_t)f * MAXM,
-                               MAXM, &nr);   // (dense contexts: track_replay_kernel below)
-        ws.n_reserve[f] = nr;
-        ws.n_squares[f] = nn;
-        s_n = nn;
-    }
-    __syncthreads();
-    n = s_n;
-    for (int i = tid; i < n; i += blockDim.x) {
-        float* out = ws.squares + ((size_t)f * ws.maxq + i) * 8;
-        for (int k = 0; k < 8; k++) out[k] = s_sq[i][k];
-        setup_crop(ws, f, i, s_sq[i]);
-    }
-}
-
-// ---- dense contexts (ocvar_hip_create_dense): the same per-frame tail for up to 16384 squares and 4096 markers ----------------
-// order_and_crops_kernel holds a frame's squares in LDS (maxq x 9 ints), ranks them with an O(n^2) count and replays the
-// tracking loop on one lane (O(markers x squares)).  Dense contexts cut it in four launches:
-//   order_sort_kernel   (frame, chunk of ws.order_chunk squares: ORDER_CHUNK, or maxq rounded up to a power of two when that
-//                       is smaller): the chunk's discovery positions bitonic-sorted in LDS
-//   order_place_kernel  (frame, chunk): square i goes to slot "squares with a larger position" (the rank rule of
-//                       order_and_crops_kernel, same slot for every input), counted by binary search in every sorted chunk
-//   track_replay_kernel (frame): the corner grid and the sparse tracking replay (tail_core.h: track_markers_sparse), then the
-//                       list compacted into ws.squares; a frame without previous markers only copies
-//   crops_kernel        (frame, chunk): setup_crop of every square
-constexpr int ORDER_THREADS = ORDER_CHUNK / 2;
-
-__global__ __launch_bounds__(ORDER_THREADS) void order_sort_kernel(Workspace ws) {
-    __shared__ int s_key[ORDER_CHUNK];
-    const int CH = ws.order_chunk;   // a power of two <= ORDER_CHUNK; the block has max(64, CH / 2) threads
-    const int nch = (ws.maxq + CH - 1) / CH;
-    const int f = blockIdx.x / nch, c = blockIdx.x % nch;
-    int n = ws.n_quads_frame[f];
-    if (n > ws.maxq) n = ws.maxq;
-    const int lo = c * CH, len = n - lo < CH ? n - lo : CH;
-    if (len <= 0) return;
-    const QuadRec* q = ws.quads_frame + (size_t)f * ws.maxq + lo;
-    const int tid = threadIdx.x;
-    for (int k = tid; k < CH; k += blockDim.x) s_key[k] = k < len ? q[k].start : 0x7fffffff;
-    __syncthreads();
-    for (int k = 2; k <= CH; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            if (tid < CH / 2) bitonic_step(s_key, k, j, tid);
-            __syncthreads();
-        }
-    int* out = ws.sorted_starts + (size_t)f * ws.maxq + lo;
-    for (int k = tid; k < len; k += blockDim.x) out[k] = s_key[k];
-}
-
-__global__ __launch_bounds__(256) void order_place_kernel(Workspace ws) {
-    const int CH = ws.order_chunk;
-    const int nch = (ws.maxq + CH - 1) / CH;
-    const int f = blockIdx.x / nch, c = blockIdx.x % nch;
-    int n = ws.n_quads_frame[f];
-    if (n > ws.maxq) n = ws.maxq;
-    const int lo = c * CH, hi = n < lo + CH ? n : lo + CH;
-    const QuadRec* q = ws.quads_frame + (size_t)f * ws.maxq;
-    const int* sorted = ws.sorted_starts + (size_t)f * ws.maxq;
-    for (int i = lo + (int)threadIdx.x; i < hi; i += blockDim.x) {
-        const QuadRec qi = q[i];
-        int rank = 0;
-        for (int b = 0; b < n; b += CH) rank += count_greater_sorted(sorted + b, n - b < CH ? n - b : CH, qi.start);
-        float* out = ws.sq_tmp + ((size_t)f * ws.maxq + rank) * 8;
-        for (int k = 0; k < 8; k++) out[k] = (float)qi.pt[k];
-    }
-}
-
-constexpr int REPLAY_THREADS = 1024;
-
-__global__ __launch_bounds__(REPLAY_THREADS) void track_replay_kernel(Workspace ws) {
-    __shared__ int s_part[REPLAY_THREADS];
-    __shared__ int s_left;
-    const int f = blockIdx.x, tid = threadIdx.x;
-    int n = ws.n_quads_frame[f];
-    if (n > ws.maxq) n = ws.maxq;
-    const int np_in = ws.n_prev[f];
-    const int np = np_in < ws.maxm ? np_in : ws.maxm;
-    const float* tmp = ws.sq_tmp + (size_t)f * ws.maxq * 8;
-    float* sq = ws.squares + (size_t)f * ws.maxq * 8;
-    if (np <= 0 || n == 0) {
-        for (int e = tid; e < n * 8; e += REPLAY_THREADS) sq[e] = tmp[e];
-        if (tid == 0) {
-            ws.n_reserve[f] = 0;
-            ws.n_squares[f] = n;
-        }
-        return;
-    }
-    const int gw = ws.track_gw, gh = ws.track_gh, nc = gw * gh;
-    int* cells = ws.trk_cells + (size_t)f * (nc + 1);
-    int* fill = ws.trk_fill + (size_t)f * nc;
-    int* items = ws.trk_items + (size_t)f * 4 * ws.maxq;
-    int* next = ws.trk_next + (size_t)f * (ws.maxq + 1);
-    // the corner grid (tail_core.h: track_grid_build, in parallel): counts, exclusive scan, fill
-    for (int c = tid; c < nc; c += REPLAY_THREADS) fill[c] = 0;
-    __syncthreads();
-    for (int j = tid; j < 4 * n; j += REPLAY_THREADS)
-        atomicAdd(fill + track_cell(tmp[2 * j + 1], gh) * gw + track_cell(tmp[2 * j], gw), 1);
-    __syncthreads();
-    const int per = (nc + REPLAY_THREADS - 1) / REPLAY_THREADS, c0 = tid * per, c1 = c0 + per < nc ? c0 + per : nc;
-    int sum = 0;
-    // (the counts were made by atomics at L2: read them past the L1)
-    for (int c = c0; c < c1; c++) sum += __hip_atomic_load(fill + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < REPLAY_THREADS; d <<= 1) {   // inclusive scan of the threads' sums
-        const int v = tid >= d ? s_part[tid - d] : 0;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    int run = s_part[tid] - sum;
-    for (int c = c0; c < c1; c++) {
-        const int k = __hip_atomic_load(fill + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cells[c] = run;
-        fill[c] = run;
-        run += k;
-    }
-    if (tid == 0) cells[nc] = 4 * n;
-    __syncthreads();
-    for (int j = tid; j < 4 * n; j += REPLAY_THREADS)
-        items[atomicAdd(fill + track_cell(tmp[2 * j + 1], gh) * gw + track_cell(tmp[2 * j], gw), 1)] = j >> 2;
-    __syncthreads();
-    // the replay itself is sequential (each marker sees the erasures of the ones before it) but sparse
-    if (tid == 0) {
-        int nr = 0;
-        s_left = track_markers_sparse(ws.prev + (size_t)f * ws.maxm, np, tmp, n, cells, items, gw, gh, next,
-                                      ws.reserve + (size_t)f * ws.maxm, ws.maxm, &nr);
-        ws.n_reserve[f] = nr;
-        ws.n_squares[f] = s_left;
-    }
-    __syncthreads();
-    // the squares still in the list, in list order (block-wide prefix count over chunks of REPLAY_THREADS)
-    int base = 0;
-    for (int b = 0; b < n; b += REPLAY_THREADS) {
-        const int i = b + tid;
-        const int keep = i < n && next[i] == i;
-        s_part[tid] = keep;
-        __syncthreads();
-        for (int d = 1; d < REPLAY_THREADS; d <<= 1) {
-            const int v = tid >= d ? s_part[tid - d] : 0;
-            __syncthreads();
-            s_part[tid] += v;
-            __syncthreads();
-        }
-        if (keep) {
-            const int o = base + s_part[tid] - 1;
-            for (int k = 0; k < 8; k++) sq[(size_t)o * 8 + k] = tmp[(size_t)i * 8 + k];
-        }
-        base += s_part[REPLAY_THREADS - 1];
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void crops_kernel(Workspace ws) {
-    const int CH = ws.order_chunk;
-    const int nch = (ws.maxq + CH - 1) / CH;
-    const int f = blockIdx.x / nch, c = blockIdx.x % nch;
-    int n = ws.n_squares[f];
-    if (n > ws.maxq) n = ws.maxq;
-    const int hi = n < (c + 1) * CH ? n : (c + 1) * CH;
-    for (int i = c * CH + (int)threadIdx.x; i < hi; i += blockDim.x) setup_crop(ws, f, i, ws.squares + ((size_t)f * ws.maxq + i) * 8);
-}
-
 void launch_ring_quads_frames(const Workspace& ws, hipStream_t stream) {
     hipLaunchKernelGGL(ring_quads_kernel<false>, dim3(ws.n_frames < 4096 ? ws.n_frames : 4096), dim3(64), 0, stream, ws);
 }
@@ -1541,16 +1213,6 @@ void launch_follow_long_frames(const Workspace& ws, hipStream_t stream) {
 void launch_follow_long_crops(const Workspace& ws, hipStream_t stream) {
     hipLaunchKernelGGL(follow_long_kernel<true>, dim3(ws.long_blocks * (4 / FW)), dim3(FOLLOW_THREADS), 0, stream, ws);
 }
-void launch_order_and_crops(const Workspace& ws, hipStream_t stream) {
-    if (ws.n_frames > 0 && ws.dense) {
-        const int grid = ws.n_frames * ((ws.maxq + ws.order_chunk - 1) / ws.order_chunk);
-        hipLaunchKernelGGL(order_sort_kernel, dim3(grid), dim3(ws.order_chunk / 2 > 64 ? ws.order_chunk / 2 : 64), 0, stream, ws);
-        hipLaunchKernelGGL(order_place_kernel, dim3(grid), dim3(256), 0, stream, ws);
-        hipLaunchKernelGGL(track_replay_kernel, dim3(ws.n_frames), dim3(REPLAY_THREADS), 0, stream, ws);
-        hipLaunchKernelGGL(crops_kernel, dim3(grid), dim3(256), 0, stream, ws);
-        return;
-    }
-    if (ws.n_frames > 0) hipLaunchKernelGGL(order_and_crops_kernel, dim3(ws.n_frames), dim3(ws.maxq <= 256 ? 64 : 256) /* one wave: starts wherever a SIMD has room */, (size_t)ws.maxq * 9 * sizeof(int), stream, ws);
-}
 
 }  // namespace ocvar
+

@@ -54,6 +54,21 @@ OCVAR_HD unsigned umul24(unsigned a, unsigned b) {
     return a * b;
 #endif
 }
+// the low byte of m in all four bytes; v rotated right by s (mod 32) bits -- one instruction each on the device
+OCVAR_HD unsigned byte_replicate(unsigned m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(m, m, 0u);
+#else
+    return (m & 0xffu) * 0x01010101u;
+#endif
+}
+OCVAR_HD unsigned rotate_right(unsigned v, unsigned s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(v, v, s);
+#else
+    return (v >> (s & 31u)) | (v << ((32u - s) & 31u));
+#endif
+}
 // y / 14 and y % 14 for 0 <= y < 43690 (2^19 / 14 rounded up: exact in that range; images are at most 32767 rows)
 OCVAR_HD unsigned div14(unsigned y) { return umul24(y, 37450u) >> 19; }
 // bytes of a plane: (ns / 16) tiles per tile row, sh rounded up to whole tile rows

@@ -32,8 +32,6 @@ constexpr int MID_BLOCKS_MAX = 1024;       // tier-2 grid limit (x256 threads, o
 constexpr int SLAB3_PTS = 8192;            // points a tier-3 wave can keep in its slab
 constexpr int SLAB3_STRIDE = SLAB3_PTS + 64;   // dwords per tier-3 wave slab
 constexpr int LONG_BLOCKS_MAX = 1024;      // tier-3 grid limit (x4 waves, one slab each)
-constexpr int TILE_TX = 4, TILE_TY = 5;    // the window of the bit plane (in 16x14 tiles) the wave-per-border follower walks in
-constexpr int TILE_W = TILE_TX * NBR_TILE_W, TILE_H = TILE_TY * NBR_TILE_H;   // 64 x 70 pixels
 
 // error bits accumulated in Workspace::err[0]
 enum { ERR_CAND_OVERFLOW = 1, ERR_POOL_OVERFLOW = 2, ERR_QUAD_OVERFLOW = 4, ERR_TRACE_OVERRUN = 8, ERR_CROP_OVERFLOW = 16,
@@ -64,7 +62,7 @@ struct Workspace {
     int max_w, max_h, max_batch;
     int maxq;               // frame-pass quads kept per frame (ocvar_hip_create: OCVAR_MAX_QUADS; ocvar_hip_create_ex/_dense: caller's choice)
     int maxm;               // marker records per frame: MAXM, or the caller's choice on a dense context (ocvar_hip_create_dense)
-    int dense;              // 1: made by ocvar_hip_create_dense -- the per-frame tail runs the scalable kernels (follow.hip, decode.hip)
+    int dense;              // 1: made by ocvar_hip_create_dense -- the per-frame tail runs the scalable kernels (order.hip, decode.hip)
     int track_gw, track_gh; // dense: corner grid of the sparse tracking replay (tail_core.h), cells of TRACK_CELL px over max_w x max_h
     int decode_slices;      // dense: waves of decode_kernel per frame (DECODE_SLICES on the other contexts)
     int order_chunk;        // dense: squares per sorted chunk of the ordering (ORDER_CHUNK, or maxq rounded up to a power of two)

@@ -165,7 +165,7 @@ OCVAR_HD int track_markers_sparse(MarkerRec* markers, int n_markers, const float
 // The order of cvarFindSquares (opencvar.cpp:187-214): square i of a frame goes to slot "number of squares with a larger
 // discovery position".  Dense contexts count it with binary searches in sorted chunks of the frame's starts (sorted: one
 // chunk of starts in ascending order, len of them): squares of the chunk whose start is larger than `start`.
-constexpr int ORDER_CHUNK = 2048;   // starts sorted per workgroup in LDS (follow.hip: order_sort_kernel), a power of two
+constexpr int ORDER_CHUNK = 2048;   // starts sorted per workgroup in LDS (order.hip: order_sort_kernel), a power of two
 
 // One compare-exchange of the bitonic network that sorts a chunk ascending (stage k = 2, 4, .. len, step j = k / 2, .. 1; len / 2
 // threads tid, each one pair per step).

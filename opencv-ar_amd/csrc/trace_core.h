@@ -58,6 +58,9 @@ struct TraceStats {
 // scan position of this border smaller than cpos is met.
 // RUN: jump over straight runs with 8 mask loads in flight (pays off for a lone long border; in a wave whose
 // lanes follow different borders the extra code path only adds divergence, so the lane tiers switch it off).
+// No kernel runs trace_border<..., true>: tier 2's overflow path runs the RUN = false form, tier 3 jumps runs 64 pixels at a
+// time in its own walker (follow.hip::trace_lean_tiled).  It is kept as a reference form of the tests (test_bitplane_cpu.py,
+// test_device_cores_cpu.py).
 template <bool STORE, bool RUN = true>
 OCVAR_HD TraceStats trace_border(const uint8_t* nbr, int sw, int plane, int cpos, int is_hole, int* out, int max_pts,
                                  int max_steps) {
@@ -198,6 +201,8 @@ OCVAR_HD TraceStats trace_border(const uint8_t* nbr, int sw, int plane, int cpos
 // recomputed from the stored points afterwards), direction deltas from packed 2-bit tables, the examined-neighbour
 // test as one rotated bit mask.  Stores up to max_pts points (out must hold max_pts + 1: one scratch slot); npts keeps
 // counting beyond that.
+// No kernel runs trace_lean: tier 1 runs trace_flat below, tier 2 the table-driven step of walk_core.h, tier 3 its own walker
+// on an LDS window.  It is kept as a reference form of the tests (test_bitplane_cpu.py, test_device_cores_cpu.py).
 struct LeanTrace {
     int status;
     int npts;
@@ -328,7 +333,7 @@ OCVAR_HD void flat_begin(FlatWalk& w, const uint8_t* nbr, int ns, int cpos, int 
 
 // one step of a running walk (w.status < 0).  store(emit, x, y) is called once per step between the request for
 // the next mask and the state update: emit = the pixel being left is a corner point, x/y its position (the caller decides
-// where a point -- or the dummy of a step without one -- goes; see flat_step and follow.hip's tier 2).
+// where a point -- or the dummy of a step without one -- goes; see flat_step).
 // BUDGET = false: the step budget is not looked at (the caller checks w.step between blocks of steps instead).
 template <bool BUDGET = true, class Store>
 OCVAR_HD void flat_step_t(FlatWalk& w, const uint8_t* nbr, int ns, int plane, int cpos, int max_steps, Store&& store) {

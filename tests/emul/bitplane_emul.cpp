@@ -4,48 +4,18 @@
 // (the raster byte plane of the host emulation).  Both builds export the same functions; the test runs the followers of
 // trace_core.h on the same binary images in both and compares what they return.
 #include "trace_core.h"
+#include "plane_writer.h"
 #include <vector>
 
 using namespace ocvar;
 
-// the binary image as cvFindContours sees it: the 1-px frame zeroed
-static int bin_at(const uint8_t* bin, int w, int h, int x, int y) {
-    if (x < 1 || y < 1 || x > w - 2 || y > h - 2) return 0;
-    return bin[(size_t)y * w + x] != 0;
-}
+static int bin_at(const uint8_t* bin, int w, int h, int x, int y) { return emul_bin_at(bin, w, h, x, y); }
 
-extern "C" int bp_ns(int sw) {
-#if defined(OCVAR_NBR_TILED)
-    return (sw + 15) & ~15;
-#else
-    return sw;
-#endif
-}
+extern "C" int bp_ns(int sw) { return emul_plane_ns(sw); }
 
 extern "C" long long bp_plane_bytes(int sw, int sh) { return nbr_plane_bytes(bp_ns(sw), sh); }
 
-// the plane of an sw x sh binary image, written straight from the layout's definition
-extern "C" void bp_make_plane(const uint8_t* bin, int sw, int sh, uint8_t* plane) {
-    const int ns = bp_ns(sw);
-#if defined(OCVAR_NBR_TILED)
-    const int ntx = ns / NBR_TILE_W, nty = (sh + NBR_TILE_H - 1) / NBR_TILE_H;
-    unsigned* d = reinterpret_cast<unsigned*>(plane);
-    for (int ty = 0; ty < nty; ty++)
-        for (int tx = 0; tx < ntx; tx++)
-            for (int j = 0; j < 16; j++) {
-                unsigned v = 0;
-                for (int b = 0; b < 18; b++) v |= (unsigned)bin_at(bin, sw, sh, NBR_TILE_W * tx + b - 1, NBR_TILE_H * ty + j - 1) << b;
-                d[((size_t)ty * ntx + tx) * 16 + j] = v;
-            }
-#else
-    for (int y = 0; y < sh; y++)
-        for (int x = 0; x < ns; x++) {
-            unsigned m = 0;
-            for (int s = 0; s < 8; s++) m |= (unsigned)bin_at(bin, sw, sh, x + dir_dx(s), y + dir_dy(s)) << s;
-            plane[(size_t)y * ns + x] = (uint8_t)m;
-        }
-#endif
-}
+extern "C" void bp_make_plane(const uint8_t* bin, int sw, int sh, uint8_t* plane) { emul_make_plane(bin, sw, sh, plane); }
 
 // mask byte of every pixel through the build's reader (nbr_at), and -- bit plane -- through the followers' packed-point
 // address (nbr_win_off_xy) and the own-pixel bit; returns the number of pixels where a reader disagrees with the definition
@@ -69,8 +39,10 @@ extern "C" long long bp_check_readers(const uint8_t* bin, int sw, int sh, const 
 }
 
 // Every plausible border start of the image (cvFindContours' outer / hole start conditions), through every reader of the
-// followers: the run test, the look behind, the lean and flat walks (tiers 1 and 2) and trace_border with and without
-// run skipping.  Per start 16 ints: position, kind, then the results; the walks' points go into a running hash.
+// followers in trace_core.h: the run test, the look behind, the flat walk (tier 1's probe), trace_border without run skipping
+// (tier 2's overflow path), and the two forms no kernel runs, kept as the tests' references: the lean walk and trace_border
+// with run skipping.  (Tier 2's own step and tier 3's window are walk_core.h's: follow_emul.cpp, test_follow_tiers_cpu.py.)
+// Per start 16 ints: position, kind, then the results; the walks' points go into a running hash.
 extern "C" int bp_walks(const uint8_t* bin, int sw, int sh, const uint8_t* plane, int* out, int max_starts) {
     const int ns = bp_ns(sw), plane_pos = ns * sh;
     std::vector<int> pts(2 * (4 * (size_t)sw * sh + 16));

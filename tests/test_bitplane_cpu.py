@@ -13,7 +13,7 @@ import helpers as H
 from helpers import P
 
 SRC = os.path.join(H.ROOT, "tests", "emul", "bitplane_emul.cpp")
-DEPS = [SRC] + [os.path.join(H.PKG, "csrc", f) for f in ("hd.h", "trace_core.h")]
+DEPS = [SRC, os.path.join(H.ROOT, "tests", "emul", "plane_writer.h")] + [os.path.join(H.PKG, "csrc", f) for f in ("hd.h", "trace_core.h")]
 
 
 def _lib(tiled):

@@ -32,7 +32,7 @@ def test_parallel_border_starts_equal_sequential_scan(emul):
     rng = np.random.default_rng(1)
     for trial in range(300):
         emul.emul_set_run(trial & 1)  # with and without straight-run skipping
-        emul.emul_set_lean((trial >> 1) % 3)  # 1: the lean follower, 2: its straight-line form (tiers 1/2 on the GPU)
+        emul.emul_set_lean((trial >> 1) % 3)  # 1: the lean follower (a reference form), 2: its straight-line form (tier 1 on the GPU)
         h, w = int(rng.integers(3, 40)), int(rng.integers(3, 40))
         dens = rng.choice([0.1, 0.3, 0.5, 0.6, 0.7, 0.9])
         b = (rng.random((h, w)) < dens).astype(np.uint8) * 255
@@ -58,7 +58,7 @@ def emul_squares(em, gray):
 
 
 def test_follow_approx_filter_on_synthetic_frames_and_crops(emul):
-    for lean in (0, 1):  # 1: the lean store-while-following flow of tiers 2/3
+    for lean in (0, 1):  # 1: store while following, statistics from the points (the flow of tiers 2/3; their own walkers: test_follow_tiers_cpu.py)
         emul.emul_set_lean(lean)
         _follow_approx_filter(emul)
     emul.emul_set_lean(0)

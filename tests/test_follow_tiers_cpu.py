@@ -1,0 +1,172 @@
+"""CPU tests of follower tiers 2 and 3 (opencv-ar_amd/csrc/walk_core.h, built for the host from tests/emul/follow_emul.cpp).
+
+Tier 2's step is the code follow_mid_kernel compiles (lean_begin, lean_step, lean_table_entry, lean_budget).  Tier 3 is a host
+emulation of follow_long_kernel's wave built on the arithmetic the kernel compiles (the window's constants, origin and
+quarter-tile mapping, tile_misses, tile_mask, tile_step).  Every plausible border start of every image -- an outer or a hole
+start condition -- is walked on the same bit plane by tier 2 and trace_flat, and by tier 3 and trace_border<true, false>, with
+the budget 4 ns sh + 16; status, corner count and, for closed borders, every corner point must be equal.
+
+Step counts.  flat_step_t counts a step only when the walk is still running after it, lean_step counts every step it is
+called for, so a walk that ends (closed, or not its border's first position) has LeanWalk::step == LeanTrace::steps + 1; a
+single pixel takes no step in either.  A walk the budget ends is different: trace_flat refuses the step after max_steps steps
+and tier 2 looks at the budget after whole blocks of steps, so both have taken exactly max_steps steps when max_steps is a
+whole number of blocks -- same count, same corner count -- and tier 2 runs on to the end of the block when it is not.
+Tier 3 and trace_border both count the pixel moves made, less the closing move.  A run is jumped as k moves at once; when
+the border closes inside a run, the move that entered the run (the loop's own, counted at the loop's end, which the closing
+`break` skips) is missing as well: one less.  trace_border reports no count for a walk that does not close, so nothing is
+asserted about tier 3's there."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+from border_shapes import sawtooth_frame
+from helpers import P
+
+OK, NOT_FIRST, SINGLE, OVERRUN = 0, 1, 2, 3   # trace_core.h: TraceStatus
+
+
+@pytest.fixture(scope="module")
+def lib(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("follow_emul") / "libfollow_emul.so")
+    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
+                           "-Wno-unknown-pragmas", "-DOCVAR_NBR_TILED", "-I" + os.path.join(H.PKG, "csrc"), "-I" + os.path.join(H.ROOT, "include"),
+                           "-shared", "-o", so, os.path.join(H.ROOT, "tests", "emul", "follow_emul.cpp")])
+    L = C.CDLL(so)
+    assert L.fe_row_ints() == 24
+    return L
+
+
+def _sawtooth(sw, sh):
+    tooth = max(1, min(sw, sh) // 20)
+    m = tooth + 3
+    return (sawtooth_frame(sw, sh, tooth, [(m, m, sw - m, sh - m)])[..., 0] == 20).astype(np.uint8)
+
+
+def patterns(sw, sh, seed):
+    """name -> binary image (sh x sw, 0 / 1)"""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:sh, 0:sw]
+    return {
+        "ones": np.ones((sh, sw), np.uint8),                       # the ROI's own frame border: runs across several windows
+        "noise50": (rng.random((sh, sw)) < 0.5).astype(np.uint8),  # short walks, not-first starts, single pixels
+        "noise85": (rng.random((sh, sw)) < 0.85).astype(np.uint8),
+        "chequer": (((x // 7) + (y // 5)) & 1).astype(np.uint8),   # nested borders
+        "stripes": ((x + y) % 9 < 5).astype(np.uint8),             # staircases
+        "rects": ((x % 40 > 3) & (y % 33 > 2)).astype(np.uint8),   # holes and outer borders of marker-like size
+        "sawtooth": _sawtooth(sw, sh),
+    }
+
+
+def walks(lib, b, stride=1):
+    b = np.ascontiguousarray(b, np.uint8)
+    sh, sw = b.shape
+    cap = b.size + 16
+    rows = np.zeros((cap, 24), np.int32)
+    n = lib.fe_walks(P(b), sw, sh, stride, P(rows), cap)
+    assert n >= 0
+    return rows[:n]
+
+
+def check_walks(r, what):
+    flat, t2, b, t3 = r[:, 2:5], r[:, 5:8], r[:, 9:12], r[:, 12:15]
+    # a consistent plane and the full budget: no walk ends on its budget or outside the plane
+    assert (flat[:, 0] != OVERRUN).all() and (b[:, 0] != OVERRUN).all(), what
+    # tier 2 == trace_flat
+    assert (t2[:, 0] == flat[:, 0]).all(), (what, r[t2[:, 0] != flat[:, 0]][:4])
+    assert (t2[:, 1] == flat[:, 1]).all(), (what, r[t2[:, 1] != flat[:, 1]][:4])
+    assert (r[:, 8] == 1).all(), (what, r[r[:, 8] != 1][:4])
+    single = flat[:, 0] == SINGLE
+    assert (t2[single, 2] == 0).all() and (flat[single, 2] == 0).all(), what
+    assert (t2[~single, 2] == flat[~single, 2] + 1).all(), (what, r[~single][t2[~single, 2] != flat[~single, 2] + 1][:4])
+    # tier 3 == trace_border<true, false>
+    assert (t3[:, 0] == b[:, 0]).all(), (what, r[t3[:, 0] != b[:, 0]][:4])
+    assert (t3[:, 1] == b[:, 1]).all(), (what, r[t3[:, 1] != b[:, 1]][:4])
+    assert (r[:, 15] == 1).all(), (what, r[r[:, 15] != 1][:4])
+    closed = b[:, 0] == OK
+    assert (t3[closed, 2] == b[closed, 2] - r[closed, 16]).all(), (what, r[closed][t3[closed, 2] != b[closed, 2] - r[closed, 16]][:4])
+    assert (r[~closed, 16] == 0).all(), what
+    # the window: every slot written inside the array, shared slots written with equal values, every read inside the window
+    # and the plane, no spinning run; at least one load per walk
+    assert (r[:, 18:23] == 0).all(), (what, r[(r[:, 18:23] != 0).any(axis=1)][:4])
+    assert (r[:, 17] >= 1).all(), what
+
+
+SIZES = [(16, 16),      # the smallest the ABI admits: one tile column, the window's other three columns lie outside the plane
+         (34, 30),      # ns > sw, a partial last tile row
+         (130, 100),    # several windows each way; the window origin goes negative near the left and top edges
+         (198, 180),    # ... and a partial last tile row
+         (330, 76),     # runs longer than four windows, horizontally
+         (76, 330)]     # ... and vertically
+
+
+@pytest.mark.parametrize("sw,sh", SIZES)
+def test_tiers_2_and_3_walk_every_start_as_the_reference_forms_do(lib, sw, sh):
+    starts = closed = 0
+    for name, b in patterns(sw, sh, 1000 * sw + sh).items():
+        r = walks(lib, b)
+        check_walks(r, (sw, sh, name))
+        starts += len(r)
+        closed += int((r[:, 9] == OK).sum())
+        if name == "ones":
+            # one border, the rectangle next to the zeroed frame, found at (1, 1): the starts of the rows below are not its first
+            # position; the window is re-centred along the sides
+            assert r[0, 9] == OK and r[0, 10] == 4 and (r[1:, 9] == NOT_FIRST).all(), (sw, sh)
+            assert r[0, 17] >= 2 * ((sw - 2) // 64 + (sh - 2) // 70), (sw, sh, r[0, 17])
+    assert starts >= 100 and closed >= 10, (sw, sh, starts, closed)
+
+
+@pytest.mark.parametrize("sw,sh", [(16, 32766), (32766, 16)])
+def test_tiers_2_and_3_at_the_coordinate_limit(lib, sw, sh):
+    """packed points and div14's operands at the largest coordinates: the frame border of an all-ones image, ~65 k steps.
+    Every row has a plausible start that follows nearly the whole border before it meets an earlier position; so that the
+    test takes seconds only every 4096th start is walked: the border's first position and a few of the others."""
+    r = walks(lib, np.ones((sh, sw), np.uint8), stride=4096)
+    check_walks(r, (sw, sh))
+    assert len(r) == (sh - 2 + 4095) // 4096
+    assert r[0, 9] == OK and r[0, 10] == 4 and r[0, 11] >= 2 * (sw + sh) - 16 and (r[1:, 9] == NOT_FIRST).all()
+
+
+def test_tier_2_ends_on_its_budget_where_trace_flat_does(lib):
+    blk = lib.fe_block()
+    assert blk == 32
+    sw, sh = 130, 100
+    hit = finished = 0
+    for name, b in patterns(sw, sh, 7).items():
+        b = np.ascontiguousarray(b, np.uint8)
+        for budget in (blk, 2 * blk, 50, 8 * blk, 1000):
+            whole = (budget + blk - 1) // blk * blk   # tier 2 runs to the end of the block in which the budget is reached
+            rows = np.zeros((b.size + 16, 8), np.int32)
+            n = lib.fe_budget_walks(P(b), sw, sh, budget, whole, P(rows), len(rows))
+            assert n >= 0
+            r = rows[:n]
+            what = (name, budget)
+            assert (r[:, 5] == r[:, 2]).all() and (r[:, 6] == r[:, 3]).all(), (what, r[(r[:, 5] != r[:, 2]) | (r[:, 6] != r[:, 3])][:4])
+            over = r[:, 2] == OVERRUN
+            assert (r[over, 4] == whole).all() and (r[over, 7] == whole).all(), what
+            rest = ~over & (r[:, 2] != SINGLE)
+            assert (r[rest, 7] == r[rest, 4] + 1).all() and (r[rest, 7] <= whole).all(), what
+            hit += int(over.sum())
+            finished += int(rest.sum())
+    assert hit > 100 and finished > 1000
+
+
+def test_budget_of_a_tier_2_walk(lib):
+    """frames: the batch's budget; crops: 6 (sw + sh) of the crop's even size in whole blocks, between mid_steps and the cap"""
+    rng = np.random.default_rng(11)
+    for _ in range(2000):
+        w, h = int(rng.integers(16, 2000)), int(rng.integers(16, 2000))
+        mid, cap = int(rng.choice([96, 1536, 3072])), int(rng.choice([1536, 3072, 100000]))
+        cap = max(cap, mid)
+        assert lib.fe_lean_budget(0, w, h, mid, cap) == cap
+        fit = (6 * ((w & ~1) + (h & ~1)) + 31) // 32 * 32
+        assert lib.fe_lean_budget(1, w, h, mid, cap) == min(max(fit, mid), cap)
+
+
+def test_window_is_four_by_five_tiles_with_an_apron_row_either_side(lib):
+    out = np.zeros(6, np.int32)
+    assert lib.fe_window(P(out)) == 6
+    assert out.tolist() == [4, 5, 64, 70, 72, 80]
