@@ -269,6 +269,38 @@ int ocvar_hip_patches_records(OcvarHip* ctx, const uint8_t* d_frames, int width,
                               int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
                               uint8_t* d_patches, int patch_w, int patch_h, int flags, int* d_status, void* stream);
 
+/* Undistortion: frames of a distorting camera, and the marker records found on them, turned into the pinhole world of the same
+ * camera matrix without leaving device memory -- what glProjection, ocvar_hip_render* (plain homographies) and ocvar_hip_patches*
+ * (straight-edged quads) assume of the frame they are shown over.  The definition, bit for bit, is
+ * opencv-ar_amd/csrc/undistort_core.h, with the context's camera (ocvar_hip_set_camera) as it is at the call: fx fy cx cy of
+ * cameraMatrix and distCoeffs k1 k2 p1 p2 k3.
+ * ocvar_hip_undistort stands for OpenCV's undistort(src, dst, cameraMatrix, distCoeffs, newCameraMatrix = cameraMatrix):
+ * destination pixel (u, v) samples the source where the lens model puts the pixel's normalised point, computed in double per
+ * pixel (no map is stored), with cvWarpPerspective's 1/32-px bilinear sampling (decode_core.h) and a constant 0 outside the
+ * frame.  Every byte of a pixel is remapped alike, byte 3 of a four-channel pixel included.  With all five coefficients zero the
+ * frames are copied.
+ *   d_src / d_dst  n_frames frames of width x height pixels in `format` (any OCVAR_FMT_*), rows *_row_stride and frames
+ *                  *_frame_stride bytes apart, at any address; their byte ranges must not intersect (nothing in place)
+ * ocvar_hip_undistort_records stands for undistortPoints(square, cameraMatrix, distCoeffs, R = I, P = cameraMatrix) on the four
+ * corners of every record: cvUndistortPoints' five iterations, back to pixels with fx fy cx cy, rounded to float32 (a NaN is
+ * stored as 0x7FC00000); with all five coefficients zero the square is copied unchanged.  Every other field is copied as it is, glMatrix included: the pose already
+ * accounts for the lens, and its pinhole projection lands on the undistorted corners.
+ *   d_markers / d_out  [n_frames][records_per_frame] records (1 <= records_per_frame <= M = ocvar_hip_max_markers(ctx)); slot k
+ *                  of frame f is written when k < min(d_counts[f], records_per_frame), no other slot is touched; d_out may be
+ *                  d_markers
+ * Parity with a real OpenCV build is unpinned: none is at hand where this library is built and tested; the tests pin the host
+ * build of undistort_core.h, the agreement of the two maps and detection on undistorted views.
+ * Both need no batch and no workspace and can run at any time: a context that never calls them allocates and launches nothing.
+ * Frames of up to the context's max_width x max_height; any n_frames >= 1; stream NULL: the context's own stream.  Neither
+ * waits.  OCVAR_E_ARG, before any device call and with a text in ocvar_hip_last_error, for NULL pointers, no camera set, fx or fy
+ * zero or one of the nine camera numbers not finite, an unknown format, a row stride below the format's bytes per pixel times
+ * width, a size above the context's, n_frames < 1, rows that span more than 2^31 - 1 bytes (the rule of
+ * ocvar_hip_set_input_format, for source and destination), intersecting byte ranges, records_per_frame outside 1 .. M. */
+int ocvar_hip_undistort(OcvarHip* ctx, const uint8_t* d_src, int src_row_stride, size_t src_frame_stride, uint8_t* d_dst,
+                        int dst_row_stride, size_t dst_frame_stride, int width, int height, int n_frames, int format, void* stream);
+int ocvar_hip_undistort_records(OcvarHip* ctx, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
+                                OcvarMarker* d_out, void* stream);
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart

@@ -31,6 +31,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_set_board", "ocvar_hip_board_poses", "ocvar_hip_board_poses_to_device",
     "ocvar_hip_set_overlay", "ocvar_hip_render", "ocvar_hip_render_records",
     "ocvar_hip_patches", "ocvar_hip_patches_records",
+    "ocvar_hip_undistort", "ocvar_hip_undistort_records",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -218,6 +219,8 @@ def hip_lib():
         lib.ocvar_hip_render_records.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, i, vp]
         lib.ocvar_hip_patches.argtypes = [vp, vp, i, i, i, sz, i, vp, i, i, i, i, vp, vp]
         lib.ocvar_hip_patches_records.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, i, vp, i, i, i, vp, vp]
+        lib.ocvar_hip_undistort.argtypes = [vp, vp, i, sz, vp, i, sz, i, i, i, i, vp]
+        lib.ocvar_hip_undistort_records.argtypes = [vp, vp, vp, i, i, vp, vp]
         _hip = lib
     return _hip
 
@@ -603,6 +606,29 @@ class Detector:
         self._check(self._lib.ocvar_hip_patches_records(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames, code,
                                                         d_markers_ptr, d_counts_ptr, per_frame, d_patches_ptr, patch_w, patch_h, flags,
                                                         d_status_ptr, stream), "patches_records")
+
+    def undistort(self, d_src, d_dst, width, height, n_frames, fmt=None, src_row_stride=None, src_frame_stride=None, dst_row_stride=None,
+                  dst_frame_stride=None, stream=None):
+        """n_frames device frames at d_src in format fmt (default: the input format), taken with the camera of set_camera, into the
+        device frames at d_dst as a pinhole camera with the same camera matrix sees them (OpenCV's undistort with newCameraMatrix =
+        cameraMatrix; 0 where the source lies outside the frame).  Source and destination must not overlap.  Needs no batch, does
+        not wait (stream None: the detector's own stream); the camera is the one set at the call."""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        src_row_stride = src_row_stride or FORMAT_BPP[code] * width
+        src_frame_stride = src_frame_stride or src_row_stride * height
+        dst_row_stride = dst_row_stride or FORMAT_BPP[code] * width
+        dst_frame_stride = dst_frame_stride or dst_row_stride * height
+        self._check(self._lib.ocvar_hip_undistort(self._ctx, d_src, src_row_stride, src_frame_stride, d_dst, dst_row_stride, dst_frame_stride,
+                                                  width, height, n_frames, code, stream), "undistort")
+
+    def undistort_records(self, d_markers, d_counts, n_frames, d_out, per_frame=None, stream=None):
+        """the squares of the device records [n_frames, per_frame] (default per_frame: max_markers) under counts [n_frames] moved
+        to where the undistorted frames show them (OpenCV's undistortPoints with P = cameraMatrix), every other field copied, into
+        the device records at d_out (which may be d_markers); slots at or beyond a frame's count are not written.  Needs no
+        batch, does not wait (stream None: the detector's own stream)."""
+        per_frame = self.max_markers if per_frame is None else per_frame
+        self._check(self._lib.ocvar_hip_undistort_records(self._ctx, d_markers, d_counts, n_frames, per_frame, d_out, stream),
+                    "undistort_records")
 
     TUNE = {"crop_phases": 1, "mid_steps": 2, "mid_blocks": 3, "long_blocks": 4, "short_blocks": 5, "min_units": 6, "hp_mask": 7, "gate_mode": 8}
 

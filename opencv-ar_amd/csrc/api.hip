@@ -219,6 +219,7 @@ extern "C" int ocvar_hip_set_camera(OcvarHip* c, const OcvarCamera* cam) {
     if (!c || !cam) return OCVAR_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemcpy(c->ws.camera, cam, sizeof(OcvarCamera), hipMemcpyHostToDevice));
+    std::memcpy(&c->h_camera, cam, sizeof(OcvarCamera));
     c->have_camera = true;
     return OCVAR_OK;
 }
@@ -845,6 +846,92 @@ extern "C" int ocvar_hip_patches_records(OcvarHip* c, const uint8_t* d_frames, i
     const PatchArgs a{d_frames, width, height, (long long)row_stride, (long long)frame_stride, reinterpret_cast<const MarkerRec*>(d_markers),
                       d_counts, records_per_frame, d_patches, patch_w, patch_h, records_per_frame, flags, d_status};
     return patch_launch(c, a, n_frames, format, stream ? (hipStream_t)stream : c->stream.s);
+}
+
+// the context's camera as the undistort entry points take it; false (and the text) when there is none they can use
+static bool undistort_camera(OcvarHip* c, const char* what, UndistortCam* cam) {
+    if (!c->have_camera) {
+        c->err = std::string(what) + ": no camera set";
+        return false;
+    }
+    *cam = undistort_cam(c->h_camera);
+    if (!undistort_cam_ok(*cam)) {
+        c->err = std::string(what) + ": the camera's fx or fy is zero, or one of fx fy cx cy k1 k2 p1 p2 k3 is not finite";
+        return false;
+    }
+    return true;
+}
+
+// the bytes from a frame block's first to its last pixel byte
+static unsigned long long frames_extent(int width, int height, int bpp, long long row_stride, size_t frame_stride, int n_frames) {
+    return (unsigned long long)(n_frames - 1) * frame_stride + (unsigned long long)(height - 1) * (unsigned long long)row_stride +
+           (unsigned long long)bpp * width;
+}
+
+extern "C" int ocvar_hip_undistort(OcvarHip* c, const uint8_t* d_src, int src_row_stride, size_t src_frame_stride, uint8_t* d_dst,
+                                   int dst_row_stride, size_t dst_frame_stride, int width, int height, int n_frames, int format, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    const int bpp = patch_bpp(format);
+    if (!d_src || !d_dst) {
+        c->err = "undistort: no source or no destination frames";
+        return OCVAR_E_ARG;
+    }
+    if (n_frames < 1 || width < 1 || height < 1 || width > c->ws.max_w || height > c->ws.max_h) {
+        c->err = "undistort: frames of 1 .. the context's size, n_frames >= 1";
+        return OCVAR_E_ARG;
+    }
+    if (bpp == 0 || (long long)src_row_stride < (long long)bpp * width || (long long)dst_row_stride < (long long)bpp * width) {
+        c->err = "undistort: an unknown format or a row stride below the format's bytes per pixel times width";
+        return OCVAR_E_ARG;
+    }
+    if (int rc = frame_span_check(c, width, height, src_row_stride, format)) return rc;
+    if (int rc = frame_span_check(c, width, height, dst_row_stride, format)) return rc;
+    const unsigned long long s0 = (unsigned long long)(uintptr_t)d_src, d0 = (unsigned long long)(uintptr_t)d_dst;
+    const unsigned long long s1 = s0 + frames_extent(width, height, bpp, src_row_stride, src_frame_stride, n_frames);
+    const unsigned long long d1 = d0 + frames_extent(width, height, bpp, dst_row_stride, dst_frame_stride, n_frames);
+    if (s0 < d1 && d0 < s1) {
+        c->err = "undistort: the byte ranges of source and destination frames intersect (no undistortion in place)";
+        return OCVAR_E_ARG;
+    }
+    UndistortCam cam;
+    if (!undistort_camera(c, "undistort", &cam)) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    const int chunk = 65535;
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const UndistortArgs a{d_src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, width, height,
+                              (long long)src_row_stride, (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride, cam};
+        launch_undistort(a, std::min(chunk, n_frames - f0), format, s);
+        TRACE_LAUNCH("undistort", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_undistort_records(OcvarHip* c, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
+                                           OcvarMarker* d_out, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    if (!d_markers || !d_counts || !d_out) {
+        c->err = "undistort_records: no records, no counts or no output";
+        return OCVAR_E_ARG;
+    }
+    if (n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm) {
+        c->err = "undistort_records: n_frames >= 1, 1 .. M records per frame";
+        return OCVAR_E_ARG;
+    }
+    UndistortCam cam;
+    if (!undistort_camera(c, "undistort_records", &cam)) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    const int chunk = 65535;
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const UndistortRecArgs a{reinterpret_cast<const MarkerRec*>(d_markers) + (size_t)f0 * records_per_frame,
+                                 reinterpret_cast<MarkerRec*>(d_out) + (size_t)f0 * records_per_frame, d_counts + f0, records_per_frame, cam};
+        launch_undistort_records(a, std::min(chunk, n_frames - f0), s);
+        TRACE_LAUNCH("undistort_records", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
 }
 
 extern "C" int ocvar_hip_detect_device(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride,

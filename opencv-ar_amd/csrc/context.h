@@ -119,6 +119,7 @@ struct OcvarHip {
     ocvar::PinnedBuffer<int> h_counters;
     bool pending = false;
     bool have_templates = false, have_camera = false;
+    ocvar::CameraRec h_camera{};   // the camera as last set, for the entry points that pass it by value (ocvar_hip_undistort)
     ocvar::Library lib;       // the templates' table as uploaded (ocvar_hip_debug_candidates expands a square with it)
     int capacity_flags = 0;   // flag word of the last batch that failed with OCVAR_E_CAPACITY
     // planar board (ocvar_hip_set_board): the device table is allocated by the first board set

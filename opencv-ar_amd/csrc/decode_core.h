@@ -71,18 +71,13 @@ OCVAR_HD void invert_map(const float* m32, double* M) {
     }
 }
 
-// One destination pixel (x,y) of cvWarpPerspective(INTER_LINEAR, fill 0) on a single-channel crop.
-// (px(ix, iy): the crop's pixel at column ix, row iy -- the device reads the panelled grey plane through it)
+// A source coordinate in 1/32 px as cvWarpPerspective fixes it: clamped to the int range, rounded to nearest even.
+OCVAR_HD int warp_fixed32(double v32) { return (int)rint(fmax(-2147483648.0, fmin(2147483647.0, v32))); }
+
+// The sample of a cw x ch single-channel image at the fixed-point source position (X, Y), 1/32 px each: bilinear with OpenCV's
+// 15-bit weights, a constant 0 outside the image.  (px(ix, iy): the pixel at column ix, row iy)
 template <class Px>
-OCVAR_HD int warp_sample_px(Px px, int cw, int ch, const double* M, int x, int y) {
-    const double X0 = M[0] * 0 + M[1] * y + M[2];
-    const double Y0 = M[3] * 0 + M[4] * y + M[5];
-    const double W0 = M[6] * 0 + M[7] * y + M[8];
-    double W = W0 + M[6] * x;
-    W = W ? 32. / W : 0;
-    const double fX = fmax(-2147483648.0, fmin(2147483647.0, (X0 + M[0] * x) * W));
-    const double fY = fmax(-2147483648.0, fmin(2147483647.0, (Y0 + M[3] * x) * W));
-    const int X = (int)rint(fX), Y = (int)rint(fY);
+OCVAR_HD int warp_sample_fixed(Px px, int cw, int ch, int X, int Y) {
     int ix = X >> 5, iy = Y >> 5;
     ix = ix > 32767 ? 32767 : (ix < -32768 ? -32768 : ix);
     iy = iy > 32767 ? 32767 : (iy < -32768 ? -32768 : iy);
@@ -99,6 +94,19 @@ OCVAR_HD int warp_sample_px(Px px, int cw, int ch, const double* M, int x, int y
     const int p10 = (x0ok && y1ok) ? px(ix, iy + 1) : 0;
     const int p11 = (x1ok && y1ok) ? px(ix + 1, iy + 1) : 0;
     return (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + 16384) >> 15;
+}
+
+// One destination pixel (x,y) of cvWarpPerspective(INTER_LINEAR, fill 0) on a single-channel crop.
+// (px(ix, iy): the crop's pixel at column ix, row iy -- the device reads the panelled grey plane through it)
+template <class Px>
+OCVAR_HD int warp_sample_px(Px px, int cw, int ch, const double* M, int x, int y) {
+    const double X0 = M[0] * 0 + M[1] * y + M[2];
+    const double Y0 = M[3] * 0 + M[4] * y + M[5];
+    const double W0 = M[6] * 0 + M[7] * y + M[8];
+    double W = W0 + M[6] * x;
+    W = W ? 32. / W : 0;
+    const int X = warp_fixed32((X0 + M[0] * x) * W), Y = warp_fixed32((Y0 + M[3] * x) * W);
+    return warp_sample_fixed(px, cw, ch, X, Y);
 }
 OCVAR_HD int warp_sample(const uint8_t* crop, int cw, int ch, int stride, const double* M, int x, int y) {
     return warp_sample_px([=](int ix, int iy) -> int { return crop[(long long)iy * stride + ix]; }, cw, ch, M, x, y);

@@ -8,6 +8,7 @@
 #include "board_core.h"
 #include "overlay_core.h"
 #include "patch_core.h"
+#include "undistort_core.h"
 #include "croplist_core.h"
 #include "ocvar_hip.h"
 
@@ -197,5 +198,29 @@ struct PatchArgs {
 };
 // n_frames (at most 32768: the grid's z) frames in `format`
 void launch_patches(const PatchArgs& a, int n_frames, int format, hipStream_t stream);
+
+// One launch of undistort_kernel (undistort.hip), all pointers in device memory: n_frames frames of W x H pixels from src to dst
+// (which do not overlap), rows and frames the given bytes apart, under the camera `cam` (by value: the context's at the call).
+struct UndistortArgs {
+    const uint8_t* src;
+    uint8_t* dst;
+    int W, H;
+    long long src_row_stride, src_frame_stride, dst_row_stride, dst_frame_stride;
+    UndistortCam cam;
+};
+// n_frames (at most 65535: the grid's z) frames in `format`
+void launch_undistort(const UndistortArgs& a, int n_frames, int format, hipStream_t stream);
+
+// One launch of undistort_records_kernel: of frame f the records in[f * slots + k], k < min(counts[f], slots), to the same slots
+// of out (which may be in).
+struct UndistortRecArgs {
+    const MarkerRec* in;
+    MarkerRec* out;
+    const int* counts;
+    int slots;
+    UndistortCam cam;
+};
+// n_frames (at most 65535: the grid's y) frames
+void launch_undistort_records(const UndistortRecArgs& a, int n_frames, hipStream_t stream);
 
 }  // namespace ocvar
