@@ -301,6 +301,56 @@ int ocvar_hip_undistort(OcvarHip* ctx, const uint8_t* d_src, int src_row_stride,
 int ocvar_hip_undistort_records(OcvarHip* ctx, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
                                 OcvarMarker* d_out, void* stream);
 
+/* Flow tracking: marker records carried from a block of previous frames to a block of next frames by sparse pyramidal
+ * Lucas-Kanade (the equations of OpenCV's calcOpticalFlowPyrLK) on their four corners, without anything leaving device memory
+ * -- the "four points from optical flow" cvarCompareSquare (opencvar.cpp:323-367) expects and nothing in the reference
+ * produces.  Two uses: the tracked records as d_prev of ocvar_hip_enqueue_tracked, so that the 20-px rule of cvarTrack compares
+ * detections with where the markers are, not where they were; and records and poses carried over frames that are not detected
+ * at all.  The definition, bit for bit, is opencv-ar_amd/csrc/flow_core.h: the integer pyramid (the library's grey, OpenCV's
+ * 8-bit pyrDown), central differences, float bilinear sampling, sums in double in a fixed order.
+ *   d_prev_frames / d_next_frames  n_frames frames of width x height pixels in `format` (any OCVAR_FMT_*), rows *_row_stride and
+ *                  frames *_frame_stride bytes apart, at any address; read only.  The two blocks may lie in one buffer at
+ *                  different offsets (frame t and t + 1 of a stream, or stream-major blocks).  Flow should see the frames as the
+ *                  camera gave them, or the same treatment on both sides: grey_in_place and ocvar_hip_render change frames.
+ *   d_markers / d_counts  [n_frames][records_per_frame] records on the previous frames and [n_frames] counts (1 <=
+ *                  records_per_frame <= M = ocvar_hip_max_markers(ctx)); slot k of frame f is live when k < min(d_counts[f],
+ *                  records_per_frame)
+ *   params         NULL: half_win 10, levels 3, max_iter 30, flags 0, eps 0.03, min_eig 1e-3, max_err 0, fb_max 0.  The window
+ *                  is (2 half_win + 1)^2 px; the levels used are 0 .. L, L the largest l <= levels whose shorter side is at
+ *                  least 2 half_win + 3; min_eig: the smallest eigenvalue of the window's gradient matrix per pixel a corner
+ *                  needs; max_err > 0: the largest mean absolute difference of the windows (grey levels) a tracked corner may
+ *                  have; fb_max > 0: the corner is tracked back, and may land at most fb_max px from where it started.
+ *                  OCVAR_FLOW_POSE: glMatrix of a tracked record is solved from its new square with the context's camera as it
+ *                  is at the call (by value) and the record's aspectRatio.
+ *   d_out          [n_frames][records_per_frame] records, may be d_markers: a live slot gets the input record with its square
+ *                  replaced (status 1), or unchanged (any other status)
+ *   d_status       [n_frames][records_per_frame] ints, may be NULL: 1 tracked; the code of the lowest-numbered failing corner: -1
+ *                  the corner does not start inside the frame (or is not finite), -2 no texture at level 0, -3 left the frame,
+ *                  -4 error above max_err, -5 forward-backward check; -6 all four tracked but the quad is not strictly convex;
+ *                  0 the slot is not live -- nothing else of such a slot is touched
+ *   d_err          [n_frames][records_per_frame][4] floats, may be NULL: of a live slot the corners' mean absolute differences
+ *                  at level 0, -1.0f for a corner that did not get that far
+ * Needs no batch and does not wait; stream NULL: the context's own stream.  Frames of up to the context's max_width x
+ * max_height with no side below 2 half_win + 3; any n_frames >= 1.  The workspace is allocated by the first call and freed with
+ * the context (a context that never calls allocates and launches nothing): two pyramids for each of min(max_batch, 32) frames,
+ * a pyramid being the six levels of a max_width x max_height frame with every row rounded up to 64 bytes and the whole to 256
+ * -- under 2 (4/3 W H + 2 W + 128 H + 1024) bytes per frame pair; more frames go through it in chunks, in stream order.  Calls of one
+ * context that name different streams are ordered by the library (an event behind the last chunk, which the next call's stream
+ * waits for), so the workspace is never shared by two calls at once.
+ * Parity with a real OpenCV build is unpinned (see ocvar_hip_undistort); the tests pin the host build of flow_core.h, a numpy
+ * restatement of the equations and the truth of rendered views.
+ * OCVAR_E_ARG, before any device call and with a text in ocvar_hip_last_error, for NULL frames, records, counts or output, an
+ * unknown format, a row stride below the format's bytes per pixel times width, rows that span more than 2^31 - 1 bytes (the rule
+ * of ocvar_hip_set_input_format), a size above the context's or a side below 2 half_win + 3, n_frames < 1, records_per_frame
+ * outside 1 .. M, half_win outside 1 .. OCVAR_MAX_FLOW_HALF_WIN, levels outside 0 .. OCVAR_MAX_FLOW_LEVELS, max_iter outside
+ * 1 .. 100, a negative or non-finite eps, min_eig, max_err or fb_max, unknown flag bits, OCVAR_FLOW_POSE without a camera. */
+enum { OCVAR_MAX_FLOW_HALF_WIN = 15, OCVAR_MAX_FLOW_LEVELS = 5, OCVAR_FLOW_POSE = 1 };
+typedef struct { int half_win, levels, max_iter, flags; float eps, min_eig, max_err, fb_max; } OcvarFlowParams;   /* 32 bytes */
+int ocvar_hip_flow_records(OcvarHip* ctx, const uint8_t* d_prev_frames, int prev_row_stride, size_t prev_frame_stride,
+                           const uint8_t* d_next_frames, int next_row_stride, size_t next_frame_stride, int width, int height,
+                           int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
+                           const OcvarFlowParams* params, OcvarMarker* d_out, int* d_status, float* d_err, void* stream);
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart

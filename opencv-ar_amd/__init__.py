@@ -32,6 +32,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_set_overlay", "ocvar_hip_render", "ocvar_hip_render_records",
     "ocvar_hip_patches", "ocvar_hip_patches_records",
     "ocvar_hip_undistort", "ocvar_hip_undistort_records",
+    "ocvar_hip_flow_records",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -79,6 +80,24 @@ def corner_refine_args(half_win, max_iter, eps):
 MAX_BOARD_MARKERS = 256   # include/ocvar_hip.h: OCVAR_MAX_BOARD_MARKERS
 MAX_OVERLAYS, MAX_OVERLAY_SIDE = 64, 1024   # include/ocvar_hip.h: OCVAR_MAX_OVERLAYS, OCVAR_MAX_OVERLAY_SIDE
 MAX_PATCH_SIDE, PATCH_FLIP_ROWS, PATCH_MATCHED_ONLY = 256, 1, 2   # include/ocvar_hip.h: OCVAR_MAX_PATCH_SIDE, OCVAR_PATCH_*
+MAX_FLOW_HALF_WIN, MAX_FLOW_LEVELS, FLOW_POSE = 15, 5, 1   # include/ocvar_hip.h: OCVAR_MAX_FLOW_HALF_WIN, OCVAR_MAX_FLOW_LEVELS, OCVAR_FLOW_POSE
+
+
+class FlowParams(C.Structure):  # OcvarFlowParams
+    _fields_ = [("half_win", C.c_int), ("levels", C.c_int), ("max_iter", C.c_int), ("flags", C.c_int),
+                ("eps", C.c_float), ("min_eig", C.c_float), ("max_err", C.c_float), ("fb_max", C.c_float)]
+
+
+def flow_params(half_win=10, levels=3, max_iter=30, eps=0.03, min_eig=1e-3, max_err=0.0, fb_max=0.0, pose=False):
+    """The parameters of Detector.flow_records (include/ocvar_hip.h: OcvarFlowParams; the defaults are the library's), checked:
+    ValueError outside half_win 1..15, levels 0..5, max_iter 1..100, or for a negative or non-finite eps, min_eig, max_err, fb_max"""
+    for name, v, lo, hi in (("half_win", half_win, 1, MAX_FLOW_HALF_WIN), ("levels", levels, 0, MAX_FLOW_LEVELS), ("max_iter", max_iter, 1, 100)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an int in {lo} .. {hi}, got {v!r}")
+    for name, v in (("eps", eps), ("min_eig", min_eig), ("max_err", max_err), ("fb_max", fb_max)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < 3e38:
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+    return FlowParams(int(half_win), int(levels), int(max_iter), FLOW_POSE if pose else 0, float(eps), float(min_eig), float(max_err), float(fb_max))
 
 
 class BoardMarker(C.Structure):  # OcvarBoardMarker: a template and the board-plane (z = 0) coordinates of its corners 0..3
@@ -221,6 +240,7 @@ def hip_lib():
         lib.ocvar_hip_patches_records.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, i, vp, i, i, i, vp, vp]
         lib.ocvar_hip_undistort.argtypes = [vp, vp, i, sz, vp, i, sz, i, i, i, i, vp]
         lib.ocvar_hip_undistort_records.argtypes = [vp, vp, vp, i, i, vp, vp]
+        lib.ocvar_hip_flow_records.argtypes = [vp, vp, i, sz, vp, i, sz, i, i, i, i, vp, vp, i, vp, vp, vp, vp, vp]
         _hip = lib
     return _hip
 
@@ -629,6 +649,30 @@ class Detector:
         per_frame = self.max_markers if per_frame is None else per_frame
         self._check(self._lib.ocvar_hip_undistort_records(self._ctx, d_markers, d_counts, n_frames, per_frame, d_out, stream),
                     "undistort_records")
+
+    def flow_records(self, d_prev, d_next, width, height, n_frames, d_markers, d_counts, d_out, per_frame=None, fmt=None,
+                     prev_row_stride=None, prev_frame_stride=None, next_row_stride=None, next_frame_stride=None, params=None, pose=False,
+                     d_status_ptr=None, d_err_ptr=None, stream=None):
+        """the device records [n_frames, per_frame] (default per_frame: max_markers) under counts [n_frames], found on the n_frames
+        device frames at d_prev, carried to the frames at d_next in format fmt (default: the input format) by pyramidal Lucas-Kanade
+        on their corners, into the device records at d_out (which may be d_markers): a tracked record (status 1) has its square
+        replaced -- and with pose (or params made with pose=True) its glMatrix solved from it with the camera set at the call --,
+        a failed one (status -1 .. -6: include/ocvar_hip.h) is copied unchanged; slots at or beyond a frame's count get status 0 and
+        are not written.  params: flow_params(...), default the library's.  d_status_ptr: device ints [n_frames, per_frame];
+        d_err_ptr: device floats [n_frames, per_frame, 4], the corners' mean absolute differences.  Needs no batch, does not wait
+        (stream None: the detector's own stream); the frames are only read."""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        per_frame = self.max_markers if per_frame is None else per_frame
+        prev_row_stride = prev_row_stride or FORMAT_BPP[code] * width
+        prev_frame_stride = prev_frame_stride or prev_row_stride * height
+        next_row_stride = next_row_stride or FORMAT_BPP[code] * width
+        next_frame_stride = next_frame_stride or next_row_stride * height
+        p = flow_params() if params is None else FlowParams.from_buffer_copy(bytes(params))
+        if pose:
+            p.flags |= FLOW_POSE
+        self._check(self._lib.ocvar_hip_flow_records(self._ctx, d_prev, prev_row_stride, prev_frame_stride, d_next, next_row_stride,
+                                                     next_frame_stride, width, height, n_frames, code, d_markers, d_counts, per_frame,
+                                                     C.byref(p), d_out, d_status_ptr, d_err_ptr, stream), "flow_records")
 
     TUNE = {"crop_phases": 1, "mid_steps": 2, "mid_blocks": 3, "long_blocks": 4, "short_blocks": 5, "min_units": 6, "hp_mask": 7, "gate_mode": 8}
 

@@ -934,6 +934,83 @@ extern "C" int ocvar_hip_undistort_records(OcvarHip* c, const OcvarMarker* d_mar
     return OCVAR_OK;
 }
 
+// a parameter of ocvar_hip_flow_records that must be a finite number >= 0
+static bool flow_number_ok(float v) { return v >= 0.0f && v <= 3.0e38f; }
+
+extern "C" int ocvar_hip_flow_records(OcvarHip* c, const uint8_t* d_prev_frames, int prev_row_stride, size_t prev_frame_stride,
+                                      const uint8_t* d_next_frames, int next_row_stride, size_t next_frame_stride, int width, int height,
+                                      int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
+                                      const OcvarFlowParams* params, OcvarMarker* d_out, int* d_status, float* d_err, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    const OcvarFlowParams p = params ? *params : OcvarFlowParams{10, 3, 30, 0, 0.03f, 1e-3f, 0.0f, 0.0f};
+    const int bpp = patch_bpp(format);
+    if (!d_prev_frames || !d_next_frames || !d_markers || !d_counts || !d_out) {
+        c->err = "flow_records: no frames, no records, no counts or no output";
+        return OCVAR_E_ARG;
+    }
+    if (p.half_win < 1 || p.half_win > OCVAR_MAX_FLOW_HALF_WIN || p.levels < 0 || p.levels > OCVAR_MAX_FLOW_LEVELS || p.max_iter < 1 ||
+        p.max_iter > 100) {
+        c->err = "flow_records: half_win 1 .. " + std::to_string(OCVAR_MAX_FLOW_HALF_WIN) + ", levels 0 .. " +
+                 std::to_string(OCVAR_MAX_FLOW_LEVELS) + ", max_iter 1 .. 100";
+        return OCVAR_E_ARG;
+    }
+    if (!flow_number_ok(p.eps) || !flow_number_ok(p.min_eig) || !flow_number_ok(p.max_err) || !flow_number_ok(p.fb_max)) {
+        c->err = "flow_records: eps, min_eig, max_err and fb_max are finite numbers >= 0";
+        return OCVAR_E_ARG;
+    }
+    if (p.flags & ~FLOW_FLAGS) {
+        c->err = "flow_records: unknown flag bits";
+        return OCVAR_E_ARG;
+    }
+    if (n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm) {
+        c->err = "flow_records: n_frames >= 1, 1 .. M records per frame";
+        return OCVAR_E_ARG;
+    }
+    const int side = 2 * p.half_win + 3;
+    if (width < side || height < side || width > c->ws.max_w || height > c->ws.max_h) {
+        c->err = "flow_records: frames of 2 half_win + 3 pixels each way .. the context's size";
+        return OCVAR_E_ARG;
+    }
+    if (bpp == 0 || (long long)prev_row_stride < (long long)bpp * width || (long long)next_row_stride < (long long)bpp * width) {
+        c->err = "flow_records: an unknown format or a row stride below the format's bytes per pixel times width";
+        return OCVAR_E_ARG;
+    }
+    if (int rc = frame_span_check(c, width, height, prev_row_stride, format)) return rc;
+    if (int rc = frame_span_check(c, width, height, next_row_stride, format)) return rc;
+    if ((p.flags & OCVAR_FLOW_POSE) && !c->have_camera) {
+        c->err = "flow_records: OCVAR_FLOW_POSE without a camera";
+        return OCVAR_E_ARG;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int chunk = std::min(c->ws.max_batch, 32);
+    const size_t slot = (size_t)flow_geom(c->ws.max_w, c->ws.max_h, 1, 0).bytes;
+    HIP_TRY(c, c->flow_ws.reserve(2 * (size_t)chunk * slot));
+    HIP_TRY(c, c->flow_done.ensure(hipEventDisableTiming));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    if (c->flow_used && c->flow_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->flow_done, 0));
+    const FlowGeom g = flow_geom(width, height, p.half_win, p.levels);
+    uint8_t* pyr_a = c->flow_ws;
+    uint8_t* pyr_b = pyr_a + (size_t)chunk * slot;
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int n = std::min(chunk, n_frames - f0);
+        launch_flow_pyramids(FlowPyrArgs{d_prev_frames + (size_t)f0 * prev_frame_stride, (long long)prev_row_stride, (long long)prev_frame_stride,
+                                         pyr_a, (long long)slot, g}, n, format, s);
+        launch_flow_pyramids(FlowPyrArgs{d_next_frames + (size_t)f0 * next_frame_stride, (long long)next_row_stride, (long long)next_frame_stride,
+                                         pyr_b, (long long)slot, g}, n, format, s);
+        TRACE_LAUNCH("flow_pyramids", s);
+        const size_t r0 = (size_t)f0 * records_per_frame;
+        launch_flow_track(FlowTrackArgs{pyr_a, pyr_b, (long long)slot, g, flow_args_make(p), c->h_camera,
+                                        reinterpret_cast<const MarkerRec*>(d_markers) + r0, d_counts + f0, reinterpret_cast<MarkerRec*>(d_out) + r0,
+                                        d_status ? d_status + r0 : nullptr, d_err ? d_err + 4 * r0 : nullptr, records_per_frame, n}, s);
+        TRACE_LAUNCH("flow_track", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->flow_done, s));
+    c->flow_stream = s;
+    c->flow_used = true;
+    return OCVAR_OK;
+}
+
 extern "C" int ocvar_hip_detect_device(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride,
                                        int n_frames, int grey_in_place, const OcvarMarker* prev, const int* prev_counts,
                                        OcvarMarker* markers, int* counts, int max_per_frame) {

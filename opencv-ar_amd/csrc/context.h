@@ -140,6 +140,11 @@ struct OcvarHip {
     int n_overlays = 0;
     hipStream_t ovl_stream = nullptr;
     bool ovl_used = false;
+    // flow tracking (ocvar_hip_flow_records): the pyramids' workspace is allocated by the first call
+    ocvar::Event flow_done;                        // behind the last use of the workspace, on flow_stream (created on first use)
+    ocvar::DeviceBuffer<uint8_t> flow_ws;          // [2][min(max_batch, 32)] pyramids of a max_w x max_h frame (flow_core.h: flow_geom)
+    hipStream_t flow_stream = nullptr;
+    bool flow_used = false;
     std::string err;
 
     ~OcvarHip();   // (api.hip: the fixed arrays and the overlay images; the holders release the rest)

@@ -9,6 +9,7 @@
 #include "overlay_core.h"
 #include "patch_core.h"
 #include "undistort_core.h"
+#include "flow_core.h"
 #include "croplist_core.h"
 #include "ocvar_hip.h"
 
@@ -222,5 +223,36 @@ struct UndistortRecArgs {
 };
 // n_frames (at most 65535: the grid's y) frames
 void launch_undistort_records(const UndistortRecArgs& a, int n_frames, hipStream_t stream);
+
+// The pyramids of n_frames frames in `format` (flow.hip: flow_grey_kernel, then flow_down_kernel level by level): frame f's
+// levels 0 .. g.L go to pyr + f * slot_bytes, laid out as g says.
+struct FlowPyrArgs {
+    const uint8_t* frames;
+    long long row_stride, frame_stride;
+    uint8_t* pyr;
+    long long slot_bytes;
+    FlowGeom g;
+};
+// n_frames (at most 65535: the grid's z) frames
+void launch_flow_pyramids(const FlowPyrArgs& a, int n_frames, int format, hipStream_t stream);
+
+// One launch of flow_track_kernel: of frame f the records in[f * slots + k], k < min(counts[f], slots), from the pyramid at
+// pyr_a + f * slot_bytes to the one at pyr_b + f * slot_bytes, into the same slots of out (which may be in); status
+// [n_frames][slots] and err [n_frames][slots][4] or nullptr.  Parameters and camera by value.
+struct FlowTrackArgs {
+    const uint8_t* pyr_a;
+    const uint8_t* pyr_b;
+    long long slot_bytes;
+    FlowGeom g;
+    FlowArgs fa;
+    CameraRec cam;
+    const MarkerRec* in;
+    const int* counts;
+    MarkerRec* out;
+    int* status;
+    float* err;
+    int slots, n_frames;
+};
+void launch_flow_track(const FlowTrackArgs& a, hipStream_t stream);
 
 }  // namespace ocvar

@@ -73,6 +73,20 @@ OCVAR_HD int overlay_bpp(int fmt) {
     return (fmt == OCVAR_FMT_BGR || fmt == OCVAR_FMT_RGB) ? 3 : ((fmt == OCVAR_FMT_BGRA || fmt == OCVAR_FMT_RGBA) ? 4 : (fmt == OCVAR_FMT_GRAY ? 1 : 0));
 }
 
+// Strictly convex: the four turns of the quad sq (8 floats) have one strict sign.  (flow_core.h asks the same of a tracked quad.)
+OCVAR_HD bool quad_strictly_convex(const float* sq) {
+    int pos = 0, neg = 0;
+    for (int i = 0; i < 4; i++) {
+        const float* p = sq + 2 * i;
+        const float* q = sq + 2 * ((i + 1) & 3);
+        const float* s = sq + 2 * ((i + 2) & 3);
+        const double z = ((double)q[0] - p[0]) * ((double)s[1] - q[1]) - ((double)q[1] - p[1]) * ((double)s[0] - q[0]);
+        pos += z > 0.0;
+        neg += z < 0.0;
+    }
+    return pos == 4 || neg == 4;
+}
+
 // One record of a W x H frame: its map, overlay and box; false (and an empty box): it draws nothing.
 OCVAR_HD bool overlay_setup(const MarkerRec& r, const OverlayTable& tab, int W, int H, OverlayDraw& d, OverlayBox& b) {
     b.x0 = 1; b.y0 = 1; b.x1 = 0; b.y1 = 0;
@@ -93,16 +107,7 @@ OCVAR_HD bool overlay_setup(const MarkerRec& r, const OverlayTable& tab, int W, 
         miny = y < miny ? y : miny;
         maxy = y > maxy ? y : maxy;
     }
-    int pos = 0, neg = 0;   // strictly convex: the four turns have one strict sign
-    for (int i = 0; i < 4; i++) {
-        const float* p = r.square + 2 * i;
-        const float* q = r.square + 2 * ((i + 1) & 3);
-        const float* s = r.square + 2 * ((i + 2) & 3);
-        const double z = ((double)q[0] - p[0]) * ((double)s[1] - q[1]) - ((double)q[1] - p[1]) * ((double)s[0] - q[0]);
-        pos += z > 0.0;
-        neg += z < 0.0;
-    }
-    if (pos != 4 && neg != 4) return false;
+    if (!quad_strictly_convex(r.square)) return false;
     const OverlayTex tex = tab.tex[slot];
     if (!perspective_from_quad(r.square, tex.w, tex.h, d.m)) return false;
     const double side = (maxx - minx) > (maxy - miny) ? (maxx - minx) : (maxy - miny);
