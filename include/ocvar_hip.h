@@ -139,7 +139,8 @@ int ocvar_hip_set_camera(OcvarHip* ctx, const OcvarCamera* camera);
  * OCVAR_FMT_GRAY it does nothing (no kernel, and ocvar_hip_detect_host copies nothing back).
  * YUV sources (NV12, I420): OCVAR_FMT_GRAY on the luma plane -- row_stride = the plane's pitch, frame_stride = the whole
  * YUV frame's size (pitch * height * 3 / 2 for NV12 and I420 with a common pitch); the chroma bytes are never read.  The result
- * is the reference on the luma image; it is NOT the reference on a BT.601 conversion of the YUV frame to BGR. */
+ * is the reference on the luma image.  For the reference on the colour conversion of the YUV frame, and for everything that needs
+ * colour (overlays, patches, undistortion), convert on the device first: ocvar_hip_yuv_to_frames below. */
 enum { OCVAR_FMT_BGR = 0, OCVAR_FMT_RGB = 1, OCVAR_FMT_BGRA = 2, OCVAR_FMT_RGBA = 3, OCVAR_FMT_GRAY = 4 };
 /* Context state like the result limit and the camera: read when a batch is enqueued, by every entry point that takes frames
  * (detect_device, enqueue, enqueue_tracked, detect_host).  Default OCVAR_FMT_BGR.  OCVAR_E_ARG for an unknown format, or
@@ -350,6 +351,45 @@ int ocvar_hip_flow_records(OcvarHip* ctx, const uint8_t* d_prev_frames, int prev
                            const uint8_t* d_next_frames, int next_row_stride, size_t next_frame_stride, int width, int height,
                            int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
                            const OcvarFlowParams* params, OcvarMarker* d_out, int* d_status, float* d_err, void* stream);
+
+/* YUV conversion: 8-bit limited-range NV12, I420, YUYV and UYVY frames, as a video decoder or a capture card leaves them in
+ * device memory, to the interleaved frame formats every other entry point takes, and back for an encoder -- the one full-frame
+ * pass of a device-resident decode, detect, draw, encode loop the library did not have.  The definition, bit for bit, is
+ * opencv-ar_amd/csrc/yuv_core.h: 20-bit fixed-point integer arithmetic, the chroma sample used as it is (nearest) towards colour,
+ * the mean colour of the 2 x 2 (4:2:0) or 2 x 1 (4:2:2) block towards chroma.  ocvar_hip_yuv_to_frames stands for OpenCV's
+ * cvtColor with COLOR_YUV2BGR_NV12 / _I420 / _YUY2 / _UYVY (and the RGB, four-channel and grey relatives),
+ * ocvar_hip_frames_to_yuv for COLOR_BGR2YUV_I420 and its relatives.
+ *   OcvarYuvFrames  layout: OCVAR_YUV_NV12 (a Y plane at y, interleaved U V at c0), OCVAR_YUV_I420 (Y at y, U at c0, V at c1),
+ *                  OCVAR_YUV_YUYV (Y0 U Y1 V at y), OCVAR_YUV_UYVY (U Y0 V Y1 at y); plane pointers a layout does not use are
+ *                  ignored.  matrix: OCVAR_YUV_BT601 (the constants of OpenCV's YUV family) or OCVAR_YUV_BT709, both limited range
+ *                  (Y 16 .. 235, U V 16 .. 240).  y_pitch: bytes between rows of the Y or packed plane; c_pitch: between rows of
+ *                  the chroma planes (NV12: at least width, I420: at least width / 2).  Frame f's planes start at plane +
+ *                  f * frame_stride, each plane pointer on its own: a decoder surface with a chroma offset fits.  The planes of
+ *                  a destination must not overlap each other.
+ *   d_dst / d_src  n_frames frames of width x height pixels in `format` (any OCVAR_FMT_*; it need not be the input format), rows
+ *                  *_row_stride and frames *_frame_stride bytes apart, at any address.  As a destination BGRA and RGBA get byte
+ *                  3 = 255 and GRAY gets the library's grey of the converted colour, so that detection on it is detection on the
+ *                  converted BGR frame; as a source byte 3 is ignored and GRAY reads as B = G = R = g.
+ * When every plane address, pitch, row stride and frame stride is a multiple of 4 the kernels move whole dwords; otherwise, and
+ * in the last pixels of a row, bytes -- with the same result.  No byte outside the pixels and samples is written.
+ * Parity with a real OpenCV build is unpinned (see ocvar_hip_undistort): the BT.601 constants are written down from memory of
+ * OpenCV; the tests pin the host build of yuv_core.h, a numpy restatement of the equations and the float64 matrices.
+ * Both need no batch and no workspace and can run at any time: a context that never calls them allocates and launches nothing.
+ * Frames of up to the context's max_width x max_height; any n_frames >= 1 (more than 65535 go in several launches, in stream
+ * order); stream NULL: the context's own stream.  Neither waits.  OCVAR_E_ARG, before any device call and with a text in
+ * ocvar_hip_last_error, for NULL pointers (of the planes the layout uses), an unknown layout, matrix or format, an odd width, an
+ * odd height with NV12 or I420, a size above the context's, n_frames < 1, a pitch below the plane's bytes per row, a row stride
+ * below the format's bytes per pixel times width, rows of a plane or of a frame that span more than 2^31 - 1 bytes, byte ranges
+ * of a plane and of the frames that intersect (nothing in place). */
+enum { OCVAR_YUV_NV12 = 0, OCVAR_YUV_I420 = 1, OCVAR_YUV_YUYV = 2, OCVAR_YUV_UYVY = 3 };
+enum { OCVAR_YUV_BT601 = 0, OCVAR_YUV_BT709 = 1 };
+typedef struct { int layout, matrix;                    /* OCVAR_YUV_NV12 .., OCVAR_YUV_BT601 / OCVAR_YUV_BT709 */
+                 uint8_t* y; uint8_t* c0; uint8_t* c1;  /* Y (or the packed plane); NV12: U V, I420: U; I420: V */
+                 int y_pitch, c_pitch; size_t frame_stride; } OcvarYuvFrames;   /* 48 bytes */
+int ocvar_hip_yuv_to_frames(OcvarHip* ctx, const OcvarYuvFrames* src, uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride,
+                            int width, int height, int n_frames, int format, void* stream);
+int ocvar_hip_frames_to_yuv(OcvarHip* ctx, const uint8_t* d_src, int src_row_stride, size_t src_frame_stride, const OcvarYuvFrames* dst,
+                            int width, int height, int n_frames, int format, void* stream);
 
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f

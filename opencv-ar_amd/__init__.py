@@ -33,6 +33,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_patches", "ocvar_hip_patches_records",
     "ocvar_hip_undistort", "ocvar_hip_undistort_records",
     "ocvar_hip_flow_records",
+    "ocvar_hip_yuv_to_frames", "ocvar_hip_frames_to_yuv",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -98,6 +99,42 @@ def flow_params(half_win=10, levels=3, max_iter=30, eps=0.03, min_eig=1e-3, max_
         if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < 3e38:
             raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
     return FlowParams(int(half_win), int(levels), int(max_iter), FLOW_POSE if pose else 0, float(eps), float(min_eig), float(max_err), float(fb_max))
+
+
+YUV_LAYOUTS = {"nv12": 0, "i420": 1, "yuyv": 2, "uyvy": 3}   # include/ocvar_hip.h: OCVAR_YUV_NV12 ..
+YUV_MATRICES = {"bt601": 0, "bt709": 1}                      # include/ocvar_hip.h: OCVAR_YUV_BT601, OCVAR_YUV_BT709
+
+
+def _yuv_code(table, what, v):
+    if isinstance(v, str) and v.lower() in table:
+        return table[v.lower()]
+    if isinstance(v, int) and not isinstance(v, bool) and v in table.values():
+        return v
+    raise ValueError(f"unknown YUV {what} {v!r}: one of {sorted(table)}")
+
+
+class YuvFrames(C.Structure):  # OcvarYuvFrames: where the planes of a block of YUV frames lie in device memory
+    _fields_ = [("layout", C.c_int), ("matrix", C.c_int), ("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p),
+                ("y_pitch", C.c_int), ("c_pitch", C.c_int), ("frame_stride", C.c_size_t)]
+
+    @classmethod
+    def from_surface(cls, ptr, width, height, layout, pitch=None, matrix="bt601"):
+        """Frames whose planes follow each other without a gap, the way a decoder lays a surface out, frame after frame: 'nv12' --
+        height rows of Y, then height / 2 rows of U V, all `pitch` bytes apart (default: width); 'i420' -- Y, then U, then V, the
+        chroma rows pitch / 2 apart; 'yuyv' / 'uyvy' -- one plane, rows `pitch` apart (default: 2 * width).  For any other
+        arrangement (a chroma offset, a gap between frames) fill the fields in directly."""
+        code = _yuv_code(YUV_LAYOUTS, "layout", layout)
+        m = _yuv_code(YUV_MATRICES, "matrix", matrix)
+        if code in (0, 1):
+            pitch = width if pitch is None else pitch
+            if height % 2 or (code == 1 and pitch % 2):
+                raise ValueError("4:2:0 surfaces have an even height, and an even pitch when planar")
+            c_pitch = pitch if code == 0 else pitch // 2
+            c0 = ptr + pitch * height
+            c1 = c0 + c_pitch * (height // 2) if code == 1 else None
+            return cls(code, m, ptr, c0, c1, pitch, c_pitch, pitch * height * 3 // 2)
+        pitch = 2 * width if pitch is None else pitch
+        return cls(code, m, ptr, None, None, pitch, 0, pitch * height)
 
 
 class BoardMarker(C.Structure):  # OcvarBoardMarker: a template and the board-plane (z = 0) coordinates of its corners 0..3
@@ -241,6 +278,8 @@ def hip_lib():
         lib.ocvar_hip_undistort.argtypes = [vp, vp, i, sz, vp, i, sz, i, i, i, i, vp]
         lib.ocvar_hip_undistort_records.argtypes = [vp, vp, vp, i, i, vp, vp]
         lib.ocvar_hip_flow_records.argtypes = [vp, vp, i, sz, vp, i, sz, i, i, i, i, vp, vp, i, vp, vp, vp, vp, vp]
+        lib.ocvar_hip_yuv_to_frames.argtypes = [vp, vp, vp, i, sz, i, i, i, i, vp]
+        lib.ocvar_hip_frames_to_yuv.argtypes = [vp, vp, i, sz, vp, i, i, i, i, vp]
         _hip = lib
     return _hip
 
@@ -649,6 +688,28 @@ class Detector:
         per_frame = self.max_markers if per_frame is None else per_frame
         self._check(self._lib.ocvar_hip_undistort_records(self._ctx, d_markers, d_counts, n_frames, per_frame, d_out, stream),
                     "undistort_records")
+
+    def yuv_to_frames(self, yuv, d_dst, width, height, n_frames, fmt=None, dst_row_stride=None, dst_frame_stride=None, stream=None):
+        """n_frames device frames in NV12, I420, YUYV or UYVY (yuv: a YuvFrames) converted into the device frames at d_dst in format
+        fmt (default: the input format): OpenCV's cvtColor COLOR_YUV2BGR_NV12 and its relatives, limited range, the matrix yuv names.
+        A four-channel destination gets byte 3 = 255, 'gray' the library's grey of the converted colour.  The two sides must not
+        overlap.  Needs no batch, does not wait (stream None: the detector's own stream)."""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        dst_row_stride = dst_row_stride or FORMAT_BPP[code] * width
+        dst_frame_stride = dst_frame_stride or dst_row_stride * height
+        self._check(self._lib.ocvar_hip_yuv_to_frames(self._ctx, C.byref(yuv), d_dst, dst_row_stride, dst_frame_stride, width, height, n_frames,
+                                                      code, stream), "yuv_to_frames")
+
+    def frames_to_yuv(self, d_src, yuv, width, height, n_frames, fmt=None, src_row_stride=None, src_frame_stride=None, stream=None):
+        """n_frames device frames at d_src in format fmt (default: the input format) converted into the NV12, I420, YUYV or UYVY device
+        frames yuv (a YuvFrames) describes: OpenCV's cvtColor COLOR_BGR2YUV_I420 and its relatives, limited range, a chroma sample from
+        the mean colour of its 2 x 2 or 2 x 1 pixels.  The two sides must not overlap.  Needs no batch, does not wait (stream None:
+        the detector's own stream)."""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        src_row_stride = src_row_stride or FORMAT_BPP[code] * width
+        src_frame_stride = src_frame_stride or src_row_stride * height
+        self._check(self._lib.ocvar_hip_frames_to_yuv(self._ctx, d_src, src_row_stride, src_frame_stride, C.byref(yuv), width, height, n_frames,
+                                                      code, stream), "frames_to_yuv")
 
     def flow_records(self, d_prev, d_next, width, height, n_frames, d_markers, d_counts, d_out, per_frame=None, fmt=None,
                      prev_row_stride=None, prev_frame_stride=None, next_row_stride=None, next_frame_stride=None, params=None, pose=False,

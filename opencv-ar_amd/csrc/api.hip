@@ -934,6 +934,73 @@ extern "C" int ocvar_hip_undistort_records(OcvarHip* c, const OcvarMarker* d_mar
     return OCVAR_OK;
 }
 
+// What ocvar_hip_yuv_to_frames and ocvar_hip_frames_to_yuv refuse alike, and the launches: yuv describes one side, pix the other.
+static int yuv_convert(OcvarHip* c, const char* what, const OcvarYuvFrames* yuv, const uint8_t* pix, int row_stride, size_t frame_stride,
+                       int width, int height, int n_frames, int format, bool to_frames, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    const std::string w = std::string(what) + ": ";
+    const auto refuse = [&](const std::string& text) {
+        c->err = w + text;
+        return OCVAR_E_ARG;
+    };
+    if (!yuv || !pix) return refuse("no YUV frames or no frames");
+    if (!yuv_layout_ok(yuv->layout) || !yuv_matrix_ok(yuv->matrix) || patch_bpp(format) == 0) return refuse("an unknown layout, matrix or format");
+    const bool s420 = yuv_is_420(yuv->layout);
+    if (!yuv->y || (s420 && !yuv->c0) || (yuv->layout == OCVAR_YUV_I420 && !yuv->c1)) return refuse("a plane the layout uses is NULL");
+    if (n_frames < 1 || width < 1 || height < 1 || width > c->ws.max_w || height > c->ws.max_h)
+        return refuse("frames of 1 .. the context's size, n_frames >= 1");
+    if ((width & 1) || (s420 && (height & 1))) return refuse("an odd width, or an odd height with NV12 or I420");
+    const int bpp = patch_bpp(format);
+    // the planes: first byte, bytes per row, rows, pitch
+    struct Plane { const uint8_t* p; long long row_bytes, rows, pitch; };
+    Plane planes[3];
+    int n_planes = 0;
+    planes[n_planes++] = Plane{yuv->y, s420 ? (long long)width : 2LL * width, height, yuv->y_pitch};
+    if (yuv->layout == OCVAR_YUV_NV12) planes[n_planes++] = Plane{yuv->c0, width, height / 2, yuv->c_pitch};
+    if (yuv->layout == OCVAR_YUV_I420) {
+        planes[n_planes++] = Plane{yuv->c0, width / 2, height / 2, yuv->c_pitch};
+        planes[n_planes++] = Plane{yuv->c1, width / 2, height / 2, yuv->c_pitch};
+    }
+    for (int i = 0; i < n_planes; i++)
+        if (planes[i].pitch < planes[i].row_bytes) return refuse("a pitch below the plane's bytes per row");
+    if ((long long)row_stride < (long long)bpp * width) return refuse("a row stride below the format's bytes per pixel times width");
+    const auto span = [](long long rows, long long stride, long long row_bytes) { return (rows - 1) * stride + row_bytes; };
+    const long long pix_span = span(height, row_stride, (long long)bpp * width);
+    bool spans_ok = pix_span <= 2147483647LL;
+    for (int i = 0; i < n_planes; i++) spans_ok = spans_ok && span(planes[i].rows, planes[i].pitch, planes[i].row_bytes) <= 2147483647LL;
+    if (!spans_ok) return refuse("the rows of a plane or of a frame span more than 2147483647 bytes");
+    const unsigned long long p0 = (unsigned long long)(uintptr_t)pix;
+    const unsigned long long p1 = p0 + (unsigned long long)(n_frames - 1) * frame_stride + (unsigned long long)pix_span;
+    for (int i = 0; i < n_planes; i++) {
+        const unsigned long long q0 = (unsigned long long)(uintptr_t)planes[i].p;
+        const unsigned long long q1 = q0 + (unsigned long long)(n_frames - 1) * yuv->frame_stride +
+                                      (unsigned long long)span(planes[i].rows, planes[i].pitch, planes[i].row_bytes);
+        if (p0 < q1 && q0 < p1) return refuse("the byte ranges of a YUV plane and of the frames intersect (no conversion in place)");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    for (int f0 = 0; f0 < n_frames; f0 += YUV_CHUNK_FRAMES) {
+        const size_t yo = (size_t)f0 * yuv->frame_stride;
+        const YuvArgs a{yuv->y + yo, yuv->c0 ? yuv->c0 + yo : nullptr, yuv->c1 ? yuv->c1 + yo : nullptr, (long long)yuv->y_pitch,
+                        (long long)yuv->c_pitch, (long long)yuv->frame_stride, const_cast<uint8_t*>(pix) + (size_t)f0 * frame_stride,
+                        (long long)row_stride, (long long)frame_stride, width, height, yuv->layout, format, yuv_coef(yuv->matrix)};
+        launch_yuv(a, std::min(YUV_CHUNK_FRAMES, n_frames - f0), to_frames, s);
+        TRACE_LAUNCH(what, s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_yuv_to_frames(OcvarHip* c, const OcvarYuvFrames* src, uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride,
+                                       int width, int height, int n_frames, int format, void* stream) {
+    return yuv_convert(c, "yuv_to_frames", src, d_dst, dst_row_stride, dst_frame_stride, width, height, n_frames, format, true, stream);
+}
+
+extern "C" int ocvar_hip_frames_to_yuv(OcvarHip* c, const uint8_t* d_src, int src_row_stride, size_t src_frame_stride, const OcvarYuvFrames* dst,
+                                       int width, int height, int n_frames, int format, void* stream) {
+    return yuv_convert(c, "frames_to_yuv", dst, d_src, src_row_stride, src_frame_stride, width, height, n_frames, format, false, stream);
+}
+
 // a parameter of ocvar_hip_flow_records that must be a finite number >= 0
 static bool flow_number_ok(float v) { return v >= 0.0f && v <= 3.0e38f; }
 

@@ -9,6 +9,7 @@
 #include "overlay_core.h"
 #include "patch_core.h"
 #include "undistort_core.h"
+#include "yuv_core.h"
 #include "flow_core.h"
 #include "croplist_core.h"
 #include "ocvar_hip.h"
@@ -223,6 +224,11 @@ struct UndistortRecArgs {
 };
 // n_frames (at most 65535: the grid's y) frames
 void launch_undistort_records(const UndistortRecArgs& a, int n_frames, hipStream_t stream);
+
+// One launch of yuv_to_frames_kernel (to_frames) or frames_to_yuv_kernel (yuv.hip) on the n_frames (at most YUV_CHUNK_FRAMES: the
+// grid's z) frames of a (yuv_core.h: YuvArgs), whose two sides do not overlap.
+constexpr int YUV_CHUNK_FRAMES = 65535;
+void launch_yuv(const YuvArgs& a, int n_frames, bool to_frames, hipStream_t stream);
 
 // The pyramids of n_frames frames in `format` (flow.hip: flow_grey_kernel, then flow_down_kernel level by level): frame f's
 // levels 0 .. g.L go to pyr + f * slot_bytes, laid out as g says.
