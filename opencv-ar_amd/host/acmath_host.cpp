@@ -157,11 +157,15 @@ void acArray2DRotateub(unsigned char* arr, int w, int h, int rot) {
     unsigned char t[4096];
     if (w * h > (int)sizeof t) return;
     std::memcpy(t, arr, (size_t)w * h);
+    // The reference's index formulas are those of a square grid: with w != h some fall outside its copy of the grid, where
+    // what it reads is not defined.  Such a cell is 0 here; indices inside the copy are read as the reference reads them.
+    const int n = w * h;
+    auto at = [&](int k) -> unsigned char { return k >= 0 && k < n ? t[k] : 0; };
     for (int i = 0; i < h; i++)
         for (int j = 0; j < w; j++) {
-            if (rot == 1) arr[i * w + j] = t[(h - 1 - j) * w + i];
-            else if (rot == 2) arr[i * w + j] = t[(h - 1 - i) * w + (h - 1 - j)];
-            else if (rot == 3) arr[i * w + j] = t[j * w + (h - 1 - i)];
+            if (rot == 1) arr[i * w + j] = at((h - 1 - j) * w + i);
+            else if (rot == 2) arr[i * w + j] = at((h - 1 - i) * w + (h - 1 - j));
+            else if (rot == 3) arr[i * w + j] = at(j * w + (h - 1 - i));
         }
 }
 void acArray2DPrintub(unsigned char* arr, int w, int h) {

@@ -26,12 +26,17 @@ extern "C" void orc_acBitToArray2D(long long bit, unsigned char* arr, int w, int
 }
 
 extern "C" void orc_acArray2DRotateub(unsigned char* arr, int w, int h, int rot) {
+    // The reference's index formulas are those of a square grid.  With w != h some of them fall outside its malloc'ed copy,
+    // where what it reads is not defined; such a cell is 0 here (and in host/acmath_host.cpp).  Indices that stay inside the
+    // copy are read as the reference reads them.
     std::vector<unsigned char> t(arr, arr + w * h);
+    const int n = w * h;
+    auto at = [&](int k) -> unsigned char { return k >= 0 && k < n ? t[k] : 0; };
     for (int i = 0; i < h; i++)
         for (int j = 0; j < w; j++) {
-            if (rot == 1) arr[i * w + j] = t[(h - 1 - j) * w + i];
-            else if (rot == 2) arr[i * w + j] = t[(h - 1 - i) * w + (h - 1 - j)];
-            else if (rot == 3) arr[i * w + j] = t[j * w + (h - 1 - i)];
+            if (rot == 1) arr[i * w + j] = at((h - 1 - j) * w + i);
+            else if (rot == 2) arr[i * w + j] = at((h - 1 - i) * w + (h - 1 - j));
+            else if (rot == 3) arr[i * w + j] = at(j * w + (h - 1 - i));
         }
 }
 
