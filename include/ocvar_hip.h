@@ -391,6 +391,49 @@ int ocvar_hip_yuv_to_frames(OcvarHip* ctx, const OcvarYuvFrames* src, uint8_t* d
 int ocvar_hip_frames_to_yuv(OcvarHip* ctx, const uint8_t* d_src, int src_row_stride, size_t src_frame_stride, const OcvarYuvFrames* dst,
                             int width, int height, int n_frames, int format, void* stream);
 
+/* Resizing: device-resident frames brought to another size, and the marker records found at one size carried to the other --
+ * a 3840 x 2160 stream is shrunk to 1920 x 1080 for a context of that size (with the camera of cvarCameraScale), and the records
+ * it finds are scaled up and drawn on the large frames; previews and thumbnails of rendered frames stay on the device.  The
+ * definition, bit for bit, is opencv-ar_amd/csrc/resize_core.h.  ocvar_hip_resize stands for OpenCV's resize(src, dst, dsize, 0,
+ * 0, interpolation) on 8-bit images, every byte of a pixel treated alike (byte 3 of a four-channel pixel included):
+ *   OCVAR_RESIZE_NEAREST  INTER_NEAREST: source index min(floor(x * scale), s - 1) per axis, scale = 1.0 / ((double)d / s).
+ *   OCVAR_RESIZE_LINEAR   INTER_LINEAR of 8-bit images: pixel centres aligned, two 11-bit weights per axis, 32-bit integers.  A
+ *                  call whose two scales are exactly 2 gives the AREA result, as in OpenCV.
+ *   OCVAR_RESIZE_AREA     INTER_AREA, shrinking only (dst_width <= src_width, dst_height <= src_height, by at most
+ *                  OCVAR_MAX_RESIZE_RATIO per axis): the rounded mean of the block when both scales are whole numbers -- the
+ *                  2 x 2 block is (sum + 2) >> 2 --, else the fractional coverage table, accumulated in float in a fixed order.
+ *   d_src / d_dst  n_frames frames of src_width x src_height and of dst_width x dst_height pixels in `format` (any OCVAR_FMT_*; it
+ *                  need not be the input format), rows *_row_stride and frames *_frame_stride bytes apart, at any address; their
+ *                  byte ranges must not intersect.  A source rectangle (crop and resize) is d_src moved to the rectangle's first
+ *                  pixel with the rectangle's size and the full frame's strides.
+ * Sides are 1 .. 32767 on both ends and are NOT bound by the context's max_width x max_height: there is no workspace, and the
+ * point is to feed a small context from large frames.  When every address, row stride and frame stride is a multiple of 4 the
+ * kernels move whole dwords; otherwise, and in the last pixels of a row, bytes -- with the same result.  No byte outside the
+ * destination's pixels is written.
+ * ocvar_hip_scale_records carries the four corners of every record from a src_width x src_height frame to a dst_width x
+ * dst_height one by the pixel-centre rule of the linear map, (p + 0.5) * ((double)d / s) - 0.5 in double per axis, rounded to
+ * float32 (a NaN is stored as 0x7FC00000); on an axis whose extents are equal the coordinate is copied.  Every other field is
+ * copied as it is; with OCVAR_SCALE_POSE glMatrix is solved from the new square with the context's camera as it is at the call
+ * (by value) -- the camera of the destination size -- and the record's aspectRatio.
+ *   d_markers / d_out  [n_frames][records_per_frame] records (1 <= records_per_frame <= M = ocvar_hip_max_markers(ctx)); slot k
+ *                  of frame f is written when k < min(d_counts[f], records_per_frame), no other slot is touched; d_out may be
+ *                  d_markers
+ * Parity with a real OpenCV build is unpinned (see ocvar_hip_undistort): the rules are written down from memory of OpenCV; the
+ * tests pin the host build of resize_core.h and a numpy restatement of the rules.
+ * Both need no batch and no workspace and can run at any time: a context that never calls them allocates and launches nothing.
+ * Any n_frames >= 1 (more than 65535 go in several launches, in stream order); stream NULL: the context's own stream.  Neither
+ * waits.  OCVAR_E_ARG, before any device call and with a text in ocvar_hip_last_error, for NULL pointers, an unknown format,
+ * interpolation or flag bit, a side outside 1 .. 32767, a row stride below the format's bytes per pixel times width, rows that
+ * span more than 2^31 - 1 bytes, n_frames < 1, intersecting source and destination byte ranges, AREA with a destination side
+ * above the source's or a source side above OCVAR_MAX_RESIZE_RATIO times the destination's, records_per_frame outside 1 .. M,
+ * OCVAR_SCALE_POSE with no camera set. */
+enum { OCVAR_RESIZE_NEAREST = 0, OCVAR_RESIZE_LINEAR = 1, OCVAR_RESIZE_AREA = 2, OCVAR_MAX_RESIZE_RATIO = 16, OCVAR_SCALE_POSE = 1 };
+int ocvar_hip_resize(OcvarHip* ctx, const uint8_t* d_src, int src_width, int src_height, int src_row_stride, size_t src_frame_stride,
+                     uint8_t* d_dst, int dst_width, int dst_height, int dst_row_stride, size_t dst_frame_stride,
+                     int n_frames, int format, int interpolation, void* stream);
+int ocvar_hip_scale_records(OcvarHip* ctx, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
+                            int src_width, int src_height, int dst_width, int dst_height, int flags, OcvarMarker* d_out, void* stream);
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart

@@ -34,6 +34,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_undistort", "ocvar_hip_undistort_records",
     "ocvar_hip_flow_records",
     "ocvar_hip_yuv_to_frames", "ocvar_hip_frames_to_yuv",
+    "ocvar_hip_resize", "ocvar_hip_scale_records",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -103,6 +104,8 @@ def flow_params(half_win=10, levels=3, max_iter=30, eps=0.03, min_eig=1e-3, max_
 
 YUV_LAYOUTS = {"nv12": 0, "i420": 1, "yuyv": 2, "uyvy": 3}   # include/ocvar_hip.h: OCVAR_YUV_NV12 ..
 YUV_MATRICES = {"bt601": 0, "bt709": 1}                      # include/ocvar_hip.h: OCVAR_YUV_BT601, OCVAR_YUV_BT709
+RESIZE_INTERPS = {"nearest": 0, "linear": 1, "area": 2}     # include/ocvar_hip.h: OCVAR_RESIZE_NEAREST ..
+SCALE_POSE = 1                                              # include/ocvar_hip.h: OCVAR_SCALE_POSE
 
 
 def _yuv_code(table, what, v):
@@ -280,6 +283,8 @@ def hip_lib():
         lib.ocvar_hip_flow_records.argtypes = [vp, vp, i, sz, vp, i, sz, i, i, i, i, vp, vp, i, vp, vp, vp, vp, vp]
         lib.ocvar_hip_yuv_to_frames.argtypes = [vp, vp, vp, i, sz, i, i, i, i, vp]
         lib.ocvar_hip_frames_to_yuv.argtypes = [vp, vp, i, sz, vp, i, i, i, i, vp]
+        lib.ocvar_hip_resize.argtypes = [vp, vp, i, i, i, sz, vp, i, i, i, sz, i, i, i, vp]
+        lib.ocvar_hip_scale_records.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp, vp]
         _hip = lib
     return _hip
 
@@ -710,6 +715,35 @@ class Detector:
         src_frame_stride = src_frame_stride or src_row_stride * height
         self._check(self._lib.ocvar_hip_frames_to_yuv(self._ctx, d_src, src_row_stride, src_frame_stride, C.byref(yuv), width, height, n_frames,
                                                       code, stream), "frames_to_yuv")
+
+    def resize(self, d_src, src_width, src_height, d_dst, dst_width, dst_height, n_frames, interp="area", fmt=None, src_row_stride=None,
+               src_frame_stride=None, dst_row_stride=None, dst_frame_stride=None, stream=None):
+        """n_frames device frames of src_width x src_height pixels at d_src in format fmt (default: the input format) resized into
+        the device frames of dst_width x dst_height at d_dst: OpenCV's resize on 8-bit images with interp 'nearest', 'linear' or
+        'area' ('area' shrinks only, by at most 16 per axis; a whole-number ratio is the rounded mean of the block).  The sizes are
+        not bound by the detector's: large frames feed a small detector.  A source rectangle is d_src moved to its first pixel with
+        the full frame's strides.  Source and destination must not overlap.  Needs no batch, does not wait (stream None: the
+        detector's own stream)."""
+        if not (isinstance(interp, str) and interp.lower() in RESIZE_INTERPS):
+            raise ValueError(f"unknown interpolation {interp!r}: one of {sorted(RESIZE_INTERPS)}")
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        src_row_stride = src_row_stride or FORMAT_BPP[code] * src_width
+        src_frame_stride = src_frame_stride or src_row_stride * src_height
+        dst_row_stride = dst_row_stride or FORMAT_BPP[code] * dst_width
+        dst_frame_stride = dst_frame_stride or dst_row_stride * dst_height
+        self._check(self._lib.ocvar_hip_resize(self._ctx, d_src, src_width, src_height, src_row_stride, src_frame_stride, d_dst, dst_width,
+                                               dst_height, dst_row_stride, dst_frame_stride, n_frames, code, RESIZE_INTERPS[interp.lower()],
+                                               stream), "resize")
+
+    def scale_records(self, d_markers, d_counts, n_frames, d_out, src_size, dst_size, per_frame=None, pose=False, stream=None):
+        """the squares of the device records [n_frames, per_frame] (default per_frame: max_markers) under counts [n_frames], found on
+        frames of src_size = (width, height), carried to frames of dst_size by the pixel-centre rule of resize, every other field
+        copied, into the device records at d_out (which may be d_markers); slots at or beyond a frame's count are not written.
+        pose: glMatrix is solved again from the new square with the camera set at the call, which must be that of dst_size.  Needs no
+        batch, does not wait (stream None: the detector's own stream)."""
+        per_frame = self.max_markers if per_frame is None else per_frame
+        self._check(self._lib.ocvar_hip_scale_records(self._ctx, d_markers, d_counts, n_frames, per_frame, src_size[0], src_size[1],
+                                                      dst_size[0], dst_size[1], SCALE_POSE if pose else 0, d_out, stream), "scale_records")
 
     def flow_records(self, d_prev, d_next, width, height, n_frames, d_markers, d_counts, d_out, per_frame=None, fmt=None,
                      prev_row_stride=None, prev_frame_stride=None, next_row_stride=None, next_frame_stride=None, params=None, pose=False,

@@ -1001,6 +1001,82 @@ extern "C" int ocvar_hip_frames_to_yuv(OcvarHip* c, const uint8_t* d_src, int sr
     return yuv_convert(c, "frames_to_yuv", dst, d_src, src_row_stride, src_frame_stride, width, height, n_frames, format, false, stream);
 }
 
+extern "C" int ocvar_hip_resize(OcvarHip* c, const uint8_t* d_src, int src_width, int src_height, int src_row_stride, size_t src_frame_stride,
+                                uint8_t* d_dst, int dst_width, int dst_height, int dst_row_stride, size_t dst_frame_stride, int n_frames,
+                                int format, int interpolation, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    const auto refuse = [&](const char* text) {
+        c->err = std::string("resize: ") + text;
+        return OCVAR_E_ARG;
+    };
+    if (!d_src || !d_dst) return refuse("no source or no destination frames");
+    const int bpp = patch_bpp(format);
+    if (bpp == 0 || !resize_interp_ok(interpolation)) return refuse("an unknown format or interpolation");
+    const auto side_ok = [](int v) { return v >= 1 && v <= RESIZE_MAX_SIDE; };
+    if (!side_ok(src_width) || !side_ok(src_height) || !side_ok(dst_width) || !side_ok(dst_height)) return refuse("sides of 1 .. 32767 pixels");
+    if (n_frames < 1) return refuse("n_frames >= 1");
+    if ((long long)src_row_stride < (long long)bpp * src_width || (long long)dst_row_stride < (long long)bpp * dst_width)
+        return refuse("a row stride below the format's bytes per pixel times width");
+    const auto span = [&](int width, int height, int row_stride) { return (long long)(height - 1) * row_stride + (long long)bpp * width; };
+    if (span(src_width, src_height, src_row_stride) > 2147483647LL || span(dst_width, dst_height, dst_row_stride) > 2147483647LL)
+        return refuse("the rows of a frame span more than 2147483647 bytes");
+    const unsigned long long s0 = (unsigned long long)(uintptr_t)d_src, d0 = (unsigned long long)(uintptr_t)d_dst;
+    const unsigned long long s1 = s0 + frames_extent(src_width, src_height, bpp, src_row_stride, src_frame_stride, n_frames);
+    const unsigned long long d1 = d0 + frames_extent(dst_width, dst_height, bpp, dst_row_stride, dst_frame_stride, n_frames);
+    if (s0 < d1 && d0 < s1) return refuse("the byte ranges of source and destination frames intersect (no resizing in place)");
+    if (interpolation == OCVAR_RESIZE_AREA && !resize_area_ok(src_width, src_height, dst_width, dst_height))
+        return refuse("AREA shrinks only, by at most OCVAR_MAX_RESIZE_RATIO per axis");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    const ResizePlan plan = resize_plan(src_width, src_height, dst_width, dst_height, interpolation);
+    for (int f0 = 0; f0 < n_frames; f0 += RESIZE_CHUNK_FRAMES) {
+        const ResizeArgs a{d_src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, src_width, src_height, dst_width, dst_height,
+                           (long long)src_row_stride, (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride, plan};
+        launch_resize(a, std::min(RESIZE_CHUNK_FRAMES, n_frames - f0), format, s);
+        TRACE_LAUNCH("resize", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_scale_records(OcvarHip* c, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
+                                       int src_width, int src_height, int dst_width, int dst_height, int flags, OcvarMarker* d_out, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    if (!d_markers || !d_counts || !d_out) {
+        c->err = "scale_records: no records, no counts or no output";
+        return OCVAR_E_ARG;
+    }
+    if (n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm) {
+        c->err = "scale_records: n_frames >= 1, 1 .. M records per frame";
+        return OCVAR_E_ARG;
+    }
+    const auto side_ok = [](int v) { return v >= 1 && v <= RESIZE_MAX_SIDE; };
+    if (!side_ok(src_width) || !side_ok(src_height) || !side_ok(dst_width) || !side_ok(dst_height)) {
+        c->err = "scale_records: sides of 1 .. 32767 pixels";
+        return OCVAR_E_ARG;
+    }
+    if (flags & ~RESIZE_FLAGS) {
+        c->err = "scale_records: unknown flag bits";
+        return OCVAR_E_ARG;
+    }
+    if ((flags & OCVAR_SCALE_POSE) && !c->have_camera) {
+        c->err = "scale_records: OCVAR_SCALE_POSE without a camera";
+        return OCVAR_E_ARG;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    const int chunk = 65535;
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const ScaleRecArgs a{reinterpret_cast<const MarkerRec*>(d_markers) + (size_t)f0 * records_per_frame,
+                       reinterpret_cast<MarkerRec*>(d_out) + (size_t)f0 * records_per_frame, d_counts + f0, records_per_frame,
+                       src_width, src_height, dst_width, dst_height, flags, c->h_camera};
+        launch_scale_records(a, std::min(chunk, n_frames - f0), s);
+        TRACE_LAUNCH("scale_records", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
 // a parameter of ocvar_hip_flow_records that must be a finite number >= 0
 static bool flow_number_ok(float v) { return v >= 0.0f && v <= 3.0e38f; }
 

@@ -10,6 +10,7 @@
 #include "patch_core.h"
 #include "undistort_core.h"
 #include "yuv_core.h"
+#include "resize_core.h"
 #include "flow_core.h"
 #include "croplist_core.h"
 #include "ocvar_hip.h"
@@ -229,6 +230,24 @@ void launch_undistort_records(const UndistortRecArgs& a, int n_frames, hipStream
 // grid's z) frames of a (yuv_core.h: YuvArgs), whose two sides do not overlap.
 constexpr int YUV_CHUNK_FRAMES = 65535;
 void launch_yuv(const YuvArgs& a, int n_frames, bool to_frames, hipStream_t stream);
+
+// One launch of a resize kernel (resize.hip) on the n_frames (at most RESIZE_CHUNK_FRAMES: the grid's z) frames in `format` of a
+// (resize_core.h: ResizeArgs), whose two sides do not overlap.
+constexpr int RESIZE_CHUNK_FRAMES = 65535;
+void launch_resize(const ResizeArgs& a, int n_frames, int format, hipStream_t stream);
+
+// One launch of scale_records_kernel: of frame f the records in[f * slots + k], k < min(counts[f], slots), to the same slots of out
+// (which may be in), their squares carried from a sw x sh frame to a dw x dh one; flags OCVAR_SCALE_*, cam by value: the
+// context's at the call.
+struct ScaleRecArgs {
+    const MarkerRec* in;
+    MarkerRec* out;
+    const int* counts;
+    int slots, sw, sh, dw, dh, flags;
+    CameraRec cam;
+};
+// n_frames (at most 65535: the grid's y) frames
+void launch_scale_records(const ScaleRecArgs& a, int n_frames, hipStream_t stream);
 
 // The pyramids of n_frames frames in `format` (flow.hip: flow_grey_kernel, then flow_down_kernel level by level): frame f's
 // levels 0 .. g.L go to pyr + f * slot_bytes, laid out as g says.
