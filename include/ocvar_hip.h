@@ -434,6 +434,57 @@ int ocvar_hip_resize(OcvarHip* ctx, const uint8_t* d_src, int src_width, int src
 int ocvar_hip_scale_records(OcvarHip* ctx, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
                             int src_width, int src_height, int dst_width, int dst_height, int flags, OcvarMarker* d_out, void* stream);
 
+/* Orientation: device-resident frames turned and mirrored, the marker records found on them carried to the other orientation, and
+ * the camera that belongs to the turned frames -- a sideways camera, a clip with a 90 degree display matrix or a mirrored front
+ * camera is turned upright before it is detected (the registration is not invariant to the frame's orientation), and the records
+ * go back to the frames as they were delivered, without a trip through host memory.  The definition, bit for bit, is
+ * opencv-ar_amd/csrc/orient_core.h.  ocvar_hip_orient is a pure permutation of pixels, so OpenCV's rotate, flip and transpose
+ * cannot differ from it.  A source pixel or coordinate (x, y) of a src_width x src_height = W x H frame goes to (x', y'):
+ *   OCVAR_ORIENT_IDENTITY    (x, y)                  W x H   a copy
+ *   OCVAR_ORIENT_ROT90_CW    (H - 1 - y, x)          H x W   rotate(ROTATE_90_CLOCKWISE)
+ *   OCVAR_ORIENT_ROT180      (W - 1 - x, H - 1 - y)  W x H   rotate(ROTATE_180)
+ *   OCVAR_ORIENT_ROT270_CW   (y, W - 1 - x)          H x W   rotate(ROTATE_90_COUNTERCLOCKWISE)
+ *   OCVAR_ORIENT_FLIP_H      (W - 1 - x, y)          W x H   flip(1)
+ *   OCVAR_ORIENT_FLIP_V      (x, H - 1 - y)          W x H   flip(0)
+ *   OCVAR_ORIENT_TRANSPOSE   (y, x)                  H x W   transpose
+ *   OCVAR_ORIENT_TRANSVERSE  (H - 1 - y, W - 1 - x)  H x W   transpose of flip(-1)
+ *   d_src / d_dst  n_frames frames of src_width x src_height pixels and of the destination size the table names, in `format` (any
+ *                  OCVAR_FMT_*; it need not be the input format), rows *_row_stride and frames *_frame_stride bytes apart, at any
+ *                  address; their byte ranges must not intersect (no turning in place, IDENTITY included).  A source rectangle
+ *                  is d_src moved to the rectangle's first pixel with the rectangle's size and the full frame's strides.
+ * Sides are 1 .. 32767 and are NOT bound by the context's max_width x max_height: there is no workspace.  When every address, row
+ * stride and frame stride is a multiple of 4 the kernels move whole dwords; otherwise, and in the last pixels of a row or tile,
+ * bytes -- with the same result.  No byte outside the destination's pixels is written; the source is never written.
+ * ocvar_hip_orient_records carries the four corners of every record found on a src_width x src_height frame through the table,
+ * in double per coordinate, rounded to float32 (a NaN is stored as 0x7FC00000); a coordinate the table passes on unchanged, or
+ * only swaps between the axes, is copied bit for bit.  Corner k stays in slot k, so the mirroring orientations (FLIP_H, FLIP_V,
+ * TRANSPOSE, TRANSVERSE) reverse the winding of the square.  Every other field is copied as it is; with OCVAR_ORIENT_POSE glMatrix
+ * is solved from the new square with the context's camera as it is at the call (by value) -- which must be the camera of the
+ * destination orientation: ocvar_hip_orient_camera -- and the record's aspectRatio.  A reflected view has no rigid pose: the flag
+ * is refused for the mirroring orientations.
+ *   d_markers / d_out  [n_frames][records_per_frame] records (1 <= records_per_frame <= M = ocvar_hip_max_markers(ctx)); slot k
+ *                  of frame f is written when k < min(d_counts[f], records_per_frame), no other slot is touched; d_out may be
+ *                  d_markers
+ * ocvar_hip_orient_camera (host only: no context, no device call) writes the camera of the turned frames: width and height the
+ * destination's, fx and fy swapped when the orientation transposes, the principal point through the table (cx' = H - 1 - cy for
+ * ROT90_CW), glProjection as cvarCameraScale computes it, k1 k2 k3 kept and (p1, p2) turned with the image plane ((p2, -p1) for
+ * ROT90_CW; the full list is in orient_core.h).  out may be in.  OCVAR_E_ARG, with nothing written, for NULL pointers, an unknown
+ * orientation, and under any orientation but IDENTITY for a camera matrix that is not fx 0 cx / 0 fy cy / 0 0 1.
+ * The two device calls need no batch and no workspace and can run at any time: a context that never calls them allocates and
+ * launches nothing.  Any n_frames >= 1 (more than 65535 go in several launches, in stream order); stream NULL: the context's own
+ * stream.  Neither waits.  OCVAR_E_ARG, before any device call and with a text in ocvar_hip_last_error, for NULL pointers, an
+ * unknown format, orientation or flag bit, a side outside 1 .. 32767, a row stride below the format's bytes per pixel times the
+ * width of that side, rows that span more than 2^31 - 1 bytes, n_frames < 1, intersecting source and destination byte ranges,
+ * records_per_frame outside 1 .. M, OCVAR_ORIENT_POSE with a mirroring orientation or with no camera set. */
+enum { OCVAR_ORIENT_IDENTITY = 0, OCVAR_ORIENT_ROT90_CW = 1, OCVAR_ORIENT_ROT180 = 2, OCVAR_ORIENT_ROT270_CW = 3,
+       OCVAR_ORIENT_FLIP_H = 4, OCVAR_ORIENT_FLIP_V = 5, OCVAR_ORIENT_TRANSPOSE = 6, OCVAR_ORIENT_TRANSVERSE = 7,
+       OCVAR_ORIENT_POSE = 1 /* flag of ocvar_hip_orient_records */ };
+int ocvar_hip_orient(OcvarHip* ctx, const uint8_t* d_src, int src_width, int src_height, int src_row_stride, size_t src_frame_stride,
+                     uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride, int n_frames, int format, int orientation, void* stream);
+int ocvar_hip_orient_records(OcvarHip* ctx, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
+                             int src_width, int src_height, int orientation, int flags, OcvarMarker* d_out, void* stream);
+int ocvar_hip_orient_camera(const OcvarCamera* in, int orientation, OcvarCamera* out);   /* host only, no context, no device call */
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart

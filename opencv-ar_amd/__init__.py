@@ -35,6 +35,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_flow_records",
     "ocvar_hip_yuv_to_frames", "ocvar_hip_frames_to_yuv",
     "ocvar_hip_resize", "ocvar_hip_scale_records",
+    "ocvar_hip_orient", "ocvar_hip_orient_records", "ocvar_hip_orient_camera",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -106,6 +107,48 @@ YUV_LAYOUTS = {"nv12": 0, "i420": 1, "yuyv": 2, "uyvy": 3}   # include/ocvar_hip
 YUV_MATRICES = {"bt601": 0, "bt709": 1}                      # include/ocvar_hip.h: OCVAR_YUV_BT601, OCVAR_YUV_BT709
 RESIZE_INTERPS = {"nearest": 0, "linear": 1, "area": 2}     # include/ocvar_hip.h: OCVAR_RESIZE_NEAREST ..
 SCALE_POSE = 1                                              # include/ocvar_hip.h: OCVAR_SCALE_POSE
+# include/ocvar_hip.h: OCVAR_ORIENT_IDENTITY ..; a pixel (x, y) of a W x H frame goes to (x, y), (H-1-y, x), (W-1-x, H-1-y), (y, W-1-x),
+# (W-1-x, y), (x, H-1-y), (y, x), (H-1-y, W-1-x)
+ORIENTATIONS = {"identity": 0, "rot90": 1, "rot180": 2, "rot270": 3, "flip_h": 4, "flip_v": 5, "transpose": 6, "transverse": 7}
+ORIENT_POSE = 1                                             # include/ocvar_hip.h: OCVAR_ORIENT_POSE
+
+
+def orientation_code(o):
+    """'identity' | 'rot90' | 'rot180' | 'rot270' (clockwise) | 'flip_h' | 'flip_v' | 'transpose' | 'transverse' (or the
+    OCVAR_ORIENT_* value) -> the OCVAR_ORIENT_* value"""
+    if isinstance(o, str) and o.lower() in ORIENTATIONS:
+        return ORIENTATIONS[o.lower()]
+    if isinstance(o, (int, np.integer)) and not isinstance(o, bool) and int(o) in ORIENTATIONS.values():
+        return int(o)
+    raise ValueError(f"unknown orientation {o!r}: one of {list(ORIENTATIONS)}")
+
+
+def orientation_inverse(o):
+    """the orientation that undoes o: 'rot90' and 'rot270' undo each other, every other one undoes itself -> OCVAR_ORIENT_* value"""
+    return {1: 3, 3: 1}.get(orientation_code(o), orientation_code(o))
+
+
+def oriented_size(size, o):
+    """(width, height) of the frames orientation o makes from frames of size = (width, height)"""
+    return (size[1], size[0]) if orientation_code(o) in (1, 3, 6, 7) else (size[0], size[1])
+
+
+def orientation_from_rotation(degrees):
+    """the orientation that turns a frame by `degrees` clockwise (what a decoder reports as the rotation to apply for display): a
+    multiple of 90, negative or beyond 360 included; ValueError otherwise"""
+    if isinstance(degrees, bool) or not isinstance(degrees, (int, float, np.integer, np.floating)) or degrees != degrees or float(degrees) % 90 != 0:
+        raise ValueError(f"a rotation must be a multiple of 90 degrees, got {degrees!r}")
+    return int(float(degrees) // 90) % 4
+
+
+def orientation_from_exif(tag):
+    """the orientation that makes a picture stored under EXIF Orientation `tag` upright:
+    1 identity, 2 flip_h, 3 rot180, 4 flip_v, 5 transpose, 6 rot90, 7 transverse, 8 rot270 (tag 6: row 0 of the stored picture is
+    the visual right-hand side, so it is turned 90 degrees clockwise; tag 8: row 0 is the left-hand side); ValueError otherwise"""
+    table = {1: 0, 2: 4, 3: 2, 4: 5, 5: 6, 6: 1, 7: 7, 8: 3}
+    if isinstance(tag, bool) or not isinstance(tag, (int, np.integer)) or int(tag) not in table:
+        raise ValueError(f"an EXIF orientation tag is 1 .. 8, got {tag!r}")
+    return table[int(tag)]
 
 
 def _yuv_code(table, what, v):
@@ -285,6 +328,9 @@ def hip_lib():
         lib.ocvar_hip_frames_to_yuv.argtypes = [vp, vp, i, sz, vp, i, i, i, i, vp]
         lib.ocvar_hip_resize.argtypes = [vp, vp, i, i, i, sz, vp, i, i, i, sz, i, i, i, vp]
         lib.ocvar_hip_scale_records.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp, vp]
+        lib.ocvar_hip_orient.argtypes = [vp, vp, i, i, i, sz, vp, i, sz, i, i, i, vp]
+        lib.ocvar_hip_orient_records.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp, vp]
+        lib.ocvar_hip_orient_camera.argtypes = [vp, i, vp]
         _hip = lib
     return _hip
 
@@ -308,6 +354,17 @@ def host_lib():
 
 
 TEMPLATE_DIR = os.path.join(os.path.dirname(_HERE), "assets", "templates")
+
+
+def orient_camera(camera, o):
+    """the Camera of the frames orientation o makes from the frames of `camera` (a new Camera): width and height of the turned
+    frames, fx and fy swapped when o transposes, the principal point carried like a pixel, the tangential distortion pair turned
+    with the image plane, glProjection computed as cvarCameraScale does.  ValueError for a camera matrix with skew (or one that is
+    not fx 0 cx / 0 fy cy / 0 0 1) under any orientation but 'identity'."""
+    out = Camera()
+    if hip_lib().ocvar_hip_orient_camera(C.byref(camera), orientation_code(o), C.byref(out)) != 0:
+        raise ValueError("orient_camera: the camera matrix must be fx 0 cx / 0 fy cy / 0 0 1")
+    return out
 
 
 def load_templates(paths, scale=0.01):
@@ -744,6 +801,35 @@ class Detector:
         per_frame = self.max_markers if per_frame is None else per_frame
         self._check(self._lib.ocvar_hip_scale_records(self._ctx, d_markers, d_counts, n_frames, per_frame, src_size[0], src_size[1],
                                                       dst_size[0], dst_size[1], SCALE_POSE if pose else 0, d_out, stream), "scale_records")
+
+    def orient(self, d_src, src_width, src_height, d_dst, n_frames, orientation, fmt=None, src_row_stride=None, src_frame_stride=None,
+               dst_row_stride=None, dst_frame_stride=None, stream=None):
+        """n_frames device frames of src_width x src_height pixels at d_src in format fmt (default: the input format) turned or
+        mirrored into the device frames at d_dst, whose size is oriented_size((src_width, src_height), orientation): OpenCV's rotate,
+        flip and transpose, a pure permutation of pixels.  orientation: a name of ORIENTATIONS ('rot90' is clockwise) or its code.
+        The sizes are not bound by the detector's.  A source rectangle is d_src moved to its first pixel with the full frame's
+        strides.  Source and destination must not overlap, 'identity' included.  Needs no batch, does not wait (stream None: the
+        detector's own stream)."""
+        o = orientation_code(orientation)
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        dst_width, dst_height = oriented_size((src_width, src_height), o)
+        src_row_stride = src_row_stride or FORMAT_BPP[code] * src_width
+        src_frame_stride = src_frame_stride or src_row_stride * src_height
+        dst_row_stride = dst_row_stride or FORMAT_BPP[code] * dst_width
+        dst_frame_stride = dst_frame_stride or dst_row_stride * dst_height
+        self._check(self._lib.ocvar_hip_orient(self._ctx, d_src, src_width, src_height, src_row_stride, src_frame_stride, d_dst, dst_row_stride,
+                                               dst_frame_stride, n_frames, code, o, stream), "orient")
+
+    def orient_records(self, d_markers, d_counts, n_frames, d_out, src_size, orientation, per_frame=None, pose=False, stream=None):
+        """the squares of the device records [n_frames, per_frame] (default per_frame: max_markers) under counts [n_frames], found on
+        frames of src_size = (width, height), carried to where orient(..., orientation) puts those frames' pixels, every other field
+        copied, into the device records at d_out (which may be d_markers); slots at or beyond a frame's count are not written.
+        Corner k stays in slot k: the mirroring orientations reverse the winding of the square.  pose: glMatrix is solved again from
+        the new square with the camera set at the call, which must be orient_camera(camera of src_size, orientation); refused for
+        the mirroring orientations.  Needs no batch, does not wait (stream None: the detector's own stream)."""
+        per_frame = self.max_markers if per_frame is None else per_frame
+        self._check(self._lib.ocvar_hip_orient_records(self._ctx, d_markers, d_counts, n_frames, per_frame, src_size[0], src_size[1],
+                                                       orientation_code(orientation), ORIENT_POSE if pose else 0, d_out, stream), "orient_records")
 
     def flow_records(self, d_prev, d_next, width, height, n_frames, d_markers, d_counts, d_out, per_frame=None, fmt=None,
                      prev_row_stride=None, prev_frame_stride=None, next_row_stride=None, next_frame_stride=None, params=None, pose=False,

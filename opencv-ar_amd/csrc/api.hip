@@ -1077,6 +1077,75 @@ extern "C" int ocvar_hip_scale_records(OcvarHip* c, const OcvarMarker* d_markers
     return OCVAR_OK;
 }
 
+extern "C" int ocvar_hip_orient(OcvarHip* c, const uint8_t* d_src, int src_width, int src_height, int src_row_stride, size_t src_frame_stride,
+                                uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride, int n_frames, int format, int orientation, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    const auto refuse = [&](const char* text) {
+        c->err = std::string("orient: ") + text;
+        return OCVAR_E_ARG;
+    };
+    if (!d_src || !d_dst) return refuse("no source or no destination frames");
+    const int bpp = patch_bpp(format);
+    if (bpp == 0 || !orient_ok(orientation)) return refuse("an unknown format or orientation");
+    const auto side_ok = [](int v) { return v >= 1 && v <= ORIENT_MAX_SIDE; };
+    if (!side_ok(src_width) || !side_ok(src_height)) return refuse("sides of 1 .. 32767 pixels");
+    if (n_frames < 1) return refuse("n_frames >= 1");
+    const int dst_width = orient_dst_width(orientation, src_width, src_height), dst_height = orient_dst_height(orientation, src_width, src_height);
+    if ((long long)src_row_stride < (long long)bpp * src_width || (long long)dst_row_stride < (long long)bpp * dst_width)
+        return refuse("a row stride below the format's bytes per pixel times the width of that side");
+    const auto span = [&](int width, int height, int row_stride) { return (long long)(height - 1) * row_stride + (long long)bpp * width; };
+    if (span(src_width, src_height, src_row_stride) > 2147483647LL || span(dst_width, dst_height, dst_row_stride) > 2147483647LL)
+        return refuse("the rows of a frame span more than 2147483647 bytes");
+    const unsigned long long s0 = (unsigned long long)(uintptr_t)d_src, d0 = (unsigned long long)(uintptr_t)d_dst;
+    const unsigned long long s1 = s0 + frames_extent(src_width, src_height, bpp, src_row_stride, src_frame_stride, n_frames);
+    const unsigned long long d1 = d0 + frames_extent(dst_width, dst_height, bpp, dst_row_stride, dst_frame_stride, n_frames);
+    if (s0 < d1 && d0 < s1) return refuse("the byte ranges of source and destination frames intersect (no turning in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    for (int f0 = 0; f0 < n_frames; f0 += ORIENT_CHUNK_FRAMES) {
+        const OrientArgs a{d_src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, src_width, src_height,
+                           (long long)src_row_stride, (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride, orientation};
+        launch_orient(a, std::min(ORIENT_CHUNK_FRAMES, n_frames - f0), format, s);
+        TRACE_LAUNCH("orient", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_orient_records(OcvarHip* c, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
+                                        int src_width, int src_height, int orientation, int flags, OcvarMarker* d_out, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    const auto refuse = [&](const char* text) {
+        c->err = std::string("orient_records: ") + text;
+        return OCVAR_E_ARG;
+    };
+    if (!d_markers || !d_counts || !d_out) return refuse("no records, no counts or no output");
+    if (n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm) return refuse("n_frames >= 1, 1 .. M records per frame");
+    if (src_width < 1 || src_width > ORIENT_MAX_SIDE || src_height < 1 || src_height > ORIENT_MAX_SIDE) return refuse("sides of 1 .. 32767 pixels");
+    if (!orient_ok(orientation)) return refuse("an unknown orientation");
+    if (flags & ~ORIENT_FLAGS) return refuse("unknown flag bits");
+    if ((flags & OCVAR_ORIENT_POSE) && orient_mirrors(orientation)) return refuse("OCVAR_ORIENT_POSE with a mirroring orientation: a reflected view has no rigid pose");
+    if ((flags & OCVAR_ORIENT_POSE) && !c->have_camera) return refuse("OCVAR_ORIENT_POSE without a camera");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    const int chunk = 65535;
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const OrientRecArgs a{reinterpret_cast<const MarkerRec*>(d_markers) + (size_t)f0 * records_per_frame,
+                              reinterpret_cast<MarkerRec*>(d_out) + (size_t)f0 * records_per_frame, d_counts + f0, records_per_frame,
+                              src_width, src_height, orientation, flags, c->h_camera};
+        launch_orient_records(a, std::min(chunk, n_frames - f0), s);
+        TRACE_LAUNCH("orient_records", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_orient_camera(const OcvarCamera* in, int orientation, OcvarCamera* out) {
+    static_assert(sizeof(OcvarCamera) == sizeof(CameraRec), "the same 248 bytes");
+    if (!in || !out) return OCVAR_E_ARG;
+    return orient_camera(*reinterpret_cast<const CameraRec*>(in), orientation, reinterpret_cast<CameraRec*>(out)) ? OCVAR_OK : OCVAR_E_ARG;
+}
+
 // a parameter of ocvar_hip_flow_records that must be a finite number >= 0
 static bool flow_number_ok(float v) { return v >= 0.0f && v <= 3.0e38f; }
 

@@ -11,6 +11,7 @@
 #include "undistort_core.h"
 #include "yuv_core.h"
 #include "resize_core.h"
+#include "orient_core.h"
 #include "flow_core.h"
 #include "croplist_core.h"
 #include "ocvar_hip.h"
@@ -248,6 +249,24 @@ struct ScaleRecArgs {
 };
 // n_frames (at most 65535: the grid's y) frames
 void launch_scale_records(const ScaleRecArgs& a, int n_frames, hipStream_t stream);
+
+// One launch of an orient kernel (orient.hip) on the n_frames (at most ORIENT_CHUNK_FRAMES: the grid's z) frames in `format` of a
+// (orient_core.h: OrientArgs), whose two sides do not overlap.
+constexpr int ORIENT_CHUNK_FRAMES = 65535;
+void launch_orient(const OrientArgs& a, int n_frames, int format, hipStream_t stream);
+
+// One launch of orient_records_kernel: of frame f the records in[f * slots + k], k < min(counts[f], slots), to the same slots of out
+// (which may be in), their squares carried from a sw x sh frame to its orientation; flags OCVAR_ORIENT_*, cam by value: the
+// context's at the call.
+struct OrientRecArgs {
+    const MarkerRec* in;
+    MarkerRec* out;
+    const int* counts;
+    int slots, sw, sh, orientation, flags;
+    CameraRec cam;
+};
+// n_frames (at most 65535: the grid's y) frames
+void launch_orient_records(const OrientRecArgs& a, int n_frames, hipStream_t stream);
 
 // The pyramids of n_frames frames in `format` (flow.hip: flow_grey_kernel, then flow_down_kernel level by level): frame f's
 // levels 0 .. g.L go to pyr + f * slot_bytes, laid out as g says.

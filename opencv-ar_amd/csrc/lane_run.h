@@ -1,0 +1,42 @@
+// lane_run.h -- a lane's run of consecutive bytes of one row, held in registers: what the streaming frame kernels (resize.hip,
+// orient.hip) load and store.  Byte j of a run lives in bits 8 (j & 3) of dword j >> 2 (constant indices once unrolled).
+#pragma once
+#include "hd.h"
+
+namespace ocvar {
+
+template <int ND>
+OCVAR_D int run_byte(const unsigned (&q)[ND], int j) { return (int)((q[j >> 2] >> (8 * (j & 3))) & 255u); }
+template <int ND>
+OCVAR_D void run_put(unsigned (&q)[ND], int j, int b) { q[j >> 2] |= (unsigned)b << (8 * (j & 3)); }
+
+// The lane's run of bytes at p: whole dwords (p is a multiple of 4 then, and all ND dwords belong to the lane), or the first
+// nbytes of them byte by byte, the others read as 0 / not written.
+template <int ND>
+OCVAR_D void run_load(unsigned (&q)[ND], const uint8_t* p, bool dwords, int nbytes) {
+    if (dwords) {
+        const unsigned* w = reinterpret_cast<const unsigned*>(p);
+        OCVAR_UNROLL
+        for (int j = 0; j < ND; j++) q[j] = w[j];
+    } else {
+        OCVAR_UNROLL
+        for (int j = 0; j < ND; j++) q[j] = 0;
+        OCVAR_UNROLL
+        for (int b = 0; b < 4 * ND; b++)
+            if (b < nbytes) q[b >> 2] |= (unsigned)p[b] << (8 * (b & 3));
+    }
+}
+template <int ND>
+OCVAR_D void run_store(const unsigned (&q)[ND], uint8_t* p, bool dwords, int nbytes) {
+    if (dwords) {
+        unsigned* w = reinterpret_cast<unsigned*>(p);
+        OCVAR_UNROLL
+        for (int j = 0; j < ND; j++) w[j] = q[j];
+    } else {
+        OCVAR_UNROLL
+        for (int b = 0; b < 4 * ND; b++)
+            if (b < nbytes) p[b] = (uint8_t)(q[b >> 2] >> (8 * (b & 3)));
+    }
+}
+
+}  // namespace ocvar

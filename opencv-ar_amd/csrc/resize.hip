@@ -4,46 +4,12 @@
 // lane computes the taps of its pixels from the core's functions (double per column and row, cheap next to the loads).  The
 // arguments travel by value; the kernels are templates of the bytes per pixel, the alignment and the rule, not of the sizes.
 #include "kernels.h"
+#include "lane_run.h"
 
 namespace ocvar {
 
 constexpr int RESIZE_LANE_PX = 8;                       // consecutive destination pixels of one row a lane owns: 8, 24 or 32 bytes
 constexpr int RESIZE_WAVE_PX = 64 * RESIZE_LANE_PX;     // destination pixels of one wave's span
-
-// A lane's bytes live in registers, byte j of a run in bits 8 (j & 3) of dword j >> 2 (constant indices once unrolled).
-template <int ND>
-OCVAR_D int run_byte(const unsigned (&q)[ND], int j) { return (int)((q[j >> 2] >> (8 * (j & 3))) & 255u); }
-template <int ND>
-OCVAR_D void run_put(unsigned (&q)[ND], int j, int b) { q[j >> 2] |= (unsigned)b << (8 * (j & 3)); }
-
-// The lane's run of bytes at p: whole dwords (p is a multiple of 4 then, and all ND dwords belong to the lane), or the first
-// nbytes of them byte by byte, the others read as 0 / not written.
-template <int ND>
-OCVAR_D void run_load(unsigned (&q)[ND], const uint8_t* p, bool dwords, int nbytes) {
-    if (dwords) {
-        const unsigned* w = reinterpret_cast<const unsigned*>(p);
-        OCVAR_UNROLL
-        for (int j = 0; j < ND; j++) q[j] = w[j];
-    } else {
-        OCVAR_UNROLL
-        for (int j = 0; j < ND; j++) q[j] = 0;
-        OCVAR_UNROLL
-        for (int b = 0; b < 4 * ND; b++)
-            if (b < nbytes) q[b >> 2] |= (unsigned)p[b] << (8 * (b & 3));
-    }
-}
-template <int ND>
-OCVAR_D void run_store(const unsigned (&q)[ND], uint8_t* p, bool dwords, int nbytes) {
-    if (dwords) {
-        unsigned* w = reinterpret_cast<unsigned*>(p);
-        OCVAR_UNROLL
-        for (int j = 0; j < ND; j++) w[j] = q[j];
-    } else {
-        OCVAR_UNROLL
-        for (int b = 0; b < 4 * ND; b++)
-            if (b < nbytes) p[b] = (uint8_t)(q[b >> 2] >> (8 * (b & 3)));
-    }
-}
 
 // Every kernel: a one-wave workgroup owns a span of RESIZE_WAVE_PX pixels of one destination row (blockIdx: span, row, frame), a
 // lane RESIZE_LANE_PX consecutive ones, put together in registers.  A full lane stores them as 2 BPP whole dwords when the

@@ -1,0 +1,372 @@
+"""The orientation core (opencv-ar_amd/csrc/orient_core.h) on the host (tests/orient_chain.py builds it) against numpy's own
+rot90 / slicing / transpose, byte for byte; the group the eight orientations form; the record map against numpy float64 and against
+the pixels themselves; the camera map against the lens model, which pins the signs of the tangential pair; the pose flag against
+the original pose turned about the optical axis; the chain "turn upright, detect, carry the records back" through the oracle; the
+stand-alone program under the sanitizers; the ABI.  tests/test_gpu_orient.py holds the kernels to this build byte for byte."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+import orient_chain as OR
+import persp_synth as PS
+from helpers import P
+
+CHANNELS = {"bgr": 3, "rgb": 3, "bgra": 4, "rgba": 4, "gray": 1}
+POSE_RTOL = 1e-4   # tests/test_gpu_parity.py: check_markers
+
+
+@pytest.fixture(scope="module")
+def L(tmp_path_factory):
+    return OR.build_emul(tmp_path_factory.mktemp("orient_emul"))
+
+
+def sweep_sizes():
+    """(W, H): every pair of OR.SIDES, then the widths around a wave's span of the row kernels with three heights"""
+    return [(w, h) for w in OR.SIDES for h in OR.SIDES] + [(w, h) for w in OR.WIDE for h in (1, 3, OR.TILE + 1)]
+
+
+@pytest.mark.parametrize("fmt", OR.FMTS)
+def test_frame_sweep(L, fmt):
+    """every orientation on guarded frames with padded rows, 1 and 2 frames, aligned and odd layouts: numpy's pixels, every guard byte
+    kept"""
+    ch = CHANNELS[fmt]
+    done = 0
+    for j, (w, h) in enumerate(sweep_sizes()):
+        for o in range(8):
+            n = 1 + (j + o) % 2
+            src = OR.pix_layout(n, w, h, fmt, aligned=bool((j + o) & 2), seed=j)
+            dst = OR.dst_layout(src, o, aligned=bool((j + o) & 4))
+            rc, out = OR.host_orient(L, src, dst, o)
+            assert rc == 0
+            assert (out[~dst.pixel_mask()] == OR.GUARD).all(), (o, w, h)
+            for f in range(n):
+                want = OR.np_orient(src.view(f), o)
+                got = dst.view(f, out)
+                assert got.shape == want.shape == (OR.oriented_size((w, h), o)[1], OR.oriented_size((w, h), o)[0], ch)
+                assert np.array_equal(got, want), (OR.NAMES[o], fmt, w, h, f, np.argwhere(got != want)[:3].tolist())
+            done += 1
+    assert done == 8 * len(sweep_sizes())
+
+
+def test_queries_and_source_index(L):
+    """transposes / mirrors / inverse / destination size, and the source index of every destination pixel of a 5 x 3 frame against
+    the forward table"""
+    W, Hh = 5, 3
+    out = np.zeros(7, np.int32)
+    for o in range(8):
+        dw, dh = OR.oriented_size((W, Hh), o)
+        seen = set()
+        for dy in range(dh):
+            for dx in range(dw):
+                L.orient_source_index_emul(o, W, Hh, dx, dy, P(out))
+                sx, sy = int(out[0]), int(out[1])
+                assert 0 <= sx < W and 0 <= sy < Hh
+                assert OR.np_orient_points([sx, sy], (W, Hh), o).tolist() == [dx, dy], (o, dx, dy)
+                seen.add((sx, sy))
+        assert len(seen) == W * Hh
+        assert (bool(out[2]), bool(out[3]), int(out[4]), int(out[5]), int(out[6])) == (o in OR.TRANSPOSING, o in OR.MIRRORING, OR.INVERSE[o], dw, dh)
+
+
+def test_group_properties(L):
+    """on random images: the inverse undoes, four quarter turns are the identity, TRANSPOSE is FLIP_H after ROT90_CW, TRANSVERSE is
+    FLIP_V after ROT90_CW, ROT180 is FLIP_V after FLIP_H ("B after A": B applied to the result of A)"""
+    rng = np.random.default_rng(1)
+    t = lambda a, o: OR.host_orient_image(L, a, o)   # noqa: E731
+    for w, h, ch in [(1, 1, 1), (5, 3, 3), (64, 17, 4), (33, 65, 1), (129, 8, 3)]:
+        a = rng.integers(0, 256, (h, w, ch), dtype=np.uint8)
+        for o in range(8):
+            assert np.array_equal(t(t(a, o), OR.INVERSE[o]), a), o
+        assert np.array_equal(t(t(t(t(a, 1), 1), 1), 1), a)
+        assert np.array_equal(t(t(a, 1), 1), t(a, 2)) and np.array_equal(t(t(a, 2), 1), t(a, 3))
+        assert np.array_equal(t(t(a, "rot90"), "flip_h"), t(a, "transpose"))      # FLIP_H applied to the result of ROT90_CW
+        assert np.array_equal(t(t(a, "rot90"), "flip_v"), t(a, "transverse"))
+        assert np.array_equal(t(t(a, "flip_h"), "flip_v"), t(a, "rot180"))
+        assert np.array_equal(t(a, "identity"), a)
+
+
+# ---- records --------------------------------------------------------------------------------------------------------------------------
+
+def test_records_index_the_same_pixels(L):
+    """a record holding the integer positions of four distinguishable pixels: the mapped corners index the same pixel values in the
+    oriented image, for every orientation"""
+    rng = np.random.default_rng(2)
+    for w, h in [(7, 5), (64, 33), (130, 9)]:
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        pts = np.array([[0, 0], [w - 1, 0], [w - 2, h - 1], [w // 2, h // 2]])
+        for k, (x, y) in enumerate(pts):     # make the four pixels unmistakable
+            img[y, x] = [250 - k, k, 100 + k]
+        recs = OR.records_of([]).copy()
+        recs["square"][0, 0] = pts.reshape(-1)
+        for o in range(8):
+            rc, out = OR.host_orient_records(L, recs, [1], (w, h), o)
+            assert rc == 0
+            turned = OR.host_orient_image(L, img, o)
+            sq = out["square"][0, 0].reshape(4, 2)
+            assert (sq == np.rint(sq)).all()
+            for k in range(4):
+                assert turned[int(sq[k, 1]), int(sq[k, 0])].tolist() == img[pts[k, 1], pts[k, 0]].tolist(), (o, k)
+
+
+def test_record_map_against_numpy(L):
+    """random, huge, infinite and NaN coordinates: the float64 numpy map's bits; every other field and every slot at or beyond the
+    count untouched; into the block itself"""
+    rng = np.random.default_rng(5)
+    n, slots = 3, 6
+    raw = rng.integers(0, 256, n * slots * OR.MARKER_DTYPE.itemsize, dtype=np.uint8)
+    recs = np.frombuffer(raw.tobytes(), OR.MARKER_DTYPE).reshape(n, slots).copy()
+    recs["square"] = rng.uniform(-50, 4000, (n, slots, 8)).astype(np.float32)
+    recs["square"][0, 0] = [0.0, -0.5, 0.25, 1e30, -1e30, np.inf, -np.inf, np.nan]
+    recs["square"][0, 1, 2] = np.array([0xFFC12345], np.uint32).view(np.float32)[0]     # a NaN with a payload and a sign
+    recs["square"][0, 1, 3] = np.array([0x7FC54321], np.uint32).view(np.float32)[0]
+    counts = [slots, 2, 0]
+    written = np.arange(slots)[None, :] < np.array(counts)[:, None]
+    for size in [(640, 480), (1920, 1080), (3, 32767), (32767, 1)]:
+        for o in range(8):
+            rc, out = OR.host_orient_records(L, recs, counts, size, o)
+            assert rc == 0
+            want = OR.np_orient_squares(recs["square"], size, o)
+            assert out["square"][written].view(np.uint32).tolist() == want[written].view(np.uint32).tolist(), (size, o)
+            assert out[~written].tobytes() == recs[~written].tobytes()
+            for name in ("glMatrix", "templateId", "markerId", "score", "aspectRatio"):
+                assert out[name].tobytes() == recs[name].tobytes()
+            # in place
+            same = recs.copy()
+            c = np.asarray(counts, np.int32)
+            assert L.orient_records_emul(same.ctypes.data, c.ctypes.data, n, slots, size[0], size[1], o, 0, None, same.ctypes.data) == 0
+            assert same.tobytes() == out.tobytes()
+    # a passed-on coordinate keeps its NaN's bits, a reversed one gets the canonical NaN
+    rc, out = OR.host_orient_records(L, recs, counts, (640, 480), "flip_h")
+    assert out["square"][0, 1, 3:4].view(np.uint32)[0] == 0x7FC54321 and out["square"][0, 1, 2:3].view(np.uint32)[0] == OR.NAN_BITS
+    assert OR.np_orient_squares(np.float32([np.nan] * 8), (2, 4), 2).view(np.uint32).tolist() == [OR.NAN_BITS] * 8
+
+
+def test_records_there_and_back(L):
+    """the inverse orientation on the destination size returns every coordinate within 1 ulp at the larger magnitude on the way
+    (each reversed coordinate is rounded once per direction)"""
+    rng = np.random.default_rng(7)
+    recs = OR.records_of([], slots=500).copy()
+    recs["square"] = rng.uniform(-20, 2200, (1, 500, 8)).astype(np.float32)
+    for size in [(640, 480), (1920, 1080)]:
+        for o in range(8):
+            _, there = OR.host_orient_records(L, recs, [500], size, o)
+            _, back = OR.host_orient_records(L, there, [500], OR.oriented_size(size, o), OR.INVERSE[o])
+            a, b = recs["square"], back["square"]
+            mid = there["square"] if o not in OR.TRANSPOSING else there["square"].reshape(1, 500, 4, 2)[..., ::-1].reshape(1, 500, 8)
+            tol = np.spacing(np.maximum(np.maximum(np.abs(a), np.abs(mid)), np.float32(1)))
+            assert (np.abs(b.astype(np.float64) - a) <= tol).all(), (size, o)
+
+
+# ---- the camera ------------------------------------------------------------------------------------------------------------------------
+
+def lens_camera(width, height):
+    """focal lengths of about 500, an off-centre principal point, all five coefficients non-zero"""
+    cam = H.oracle_camera(width, height)
+    cam.cameraMatrix[0], cam.cameraMatrix[4] = 512.25, 487.5
+    cam.cameraMatrix[2], cam.cameraMatrix[5] = 0.47 * width, 0.55 * height
+    cam.distCoeffs[:] = [-0.21, 0.09, 0.0035, -0.0021, -0.02]
+    return cam
+
+
+def test_camera_map_commutes_with_the_lens(L):
+    """distorting a normalised point and orienting the pixel equals orienting the point and distorting it under the oriented camera:
+    exact mathematics, evaluated on both sides in float64 numpy -- the bound is float64 rounding at pixel magnitudes of about 1000
+    (2.3e-13 per operation, a few dozen operations): 1e-9 px.  A wrong sign of the tangential pair misses it by about
+    2 f p r^2 = 0.5 px at r = 0.4.  glProjection is cvarCameraProjection's formula; the host core's camera is the numpy one"""
+    rng = np.random.default_rng(11)
+    nrm = rng.uniform(-0.6, 0.6, (4000, 2))
+    worst = 0.0
+    for size in [(640, 480), (1921, 1081)]:
+        cam = lens_camera(*size)
+        K = np.array(list(cam.cameraMatrix)).reshape(3, 3)
+        d = np.array(list(cam.distCoeffs))
+        for o in range(8):
+            rc, got = OR.host_orient_camera(L, cam, o)
+            assert rc == 0
+            w, h, K2, d2, gl = OR.np_orient_camera(cam, o)
+            assert (got.width, got.height) == (w, h) == OR.oriented_size(size, o)
+            assert np.abs(np.array(list(got.cameraMatrix)).reshape(3, 3) - K2).max() <= 1e-12 and list(got.distCoeffs) == d2.tolist()
+            assert np.abs(np.array(list(got.glProjection)) - gl).max() <= 1e-15
+            K2c, d2c = np.array(list(got.cameraMatrix)).reshape(3, 3), np.array(list(got.distCoeffs))
+            assert K2c[0, 1] == 0 and K2c[1, 0] == 0 and K2c[2].tolist() == [0, 0, 1]
+            assert (d2c[[0, 1, 4]] == d[[0, 1, 4]]).all() and np.abs(d2c[[2, 3]]).tolist() == (np.abs(d[[3, 2]]) if o in OR.TRANSPOSING else np.abs(d[[2, 3]])).tolist()
+            left = OR.np_orient_points(OR.np_distort(K, d, nrm), size, o)                       # distort, then orient the pixel
+            right = OR.np_distort(K2c, d2c, nrm @ OR.PLANE_TURN[o].T)                           # orient the point, then distort
+            err = np.abs(left - right).max()
+            worst = max(worst, err)
+            assert err <= 1e-9, (size, OR.NAMES[o], err)
+    print("camera: distort-then-orient against orient-then-distort, at most %.3g px" % worst)
+    # ROT90_CW as the issue spells it out
+    cam = lens_camera(640, 480)
+    _, got = OR.host_orient_camera(L, cam, "rot90")
+    assert got.cameraMatrix[2] == 480 - 1 - cam.cameraMatrix[5] and got.cameraMatrix[5] == cam.cameraMatrix[2]
+    assert (got.distCoeffs[2], got.distCoeffs[3]) == (cam.distCoeffs[3], -cam.distCoeffs[2])
+    assert (got.cameraMatrix[0], got.cameraMatrix[4]) == (cam.cameraMatrix[4], cam.cameraMatrix[0])
+
+
+def test_camera_map_composes_and_refuses(L):
+    """the inverse orientation returns the camera; skew and its like are refused under every other orientation,
+    with nothing written"""
+    cam = lens_camera(800, 600)
+    for o in range(8):
+        _, there = OR.host_orient_camera(L, cam, o)
+        rc, back = OR.host_orient_camera(L, there, OR.INVERSE[o])
+        assert rc == 0 and (back.width, back.height) == (800, 600)
+        assert np.abs(np.array(list(back.cameraMatrix)) - np.array(list(cam.cameraMatrix))).max() <= 1e-12
+        assert list(back.distCoeffs) == list(cam.distCoeffs)
+    for idx, v in [(1, 0.5), (3, 1e-9), (6, 1.0), (7, -2.0), (8, 2.0)]:
+        bad = lens_camera(800, 600)
+        bad.cameraMatrix[idx] = v
+        for o in range(8):
+            out = H.Camera()
+            C.memset(C.addressof(out), 0xA5, C.sizeof(out))
+            rc = L.orient_camera_emul(C.addressof(bad), o, C.addressof(out))
+            if o == 0:   # everything but glProjection (the last 128 bytes) is kept
+                assert rc == 0 and bytes(out)[:-128] == bytes(bad)[:-128]
+            else:
+                assert rc == OR.E_ARG and bytes(out) == b"\xa5" * C.sizeof(out), (idx, o)
+    out = H.Camera()
+    assert L.orient_camera_emul(C.addressof(cam), 8, C.addressof(out)) == OR.E_ARG and L.orient_camera_emul(C.addressof(cam), -1, C.addressof(out)) == OR.E_ARG
+
+
+# ---- the pose flag ---------------------------------------------------------------------------------------------------------------------
+
+def oracle_records():
+    """[(name, camera, size, [1, k] records)]: the oracle's markers on the chain scenes and on one scene under the distorting
+    camera of persp_synth"""
+    tpls = OR.chain_templates()
+    out = []
+    scenes = OR.chain_scenes() + [PS.scene("orient", "orient-lens", 960, 540, [(500, 260, 170, 30, 60, 120, 0, None)], lens=True)]
+    for sc in scenes:
+        cam = PS.camera(sc.width, sc.height, lens=sc.lens)
+        markers, _, _ = H.oracle_registration(sc.frame, tpls, cam)
+        assert len(markers) >= 1, sc.name
+        out.append((sc.name, cam, (sc.width, sc.height), OR.records_of(markers)))
+    return out
+
+
+def test_pose_under_the_oriented_camera(L):
+    """OCVAR_ORIENT_POSE under orient_camera, for the four rotations: the new pose reprojects the model corners onto the mapped square
+    as well as the oracle's pose reprojects them onto the original square, and it is the oracle's pose turned about the optical axis
+    (orient_core.h: Z M) within POSE_RTOL.  The reprojection bound: both poses are minima of the same problem up to the turn; the
+    solver stops at a relative step of FLT_EPSILON (1.2e-7) on parameters of magnitude up to about 20, which at a focal length of
+    about 1000 px moves a corner by a few 1e-3 px, and the mapped square's float32 rounding adds 6e-5 px at coordinates below 2048:
+    0.01 px.  The mirroring orientations are refused with nothing written"""
+    worst_gl = worst_px = 0.0
+    for name, cam, size, recs in oracle_records():
+        k = recs.shape[1]
+        for o in OR.ROTATIONS:
+            rc, cam_o = OR.host_orient_camera(L, cam, o)
+            assert rc == 0
+            rc, out = OR.host_orient_records(L, recs, [k], size, o, pose=True, cam=cam_o)
+            assert rc == 0
+            for j in range(k):
+                old, new = recs[0, j], out[0, j]
+                e_old = np.abs(OR.gl_reprojection(old["glMatrix"], cam, old["aspectRatio"]) - old["square"].reshape(4, 2)).max()
+                e_new = np.abs(OR.gl_reprojection(new["glMatrix"], cam_o, new["aspectRatio"]) - new["square"].reshape(4, 2)).max()
+                want = OR.turned_glmatrix(old["glMatrix"], o)
+                d = np.abs(new["glMatrix"] - want).max() / max(1.0, np.abs(want).max())
+                worst_gl, worst_px = max(worst_gl, d), max(worst_px, e_new - e_old)
+                print("%s %s: reprojection %.4f px (original %.4f px), pose %.3g from the turned original" % (name, OR.NAMES[o], e_new, e_old, d))
+                assert e_new <= e_old + 0.01, (name, o, e_new, e_old)
+                assert d <= POSE_RTOL, (name, o, d)
+        guard = np.frombuffer(np.full(recs.nbytes, OR.GUARD, np.uint8).tobytes(), OR.MARKER_DTYPE).reshape(recs.shape)
+        for o in OR.MIRRORING:
+            rc, out = OR.host_orient_records(L, recs, [k], size, o, pose=True, cam=cam, out=guard)
+            assert rc == OR.E_ARG and out.tobytes() == guard.tobytes()
+    print("pose: at most %.3g relative from the turned pose, reprojection at most %.4f px worse" % (worst_gl, worst_px))
+
+
+# ---- the chain -------------------------------------------------------------------------------------------------------------------------
+
+def test_the_chain_on_the_cpu(L):
+    """chain-0 and chain-1 delivered turned by ROT90_CW: detected as they are, with the camera of the turned size, the oracle does
+    not return the planted template; turned upright by the host core (ROT270_CW) the frames ARE the original frames, so the oracle
+    returns what it returns there, byte for byte; the records carried back with ROT90_CW lie on the turned frames within
+    persp_synth.match's 6 px of the planted corners mapped by numpy"""
+    tpls = OR.chain_templates()
+    FW, FH = OR.CHAIN_FULL
+    cam = PS.camera(FW, FH)
+    rc, cam_turned = OR.host_orient_camera(L, cam, "rot90")
+    assert rc == 0 and (cam_turned.width, cam_turned.height) == (FH, FW)
+    for sc in OR.chain_scenes()[:2]:
+        planted = sc.markers[0]
+        delivered = OR.np_orient(sc.frame, "rot90")
+        assert delivered.shape == (FW, FH, 3)
+        as_it_is, _, _ = H.oracle_registration(delivered, tpls, cam_turned)
+        assert not any(m.templateId == planted.template and m.score > 0 for m in as_it_is), sc.name
+        upright = OR.host_orient_image(L, delivered, "rot270")
+        assert np.array_equal(upright, sc.frame)
+        found, _, _ = H.oracle_registration(upright, tpls, cam)
+        direct, _, _ = H.oracle_registration(sc.frame, tpls, cam)
+        assert len(found) == len(direct) == 1 and bytes(found[0]) == bytes(direct[0])
+        assert found[0].templateId == planted.template and found[0].score > 0
+        rc, back = OR.host_orient_records(L, OR.records_of(found), [1], (FW, FH), "rot90")
+        assert rc == 0
+        turned_truth = PS.PlantedMarker(OR.np_orient_points(planted.quad, (FW, FH), "rot90"), planted.R, planted.t, planted.template, planted.tilt, planted.size)
+        m, k, d = PS.match(back["square"][0, 0], [turned_truth])
+        print("%s: carried-back corners %.2f px from the planted corners on the turned frame" % (sc.name, d))
+        assert m is turned_truth and k is not None, (sc.name, d)
+        # and they index the turned frame: the pixel under each carried-back corner is the pixel under the upright corner
+        sq, sq0 = np.rint(back["square"][0, 0].reshape(4, 2)).astype(int), np.rint(np.array(found[0].square).reshape(4, 2)).astype(int)
+        for c in range(4):
+            assert delivered[sq[c, 1], sq[c, 0]].tolist() == sc.frame[sq0[c, 1], sq0[c, 0]].tolist()
+
+
+# ---- sanitizers ------------------------------------------------------------------------------------------------------------------------
+
+def test_stand_alone_program_under_the_sanitizers(tmp_path):
+    """tests/emul/orient_emul.cpp with its own main, built with -fsanitize=address,undefined and run as a program: sides 1 .. 32767,
+    every pixel size and orientation, on heap blocks of exactly the bytes a call may touch"""
+    exe = OR.build_sanitized_program(tmp_path)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert ", 0 bad" in r.stdout and "runtime error" not in r.stderr
+
+
+# ---- ABI -------------------------------------------------------------------------------------------------------------------------------
+
+def test_abi_and_python_names():
+    """the three entry points are declared in the header and exported by the library; the module's helpers exist and agree with the
+    core's tables"""
+    import __graft_entry__ as g
+    g.build()
+    import opencv_ar_amd as oa
+    header = open(os.path.join(H.ROOT, "include", "ocvar_hip.h")).read()
+    lib = oa.hip_lib()
+    for name in ("ocvar_hip_orient", "ocvar_hip_orient_records", "ocvar_hip_orient_camera"):
+        assert re.search(r"\bint %s\(" % name, header) and name in oa.HIP_SYMBOLS and hasattr(lib, name), name
+    for k, (name, value) in enumerate([("IDENTITY", 0), ("ROT90_CW", 1), ("ROT180", 2), ("ROT270_CW", 3), ("FLIP_H", 4), ("FLIP_V", 5),
+                                       ("TRANSPOSE", 6), ("TRANSVERSE", 7)]):
+        assert re.search(r"OCVAR_ORIENT_%s = %d\b" % (name, value), header)
+        assert list(oa.ORIENTATIONS.items())[k] == (OR.NAMES[k], value)
+    assert re.search(r"OCVAR_ORIENT_POSE = 1\b", header) and oa.ORIENT_POSE == 1
+    for o in range(8):
+        assert oa.orientation_code(OR.NAMES[o]) == oa.orientation_code(o) == o
+        assert oa.orientation_inverse(o) == OR.INVERSE[o] and oa.oriented_size((5, 3), o) == OR.oriented_size((5, 3), o)
+    assert [oa.orientation_from_rotation(d) for d in (0, 90, 180, 270, 360, -90, 450.0)] == [0, 1, 2, 3, 0, 3, 1]
+    assert [oa.orientation_from_exif(t) for t in range(1, 9)] == [0, 4, 2, 5, 6, 1, 7, 3]
+    for bad in (45, 90.5, "90", None, True, float("nan")):
+        with pytest.raises(ValueError):
+            oa.orientation_from_rotation(bad)
+    for bad in (0, 9, 1.0, "1", True):
+        with pytest.raises(ValueError):
+            oa.orientation_from_exif(bad)
+    for bad in ("rot45", 8, -1, None, True, 1.0):
+        with pytest.raises(ValueError):
+            oa.orientation_code(bad)
+    # the host-only camera call through the module: the host core's camera
+    cam = lens_camera(640, 480)
+    got = oa.orient_camera(oa.Camera.from_buffer_copy(bytes(cam)), "rot90")
+    w, h, K2, d2, gl = OR.np_orient_camera(cam, 1)
+    assert (got.width, got.height) == (w, h) and np.abs(np.array(list(got.cameraMatrix)).reshape(3, 3) - K2).max() <= 1e-12
+    assert list(got.distCoeffs) == d2.tolist()
+    cam.cameraMatrix[1] = 0.25
+    with pytest.raises(ValueError):
+        oa.orient_camera(oa.Camera.from_buffer_copy(bytes(cam)), "flip_h")
+    assert bytes(oa.orient_camera(oa.Camera.from_buffer_copy(bytes(cam)), "identity"))[:-128] == bytes(cam)[:-128]
+    assert hasattr(oa.Detector, "orient") and hasattr(oa.Detector, "orient_records")
