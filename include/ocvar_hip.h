@@ -235,6 +235,61 @@ int ocvar_hip_render_records(OcvarHip* ctx, uint8_t* d_frames, int width, int he
                              int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
                              void* stream);
 
+/* Annotation (opt-in): outlines, a corner-0 dot, pose axes, a cube and the template id of every marker record, stroked straight
+ * into frames that stay in device memory -- what a caller draws first when setting up a camera or a board (ArUco's
+ * drawDetectedMarkers / drawFrameAxes; the reference's sample draws a cube on every square).  The definition, bit for bit, is
+ * opencv-ar_amd/csrc/annotate_core.h; it is the library's own stroke rule (parity with OpenCV's line rasteriser is neither claimed
+ * nor tested).  In short: a stroke is the set of pixels whose centre lies within thickness / 2 of its segment (round ends; a
+ * zero-length segment is a disc), end points rounded once to 1/16 px and clamped to +-OCVAR_ANNO_MAX_COORD px.  Of one record, in
+ * this order: the four edges of `square`, a dot of diameter 2 thickness + 1 on corner 0, the twelve edges of a cube on the marker
+ * rectangle (+-aspectRatio, +-1, 0) with its top at z = cube_height, the axes X (red), Y (green), Z (blue) of axis_length from the
+ * model origin, and templateId in decimal in a 5 x 7 bitmap font, axis-aligned and centred on the mean of the corners.  (R, t) of
+ * cube and axes is the inverse of glMatrix's construction; their end points are projected with the context's camera as it is at
+ * the call (by value), distortion included, and joined by straight strokes; an end point at camera z <= 0 or with a projection
+ * that is not finite drops its segment.  A pixel takes the colour of the last primitive of the record that covers it and is
+ * blended once, by the overlay's rule (straight alpha, alpha 0 leaves the pixel untouched, byte 3 of a four-channel pixel is never
+ * written, OCVAR_FMT_GRAY takes the library's grey of the colour): joints and crossings of half-transparent strokes do not darken
+ * twice.  Records composite in output order, k = 0 .. min(count, stride) - 1, later over earlier.  A record draws when all eight
+ * corner coordinates are finite and score > 0; with OCVAR_ANNO_UNMATCHED a record with score <= 0 draws its outline (in the
+ * `unmatched` colour) and its corner-0 dot, where those are asked for.  Cube and axes also need a finite glMatrix.  There is no
+ * convexity requirement.
+ *
+ * The style is passed by value with every call; the context keeps none.  ocvar_hip_annotate_default_style (host only: no context,
+ * no device call) fills: OUTLINE | CORNER0 | LABEL, thickness 2, axis_length 1, cube_height 1, label_scale 0 (automatic: the
+ * largest s in 1 .. 8 with 24 s <= the quad's shortest edge, else 1), outline green, unmatched grey, corner 0 red, cube cyan, label
+ * yellow, all opaque.  With OCVAR_ANNO_COLOR_BY_TEMPLATE the outline of a matched record takes colour templateId mod 12 of a fixed
+ * palette (annotate_core.h) with the outline's alpha.
+ *
+ * ocvar_hip_annotate: after ocvar_hip_enqueue and before ocvar_hip_collect, on the enqueued batch's own records, with the same
+ * promises about streams, gates, lanes and collect as ocvar_hip_render.  ocvar_hip_render and ocvar_hip_annotate may both be
+ * called on one batch: they are stream-ordered in call order (on one stream; a caller who names two streams orders them).
+ * ocvar_hip_annotate_records: on records the caller supplies in device memory, as ocvar_hip_render_records: no batch, frames of up
+ * to the context's size, any n_frames >= 1 (more than max_batch go through the workspace in chunks, in stream order), stream
+ * NULL: the context's own stream.  Neither waits.  The first call allocates the workspace (OCVAR_ANNO_RECORD_BYTES per marker
+ * record slot of max_batch frames); a context that never annotates allocates and launches nothing.  Markers, counts and board
+ * poses never depend on these calls.  OCVAR_E_ARG, before any device call and with the frames untouched, for a size, stride or
+ * format as ocvar_hip_render / ocvar_hip_render_records refuse them, a NULL style, thickness outside 1 .. 16, label_scale outside
+ * 0 .. 8, an axis_length or cube_height that is negative or not finite, unknown flag bits, none of OUTLINE, CORNER0, AXES, CUBE
+ * and LABEL set, and AXES or CUBE while the context has no camera. */
+enum { OCVAR_ANNO_OUTLINE = 1, OCVAR_ANNO_CORNER0 = 2, OCVAR_ANNO_AXES = 4, OCVAR_ANNO_CUBE = 8, OCVAR_ANNO_LABEL = 16,
+       OCVAR_ANNO_UNMATCHED = 32, OCVAR_ANNO_COLOR_BY_TEMPLATE = 64,
+       OCVAR_ANNO_MAX_THICKNESS = 16, OCVAR_ANNO_MAX_LABEL_SCALE = 8, OCVAR_ANNO_MAX_COORD = 1048576, OCVAR_ANNO_RECORD_BYTES = 696 };
+typedef struct {
+    int flags;                       /* OCVAR_ANNO_* */
+    int thickness;                   /* stroke width in pixels, 1 .. 16 */
+    int label_scale;                 /* glyph cell in pixels, 1 .. 8; 0: automatic */
+    int reserved;                    /* 0 */
+    double axis_length, cube_height; /* in the marker model's units: the marker is (+-aspectRatio, +-1, 0) */
+    uint8_t outline[4], unmatched[4], corner0[4], cube[4], label[4];   /* straight-alpha R G B A */
+    uint8_t reserved2[4];            /* 0 */
+} OcvarAnnotateStyle;   /* 56 bytes */
+int ocvar_hip_annotate_default_style(OcvarAnnotateStyle* style);   /* host only, no context, no device call */
+int ocvar_hip_annotate(OcvarHip* ctx, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int format,
+                       const OcvarAnnotateStyle* style, void* stream);
+int ocvar_hip_annotate_records(OcvarHip* ctx, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride,
+                               int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
+                               const OcvarAnnotateStyle* style, void* stream);
+
 /* Patches: the upright, perspective-free image of every marker record, cut out of frames that stay in device memory -- the
  * reference's cvarInvertPerspective(frame, patch, record.square, cvarSquare(patch_w, patch_h, 0)) (opencvar.cpp:510-516), one
  * dense block for a whole batch.  The definition, bit for bit, is opencv-ar_amd/csrc/patch_core.h: the map

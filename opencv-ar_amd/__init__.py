@@ -30,6 +30,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_stage_ms", "ocvar_hip_stream", "ocvar_hip_stage_stamps", "ocvar_hip_counters", "ocvar_hip_results_to_device", "ocvar_hip_results_to_device_ex", "ocvar_hip_debug_calibrate",
     "ocvar_hip_set_board", "ocvar_hip_board_poses", "ocvar_hip_board_poses_to_device",
     "ocvar_hip_set_overlay", "ocvar_hip_render", "ocvar_hip_render_records",
+    "ocvar_hip_annotate_default_style", "ocvar_hip_annotate", "ocvar_hip_annotate_records",
     "ocvar_hip_patches", "ocvar_hip_patches_records",
     "ocvar_hip_undistort", "ocvar_hip_undistort_records",
     "ocvar_hip_flow_records",
@@ -101,6 +102,54 @@ def flow_params(half_win=10, levels=3, max_iter=30, eps=0.03, min_eig=1e-3, max_
         if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < 3e38:
             raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
     return FlowParams(int(half_win), int(levels), int(max_iter), FLOW_POSE if pose else 0, float(eps), float(min_eig), float(max_err), float(fb_max))
+
+
+# include/ocvar_hip.h: OCVAR_ANNO_*
+ANNO_OUTLINE, ANNO_CORNER0, ANNO_AXES, ANNO_CUBE, ANNO_LABEL, ANNO_UNMATCHED, ANNO_COLOR_BY_TEMPLATE = 1, 2, 4, 8, 16, 32, 64
+ANNO_MAX_THICKNESS, ANNO_MAX_LABEL_SCALE, ANNO_MAX_COORD, ANNO_RECORD_BYTES = 16, 8, 1048576, 696
+ANNO_FLAG_NAMES = {"outline": ANNO_OUTLINE, "corner0": ANNO_CORNER0, "axes": ANNO_AXES, "cube": ANNO_CUBE, "label": ANNO_LABEL,
+                   "unmatched": ANNO_UNMATCHED, "color_by_template": ANNO_COLOR_BY_TEMPLATE}
+ANNO_COLOUR_NAMES = ("outline_color", "unmatched_color", "corner0_color", "cube_color", "label_color")
+
+
+class AnnotateStyle(C.Structure):  # OcvarAnnotateStyle
+    _fields_ = [("flags", C.c_int), ("thickness", C.c_int), ("label_scale", C.c_int), ("reserved", C.c_int),
+                ("axis_length", C.c_double), ("cube_height", C.c_double),
+                ("outline", C.c_uint8 * 4), ("unmatched", C.c_uint8 * 4), ("corner0", C.c_uint8 * 4), ("cube", C.c_uint8 * 4),
+                ("label", C.c_uint8 * 4), ("reserved2", C.c_uint8 * 4)]
+
+
+def annotate_style(**kw):
+    """The style of Detector.annotate / annotate_records (include/ocvar_hip.h: OcvarAnnotateStyle), starting from the library's
+    defaults (ocvar_hip_annotate_default_style): flags as keyword booleans outline, corner0, axes, cube, label, unmatched,
+    color_by_template; thickness (1 .. 16), label_scale (0: automatic, .. 8), axis_length, cube_height (finite, >= 0); colours
+    outline_color, unmatched_color, corner0_color, cube_color, label_color as (R, G, B, A) of 0 .. 255.  ValueError for an unknown
+    keyword or a value outside its range."""
+    st = AnnotateStyle()
+    if hip_lib().ocvar_hip_annotate_default_style(C.byref(st)) != 0:
+        raise OcvarError("ocvar_hip_annotate_default_style failed")
+    for name, v in kw.items():
+        if name in ANNO_FLAG_NAMES:
+            st.flags = (st.flags | ANNO_FLAG_NAMES[name]) if v else (st.flags & ~ANNO_FLAG_NAMES[name])
+        elif name in ("thickness", "label_scale"):
+            lo, hi = (1, ANNO_MAX_THICKNESS) if name == "thickness" else (0, ANNO_MAX_LABEL_SCALE)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an int in {lo} .. {hi}, got {v!r}")
+            setattr(st, name, int(v))
+        elif name in ("axis_length", "cube_height"):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < float("inf"):
+                raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+            setattr(st, name, float(v))
+        elif name in ANNO_COLOUR_NAMES:
+            c = tuple(v)
+            if len(c) != 4 or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= x <= 255 for x in c):
+                raise ValueError(f"{name} must be (R, G, B, A) of 0 .. 255, got {v!r}")
+            getattr(st, name[:-len("_color")])[:] = [int(x) for x in c]
+        else:
+            raise ValueError(f"unknown style keyword {name!r}")
+    if not st.flags & (ANNO_OUTLINE | ANNO_CORNER0 | ANNO_AXES | ANNO_CUBE | ANNO_LABEL):
+        raise ValueError("a style draws at least one of outline, corner0, axes, cube and label")
+    return st
 
 
 YUV_LAYOUTS = {"nv12": 0, "i420": 1, "yuyv": 2, "uyvy": 3}   # include/ocvar_hip.h: OCVAR_YUV_NV12 ..
@@ -319,6 +368,9 @@ def hip_lib():
         lib.ocvar_hip_set_overlay.argtypes = [vp, i, vp, i, i, i]
         lib.ocvar_hip_render.argtypes = [vp, vp, i, i, i, sz, i, vp]
         lib.ocvar_hip_render_records.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, i, vp]
+        lib.ocvar_hip_annotate_default_style.argtypes = [vp]
+        lib.ocvar_hip_annotate.argtypes = [vp, vp, i, i, i, sz, i, vp, vp]
+        lib.ocvar_hip_annotate_records.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, i, vp, vp]
         lib.ocvar_hip_patches.argtypes = [vp, vp, i, i, i, sz, i, vp, i, i, i, i, vp, vp]
         lib.ocvar_hip_patches_records.argtypes = [vp, vp, i, i, i, sz, i, i, vp, vp, i, vp, i, i, i, vp, vp]
         lib.ocvar_hip_undistort.argtypes = [vp, vp, i, sz, vp, i, sz, i, i, i, i, vp]
@@ -697,6 +749,29 @@ class Detector:
         frame_stride = frame_stride or row_stride * height
         self._check(self._lib.ocvar_hip_render_records(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames, code,
                                                        d_markers_ptr, d_counts_ptr, per_frame, stream), "render_records")
+
+    def annotate(self, d_ptr, width, height, style=None, fmt=None, row_stride=None, frame_stride=None, stream=None):
+        """between enqueue and collect: strokes outlines, corner-0 dots, pose axes and cubes and template ids (what `style`, an
+        annotate_style(), asks for; default: the library's default style) of the enqueued batch's markers into the device frames
+        at d_ptr (the frames detected, or another buffer of the batch's frame count and size) in format fmt (default: the input
+        format); stream-ordered behind the batch -- and behind a render called before it -- does not wait"""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        row_stride = row_stride or FORMAT_BPP[code] * width
+        frame_stride = frame_stride or row_stride * height
+        st = annotate_style() if style is None else AnnotateStyle.from_buffer_copy(bytes(style))
+        self._check(self._lib.ocvar_hip_annotate(self._ctx, d_ptr, width, height, row_stride, frame_stride, code, C.byref(st), stream), "annotate")
+
+    def annotate_records(self, d_ptr, width, height, n_frames, d_markers_ptr, d_counts_ptr, per_frame=None, style=None, fmt=None,
+                         row_stride=None, frame_stride=None, stream=None):
+        """the same on n_frames device frames under caller-supplied device records [n_frames, per_frame] (default per_frame:
+        max_markers) and counts [n_frames]; needs no batch, does not wait (stream None: the detector's own stream)"""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        per_frame = self.max_markers if per_frame is None else per_frame
+        row_stride = row_stride or FORMAT_BPP[code] * width
+        frame_stride = frame_stride or row_stride * height
+        st = annotate_style() if style is None else AnnotateStyle.from_buffer_copy(bytes(style))
+        self._check(self._lib.ocvar_hip_annotate_records(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames, code,
+                                                         d_markers_ptr, d_counts_ptr, per_frame, C.byref(st), stream), "annotate_records")
 
     def patches(self, d_ptr, width, height, d_patches_ptr, patch_w, patch_h, per_frame=None, fmt=None, row_stride=None, frame_stride=None,
                 flip_rows=False, matched_only=False, d_status_ptr=None, stream=None):

@@ -159,6 +159,7 @@ extern "C" void ocvar_hip_destroy(OcvarHip* c) {
     gate_detach(c);   // (waits for a batch on a lane of the gate)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->ovl_used) (void)hipEventSynchronize(c->ovl_done);   // (a render_records in flight reads the overlay workspace and the images)
+    if (c->anno_used) (void)hipEventSynchronize(c->anno_done);   // (an annotate_records in flight reads its workspace)
     delete c;
 }
 
@@ -779,6 +780,79 @@ extern "C" int ocvar_hip_render_records(OcvarHip* c, uint8_t* d_frames, int widt
     HIP_TRY(c, hipSetDevice(c->device));
     return overlay_launch(c, d_frames, width, height, row_stride, frame_stride, n_frames, format,
                           reinterpret_cast<const MarkerRec*>(d_markers), d_counts, records_per_frame, stream ? (hipStream_t)stream : c->stream.s);
+}
+
+extern "C" int ocvar_hip_annotate_default_style(OcvarAnnotateStyle* style) {
+    if (!style) return OCVAR_E_ARG;
+    anno_default_style(style);
+    return OCVAR_OK;
+}
+
+// what ocvar_hip_annotate and ocvar_hip_annotate_records refuse alike
+static bool annotate_args_ok(OcvarHip* c, const uint8_t* d_frames, int width, int row_stride, int format, const OcvarAnnotateStyle* style) {
+    static const char* const why[] = {"", "no style", "thickness 1 .. 16", "label_scale 0 .. 8", "axis_length and cube_height are finite numbers >= 0",
+                                      "unknown flag bits", "none of OUTLINE, CORNER0, AXES, CUBE and LABEL is set", "AXES or CUBE without a camera"};
+    if (!d_frames || input_format_bpp(format) == 0 || (long long)row_stride < (long long)input_format_bpp(format) * width) {
+        c->err = "annotate: no frames, an unknown format or a row_stride below the format's bytes per pixel times width";
+        return false;
+    }
+    if (const int bad = anno_style_bad(style, c->have_camera)) {
+        c->err = std::string("annotate: ") + why[bad];
+        return false;
+    }
+    return true;
+}
+
+// setup + draw of n_frames frames (chunks of the workspace's max_batch) on stream s, behind the workspace's last use
+static int annotate_launch(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int n_frames,
+                           int format, const MarkerRec* recs, const int* counts, int stride, const OcvarAnnotateStyle& st, hipStream_t s) {
+    const size_t slots = (size_t)c->ws.max_batch * c->ws.maxm;
+    HIP_TRY(c, c->anno_recs.reserve(slots * sizeof(AnnoRec)));
+    HIP_TRY(c, c->anno_boxes.reserve(slots * sizeof(AnnoBox)));
+    HIP_TRY(c, c->anno_done.ensure(hipEventDisableTiming));
+    if (c->anno_used && c->anno_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->anno_done, 0));
+    const AnnoArgs aa{c->anno_recs, c->anno_boxes};
+    const int chunk = std::min(c->ws.max_batch, 32768);   // (frames are the grid's z)
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int n = std::min(chunk, n_frames - f0);
+        launch_annotate(aa, d_frames + (size_t)f0 * frame_stride, width, height, row_stride, (long long)frame_stride, n, format,
+                        recs + (size_t)f0 * stride, counts + f0, stride, st, c->h_camera, s);
+        TRACE_LAUNCH("annotate", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->anno_done, s));
+    c->anno_stream = s;
+    c->anno_used = true;
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_annotate(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int format,
+                                  const OcvarAnnotateStyle* style, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    if (!batch_frames_ok(c, "annotate", width, height)) return OCVAR_E_ARG;
+    if (!annotate_args_ok(c, d_frames, width, row_stride, format, style)) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s;
+    if (int rc = follow_begin(c, stream, &s)) return rc;
+    const int rc = annotate_launch(c, d_frames, width, height, row_stride, frame_stride, c->ws.n_frames, format, c->ws.markers,
+                                   c->ws.n_markers, c->ws.maxm, *style, s);
+    if (rc) return rc;
+    return follow_end(c, s);
+}
+
+extern "C" int ocvar_hip_annotate_records(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride,
+                                          int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts,
+                                          int records_per_frame, const OcvarAnnotateStyle* style, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    if (!d_markers || !d_counts || n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm || width < 1 || height < 1 ||
+        width > c->ws.max_w || height > c->ws.max_h) {
+        c->err = "annotate_records: frames of 1 .. the context's size, n_frames >= 1, 1 .. M records per frame";
+        return OCVAR_E_ARG;
+    }
+    if (!annotate_args_ok(c, d_frames, width, row_stride, format, style)) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return annotate_launch(c, d_frames, width, height, row_stride, frame_stride, n_frames, format,
+                           reinterpret_cast<const MarkerRec*>(d_markers), d_counts, records_per_frame, *style, stream ? (hipStream_t)stream : c->stream.s);
 }
 
 // what ocvar_hip_patches and ocvar_hip_patches_records refuse alike

@@ -145,6 +145,12 @@ struct OcvarHip {
     ocvar::DeviceBuffer<uint8_t> flow_ws;          // [2][min(max_batch, 32)] pyramids of a max_w x max_h frame (flow_core.h: flow_geom)
     hipStream_t flow_stream = nullptr;
     bool flow_used = false;
+    // annotation (ocvar_hip_annotate / ocvar_hip_annotate_records): the primitive records' workspace is allocated by the first call
+    ocvar::Event anno_done;                        // behind the last use of the workspace, on anno_stream (created on first use)
+    ocvar::DeviceBuffer<ocvar::AnnoRec> anno_recs; // [max_batch][maxm]
+    ocvar::DeviceBuffer<ocvar::AnnoBox> anno_boxes;   // [max_batch][maxm]
+    hipStream_t anno_stream = nullptr;
+    bool anno_used = false;
     std::string err;
 
     ~OcvarHip();   // (api.hip: the fixed arrays and the overlay images; the holders release the rest)

@@ -7,6 +7,7 @@
 #include "refine_core.h"
 #include "board_core.h"
 #include "overlay_core.h"
+#include "annotate_core.h"
 #include "patch_core.h"
 #include "undistort_core.h"
 #include "yuv_core.h"
@@ -185,6 +186,18 @@ struct OverlayArgs {
 // (the first min(counts[f], stride) of frame f), all in device memory
 void launch_overlay(const OverlayArgs& oa, uint8_t* frames, int W, int H, long long row_stride, long long frame_stride, int n_frames,
                     int format, const MarkerRec* recs, const int* counts, int stride, hipStream_t stream);
+
+// A context's annotation workspace (the first annotate call allocates it): per record slot of a chunk of frames its AnnoRec and
+// AnnoBox, [max_batch][maxm].
+struct AnnoArgs {
+    AnnoRec* recs;
+    AnnoBox* boxes;
+};
+// annotate_setup_kernel + annotate_draw_kernel (annotate.hip) on n_frames frames in `format` and their records recs
+// [n_frames][stride] (the first min(counts[f], stride) of frame f), all in device memory; style and camera by value
+void launch_annotate(const AnnoArgs& aa, uint8_t* frames, int W, int H, long long row_stride, long long frame_stride, int n_frames, int format,
+                     const MarkerRec* recs, const int* counts, int stride, const OcvarAnnotateStyle& st, const CameraRec& cam,
+                     hipStream_t stream);
 
 // One launch of patch_kernel (patch.hip), all pointers in device memory: frames of W x H pixels; of frame f the records
 // recs[f * rec_stride + k], k < min(counts[f], slots); patches [n_frames][slots][ph][pw][bpp] at any address; status

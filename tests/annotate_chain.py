@@ -1,0 +1,183 @@
+"""Annotation for the annotate tests (ocvar_hip_annotate / ocvar_hip_annotate_records): the host build of
+opencv-ar_amd/csrc/annotate_core.h (tests/emul/annotate_emul.cpp), its stand-alone sanitizer program, a numpy float64 restatement
+of the stroke rule that shares no code with it (distance from a pixel centre to a segment), the font restated as pictures, guarded
+frames (overlay_chain.Frames) and hand-made records with poses.  Shared by tests/test_annotate_cpu.py and
+tests/test_gpu_annotate.py."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import board_chain as BC
+import helpers as H
+import overlay_chain as OC
+from overlay_chain import BPP, FORMATS, GUARD, LEAD, MARKER_DTYPE, Frames  # noqa: F401
+
+FMTS = ["bgr", "rgb", "bgra", "rgba", "gray"]
+OUTLINE, CORNER0, AXES, CUBE, LABEL, UNMATCHED, COLOR_BY_TEMPLATE = 1, 2, 4, 8, 16, 32, 64
+DRAW_FLAGS = OUTLINE | CORNER0 | AXES | CUBE | LABEL
+ALL_FLAGS = DRAW_FLAGS | UNMATCHED | COLOR_BY_TEMPLATE
+MAX_COORD = 1048576
+E_ARG = -2
+# annotate.hip: a lane owns ANNO_LANE_PX = 4 pixels of a row, a wave 256 columns and 4 rows, a workgroup 16 rows; record slots are
+# balloted 64 at a time
+LANE_PX, TILE_W, WAVE_ROWS, TILE_H, BALLOT = 4, 256, 4, 16, 64
+EMUL_SRC = os.path.join(H.ROOT, "tests", "emul", "annotate_emul.cpp")
+EMUL_FLAGS = ["-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + OC.CSRC, "-I" + os.path.join(H.ROOT, "include")]
+
+
+class Style(C.Structure):  # OcvarAnnotateStyle, restated
+    _fields_ = [("flags", C.c_int), ("thickness", C.c_int), ("label_scale", C.c_int), ("reserved", C.c_int),
+                ("axis_length", C.c_double), ("cube_height", C.c_double),
+                ("outline", C.c_uint8 * 4), ("unmatched", C.c_uint8 * 4), ("corner0", C.c_uint8 * 4), ("cube", C.c_uint8 * 4),
+                ("label", C.c_uint8 * 4), ("reserved2", C.c_uint8 * 4)]
+
+
+assert C.sizeof(Style) == 56
+
+SEG_DTYPE = np.dtype([("a", "<i4", (2,)), ("b", "<i4", (2,)), ("box", "<i2", (4,)), ("rgba", "<u4"), ("r", "<i4")])
+REC_DTYPE = np.dtype([("seg", SEG_DTYPE, (20,)), ("origin", "<i4", (2,)), ("scale", "<i4"), ("n", "<i4"), ("digit", "u1", (12,)),
+                      ("rgba", "<u4"), ("box", "<i2", (4,))])
+assert SEG_DTYPE.itemsize == 32 and REC_DTYPE.itemsize == 680
+SEG_EDGES, SEG_DOT, SEG_CUBE, SEG_AXES = slice(0, 4), 4, slice(5, 17), slice(17, 20)
+
+# the 5 x 7 font as pictures (annotate_core.h's opening table, restated)
+FONT = {0: "01110 10001 10011 10101 11001 10001 01110", 1: "00100 01100 00100 00100 00100 00100 01110",
+        2: "01110 10001 00001 00010 00100 01000 11111", 3: "11111 00010 00100 00010 00001 10001 01110",
+        4: "00010 00110 01010 10010 11111 00010 00010", 5: "11111 10000 11110 00001 00001 10001 01110",
+        6: "00110 01000 10000 11110 10001 10001 01110", 7: "11111 00001 00010 00100 01000 01000 01000",
+        8: "01110 10001 10001 01110 10001 10001 01110", 9: "01110 10001 10001 01111 00001 00010 01100"}
+
+
+def glyph(d):
+    """[7, 5] bool picture of digit d"""
+    return np.array([[c == "1" for c in row] for row in FONT[d].split()])
+
+
+def label_picture(number, scale):
+    """[7 s, (6 n - 1) s] bool picture of a number's label"""
+    digits = [int(c) for c in str(number)]
+    pic = np.zeros((7, 6 * len(digits) - 1), bool)
+    for g, d in enumerate(digits):
+        pic[:, 6 * g:6 * g + 5] = glyph(d)
+    return np.kron(pic, np.ones((scale, scale), bool)).astype(bool)
+
+
+def build_emul(out_dir):
+    so = os.path.join(str(out_dir), "libannotate_emul.so")
+    subprocess.check_call(["g++", "-O2"] + EMUL_FLAGS + ["-shared", "-o", so, EMUL_SRC])
+    L = C.CDLL(so)
+    vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
+    L.annotate_frame_emul.argtypes = [vp, i, i, ll, i, vp, i, i, vp, vp]
+    L.annotate_setup_emul.argtypes = [vp, vp, vp, i, i, vp, vp]
+    L.annotate_style_bad_emul.argtypes = [vp, i]
+    L.annotate_default_style_emul.argtypes = [vp]
+    L.annotate_glyph_emul.argtypes = [i]
+    L.annotate_glyph_emul.restype = C.c_ulonglong
+    L.annotate_palette_emul.argtypes = [i]
+    L.annotate_palette_emul.restype = C.c_uint
+    return L
+
+
+def build_sanitized_program(out_dir):
+    """the emulation with its stand-alone main under AddressSanitizer and UndefinedBehaviorSanitizer -> the program's path"""
+    exe = os.path.join(str(out_dir), "annotate_emul_san")
+    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DANNOTATE_EMUL_MAIN"] +
+                          EMUL_FLAGS + ["-o", exe, EMUL_SRC])
+    return exe
+
+
+def style(L, flags=None, **kw):
+    """the core's default style with fields replaced: flags (an int), thickness, label_scale, axis_length, cube_height, and
+    colours outline, unmatched, corner0, cube, label as (R, G, B, A)"""
+    st = Style()
+    L.annotate_default_style_emul(C.byref(st))
+    if flags is not None:
+        st.flags = flags
+    for k, v in kw.items():
+        if k in ("outline", "unmatched", "corner0", "cube", "label"):
+            getattr(st, k)[:] = list(v)
+        else:
+            assert hasattr(st, k), k
+            setattr(st, k, v)
+    return st
+
+
+def no_camera():
+    return H.Camera()
+
+
+def host_annotate(L, frames, recs, counts, st, cam=None, buf=None):
+    """the host core on a copy of frames.buf (or of buf): recs [n, stride] records, counts [n] -> (the annotated buffer, records
+    drawn per frame)"""
+    out = (frames.buf if buf is None else buf).copy()
+    recs = np.ascontiguousarray(recs)
+    cam = no_camera() if cam is None else cam
+    drawn = []
+    for f in range(frames.n):
+        drawn.append(L.annotate_frame_emul(out.ctypes.data + frames.offset(f), frames.width, frames.height, frames.row_stride, frames.fmt,
+                                           recs[f].ctypes.data, int(counts[f]), recs.shape[1], C.addressof(st), C.addressof(cam)))
+    return out, drawn
+
+
+def host_setup(L, rec, st, W, Hh, cam=None):
+    """the host core's setup of one record -> (draws, REC_DTYPE scalar, box [4])"""
+    rec = np.ascontiguousarray(rec).reshape(1)
+    out = np.zeros(1, REC_DTYPE)
+    box = np.zeros(4, np.int32)
+    cam = no_camera() if cam is None else cam
+    ok = L.annotate_setup_emul(rec.ctypes.data, C.addressof(st), C.addressof(cam), W, Hh, out.ctypes.data, box.ctypes.data)
+    return bool(ok), out[0], box
+
+
+def rgba_word(c):
+    r, g, b, a = (int(v) for v in c)
+    return r | g << 8 | b << 16 | a << 24
+
+
+def drawn_mask(fr, before, after, f=0):
+    """[H, W] bool: the pixels of frame f whose bytes differ between two buffers"""
+    return (fr.view(f, before) != fr.view(f, after)).any(axis=2)
+
+
+# ---- numpy restatement of the stroke rule -----------------------------------------------------------------------------------------
+
+def np_distance(width, height, a, b):
+    """[H, W] float64: the distance of every pixel centre (integer coordinates) to the segment a -- b"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    ys, xs = np.mgrid[0:height, 0:width].astype(np.float64)
+    d = b - a
+    den = float(d @ d)
+    t = np.zeros_like(xs) if den == 0.0 else np.clip(((xs - a[0]) * d[0] + (ys - a[1]) * d[1]) / den, 0.0, 1.0)
+    return np.hypot(xs - (a[0] + t * d[0]), ys - (a[1] + t * d[1]))
+
+
+# ---- records with poses -----------------------------------------------------------------------------------------------------------
+
+def glmatrix_of_pose(R, t):
+    """the 16 doubles cvarGlMatrix makes of (R, t) (persp_synth.pose_of_glmatrix is the inverse)"""
+    D = np.diag([-1.0, -1.0, 1.0])
+    m = np.zeros((4, 4))
+    m[:3, :3] = D @ np.asarray(R, np.float64).T @ D
+    m[3, :3] = [t[0], t[1], -t[2]]
+    m[3, 3] = 1.0
+    return m.reshape(-1)
+
+
+def project3(cam, R, t, pts):
+    """pixels [n, 2] of model points [n, 3] under (R, t) and cam: board_chain.project of the points' in-plane part with each
+    point's z carried into the translation"""
+    K, dist = BC.cam_arrays(cam)
+    pts = np.asarray(pts, np.float64)
+    return np.concatenate([BC.project(K, dist, R, np.asarray(t) + R @ np.array([0.0, 0.0, p[2]]), p[None, :2]) for p in pts])
+
+
+def posed_record(cam, R, t, template_id=0, score=1.0, ratio=1.0):
+    """a record whose square is the projection of the model rectangle (+-ratio, +-1) under (R, t) and whose glMatrix holds the pose"""
+    K, dist = BC.cam_arrays(cam)
+    quad = BC.project(K, dist, R, t, np.array([[-ratio, -1], [ratio, -1], [ratio, 1], [-ratio, 1]], np.float64))
+    r = OC.records([quad.reshape(8)], [template_id], [score])
+    r["glMatrix"][0] = glmatrix_of_pose(R, t)
+    r["aspectRatio"] = ratio
+    return r[0]
