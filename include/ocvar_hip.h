@@ -540,6 +540,69 @@ int ocvar_hip_orient_records(OcvarHip* ctx, const OcvarMarker* d_markers, const 
                              int src_width, int src_height, int orientation, int flags, OcvarMarker* d_out, void* stream);
 int ocvar_hip_orient_camera(const OcvarCamera* in, int orientation, OcvarCamera* out);   /* host only, no context, no device call */
 
+/* Projective warp: device-resident frames mapped by one homography per frame, the marker records carried along, and the maps that
+ * show a board's plane from straight above -- a tabletop, a whiteboard, a document or an inspection fixture rectified from the
+ * pose ocvar_hip_set_board gives, without a trip through host memory.  The reference's public cvarInvertPerspective(input, output,
+ * src, dst) (cvGetPerspectiveTransform + cvWarpPerspective) for any output size and any four points.  The definition, bit for
+ * bit, is opencv-ar_amd/csrc/warp_core.h; the sampler is the one ocvar_hip_patches already uses.
+ *   d_maps   nine doubles per frame, row by row, in device memory ([n_frames][9]; with OCVAR_WARP_ONE_MAP [9], used for every
+ *            frame).  By default the FORWARD map from source pixels to destination pixels, as OpenCV's warpPerspective takes it,
+ *            inverted in double (adjugate times 1 / det); with OCVAR_WARP_INVERSE_MAP the nine doubles already map destination
+ *            pixels to source pixels.  A frame is SKIPPED when any of its nine numbers is not finite, or when the forward map's
+ *            determinant is 0 or its inverse is not finite: d_status[f] = 0 and none of the frame's destination bytes is touched.
+ *            Every other frame gets status 1.  d_status ([n_frames] ints, device memory) may be NULL.
+ *   pixel    M the destination -> source map.  OCVAR_WARP_LINEAR: cvWarpPerspective's INTER_LINEAR, the source position
+ *            ((M0 x + M1 y + M2) / w, (M3 x + M4 y + M5) / w), w = M6 x + M7 y + M8 (w = 0: position 0), fixed to 1/32 px, four taps
+ *            under 15-bit weights.  OCVAR_WARP_NEAREST: the source pixel at the position rounded to nearest (ties to even) per
+ *            axis.  Every byte of a pixel is treated alike, byte 3 of a four-channel pixel included.
+ *   border   OCVAR_WARP_BORDER_CONSTANT: a tap outside the source reads fill[c], four bytes in the format's memory order (fill
+ *            NULL: zeros, the rule of ocvar_hip_patches).  OCVAR_WARP_BORDER_REPLICATE: tap coordinates are clamped into the source.
+ *   d_src / d_dst  n_frames frames of src_width x src_height and of dst_width x dst_height pixels in `format` (any OCVAR_FMT_*; it
+ *            need not be the input format), rows *_row_stride and frames *_frame_stride bytes apart, at any address; their byte
+ *            ranges must not intersect.  A source rectangle is d_src moved to the rectangle's first pixel with the rectangle's size
+ *            and the full frame's strides (the map then speaks of the rectangle's pixels).
+ * Sides are 1 .. 32767 on both ends and are NOT bound by the context's max_width x max_height: there is no workspace.  When the
+ * destination's address, row stride and frame stride are multiples of 4 the kernel stores whole dwords; otherwise, and in the
+ * last pixels of a row, bytes -- with the same result.  No byte outside the destination's pixels is written, no byte outside the
+ * source's pixels is read; the source is never written.
+ * ocvar_hip_warp_records carries the four corners of every record through the FORWARD map (OCVAR_WARP_INVERSE_MAP is refused: the
+ * records need the forward map) in double, x' = (m0 x + m1 y + m2) / w, rounded once to float32 (a NaN is stored as 0x7FC00000); a
+ * corner whose w is 0 or not finite becomes NaN.  Every other field is copied as it is; with OCVAR_WARP_POSE glMatrix is solved
+ * from the new square with the context's camera as it is at the call (by value) -- the camera of the warped frames -- and the
+ * record's aspectRatio, as ocvar_hip_scale_records does.
+ *   d_markers / d_out  [n_frames][records_per_frame] records (1 <= records_per_frame <= M = ocvar_hip_max_markers(ctx)); slot k
+ *            of frame f is written when k < min(d_counts[f], records_per_frame), no other slot is touched; d_out may be d_markers
+ * ocvar_hip_board_plane_maps writes, for every pose of d_poses [n_frames] (ocvar_hip_board_poses_to_device), the destination ->
+ * source map K [r1 r2 t] S -- to be used with OCVAR_WARP_INVERSE_MAP -- of the rectangle rect = (x0, y0, x1, y1) of the board's
+ * plane, in board units (host memory, read at the call): K the context's camera matrix as it is at the call, r1 r2 the first two
+ * columns of the rotation of rvec, S sending destination pixel (0, 0) to board point (x0, y0) and pixel (dst_width - 1,
+ * dst_height - 1) to (x1, y1); the caller flips the picture by choosing y0 > y1.  Sine and cosine of the rotation angle are not
+ * the math library's but the definition's own (warp_core.h: warp_sincos, within 1 ulp of them), so that the maps -- which decide
+ * bytes -- are the same bits on the device and in the host build.  The lens is ignored: undistort the frames first
+ * (ocvar_hip_undistort) and the maps are exact on them.  A pose whose status is not 1, a number that is not finite, or a
+ * rectangle of zero extent on an axis whose destination side is above 1 gives nine NaNs, and ocvar_hip_warp then skips that frame
+ * (status 0).
+ * Parity with a real OpenCV build is unpinned (see ocvar_hip_undistort): the rules are written down from memory of OpenCV; the
+ * tests pin the host build of warp_core.h, a numpy restatement of the rules, and the patches' sampler.
+ * All three need no batch and no workspace and can run at any time: a context that never calls them allocates and launches
+ * nothing.  Any n_frames >= 1 (more than 65535 go in several launches, in stream order); stream NULL: the context's own stream.
+ * None waits.  OCVAR_E_ARG, before any device call and with a text in ocvar_hip_last_error, for NULL pointers (fill and d_status
+ * may be NULL), an unknown format, interpolation, border or flag bit, a side outside 1 .. 32767, a row stride below the format's
+ * bytes per pixel times width, rows that span more than 2^31 - 1 bytes, n_frames < 1, intersecting source and destination byte
+ * ranges, records_per_frame outside 1 .. M, OCVAR_WARP_POSE or ocvar_hip_board_plane_maps with no camera set,
+ * OCVAR_WARP_INVERSE_MAP given to ocvar_hip_warp_records. */
+enum { OCVAR_WARP_NEAREST = 0, OCVAR_WARP_LINEAR = 1,
+       OCVAR_WARP_BORDER_CONSTANT = 0, OCVAR_WARP_BORDER_REPLICATE = 1,
+       OCVAR_WARP_INVERSE_MAP = 1, OCVAR_WARP_ONE_MAP = 2,   /* flags of ocvar_hip_warp / _warp_records */
+       OCVAR_WARP_POSE = 4 };                                /* flag of ocvar_hip_warp_records */
+int ocvar_hip_warp(OcvarHip* ctx, const uint8_t* d_src, int src_width, int src_height, int src_row_stride, size_t src_frame_stride,
+                   uint8_t* d_dst, int dst_width, int dst_height, int dst_row_stride, size_t dst_frame_stride, int n_frames, int format,
+                   const double* d_maps, int interpolation, int border, const uint8_t fill[4], int flags, int* d_status, void* stream);
+int ocvar_hip_warp_records(OcvarHip* ctx, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
+                           const double* d_maps, int flags, OcvarMarker* d_out, void* stream);
+int ocvar_hip_board_plane_maps(OcvarHip* ctx, const OcvarBoardPose* d_poses, int n_frames, const double rect[4], int dst_width,
+                               int dst_height, double* d_maps, void* stream);
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart
@@ -582,6 +645,7 @@ enum { OCVAR_TUNE_CROP_PHASES = 1, /* crop-pass tier 2 in 1 launch or 2 (exact p
        OCVAR_TUNE_MIN_UNITS = 6,   /* binarise work units per launch below which row chunks are not made taller */
        OCVAR_TUNE_GATE_MODE = 8,   /* which of a context's two binarise kernels wait at its gate: 0 both (default), 1 the frames
                                     * kernel only, 2 the crops kernel only */
+       OCVAR_TUNE_WARP_DIRECT = 9, /* 1: every tile of ocvar_hip_warp reads the source directly, none is staged through LDS */
        OCVAR_TUNE_HP_MASK = 7 };   /* kernels launched on the context's high-priority stream, one bit per launch: 1 tier 1
                                     * (frames), 2 tier 2, 4 tier 3, 8 order/crops, 16 tier 1 (crops), 32 tier 2, 64 tier 3,
                                     * 128 decode, 256 dedupe+pose; ocvar_hip_set_tuning(ctx, OCVAR_TUNE_HP_MASK, m) sets mask m

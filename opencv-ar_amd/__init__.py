@@ -37,6 +37,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_yuv_to_frames", "ocvar_hip_frames_to_yuv",
     "ocvar_hip_resize", "ocvar_hip_scale_records",
     "ocvar_hip_orient", "ocvar_hip_orient_records", "ocvar_hip_orient_camera",
+    "ocvar_hip_warp", "ocvar_hip_warp_records", "ocvar_hip_board_plane_maps",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -160,6 +161,34 @@ SCALE_POSE = 1                                              # include/ocvar_hip.
 # (W-1-x, y), (x, H-1-y), (y, x), (H-1-y, W-1-x)
 ORIENTATIONS = {"identity": 0, "rot90": 1, "rot180": 2, "rot270": 3, "flip_h": 4, "flip_v": 5, "transpose": 6, "transverse": 7}
 ORIENT_POSE = 1                                             # include/ocvar_hip.h: OCVAR_ORIENT_POSE
+
+
+WARP_INTERPS = {"nearest": 0, "linear": 1}                  # include/ocvar_hip.h: OCVAR_WARP_NEAREST, OCVAR_WARP_LINEAR
+WARP_BORDERS = {"constant": 0, "replicate": 1}              # include/ocvar_hip.h: OCVAR_WARP_BORDER_*
+WARP_INVERSE_MAP, WARP_ONE_MAP, WARP_POSE = 1, 2, 4         # include/ocvar_hip.h: OCVAR_WARP_INVERSE_MAP ..
+
+
+def perspective_map(src_quad, dst_quad):
+    """the nine float64 numbers (row by row, the last one 1) of the projective map that sends the four points of src_quad to
+    the four points of dst_quad (4 x 2 each): OpenCV's getPerspectiveTransform, solved in float64 from the four point pairs.  As
+    it stands it is the forward map Detector.warp takes for frames whose pixels move from src_quad to dst_quad.  ValueError when
+    the pairs do not determine a map (three points of a quad on a line)."""
+    s, d = np.asarray(src_quad, np.float64), np.asarray(dst_quad, np.float64)
+    if s.shape != (4, 2) or d.shape != (4, 2):
+        raise ValueError(f"perspective_map: two 4 x 2 quads, got {s.shape} and {d.shape}")
+    A, b = np.zeros((8, 8)), np.zeros(8)
+    for k in range(4):
+        x, y, u, v = s[k, 0], s[k, 1], d[k, 0], d[k, 1]
+        A[2 * k] = [x, y, 1, 0, 0, 0, -u * x, -u * y]
+        A[2 * k + 1] = [0, 0, 0, x, y, 1, -v * x, -v * y]
+        b[2 * k], b[2 * k + 1] = u, v
+    try:
+        h = np.linalg.solve(A, b)
+    except np.linalg.LinAlgError:
+        raise ValueError("perspective_map: the four point pairs do not determine a map") from None
+    if not np.isfinite(h).all():
+        raise ValueError("perspective_map: the four point pairs do not determine a map")
+    return np.append(h, 1.0)
 
 
 def orientation_code(o):
@@ -383,6 +412,9 @@ def hip_lib():
         lib.ocvar_hip_orient.argtypes = [vp, vp, i, i, i, sz, vp, i, sz, i, i, i, vp]
         lib.ocvar_hip_orient_records.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp, vp]
         lib.ocvar_hip_orient_camera.argtypes = [vp, i, vp]
+        lib.ocvar_hip_warp.argtypes = [vp, vp, i, i, i, sz, vp, i, i, i, sz, i, i, vp, i, i, vp, i, vp, vp]
+        lib.ocvar_hip_warp_records.argtypes = [vp, vp, vp, i, i, vp, i, vp, vp]
+        lib.ocvar_hip_board_plane_maps.argtypes = [vp, vp, i, vp, i, i, vp, vp]
         _hip = lib
     return _hip
 
@@ -906,6 +938,60 @@ class Detector:
         self._check(self._lib.ocvar_hip_orient_records(self._ctx, d_markers, d_counts, n_frames, per_frame, src_size[0], src_size[1],
                                                        orientation_code(orientation), ORIENT_POSE if pose else 0, d_out, stream), "orient_records")
 
+    def warp(self, d_src, src_width, src_height, d_dst, dst_width, dst_height, n_frames, d_maps, interp="linear", border="constant", fill=None,
+             inverse_map=False, one_map=False, fmt=None, src_row_stride=None, src_frame_stride=None, dst_row_stride=None,
+             dst_frame_stride=None, d_status_ptr=None, stream=None):
+        """n_frames device frames of src_width x src_height pixels at d_src in format fmt (default: the input format) warped into the
+        device frames of dst_width x dst_height at d_dst by the projective maps at d_maps: float64 [n_frames, 9] in device memory
+        ([9] with one_map), the forward maps from source to destination pixels as OpenCV's warpPerspective takes them (perspective_map
+        makes one), or with inverse_map the maps from destination to source pixels (board_plane_maps writes those).  interp 'linear'
+        or 'nearest'; border 'constant' (taps outside the source read fill, up to four bytes in the format's memory order, default
+        zeros) or 'replicate'.  d_status_ptr: device ints [n_frames], 1 where the frame was warped, 0 where its map is not finite or
+        singular -- such a frame's destination bytes are not touched.  The sizes are not bound by the detector's.  Source and
+        destination must not overlap.  Needs no batch, does not wait (stream None: the detector's own stream)."""
+        if not (isinstance(interp, str) and interp.lower() in WARP_INTERPS):
+            raise ValueError(f"unknown interpolation {interp!r}: one of {sorted(WARP_INTERPS)}")
+        if not (isinstance(border, str) and border.lower() in WARP_BORDERS):
+            raise ValueError(f"unknown border {border!r}: one of {sorted(WARP_BORDERS)}")
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        src_row_stride = src_row_stride or FORMAT_BPP[code] * src_width
+        src_frame_stride = src_frame_stride or src_row_stride * src_height
+        dst_row_stride = dst_row_stride or FORMAT_BPP[code] * dst_width
+        dst_frame_stride = dst_frame_stride or dst_row_stride * dst_height
+        fill4 = None
+        if fill is not None:
+            f = [int(v) for v in np.atleast_1d(fill)]
+            if len(f) > 4 or any(v < 0 or v > 255 for v in f):
+                raise ValueError("fill: up to four bytes")
+            fill4 = (C.c_uint8 * 4)(*(f + [0] * (4 - len(f))))
+        flags = (WARP_INVERSE_MAP if inverse_map else 0) | (WARP_ONE_MAP if one_map else 0)
+        self._check(self._lib.ocvar_hip_warp(self._ctx, d_src, src_width, src_height, src_row_stride, src_frame_stride, d_dst, dst_width,
+                                             dst_height, dst_row_stride, dst_frame_stride, n_frames, code, d_maps, WARP_INTERPS[interp.lower()],
+                                             WARP_BORDERS[border.lower()], fill4, flags, d_status_ptr, stream), "warp")
+
+    def warp_records(self, d_markers, d_counts, n_frames, d_out, d_maps, per_frame=None, one_map=False, pose=False, stream=None):
+        """the squares of the device records [n_frames, per_frame] (default per_frame: max_markers) under counts [n_frames] carried
+        through the forward maps at d_maps (float64 [n_frames, 9] in device memory, [9] with one_map) to where warp(...) puts those
+        frames' pixels, every other field copied, into the device records at d_out (which may be d_markers); slots at or beyond a
+        frame's count are not written; a corner the map sends to infinity becomes NaN.  pose: glMatrix is solved again from the new
+        square with the camera set at the call, which must be that of the warped frames.  Needs no batch, does not wait (stream None:
+        the detector's own stream)."""
+        per_frame = self.max_markers if per_frame is None else per_frame
+        flags = (WARP_ONE_MAP if one_map else 0) | (WARP_POSE if pose else 0)
+        self._check(self._lib.ocvar_hip_warp_records(self._ctx, d_markers, d_counts, n_frames, per_frame, d_maps, flags, d_out, stream),
+                    "warp_records")
+
+    def board_plane_maps(self, d_poses_ptr, n_frames, rect, dst_width, dst_height, d_maps, stream=None):
+        """for the n_frames board poses in device memory at d_poses_ptr (board_poses_to_device) the maps, float64 [n_frames, 9] into
+        the device memory at d_maps, that show the rectangle rect = (x0, y0, x1, y1) of the board's plane (board units) from straight
+        above in frames of dst_width x dst_height pixels: pixel (0, 0) is board point (x0, y0), pixel (dst_width - 1, dst_height - 1)
+        is (x1, y1) -- flip the picture by choosing y0 > y1.  They map destination to source pixels: warp(..., inverse_map=True).  The
+        camera matrix is the one set at the call; the lens is ignored, so undistort the frames first.  A frame without a solved pose
+        gets nine NaNs and warp skips it (status 0).  Needs no batch, does not wait (stream None: the detector's own stream)."""
+        r = (C.c_double * 4)(*[float(v) for v in rect])
+        self._check(self._lib.ocvar_hip_board_plane_maps(self._ctx, d_poses_ptr, n_frames, r, dst_width, dst_height, d_maps, stream),
+                    "board_plane_maps")
+
     def flow_records(self, d_prev, d_next, width, height, n_frames, d_markers, d_counts, d_out, per_frame=None, fmt=None,
                      prev_row_stride=None, prev_frame_stride=None, next_row_stride=None, next_frame_stride=None, params=None, pose=False,
                      d_status_ptr=None, d_err_ptr=None, stream=None):
@@ -930,7 +1016,8 @@ class Detector:
                                                      next_frame_stride, width, height, n_frames, code, d_markers, d_counts, per_frame,
                                                      C.byref(p), d_out, d_status_ptr, d_err_ptr, stream), "flow_records")
 
-    TUNE = {"crop_phases": 1, "mid_steps": 2, "mid_blocks": 3, "long_blocks": 4, "short_blocks": 5, "min_units": 6, "hp_mask": 7, "gate_mode": 8}
+    TUNE = {"crop_phases": 1, "mid_steps": 2, "mid_blocks": 3, "long_blocks": 4, "short_blocks": 5, "min_units": 6, "hp_mask": 7, "gate_mode": 8,
+            "warp_direct": 9}
 
     def set_tuning(self, **kw):
         """result-invariant launch parameters (include/ocvar_hip.h: OCVAR_TUNE_*); 0 restores a default"""

@@ -1220,6 +1220,94 @@ extern "C" int ocvar_hip_orient_camera(const OcvarCamera* in, int orientation, O
     return orient_camera(*reinterpret_cast<const CameraRec*>(in), orientation, reinterpret_cast<CameraRec*>(out)) ? OCVAR_OK : OCVAR_E_ARG;
 }
 
+extern "C" int ocvar_hip_warp(OcvarHip* c, const uint8_t* d_src, int src_width, int src_height, int src_row_stride, size_t src_frame_stride,
+                              uint8_t* d_dst, int dst_width, int dst_height, int dst_row_stride, size_t dst_frame_stride, int n_frames, int format,
+                              const double* d_maps, int interpolation, int border, const uint8_t* fill, int flags, int* d_status, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    const auto refuse = [&](const char* text) {
+        c->err = std::string("warp: ") + text;
+        return OCVAR_E_ARG;
+    };
+    if (!d_src || !d_dst || !d_maps) return refuse("no source frames, no destination frames or no maps");
+    const int bpp = patch_bpp(format);
+    if (bpp == 0 || !warp_interp_ok(interpolation) || !warp_border_ok(border)) return refuse("an unknown format, interpolation or border");
+    if (flags & ~WARP_FLAGS) return refuse("unknown flag bits");
+    const auto side_ok = [](int v) { return v >= 1 && v <= WARP_MAX_SIDE; };
+    if (!side_ok(src_width) || !side_ok(src_height) || !side_ok(dst_width) || !side_ok(dst_height)) return refuse("sides of 1 .. 32767 pixels");
+    if (n_frames < 1) return refuse("n_frames >= 1");
+    if ((long long)src_row_stride < (long long)bpp * src_width || (long long)dst_row_stride < (long long)bpp * dst_width)
+        return refuse("a row stride below the format's bytes per pixel times width");
+    const auto span = [&](int width, int height, int row_stride) { return (long long)(height - 1) * row_stride + (long long)bpp * width; };
+    if (span(src_width, src_height, src_row_stride) > 2147483647LL || span(dst_width, dst_height, dst_row_stride) > 2147483647LL)
+        return refuse("the rows of a frame span more than 2147483647 bytes");
+    const unsigned long long s0 = (unsigned long long)(uintptr_t)d_src, d0 = (unsigned long long)(uintptr_t)d_dst;
+    const unsigned long long s1 = s0 + frames_extent(src_width, src_height, bpp, src_row_stride, src_frame_stride, n_frames);
+    const unsigned long long d1 = d0 + frames_extent(dst_width, dst_height, bpp, dst_row_stride, dst_frame_stride, n_frames);
+    if (s0 < d1 && d0 < s1) return refuse("the byte ranges of source and destination frames intersect (no warping in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    const bool one = (flags & OCVAR_WARP_ONE_MAP) != 0;
+    for (int f0 = 0; f0 < n_frames; f0 += WARP_CHUNK_FRAMES) {
+        WarpArgs a{d_src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, src_width, src_height, dst_width, dst_height,
+                   (long long)src_row_stride, (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride,
+                   one ? d_maps : d_maps + 9 * (size_t)f0, d_status ? d_status + f0 : nullptr, interpolation, border, flags,
+                   c->tune[OCVAR_TUNE_WARP_DIRECT] == 1, {0, 0, 0, 0}};
+        for (int k = 0; k < 4; k++) a.fill[k] = fill ? fill[k] : 0;
+        launch_warp(a, std::min(WARP_CHUNK_FRAMES, n_frames - f0), format, s);
+        TRACE_LAUNCH("warp", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_warp_records(OcvarHip* c, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
+                                      const double* d_maps, int flags, OcvarMarker* d_out, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    const auto refuse = [&](const char* text) {
+        c->err = std::string("warp_records: ") + text;
+        return OCVAR_E_ARG;
+    };
+    if (!d_markers || !d_counts || !d_maps || !d_out) return refuse("no records, no counts, no maps or no output");
+    if (n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm) return refuse("n_frames >= 1, 1 .. M records per frame");
+    if (flags & ~WARP_REC_FLAGS) return refuse("unknown flag bits");
+    if (flags & OCVAR_WARP_INVERSE_MAP) return refuse("OCVAR_WARP_INVERSE_MAP: the records need the forward map");
+    if ((flags & OCVAR_WARP_POSE) && !c->have_camera) return refuse("OCVAR_WARP_POSE without a camera");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    const int chunk = 65535;
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const WarpRecArgs a{reinterpret_cast<const MarkerRec*>(d_markers) + (size_t)f0 * records_per_frame,
+                            reinterpret_cast<MarkerRec*>(d_out) + (size_t)f0 * records_per_frame, d_counts + f0, records_per_frame,
+                            (flags & OCVAR_WARP_ONE_MAP) ? d_maps : d_maps + 9 * (size_t)f0, flags, c->h_camera};
+        launch_warp_records(a, std::min(chunk, n_frames - f0), s);
+        TRACE_LAUNCH("warp_records", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_board_plane_maps(OcvarHip* c, const OcvarBoardPose* d_poses, int n_frames, const double* rect, int dst_width,
+                                          int dst_height, double* d_maps, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    const auto refuse = [&](const char* text) {
+        c->err = std::string("board_plane_maps: ") + text;
+        return OCVAR_E_ARG;
+    };
+    if (!d_poses || !rect || !d_maps) return refuse("no poses, no rectangle or no maps");
+    if (n_frames < 1) return refuse("n_frames >= 1");
+    if (dst_width < 1 || dst_width > WARP_MAX_SIDE || dst_height < 1 || dst_height > WARP_MAX_SIDE) return refuse("sides of 1 .. 32767 pixels");
+    if (!c->have_camera) return refuse("no camera set");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    WarpBoardMapArgs a{d_poses, d_maps, n_frames, dst_width, dst_height, {}, {}};
+    for (int i = 0; i < 9; i++) a.K[i] = c->h_camera.cameraMatrix[i];
+    for (int i = 0; i < 4; i++) a.rect[i] = rect[i];
+    launch_warp_board_maps(a, s);
+    TRACE_LAUNCH("board_plane_maps", s);
+    HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
 // a parameter of ocvar_hip_flow_records that must be a finite number >= 0
 static bool flow_number_ok(float v) { return v >= 0.0f && v <= 3.0e38f; }
 

@@ -13,6 +13,7 @@
 #include "yuv_core.h"
 #include "resize_core.h"
 #include "orient_core.h"
+#include "warp_core.h"
 #include "flow_core.h"
 #include "croplist_core.h"
 #include "ocvar_hip.h"
@@ -280,6 +281,36 @@ struct OrientRecArgs {
 };
 // n_frames (at most 65535: the grid's y) frames
 void launch_orient_records(const OrientRecArgs& a, int n_frames, hipStream_t stream);
+
+// One launch of warp_kernel (warp.hip) on the n_frames (at most WARP_CHUNK_FRAMES: the grid's z) frames in `format` of a
+// (warp_core.h: WarpArgs), whose two sides do not overlap.
+constexpr int WARP_CHUNK_FRAMES = 65535;
+void launch_warp(const WarpArgs& a, int n_frames, int format, hipStream_t stream);
+
+// One launch of warp_records_kernel: of frame f the records in[f * slots + k], k < min(counts[f], slots), to the same slots of out
+// (which may be in), their squares carried through the forward map maps[9 f ..] (maps[0 ..] with OCVAR_WARP_ONE_MAP), device
+// memory; flags OCVAR_WARP_*, cam by value: the context's at the call.
+struct WarpRecArgs {
+    const MarkerRec* in;
+    MarkerRec* out;
+    const int* counts;
+    int slots;
+    const double* maps;
+    int flags;
+    CameraRec cam;
+};
+// n_frames (at most 65535: the grid's y) frames
+void launch_warp_records(const WarpRecArgs& a, int n_frames, hipStream_t stream);
+
+// One launch of warp_board_maps_kernel: maps[9 f ..] = warp_board_plane_map(poses[f], K, rect, dw, dh) for f < n_frames; K and rect
+// by value.
+struct WarpBoardMapArgs {
+    const OcvarBoardPose* poses;
+    double* maps;
+    int n_frames, dw, dh;
+    double K[9], rect[4];
+};
+void launch_warp_board_maps(const WarpBoardMapArgs& a, hipStream_t stream);
 
 // The pyramids of n_frames frames in `format` (flow.hip: flow_grey_kernel, then flow_down_kernel level by level): frame f's
 // levels 0 .. g.L go to pyr + f * slot_bytes, laid out as g says.

@@ -26,7 +26,16 @@ struct CameraRec {  // == CvarCamera (include/opencvar/opencvar.h), 248 bytes
     double glProjection[16];
 };
 
-template <bool WITH_J>
+// where rodrigues_t takes sine and cosine from: the math library (a core whose results must not depend on the library's last bits
+// names a policy of its own: warp_core.h)
+struct LibSinCos {
+    static OCVAR_HD void at(double theta, double* s, double* c) {
+        *c = cos(theta);
+        *s = sin(theta);
+    }
+};
+
+template <bool WITH_J, class SinCos = LibSinCos>
 OCVAR_HD void rodrigues_t(const double* r, double* R, double* J /* 3x9 when WITH_J */) {
     double rx = r[0], ry = r[1], rz = r[2];
     const double theta = sqrt(rx * rx + ry * ry + rz * rz);
@@ -41,7 +50,9 @@ OCVAR_HD void rodrigues_t(const double* r, double* R, double* J /* 3x9 when WITH
         }
         return;
     }
-    const double c = cos(theta), s = sin(theta), c1 = 1. - c, it = 1. / theta;
+    double c, s;
+    SinCos::at(theta, &s, &c);
+    const double c1 = 1. - c, it = 1. / theta;
     rx *= it;
     ry *= it;
     rz *= it;
