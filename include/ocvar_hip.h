@@ -740,6 +740,21 @@ int ocvar_hip_debug_frame_quads(OcvarHip* ctx, int frame, int* quads /* OCVAR_MA
 /* the pre-dedupe candidates in the reference's order (square-major, all templates of every square with a crop quad); at most
  * max_cands are written, *n_cands is the full count */
 int ocvar_hip_debug_candidates(OcvarHip* ctx, int frame, OcvarCandidate* cands, int max_cands, int* n_cands);
+/* The crop pass of the last collected batch: the rectangle around every frame-pass square (grown by 5 px, clipped by the frame)
+ * that the second pass binarises and searches on its own.  index: the ROI's place in the batch's list (the order is not
+ * defined: the squares of a batch append concurrently); owner: the index of the frame-pass square (ocvar_hip_debug_frame_quads)
+ * within `frame`; x0, y0, w, h: the rectangle in frame pixels.  ocvar_hip_debug_crop_rois writes the first max_rois records
+ * and stores the full count, which is at most the context's ROI capacity (max_batch x squares per frame).
+ * ocvar_hip_debug_crop_plane expands the bit plane of ROI `roi` to a byte per pixel, (w & ~1) x (h & ~1) bytes: masks == 0 the
+ * binary image (0 / 255, the 1-px frame zero) as ocvar_hip_debug_binary gives a frame's, else the 8-neighbour masks as
+ * ocvar_hip_debug_masks.  Both copy out of the workspace and launch nothing; they are valid from ocvar_hip_collect (or a
+ * detect call) until the context's next enqueue, and return OCVAR_E_ARG for a bad index, while a batch is in flight, and when
+ * no batch with a crop pass has been collected. */
+typedef struct OcvarCropRoi {
+    int index, frame, owner, x0, y0, w, h;
+} OcvarCropRoi;
+int ocvar_hip_debug_crop_rois(OcvarHip* ctx, OcvarCropRoi* rois, int max_rois, int* n_rois);
+int ocvar_hip_debug_crop_plane(OcvarHip* ctx, int roi, int masks, uint8_t* h_plane /* (w&~1)*(h&~1) */);
 
 /* Measurement aid: runs a dword-per-lane copy of `bytes` bytes (the binarise kernel's access widths) so that a
  * rocprofv3 PMC pass can calibrate FETCH_SIZE / WRITE_SIZE for that pattern (tools/collect_traffic.py). */

@@ -27,6 +27,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_pipe_detect_device", "ocvar_hip_pipe_track_device", "ocvar_hip_pipe_submit", "ocvar_hip_pipe_collect", "ocvar_hip_pipe_in_flight", "ocvar_hip_pipe_set_result_limit", "ocvar_hip_set_input_format", "ocvar_hip_pipe_set_input_format", "ocvar_hip_set_corner_refine", "ocvar_hip_pipe_set_corner_refine", "ocvar_hip_enqueue_tracked", "ocvar_hip_build_info", "ocvar_hip_set_tuning", "ocvar_hip_destroy", "ocvar_hip_last_error", "ocvar_hip_set_templates", "ocvar_hip_set_camera",
     "ocvar_hip_detect_device", "ocvar_hip_enqueue", "ocvar_hip_collect", "ocvar_hip_detect_host", "ocvar_hip_find_squares",
     "ocvar_hip_debug_gray", "ocvar_hip_debug_binary", "ocvar_hip_debug_masks", "ocvar_hip_debug_frame_quads", "ocvar_hip_debug_candidates",
+    "ocvar_hip_debug_crop_rois", "ocvar_hip_debug_crop_plane",
     "ocvar_hip_stage_ms", "ocvar_hip_stream", "ocvar_hip_stage_stamps", "ocvar_hip_counters", "ocvar_hip_results_to_device", "ocvar_hip_results_to_device_ex", "ocvar_hip_debug_calibrate",
     "ocvar_hip_set_board", "ocvar_hip_board_poses", "ocvar_hip_board_poses_to_device",
     "ocvar_hip_set_overlay", "ocvar_hip_render", "ocvar_hip_render_records",
@@ -308,6 +309,9 @@ class Candidate(C.Structure):
                 ("bit", C.c_longlong), ("square", C.c_float * 8), ("patPoint", C.c_float * 8)]
 
 
+# OcvarCropRoi: a crop of the second pass (Detector.debug_crops)
+CROP_ROI_DTYPE = np.dtype([(n, "<i4") for n in ("index", "frame", "owner", "x0", "y0", "w", "h")])
+
 MARKER_DTYPE = np.dtype([("glMatrix", "<f8", (16,)), ("templateId", "<i4"), ("markerId", "<i4"), ("score", "<f8"),
                          ("square", "<f4", (8,)), ("aspectRatio", "<f8")], align=True)
 assert C.sizeof(Camera) == 248 and C.sizeof(Template) == 48 and C.sizeof(Marker) == 184 and MARKER_DTYPE.itemsize == 184
@@ -383,6 +387,8 @@ def hip_lib():
         lib.ocvar_hip_debug_masks.argtypes = [vp, i, vp]
         lib.ocvar_hip_debug_frame_quads.argtypes = [vp, i, vp, vp]
         lib.ocvar_hip_debug_candidates.argtypes = [vp, i, vp, i, vp]
+        lib.ocvar_hip_debug_crop_rois.argtypes = [vp, vp, i, vp]
+        lib.ocvar_hip_debug_crop_plane.argtypes = [vp, i, i, vp]
         lib.ocvar_hip_stage_ms.argtypes = [vp, vp, i]
         lib.ocvar_hip_counters.argtypes = [vp, vp, i]
         lib.ocvar_hip_stage_stamps.argtypes = [vp, vp, vp, i]
@@ -1100,6 +1106,34 @@ class Detector:
         arr = (Candidate * max_cands)()
         self._check(self._lib.ocvar_hip_debug_candidates(self._ctx, frame, arr, max_cands, C.byref(n)), "debug_candidates")
         return [arr[i] for i in range(min(n.value, max_cands))]
+
+    def debug_crops(self):
+        """the crop ROIs of the last collected batch, [n] CROP_ROI_DTYPE (index, frame, owner = index of the frame-pass square,
+        x0, y0, w, h), in the batch's own order; valid until the next enqueue"""
+        n = C.c_int(0)
+        self._check(self._lib.ocvar_hip_debug_crop_rois(self._ctx, None, 0, C.byref(n)), "debug_crop_rois")
+        out = np.zeros(max(n.value, 1), CROP_ROI_DTYPE)
+        self._check(self._lib.ocvar_hip_debug_crop_rois(self._ctx, _ptr(out), n.value, C.byref(n)), "debug_crop_rois")
+        return out[:n.value]
+
+    def _debug_crop_plane(self, roi, masks):
+        # the buffer is sized by the ROI as the context holds it now: a record kept from an earlier batch is refused
+        rois = self.debug_crops()
+        r = rois[int(roi["index"]) if isinstance(roi, np.void) else int(roi)]   # (IndexError for an index past the list)
+        if isinstance(roi, np.void) and roi != r:
+            raise ValueError("debug_crop_plane: the record is not of the last collected batch")
+        out = np.zeros((int(r["h"]) & -2, int(r["w"]) & -2), np.uint8)
+        self._check(self._lib.ocvar_hip_debug_crop_plane(self._ctx, int(r["index"]), int(masks), _ptr(out)), "debug_crop_plane")
+        return out
+
+    def debug_crop_binary(self, roi):
+        """the binary image (0 / 255, the 1-px frame zero) of crop `roi` -- an index into debug_crops() or one of its records --
+        of the last collected batch, (h & ~1) x (w & ~1)"""
+        return self._debug_crop_plane(roi, False)
+
+    def debug_crop_masks(self, roi):
+        """the 8-neighbour masks of crop `roi`, as debug_masks gives a frame's"""
+        return self._debug_crop_plane(roi, True)
 
     def stage_ms(self):
         ms = np.zeros(12, np.float32)

@@ -306,6 +306,7 @@ int ocvar::enqueue_impl(OcvarHip* c, const BatchRequest& r, hipStream_t s, hipSt
     }
     HIP_TRY(c, hipSetDevice(c->device));
     c->batch_board = false;
+    c->crops_ran = false;   // (from here on the workspace belongs to this batch)
     plan_batch(&w, r.width, r.height, n_frames, c->gate != nullptr,
                PlanOverrides{tuned(c, OCVAR_TUNE_CROP_PHASES, "OCVAR_CROP_PHASES"), tuned(c, OCVAR_TUNE_MID_STEPS, "OCVAR_MID_STEPS"),
                              tuned(c, OCVAR_TUNE_MID_BLOCKS, "OCVAR_MID_BLOCKS"), tuned(c, OCVAR_TUNE_LONG_BLOCKS, "OCVAR_LONG_BLOCKS"),
@@ -444,6 +445,7 @@ int ocvar::enqueue_impl(OcvarHip* c, const BatchRequest& r, hipStream_t s, hipSt
     c->last_stream = s;
     c->copy_pending = false;
     c->pending = true;
+    c->crops_ran = stages > 2;
     return OCVAR_OK;
 }
 

@@ -118,6 +118,7 @@ struct OcvarHip {
     ocvar::PinnedBuffer<int> h_counts;
     ocvar::PinnedBuffer<int> h_counters;
     bool pending = false;
+    bool crops_ran = false;            // the last batch ran the crop pass (ocvar_hip_debug_crop_*: its ROIs and planes are in the workspace)
     bool have_templates = false, have_camera = false;
     ocvar::CameraRec h_camera{};   // the camera as last set, for the entry points that pass it by value (ocvar_hip_undistort)
     ocvar::Library lib;       // the templates' table as uploaded (ocvar_hip_debug_candidates expands a square with it)

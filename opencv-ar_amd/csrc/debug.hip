@@ -55,6 +55,51 @@ extern "C" int ocvar_hip_debug_frame_quads(OcvarHip* c, int frame, int* quads, i
     return quads_to_host(c, frame, c->ws.maxq < OCVAR_MAX_QUADS ? c->ws.maxq : OCVAR_MAX_QUADS, quads, n_quads);
 }
 
+// The crop pass of the last collected batch.  Its ROI records and bit planes stay in the workspace until the next enqueue;
+// nothing is launched here.  The ROI count comes from the batch's own counter copy (collect has waited for it).
+static int crop_count(const OcvarHip* c) {
+    if (!c || c->pending || !c->crops_ran || c->ws.n_frames < 1 || !c->h_counters.p) return -1;
+    if (c->h_counters[CNT_ERR] & (ERR_CROP_OVERFLOW | ERR_TILE_OVERFLOW)) return -1;   // (ROIs past a pool's end were never written)
+    const int n = c->h_counters[CNT_CROP_ROIS];
+    return n < 0 ? -1 : (n < c->ws.cap_crop_rois ? n : c->ws.cap_crop_rois);
+}
+
+extern "C" int ocvar_hip_debug_crop_rois(OcvarHip* c, OcvarCropRoi* rois, int max_rois, int* n_rois) {
+    const int n = crop_count(c);
+    if (n < 0 || !n_rois || max_rois < 0 || (max_rois > 0 && !rois)) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int k = n < max_rois ? n : max_rois;
+    std::vector<Roi> r((size_t)(k > 0 ? k : 1));
+    if (k > 0) HIP_TRY(c, hipMemcpy(r.data(), c->ws.rois_crop, (size_t)k * sizeof(Roi), hipMemcpyDeviceToHost));
+    for (int i = 0; i < k; i++) {
+        OcvarCropRoi& o = rois[i];
+        o.index = i; o.frame = r[i].frame; o.owner = r[i].owner;
+        o.x0 = r[i].x0; o.y0 = r[i].y0; o.w = r[i].w; o.h = r[i].h;
+    }
+    *n_rois = n;
+    return OCVAR_OK;
+}
+
+// One crop's bit plane expanded to a byte per pixel, (w & ~1) x (h & ~1), as plane_to_host does for a frame.
+extern "C" int ocvar_hip_debug_crop_plane(OcvarHip* c, int roi, int masks, uint8_t* h) {
+    const int n = crop_count(c);
+    if (n < 0 || !h || roi < 0 || roi >= n) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Roi r;
+    HIP_TRY(c, hipMemcpy(&r, c->ws.rois_crop + roi, sizeof(Roi), hipMemcpyDeviceToHost));
+    const long long bytes = r.ns > 0 && r.sh > 0 ? nbr_plane_bytes(r.ns, r.sh) : 0;
+    if (r.sw < 2 || r.sh < 2 || r.sw > r.ns || (r.ns & 15) || r.nbr_off < 0 || r.nbr_off + bytes > c->ws.cap_crop_pixels) {
+        c->err = "ocvar_hip_debug_crop_plane: the ROI record does not describe a plane of the crop pool";
+        return OCVAR_E_ARG;
+    }
+    std::vector<uint8_t> nbr((size_t)bytes);
+    HIP_TRY(c, hipMemcpy(nbr.data(), c->ws.nbr_crop + r.nbr_off, (size_t)bytes, hipMemcpyDeviceToHost));
+    for (int y = 0; y < r.sh; y++)
+        for (int x = 0; x < r.sw; x++)
+            h[(size_t)y * r.sw + x] = masks ? (uint8_t)nbr_of(nbr.data(), x, y, r.ns) : (nbr_bit(nbr.data(), x, y, r.ns) ? 255 : 0);
+    return OCVAR_OK;
+}
+
 extern "C" int ocvar_hip_debug_candidates(OcvarHip* c, int frame, OcvarCandidate* cands, int max_cands, int* n_cands) {
     if (!c || !cands || !n_cands || frame < 0 || frame >= c->ws.n_frames) return OCVAR_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
