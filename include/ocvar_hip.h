@@ -756,6 +756,18 @@ typedef struct OcvarCropRoi {
 int ocvar_hip_debug_crop_rois(OcvarHip* ctx, OcvarCropRoi* rois, int max_rois, int* n_rois);
 int ocvar_hip_debug_crop_plane(OcvarHip* ctx, int roi, int masks, uint8_t* h_plane /* (w&~1)*(h&~1) */);
 
+/* The border starts of the last collected batch: the list the binarise kernel of the frame pass (crop_pass == 0) or of the crop
+ * pass (crop_pass != 0) handed to the border followers -- every pixel at which a border can begin, found from the pixel's
+ * neighbours alone.  roi: the frame's index in the batch, or the crop's index in ocvar_hip_debug_crop_rois' list; x, y: the
+ * pixel in that frame's or crop's binary image; is_hole: 1 for the start of a hole border.  The order of the list differs from
+ * run to run.  Writes the first max_starts records and stores the full count (what ocvar_hip_counters reports in slots 0 and 3,
+ * clamped to the list's capacity).  Copies out of the workspace and launches nothing; valid like ocvar_hip_debug_crop_rois, and
+ * for crop_pass != 0 only after a batch that ran the crop pass. */
+typedef struct OcvarStart {
+    int roi, x, y, is_hole;
+} OcvarStart;
+int ocvar_hip_debug_starts(OcvarHip* ctx, int crop_pass, OcvarStart* starts, int max_starts, int* n_starts);
+
 /* Measurement aid: runs a dword-per-lane copy of `bytes` bytes (the binarise kernel's access widths) so that a
  * rocprofv3 PMC pass can calibrate FETCH_SIZE / WRITE_SIZE for that pattern (tools/collect_traffic.py). */
 int ocvar_hip_debug_calibrate(OcvarHip* ctx, size_t bytes);

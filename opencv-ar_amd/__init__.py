@@ -27,7 +27,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_pipe_detect_device", "ocvar_hip_pipe_track_device", "ocvar_hip_pipe_submit", "ocvar_hip_pipe_collect", "ocvar_hip_pipe_in_flight", "ocvar_hip_pipe_set_result_limit", "ocvar_hip_set_input_format", "ocvar_hip_pipe_set_input_format", "ocvar_hip_set_corner_refine", "ocvar_hip_pipe_set_corner_refine", "ocvar_hip_enqueue_tracked", "ocvar_hip_build_info", "ocvar_hip_set_tuning", "ocvar_hip_destroy", "ocvar_hip_last_error", "ocvar_hip_set_templates", "ocvar_hip_set_camera",
     "ocvar_hip_detect_device", "ocvar_hip_enqueue", "ocvar_hip_collect", "ocvar_hip_detect_host", "ocvar_hip_find_squares",
     "ocvar_hip_debug_gray", "ocvar_hip_debug_binary", "ocvar_hip_debug_masks", "ocvar_hip_debug_frame_quads", "ocvar_hip_debug_candidates",
-    "ocvar_hip_debug_crop_rois", "ocvar_hip_debug_crop_plane",
+    "ocvar_hip_debug_crop_rois", "ocvar_hip_debug_crop_plane", "ocvar_hip_debug_starts",
     "ocvar_hip_stage_ms", "ocvar_hip_stream", "ocvar_hip_stage_stamps", "ocvar_hip_counters", "ocvar_hip_results_to_device", "ocvar_hip_results_to_device_ex", "ocvar_hip_debug_calibrate",
     "ocvar_hip_set_board", "ocvar_hip_board_poses", "ocvar_hip_board_poses_to_device",
     "ocvar_hip_set_overlay", "ocvar_hip_render", "ocvar_hip_render_records",
@@ -311,6 +311,8 @@ class Candidate(C.Structure):
 
 # OcvarCropRoi: a crop of the second pass (Detector.debug_crops)
 CROP_ROI_DTYPE = np.dtype([(n, "<i4") for n in ("index", "frame", "owner", "x0", "y0", "w", "h")])
+# OcvarStart: a border start of the frame or crop pass (Detector.debug_starts)
+START_DTYPE = np.dtype([(n, "<i4") for n in ("roi", "x", "y", "is_hole")])
 
 MARKER_DTYPE = np.dtype([("glMatrix", "<f8", (16,)), ("templateId", "<i4"), ("markerId", "<i4"), ("score", "<f8"),
                          ("square", "<f4", (8,)), ("aspectRatio", "<f8")], align=True)
@@ -389,6 +391,7 @@ def hip_lib():
         lib.ocvar_hip_debug_candidates.argtypes = [vp, i, vp, i, vp]
         lib.ocvar_hip_debug_crop_rois.argtypes = [vp, vp, i, vp]
         lib.ocvar_hip_debug_crop_plane.argtypes = [vp, i, i, vp]
+        lib.ocvar_hip_debug_starts.argtypes = [vp, i, vp, i, vp]
         lib.ocvar_hip_stage_ms.argtypes = [vp, vp, i]
         lib.ocvar_hip_counters.argtypes = [vp, vp, i]
         lib.ocvar_hip_stage_stamps.argtypes = [vp, vp, vp, i]
@@ -1134,6 +1137,15 @@ class Detector:
     def debug_crop_masks(self, roi):
         """the 8-neighbour masks of crop `roi`, as debug_masks gives a frame's"""
         return self._debug_crop_plane(roi, True)
+
+    def debug_starts(self, crop_pass=False):
+        """the border starts the binarise kernel of the last collected batch's frame pass (or crop pass) handed to the followers,
+        [n] START_DTYPE (roi = frame of the batch or index into debug_crops(), x, y, is_hole); the order differs from run to run"""
+        n = C.c_int(0)
+        self._check(self._lib.ocvar_hip_debug_starts(self._ctx, int(bool(crop_pass)), None, 0, C.byref(n)), "debug_starts")
+        out = np.zeros(max(n.value, 1), START_DTYPE)
+        self._check(self._lib.ocvar_hip_debug_starts(self._ctx, int(bool(crop_pass)), _ptr(out), n.value, C.byref(n)), "debug_starts")
+        return out[:n.value]
 
     def stage_ms(self):
         ms = np.zeros(12, np.float32)

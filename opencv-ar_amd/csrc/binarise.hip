@@ -10,12 +10,11 @@
 // columns + an 8-column halo on each side) and walks down a chunk of rows.  Everything vertical lives in registers and nothing
 // is a window that is shifted: the vertical pyrDown is two accumulators, the vertical pyrUp two running sums (times four, so a
 // finished pixel is the high byte of its sum), the last 8 pyrUp rows a ring of bytes in two registers per pixel that swap names
-// every four rows, the start nibbles of the last threshold row a register; everything horizontal is a 4-pixel packed
-// word handed to the neighbour lane with a DPP wave shift.  One (unaligned) buffer load per lane and row, reflected columns
+// every four rows; everything horizontal is a 4-pixel packed word handed to the neighbour lane with a DPP wave shift.  One (unaligned) buffer load per lane and row, reflected columns
 // included, two rows under way beyond the current one; rows are addressed through buffer resources (scalar row offset,
-// loop-invariant lane offset, stores masked by range).  The image itself never goes through LDS, which only holds a 128-entry
-// table (threshold-bit window -> border-start nibbles), a ring of 16 threshold rows per wave (a nibble per lane) on their way to
-// whole 16x14 bit tiles, and the staged border starts.  The grey plane is stored in 256-byte panels, one per strip (hd.h::gray_col):
+// loop-invariant lane offset, stores masked by range).  The image itself never goes through LDS, which only holds a ring of 32
+// threshold rows per wave (a nibble per lane) on their way to whole 16x14 bit tiles -- where the border starts of the tile row are
+// found on the way, 32 columns at a time (starts_core.h) -- and the staged border starts.  The grey plane is stored in 256-byte panels, one per strip (hd.h::gray_col):
 // every store of the kernel is whole 64-byte sectors.  The row body exists in several instances (steady rows in groups of four
 // with the ring's position known, strips away from the image edges) so that the hot loop carries no range tests; the filters'
 // border rules at the image edges are per-lane byte selectors.
@@ -24,6 +23,7 @@
 //   pyrDown  [1 4 6 4 1]^2, (v+128)>>8, BORDER_REFLECT_101        pyrUp  [1 6 1]/[4 4], (v+32)>>6, borders -1->1, n->n-1
 //   Gaussian [8 28 56 72 56 28 8]^2, (v+32768)>>16, BORDER_REPLICATE    threshold  src - mean > -8
 #include "kernels.h"
+#include "starts_core.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -55,7 +55,8 @@ constexpr int SV = MARCH_STRIP;  // output columns per strip
 // lane on the right would only serve the start filter's "row above at x+2" bit of the strip's last column, which is
 // dropped instead (the filter is a necessary condition: without it that column merely yields a few more plausible starts).
 // 240 output columns: 8 strips across 1920, 16 across 3840.
-constexpr int HL = MARCH_HALO_L, HR = MARCH_HALO_R;
+constexpr int HL = MARCH_HALO_L;   // (MARCH_HALO_R lanes on the right: static_assert in kernels.h ties both to the strip)
+constexpr int RING_ROWS = 32;   // threshold rows a wave keeps in LDS (march_unit::flush_due): a tile row's 16 and the rows of one more group
 
 // A value that is the same in all lanes of the wave, moved to an SGPR.  The work-unit index comes from threadIdx.x >> 6,
 // which the compiler must treat as per-lane: without this every row counter of the march lives in a VGPR, every loop
@@ -116,34 +117,6 @@ __device__ __forceinline__ void first_bit(unsigned& nib, unsigned S, unsigned w)
     if constexpr (B == 3) asm("v_cmp_lt_i32_sdwa vcc, sext(%1), %2 src0_sel:WORD_1 src1_sel:BYTE_3\n\tv_cndmask_b32_e64 %0, 0, 1, vcc" : "=v"(nib) : "v"(S), "v"(w) : "vcc");
 }
 
-// ---- border starts by table ----------------------------------------------------------------------------------------
-// A lane's 4 threshold bits of one row plus the bits next to them form a 7-bit window: bit 0 = column c0-1 (the left
-// lane's pixel 3), bits 1..4 = the lane's pixels 0..3, bits 5, 6 = columns c0+4, c0+5 (the right lane's pixels 0, 1).
-// What a row contributes to the border-start tests of the 4 pixels depends on that window only, so it is read from a
-// 128-entry table in LDS (one ds_read_b32 per lane and row) instead of being spread out bit by bit.  Start nibbles (bit p =
-// pixel p).  Low half, the row as the pixels' own row:  [0] centre & ~W   [1] E   [2] W & ~centre   [3] ~E.  High half, the
-// row as the row above:  [4] ~(NW | N | NE)   [5] the pixel above E's east neighbour   [6] N   [7] ~NE.  With t = low(own row)
-// & high(row above), t & ~(t >> 4) has the outer starts in nibble 0 (centre & ~W & ~NW & ~N & ~NE & ~(E & NEE)) and the hole
-// starts in nibble 2 (W & ~centre & N & (E | NE)): the necessary local conditions for being the raster-first pixel of a
-// region (see march_unit).
-__device__ __forceinline__ unsigned start_table_entry(unsigned w) {
-    unsigned mA = 0, mB = 0, mC = 0, uA = 0, uB = 0, uC = 0, uD = 0;
-    for (unsigned p = 0; p < 4; p++) {
-        const unsigned xm = (w >> p) & 1u, x0 = (w >> (p + 1)) & 1u, xp = (w >> (p + 2)) & 1u, xpp = (w >> (p + 3)) & 1u;
-        mA |= (x0 & ~xm & 1u) << p;
-        mB |= xp << p;
-        mC |= (xm & ~x0 & 1u) << p;
-        uA |= (~(xm | x0 | xp) & 1u) << p;
-        uB |= xpp << p;
-        uC |= x0 << p;
-        uD |= xp << p;
-    }
-    return mA | (mB << 4) | (mC << 8) | ((~mB & 15u) << 12) | (uA << 16) | (uB << 20) | (uC << 24) | ((~uD & 15u) << 28);
-}
-
-// table index (march_unit: bits 0..3 own pixels, bit 4 the left lane's pixel 3, bits 5, 6 the right lane's pixels 0, 1) -> window
-__device__ __forceinline__ unsigned table_window(unsigned i) { return ((i >> 4) & 1u) | ((i & 15u) << 1) | ((i >> 5) << 5); }
-
 struct MarchOut {
     uint8_t* gray;          // frame mode: grey plane of this frame (stride gray_stride), else null
     long long gray_stride;
@@ -168,7 +141,7 @@ constexpr int src_bpp(int src) { return src == OCVAR_FMT_BGR || src == OCVAR_FMT
 // filters and their lane masks are compiled out -- six of a 1080p frame's eight strips; a crop's strips always touch an edge.
 template <int SRC, bool EDGE>
 __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /* crops: the ROI's first column in the frame's grey plane */, int sw, int sh, int strip, int Y0, int Y1, const MarchOut& o,
-                           unsigned* stage, uint8_t* rowbuf /* LDS, 16 rows x 64 lanes */, const unsigned* tab /* LDS, start_table_entry */) {
+                           unsigned* stage, uint8_t* rowbuf /* LDS, RING_ROWS rows x 64 lanes */) {
     constexpr bool FRAME = SRC != SRC_CROP;
     constexpr int BPP = src_bpp(SRC);   // bytes per source pixel
     constexpr bool FOUR = BPP == 4;
@@ -177,7 +150,6 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     const int c0 = XS + 4 * lane;
     const int pw = sw >> 1, ph_ = sh >> 1;
     const int k0 = c0 >> 1;  // pyramid column of the lane's first pyramid sample (c0 is a multiple of 4)
-    const bool out_lane = lane >= HL && lane < 64 - HR && (!EDGE || c0 < sw);
     const bool needed = !EDGE || (c0 + 3 >= -16 && c0 < sw + 16);  // beyond every halo: never consumed
     const bool fast = !EDGE || (c0 >= 0 && c0 + 3 < sw);
     const bool aligned = FRAME ? ((src_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0) : true;
@@ -236,58 +208,8 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     // the grey plane's panel of this strip (hd.h::gray_col): all 64 lanes store, 256 contiguous bytes at a 256-byte boundary -- the
     // halo lanes' bytes are the neighbouring strips' columns again (same values), or columns outside the image (never read)
     const unsigned out_off = (unsigned)(strip * GRAY_PANEL_BYTES + 4 * lane);
-    const unsigned rmask2 = lane == 63 - HR ? 0x04u : 0x0cu;   // the last output lane's x+2 bit (row above) is not computed
-    unsigned bit5;   // (a constant in a register, opaque to the compiler: then the AND below folds into the DPP move -- DPP operands cannot be literals)
-    asm("v_mov_b32 %0, 0x20" : "=v"(bit5));
     unsigned colmask = 0;  // which of the lane's 4 columns lie inside cvFindContours' zeroed frame
     for (int j = 0; j < 4; j++) colmask |= (!EDGE || (c0 + j >= 1 && c0 + j <= sw - 2)) ? (1u << j) : 0u;
-    // Which pixels may yield border starts: the output lanes' (inside the image).  Strips away from the edges: all four pixels of
-    // lanes HL .. 63-HR, a constant lane mask applied to the ballots (scalar); strips at an edge: per lane, bits j and 8+j (outer /
-    // hole start nibbles) of a register.
-    constexpr unsigned long long OUT_LANES = (~0ull << HL) & (~0ull >> HR);
-    unsigned pxsel = 0;
-    if (EDGE)
-        for (int j = 0; j < 4; j++) pxsel |= (out_lane && c0 + j < sw) ? (0x101u << j) : 0u;
-
-    // The bit plane (hd.h::nbr_win_off) is written a tile row at a time: threshold rows go to a ring of 16 rows in LDS (one byte
-    // per lane and row: its nibble), and when row 14 ty + 14 is in, the 16 rows 14 ty - 1 .. 14 ty + 14 of tile row ty are made
-    // into the strip's 15 tiles -- 960 contiguous bytes, ONE store instruction: lane l (< 60) stores dwords 4 (l & 3) .. 4 (l & 3) + 3
-    // of tile l >> 2, so every 64-byte sector is written whole by four neighbouring lanes.  (A row at a time would be pieces of
-    // 15 sectors per wave, and on this hardware a store issued in every iteration makes the loop-top wait for the prefetched
-    // source row wait for that store too: vmcnt counts loads and stores in order.)  A tile's dword is 18 columns, 16 tx - 1 ..
-    // 16 tx + 16: the nibbles of lanes 4 tx + 1 .. 4 tx + 6 -- the apron columns -1 and 240 of a strip are the threshold bits of
-    // halo lanes 1 and 62, which the wave computes anyway; rows Y0 - 1 and Y1, the apron rows of a unit, are computed for the
-    // start tests.  Y0 is a multiple of 14 (plan_core.h / MARCH_CROP_ROWS), so a tile row belongs to one work unit; rows outside
-    // [0, Y1] (row -1, rows below the image) are stored as 0.
-    const int tile_s = strip * (SV / NBR_TILE_W) + (lane >> 2);   // the lane's tile in the tile row
-    const unsigned flush_src = (unsigned)(lane < 60 ? lane >> 2 : 14) * 4u;   // byte of lane 4 tx in an LDS row (lanes 60..63: any tile, their store is dropped)
-    const unsigned flush_dst = lane < 60 && tile_s * NBR_TILE_W < o.ns ? (unsigned)tile_s * NBR_TILE_BYTES + (unsigned)(lane & 3) * 16u : OOB;
-    auto flush_tiles = [&](int ty) {   // the rows of tile row ty are in the ring
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        {
-            typedef unsigned v4u __attribute__((ext_vector_type(4)));   // (non-temporal stores: written once, read much later)
-            v4u d;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int r = NBR_TILE_H * ty + 4 * (lane & 3) + i - 1;   // image row of dword 4 (l & 3) + i
-                const unsigned* p = reinterpret_cast<const unsigned*>(rowbuf + (r & 15) * 64 + flush_src);   // nibbles of lanes 4 tx .. 4 tx + 7, a byte each
-                const unsigned p0 = p[0], p1 = p[1];
-                // two nibbles per byte (bytes 0 and 2 of each word), those four bytes into one word: columns 16 tx - 8 .. 16 tx + 23
-                const unsigned w = __builtin_amdgcn_perm(p1 | (p1 >> 4), p0 | (p0 >> 4), 0x06040200u);
-                d[i] = (unsigned)r <= (unsigned)Y1 ? (w >> 7) & 0x3ffffu : 0u;
-            }
-            const unsigned so = (unsigned)wave_uniform((int)nbr_tile_off(0u, (unsigned)ty, o.ns));
-            // The tile row's offset is added to the lanes' offsets, the scalar offset field stays 0.  A store of more than 64 bits
-            // must not be followed at once by a vector instruction that writes its data registers; the compiler's hazard
-            // recogniser inserts the wait state only for buffer stores WITHOUT a register in the scalar offset field (with one the
-            // ISA manual promises no hazard) -- and gfx950 has it all the same: with the offset in an SGPR a register copy the
-            // allocator placed right behind the store overwrote its first data dword now and then (only while the memory system
-            // was busy: frames >= 16 of a batch).  (OOB + so < 2^32: dropped all the same.)
-            __builtin_amdgcn_raw_buffer_store_b128(d, nbr_rs, (int)(flush_dst + so), 0, BUF_NT);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    };
-
     // Border starts are staged per wave in LDS and appended to the global list with ONE atomic per flush: a
     // single list counter only sustains ~90 atomics/us chip-wide, which one atomic per image row would exceed.
     int staged = 0;  // wave-uniform
@@ -311,6 +233,91 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         staged = 0;
+    };
+
+    // The bit plane (hd.h::nbr_win_off) is written a tile row at a time: threshold rows go to a ring of RING_ROWS rows in LDS (one
+    // byte per lane and row: its nibble), and when row 14 ty + 14 is in, the 16 rows 14 ty - 1 .. 14 ty + 14 of tile row ty are made
+    // into the strip's 15 tiles -- 960 contiguous bytes, ONE store instruction: lane l (< 60) stores dwords 4 (l & 3) .. 4 (l & 3) + 3
+    // of tile l >> 2, so every 64-byte sector is written whole by four neighbouring lanes.  (A row at a time would be pieces of
+    // 15 sectors per wave, and on this hardware a store issued in every iteration makes the loop-top wait for the prefetched
+    // source row wait for that store too: vmcnt counts loads and stores in order.)  A tile's dword is 18 columns, 16 tx - 1 ..
+    // 16 tx + 16: the nibbles of lanes 4 tx + 1 .. 4 tx + 6 -- the apron columns -1 and 240 of a strip are the threshold bits of
+    // halo lanes 1 and 62, which the wave computes anyway; rows Y0 - 1 and Y1, the apron rows of a unit, are computed for the
+    // start tests.  Y0 is a multiple of 14 (plan_core.h / MARCH_CROP_ROWS), so a tile row belongs to one work unit; rows outside
+    // [0, Y1] (row -1, rows below the image) are stored as 0.
+    // The same words, 32 columns of a row each, are where the tile row's border starts are found (starts_core.h): every lane tests
+    // the rows it assembles anyway against the row above -- its own previous word, or the last word of the lane before it in the
+    // quad -- which is ~8 vector instructions per image row of the wave, against a window, a table read and a ballot per row and
+    // lane; and the starts are then staged one per lane and turn, so the cost follows the starts that exist.
+    const int tile_s = strip * (SV / NBR_TILE_W) + (lane >> 2);   // the lane's tile in the tile row
+    const unsigned flush_src = (unsigned)(lane < 60 ? lane >> 2 : 14) * 4u;   // byte of lane 4 tx in an LDS row (lanes 60..63: any tile, their store is dropped)
+    const unsigned flush_dst = lane < 60 && tile_s * NBR_TILE_W < o.ns ? (unsigned)tile_s * NBR_TILE_BYTES + (unsigned)(lane & 3) * 16u : OOB;
+    auto flush_tiles = [&](int ty) {   // the rows of tile row ty are in the ring
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        // (what only this block needs of the lane's place is worked out here, from a copy of the lane id the compiler cannot see
+        // through: kept in registers across the row loop instead, it would cost the loop registers it does not have)
+        int fl = lane;
+        asm volatile("" : "+v"(fl));
+        const int ftx = fl >> 2, fq = fl & 3;
+        const unsigned wbits = starts_word_bits(ftx);
+        unsigned w[4];
+        {
+            typedef unsigned v4u __attribute__((ext_vector_type(4)));   // (non-temporal stores: written once, read much later)
+            v4u d;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int r = NBR_TILE_H * ty + 4 * (lane & 3) + i - 1;   // image row of dword 4 (l & 3) + i
+                const unsigned* p = reinterpret_cast<const unsigned*>(rowbuf + (r & (RING_ROWS - 1)) * 64 + flush_src);   // nibbles of lanes 4 tx .. 4 tx + 7, a byte each
+                const unsigned p0 = p[0], p1 = p[1];
+                // two nibbles per byte (bytes 0 and 2 of each word), those four bytes into one word: columns 16 tx - 8 .. 16 tx + 23
+                const unsigned ww = __builtin_amdgcn_perm(p1 | (p1 >> 4), p0 | (p0 >> 4), 0x06040200u);
+                w[i] = (unsigned)r <= (unsigned)Y1 ? ww & wbits : 0u;   // (rows the unit did not write: stale ring rows)
+                d[i] = (w[i] >> 7) & 0x3ffffu;
+            }
+            const unsigned so = (unsigned)wave_uniform((int)nbr_tile_off(0u, (unsigned)ty, o.ns));
+            // The tile row's offset is added to the lanes' offsets, the scalar offset field stays 0.  A store of more than 64 bits
+            // must not be followed at once by a vector instruction that writes its data registers; the compiler's hazard
+            // recogniser inserts the wait state only for buffer stores WITHOUT a register in the scalar offset field (with one the
+            // ISA manual promises no hazard) -- and gfx950 has it all the same: with the offset in an SGPR a register copy the
+            // allocator placed right behind the store overwrote its first data dword now and then (only while the memory system
+            // was busy: frames >= 16 of a batch).  (OOB + so < 2^32: dropped all the same.)
+            __builtin_amdgcn_raw_buffer_store_b128(d, nbr_rs, (int)(flush_dst + so), 0, BUF_NT);
+        }
+        // Plausible border starts of the tile row's rows [14 ty, min(14 ty + 14, Y1)) (sparse), staged as y * ns + x with the hole
+        // flag in bit 31: each turn of the loop takes one start from every lane that still has one.
+        const int nrows = wave_uniform(Y1 - NBR_TILE_H * ty < NBR_TILE_H ? Y1 - NBR_TILE_H * ty : NBR_TILE_H);
+        const int col0 = strip * SV + NBR_TILE_W * ftx;
+        const unsigned own = fl < 60 ? (EDGE ? starts_own_bits(col0, sw) : STARTS_OWN_BITS) : 0u;
+        unsigned long long any, hole;
+        starts_of_lane(w, up1(w[3]), 4 * fq - 1, nrows, own, any, hole);
+        const unsigned pos0 = (unsigned)((NBR_TILE_H * ty + 4 * fq - 1) * o.ns + col0);   // (the apron row of tile row 0 is row -1: never a start row)
+#pragma nounroll
+        for (;;) {
+            const unsigned long long mask = __ballot(any != 0ull);
+            const int n = wave_uniform(__popcll(mask));
+            if (n == 0) break;
+            if (staged + n > MARCH_STAGE) flush();
+            if (any != 0ull) {
+                const unsigned k = (unsigned)__builtin_ctzll(any);
+                stage[staged + __popcll(mask & ((1ull << lane) - 1ull))] = (pos0 + (k >> 4) * (unsigned)o.ns + (k & 15u)) | ((unsigned)(hole >> k) << 31);
+                any &= any - 1ull;
+            }
+            staged += n;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    };
+    // Tile rows are flushed between rows: the ring holds RING_ROWS = 32 rows, so a tile row's 16 rows are still there when up to
+    // four more have come in, and the flush -- with the start test some 200 instructions -- stands once behind each group of rows
+    // instead of behind every row of it (a 16-row ring needs the flush at the very row that completes the tile row: eight copies
+    // in the steady loop, and code size is speed here).  y_in: the last threshold row written to the ring.
+    int y_in = Y0 - 2, ty_next = Y0 / NBR_TILE_H;
+    const int ty_end = (Y1 + NBR_TILE_H - 1) / NBR_TILE_H;
+    auto flush_due = [&]() {   // a tile row is complete with its row 14 ty + 14, the unit's last one with row Y1
+#pragma nounroll
+        while (ty_next < ty_end && y_in >= (NBR_TILE_H * ty_next + NBR_TILE_H < Y1 ? NBR_TILE_H * ty_next + NBR_TILE_H : Y1)) {
+            flush_tiles(ty_next);
+            ty_next++;
+        }
     };
 
     // raw source words of virtual row v (3 dwords BGR / 4 dwords BGRA / 1 dword grey for fast lanes, 4 pixels for edge lanes)
@@ -437,7 +444,6 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     // and coefficients on the scalar unit.  (An 8-row ring without the renaming needs the loop unrolled over 8 rows: with the
     // two instances of this function in one kernel that was 52 KB of code and 30 % slower -- instruction cache.)
     unsigned wa[4] = {0u, 0u, 0u, 0u}, wb[4] = {0u, 0u, 0u, 0u};
-    unsigned x_prev = 0;   // the start nibbles of row y-1
 
     // One source row.  S ("steady"): v lies where every range test below has a known outcome -- the rows it completes are
     // inside the work unit and away from the image's first and last rows -- so the tests (a scalar compare and branch
@@ -599,40 +605,9 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
                         }
                         if (EDGE || VM < 0) nib &= colmask;   // (strips inside the image: every column counts, and the four tests above left four bits)
                     }
-                    // Row y's window -> table: its start nibbles.
-                    // Byte offset of the table entry (4 bytes each): bits 2..5 = own pixels, bit 6 = the left lane's pixel 3, bits 7, 8 =
-                    // the right lane's pixels 0, 1 -- every lane shifts its nibble once, the neighbours' parts are an AND on the
-                    // DPP-shifted value and a shift-or each.
-                    const unsigned n2 = nib << 2;
-                    const unsigned wdw4 = ((down1(n2) & rmask2) << 5) | (((up1(n2) & bit5) << 1) | n2);
-                    const unsigned Tw = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(tab) + wdw4);
-                    unsigned st;                               // row y's own nibbles (low half of Tw) & row y-1's "row above" nibbles (high half of x_prev)
-                    asm("v_and_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1" : "=v"(st) : "v"(Tw), "v"(x_prev));
-                    x_prev = Tw;
-                    st = st & ~(st >> 4);                      // bits 0..3: outer starts, bits 8..11: hole starts of row y (other bits: don't care)
-                    if (EDGE) st &= pxsel;
-                    // row y into the ring (here y >= max(Y0 - 1, 0) and y <= Y1); a tile row is complete with its row 14 ty + 14, the
-                    // unit's last one (only at the image's bottom, where Y1 = sh need not be a multiple of 14) with row Y1
-                    rowbuf[(y & 15) * 64 + lane] = (uint8_t)nib;
-                    if (y % NBR_TILE_H == 0 && y >= Y0 + NBR_TILE_H) flush_tiles(y / NBR_TILE_H - 1);
-                    else if (!S && y == Y1 && Y1 % NBR_TILE_H != 0) flush_tiles(Y1 / NBR_TILE_H);
-                    // Plausible border starts of row y (sparse): necessary local conditions for being the raster-first pixel of
-                    // a region.  Outer: foreground pixel whose W, NW, N, NE are background -- and not (E foreground and the pixel
-                    // above E's east neighbour foreground: that one belongs to the same 8-connected component and comes earlier).
-                    // Hole: background pixel whose W and N are foreground -- and E or NE foreground (if both are background they
-                    // belong to the same 4-connected background region and NE comes earlier).
-                    if ((!S && (y < Y0 || y >= Y1)) || (__ballot((st & 0xf0fu) != 0) & (EDGE ? ~0ull : OUT_LANES)) == 0) continue;
-#pragma nounroll   // (rare rows, and the steady loop holds eight copies of this: kept small)
-                    for (int j = 0; j < 4; j++) {   // (two vector instructions per pixel position that has no start: this runs on every third row)
-                        const unsigned hit = st & (0x101u << j);   // pixel j: bit j an outer start, bit 8 + j a hole start (never both: foreground / background)
-                        const unsigned long long mask = __ballot(hit != 0) & (EDGE ? ~0ull : OUT_LANES);
-                        if (!mask) continue;
-                        const int n = __popcll(mask);
-                        if (staged + n > MARCH_STAGE) flush();
-                        if ((mask >> lane) & 1ull)
-                            stage[staged + __popcll(mask & ((1ull << lane) - 1ull))] = (unsigned)(y * o.ns + c0 + j) | (hit >> 8 ? 0x80000000u : 0u);
-                        staged += n;
-                    }
+                    // row y into the ring (here y >= max(Y0 - 1, 0) and y <= Y1); flush_due, between rows, makes tile rows of it
+                    rowbuf[(y & (RING_ROWS - 1)) * 64 + lane] = (uint8_t)nib;
+                    y_in = y;
                 }
             }
         }
@@ -656,7 +631,10 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
 #pragma nounroll
     for (int phase = 0; phase < 2; phase++) {   // generic rows, steady rows, generic rows: one copy of each instance
         const int end = phase == 0 ? (vs0 <= v_last + 1 ? vs0 : v_last + 1) : v_last + 1;
-        for (; v < end; v++) row(v, std::false_type(), P0(), RX());
+        for (; v < end; v++) {
+            row(v, std::false_type(), P0(), RX());
+            flush_due();
+        }
         if (phase == 0)
             while (v + 1 <= vs1) {
                 if ((v & 3) == 1 && v + 3 <= vs1) {   // four rows with the ring's position known: the hot loop
@@ -665,10 +643,12 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
                     row(v + 2, std::true_type(), P1(), RX());
                     row(v + 3, std::true_type(), P2(), std::integral_constant<int, 0>());
                     v += 4;
+                    flush_due();
                 } else {                               // a pair before the first or after the last group of four
                     row(v, std::true_type(), P1(), RX());
                     row(v + 1, std::true_type(), P2(), RX());
                     v += 2;
+                    flush_due();
                 }
             }
     }
@@ -677,17 +657,14 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
 
 // Workgroups of ONE wave (BW = 1): the waves of a workgroup must be placed on their CU together, so a four-wave workgroup needs
 // room on all four SIMDs at once -- and with other contexts' kernels on the GPU (a follower wave of 110 registers on one SIMD)
-// a CU holds a whole workgroup less.  A one-wave workgroup takes any SIMD with 96 free registers and 6 KB of LDS.
+// a CU holds a whole workgroup less.  A one-wave workgroup takes any SIMD with 96 free registers and 4 KB of LDS.
 constexpr int BW = OCVAR_BIN_WG_WAVES;
 
 // One instance per source format (FMT: OCVAR_FMT_*); they differ in the row loads and the grey conversion only.
 template <int FMT>
 __global__ __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(OCVAR_WAVES_F, 8))) void binarise_frames_kernel(Workspace ws, const uint8_t* bgr, int row_stride, size_t frame_stride) {
     __shared__ unsigned stage[BW][MARCH_STAGE];
-    __shared__ __attribute__((aligned(16))) uint8_t rowbuf[BW][16 * 64];
-    __shared__ unsigned tab[128];
-    for (unsigned i = threadIdx.x; i < 128u; i += 64u * BW) tab[i] = start_table_entry(table_window(i));
-    __syncthreads();
+    __shared__ __attribute__((aligned(16))) uint8_t rowbuf[BW][RING_ROWS * 64];
     const int per_frame = ws.frame_strips * ws.frame_chunks;
     // XCD-aware order.  Consecutive workgroups go round the 8 XCDs, each with its own L2; in launch order the workgroups of one
     // frame -- neighbouring strips and chunks, which share halo columns and rows -- would land on 8 different L2s and every halo
@@ -720,8 +697,8 @@ __global__ __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(OCVAR_W
     o.err = ws.counters + CNT_ERR;
     const int w4 = wave_uniform((int)(threadIdx.x >> 6));
     const bool edge = strip == 0 || ((ws.sw - 1 - (strip * MARCH_STRIP - 4 * MARCH_HALO_L)) >> 2) <= 63;   // march_unit's left_edge || right_edge
-    if (edge) march_unit<FMT, true>(bgr + (size_t)f * frame_stride, row_stride, 0, ws.sw, ws.sh, strip, Y0, Y1, o, stage[w4], rowbuf[w4], tab);
-    else march_unit<FMT, false>(bgr + (size_t)f * frame_stride, row_stride, 0, ws.sw, ws.sh, strip, Y0, Y1, o, stage[w4], rowbuf[w4], tab);
+    if (edge) march_unit<FMT, true>(bgr + (size_t)f * frame_stride, row_stride, 0, ws.sw, ws.sh, strip, Y0, Y1, o, stage[w4], rowbuf[w4]);
+    else march_unit<FMT, false>(bgr + (size_t)f * frame_stride, row_stride, 0, ws.sw, ws.sh, strip, Y0, Y1, o, stage[w4], rowbuf[w4]);
 }
 
 // grey of the source pixel at p in format fmt (OCVAR_FMT_*)
@@ -768,10 +745,7 @@ __global__ __launch_bounds__(256) void grey_writeback_kernel(Workspace ws, uint8
 
 __global__ __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(OCVAR_WAVES_C, 8))) void binarise_crops_kernel(Workspace ws) {
     __shared__ unsigned stage[BW][MARCH_STAGE];
-    __shared__ __attribute__((aligned(16))) uint8_t rowbuf[BW][16 * 64];
-    __shared__ unsigned tab[128];
-    for (unsigned i = threadIdx.x; i < 128u; i += 64u * BW) tab[i] = start_table_entry(table_window(i));
-    __syncthreads();
+    __shared__ __attribute__((aligned(16))) uint8_t rowbuf[BW][RING_ROWS * 64];
     int n_units = ws.counters[CNT_CROP_TILES];
     if (n_units > ws.cap_crop_tiles) n_units = ws.cap_crop_tiles;
     const int wave = wave_uniform((int)(threadIdx.x >> 6));
@@ -806,7 +780,7 @@ __global__ __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(OCVAR_W
         o.n_cands = ws.counters + CNT_CROP_CANDS;
         o.cap_cands = ws.cap_crop_cands;
         o.err = ws.counters + CNT_ERR;
-        march_unit<SRC_CROP, true>(src, pitch, r.x0, r.sw, r.sh, td.x0, td.y0, Y1, o, stage[wave], rowbuf[wave], tab);
+        march_unit<SRC_CROP, true>(src, pitch, r.x0, r.sw, r.sh, td.x0, td.y0, Y1, o, stage[wave], rowbuf[wave]);
     }
 }
 

@@ -100,6 +100,37 @@ extern "C" int ocvar_hip_debug_crop_plane(OcvarHip* c, int roi, int masks, uint8
     return OCVAR_OK;
 }
 
+// The start list of the last collected batch (binarise.hip::march_unit stages y * ns + x with the ROI's plane stride ns), with
+// the positions taken apart.  The followers only read the lists, so they stay as the binarise kernels left them.
+extern "C" int ocvar_hip_debug_starts(OcvarHip* c, int crop_pass, OcvarStart* starts, int max_starts, int* n_starts) {
+    if (!c || c->pending || !n_starts || max_starts < 0 || (max_starts > 0 && !starts) || c->ws.n_frames < 1 || !c->h_counters.p) return OCVAR_E_ARG;
+    const int n_rois = crop_pass ? crop_count(c) : c->ws.n_frames;
+    if (n_rois < 0) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int cap = crop_pass ? c->ws.cap_crop_cands : c->ws.cap_frame_cands;
+    int n = c->h_counters[crop_pass ? CNT_CROP_CANDS : CNT_FRAME_CANDS];
+    n = n < 0 ? 0 : n < cap ? n : cap;
+    const int k = n < max_starts ? n : max_starts;
+    std::vector<StartCand> sc((size_t)(k > 0 ? k : 1));
+    if (k > 0) HIP_TRY(c, hipMemcpy(sc.data(), crop_pass ? c->ws.cands_crop : c->ws.cands_frame, (size_t)k * sizeof(StartCand), hipMemcpyDeviceToHost));
+    std::vector<Roi> rois((size_t)(crop_pass && n_rois > 0 ? n_rois : 1));
+    if (crop_pass && n_rois > 0) HIP_TRY(c, hipMemcpy(rois.data(), c->ws.rois_crop, (size_t)n_rois * sizeof(Roi), hipMemcpyDeviceToHost));
+    for (int i = 0; i < k; i++) {
+        const StartCand& s = sc[i];
+        const int ns = crop_pass ? (s.roi >= 0 && s.roi < n_rois ? rois[s.roi].ns : 0) : c->ws.ns;
+        if (s.roi < 0 || s.roi >= n_rois || ns <= 0 || s.pos < 0) {
+            c->err = "ocvar_hip_debug_starts: a record of the start list does not belong to the batch";
+            return OCVAR_E_ARG;
+        }
+        starts[i].roi = s.roi;
+        starts[i].x = s.pos % ns;
+        starts[i].y = s.pos / ns;
+        starts[i].is_hole = s.is_hole;
+    }
+    *n_starts = n;
+    return OCVAR_OK;
+}
+
 extern "C" int ocvar_hip_debug_candidates(OcvarHip* c, int frame, OcvarCandidate* cands, int max_cands, int* n_cands) {
     if (!c || !cands || !n_cands || frame < 0 || frame >= c->ws.n_frames) return OCVAR_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
