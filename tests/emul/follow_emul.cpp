@@ -30,7 +30,9 @@ struct Plane {
 
 // ---- tier 2 ----
 // pts: the corner points, packed x | y << 16 (room for every step of the walk + 1)
-LeanWalk tier2(const Plane& p, const unsigned* tab, int cpos, int is_hole, int budget, unsigned* pts) {
+// marks: the corner points completed after every block of steps -- where follow_mid_kernel flushes a walk's parked points: a
+// lane gets its start between two blocks, so a walk's blocks are counted from its own first step
+LeanWalk tier2(const Plane& p, const unsigned* tab, int cpos, int is_hole, int budget, unsigned* pts, std::vector<int>* marks = nullptr) {
     LeanWalk w;
     lean_begin(w, p.bytes.data(), p.ns, cpos, is_hole);
     const unsigned nt = (unsigned)(p.ns >> 4), last = (unsigned)nbr_plane_bytes(p.ns, p.sh) - 12u;   // (as follow_mid_kernel's pl_nt, pl_last)
@@ -38,6 +40,7 @@ LeanWalk tier2(const Plane& p, const unsigned* tab, int cpos, int is_hole, int b
         for (int k = 0; k < BLOCK && w.status < 0; k++)
             lean_step(w, tab, p.bytes.data(), nt, last, [&](unsigned xy) { pts[w.npts] = xy; });   // (every step; only a corner point advances npts)
         if (w.status < 0 && w.step >= budget) w.status = TRACE_OVERRUN;
+        if (marks) marks->push_back(w.npts);
     }
     return w;
 }
@@ -320,6 +323,22 @@ extern "C" int fe_walks(const uint8_t* bin, int sw, int sh, int stride, int* row
         o[17] = (int)t.loads;
         for (int i = 0; i < N_ERR; i++) o[18 + i] = (int)t.err[i];
     });
+}
+
+// One start (cpos at the bit plane's pitch) walked by tier 2 with the budget 4 ns sh + 16: out[i] = corner points completed
+// after block i of fe_block() steps, the last entry the border's point count.  Returns the number of blocks; -1 if the walk
+// does not close or needs more than max_out blocks.
+extern "C" int fe_tier2_marks(const uint8_t* bin, int sw, int sh, int cpos, int is_hole, int* out, int max_out) {
+    const Plane p(bin, sw, sh);
+    const int budget = 4 * p.ns * sh + 16;
+    std::vector<unsigned> got((size_t)budget + BLOCK + 64);
+    std::vector<int> marks;
+    unsigned tab[64];
+    for (unsigned i = 0; i < 64; i++) tab[i] = lean_table_entry(i);
+    const LeanWalk w = tier2(p, tab, cpos, is_hole, budget, got.data(), &marks);
+    if (w.status != TRACE_OK || (int)marks.size() > max_out) return -1;
+    for (size_t i = 0; i < marks.size(); i++) out[i] = marks[i];
+    return (int)marks.size();
 }
 
 // Every plausible start with a step budget: tier 2 as the kernel ends it (the budget looked at after every block of fe_block()

@@ -506,15 +506,23 @@ def test_round_trip_properties_full_size(oa):
 
 def test_borders_with_thousands_of_points(oa):
     """Long, point-rich borders go through the follower's upper tiers (lane slabs, wave slabs); results must not
-    depend on which tier handled a border."""
+    depend on which tier handled a border.  Frame 0 (teeth of 6 px): many borders, the longest of 26 points; frame 1 (4 px): a
+    border of 3509 points -- neither yields a quad from a long border, the adaptive threshold leaves an edge band whose teeth
+    do not approximate to four vertices; frame 2 (2 px): borders of 2974 and 2012 points that own a quad each, so their points
+    reach the result (tests/test_gpu_follow_limits.py takes such borders to the tiers' limits)."""
+    import follow_limit_scenes as S
     w, h = 1280, 960
     cfg = H.synth_config(2, width=w, height=h)
-    det, tpls, cam = make_detector(oa, cfg, ["2x2-01"], 2)
+    det, tpls, cam = make_detector(oa, cfg, ["2x2-01"], 3)
     frames = np.stack([sawtooth_frame(w, h, 6, [(100, 100, 700, 500), (800, 150, 1200, 900), (150, 600, 650, 880)]),
-                       sawtooth_frame(w, h, 4, [(60, 60, 1220, 900)])])
+                       sawtooth_frame(w, h, 4, [(60, 60, 1220, 900)]),
+                       S.thousands_tooth2()])
+    long_owners = S.analyse(frames[2], min_pts=S.SLAB_PTS + 1).owners
+    assert sorted(o.n for o in long_owners) == [2012, 2974]
     markers, counts = det.detect_host(frames.copy())
-    for f in range(2):
+    for f in range(3):
         check_frame(det, f, frames[f], tpls, cam, markers, counts)
+    assert len(det.debug_frame_quads(2)) == 2
     # the square finder alone, on a crop-sized image cut out of the first frame
     crop = np.ascontiguousarray(frames[0][80:540, 80:740, 0])
     ref = H.oracle_find_squares(crop)
