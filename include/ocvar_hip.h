@@ -603,6 +603,55 @@ int ocvar_hip_warp_records(OcvarHip* ctx, const OcvarMarker* d_markers, const in
 int ocvar_hip_board_plane_maps(OcvarHip* ctx, const OcvarBoardPose* d_poses, int n_frames, const double rect[4], int dst_width,
                                int dst_height, double* d_maps, void* stream);
 
+/* Levels: the grey levels of device-resident frames stretched, for the whole frame or per tile with the maps of neighbouring tiles
+ * blended, into one GRAY plane per frame -- an under-exposed, washed-out or unevenly lit stream brought back to where the
+ * detection's fixed thresholds (the adaptive threshold's constant 8 and the cut at grey 100 on the warped patch, reference
+ * opencvar.cpp:181 and :724) find its markers, without a trip through host memory.  The definition, bit for bit and all integer,
+ * is opencv-ar_amd/csrc/levels_core.h.  It is the library's own rule: there is no OpenCV function to be in parity with; with
+ * low_ppm = high_ppm = 0 and no gain cap reached it is normalize(..., NORM_MINMAX) up to rounding.
+ *   d_src    n_frames frames of width x height pixels in `format` (any OCVAR_FMT_*; it need not be the input format), rows
+ *            src_row_stride and frames src_frame_stride bytes apart, at any address.  g is the library's grey of a pixel,
+ *            (1868 B + 9617 G + 4899 R + 8192) >> 14 with the format's channel order, the byte itself for GRAY.
+ *   d_dst    one GRAY plane of width x height bytes per frame, rows dst_row_stride and planes dst_frame_stride bytes apart, at any
+ *            address; the byte ranges of the two sides must not intersect.  Detected with ocvar_hip_set_input_format(OCVAR_FMT_GRAY)
+ *            the plane yields records in the source frame's own coordinates: nothing needs carrying across, and drawing
+ *            (ocvar_hip_annotate_records, ocvar_hip_render_records) goes onto the original frames.
+ *   params   tiles_x, tiles_y  1 .. 16 each, tiles_x tiles_y <= 64, tiles_x <= width, tiles_y <= height (default 1, 1: one map per
+ *                              frame); low_ppm, high_ppm  0 .. 500000, the parts per million of a tile's pixels clipped at the dark
+ *            and at the bright end (default 10000 each: 1 %); max_gain_q8  256 .. 65280, the largest gain in 1/256 (default 2048:
+ *            8).  NULL: the defaults, which ocvar_hip_levels_default_params (host only) writes.
+ *   tiles    edges xe[i] = (i width) / tiles_x and ye[j] = (j height) / tiles_y by floor division; tile (j, i) owns the pixels
+ *            xe[i] <= x < xe[i+1], ye[j] <= y < ye[j+1], n in all; its histogram is the 256 counts of g over them.
+ *   LUT      per tile: k_lo = (n low_ppm) / 1000000 and k_hi = (n high_ppm) / 1000000 in 64 bits; lo the smallest v with
+ *            #{g <= v} > k_lo, hi the largest v with #{g >= v} > k_hi; minr = (255 * 256 + max_gain_q8 - 1) / max_gain_q8; if
+ *            hi - lo < minr (which also covers lo > hi): lo = min(max((lo + hi - minr) >> 1, 0), 255 - minr) with an arithmetic
+ *            shift and hi = lo + minr.  lut[v] = clamp(((v - lo) 510 + (hi - lo)) / (2 (hi - lo)), 0, 255), a floor division of a
+ *            value that is made 0 when negative.
+ *   blend    between tile centres.  Along x for pixel x: c2[i] = xe[i] + xe[i+1], p = 2 x + 1, i0 the largest i with c2[i] <= p
+ *            clamped to 0 .. max(tiles_x - 2, 0), i1 = min(i0 + 1, tiles_x - 1), wx = i1 > i0 ? clamp(((p - c2[i0]) 256) /
+ *            (c2[i1] - c2[i0]), 0, 256) : 0; along y the same with ye, giving j0, j1 and wy.  top = lut[j0][i0][g] (256 - wx) +
+ *            lut[j0][i1][g] wx, bot the same on row j1, and the output byte is (top (256 - wy) + bot wy + 32768) >> 16.  With one
+ *            tile it is lut[g].
+ * Three kernels in stream order: histograms (32-bit integer adds, which commute: the result does not depend on scheduling), one
+ * LUT per tile, the blend.  Sides are 1 .. 32767 and are NOT bound by the context's max_width x max_height.  When every address,
+ * row stride and frame stride is a multiple of 4 the kernels move whole dwords; otherwise, and at the ends of rows and tiles,
+ * bytes -- with the same result.  No byte outside the destination's pixels is written; the source is never written.
+ * The workspace -- histograms and LUTs of 64 tiles for each of 256 frames, 20 MiB -- is allocated by the first call: a context
+ * that never calls ocvar_hip_levels allocates and launches nothing.  More than 256 frames go in several rounds in stream order.
+ * Calls of one context share the workspace: like ocvar_hip_annotate_records, a call on another stream than the previous one is
+ * ordered behind it by the library, and calls of one context come from one thread at a time.  stream NULL: the context's own
+ * stream.  The call does not wait.  OCVAR_E_ARG, before any device call and with a text in ocvar_hip_last_error, for NULL
+ * pointers (params may be NULL), an unknown format, a side outside 1 .. 32767, a row stride below the bytes per pixel times
+ * width (the destination: below width), rows that span more than 2^31 - 1 bytes, n_frames < 1, intersecting source and
+ * destination byte ranges, any parameter outside its range above. */
+typedef struct OcvarLevelsParams {
+    int tiles_x, tiles_y, low_ppm, high_ppm, max_gain_q8;
+} OcvarLevelsParams;
+int ocvar_hip_levels_default_params(OcvarLevelsParams* params);   /* host only, no context, no device call */
+int ocvar_hip_levels(OcvarHip* ctx, const uint8_t* d_src, int width, int height, int src_row_stride, size_t src_frame_stride,
+                     int format, uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride, int n_frames,
+                     const OcvarLevelsParams* params, void* stream);
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart

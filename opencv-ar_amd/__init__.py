@@ -39,6 +39,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_resize", "ocvar_hip_scale_records",
     "ocvar_hip_orient", "ocvar_hip_orient_records", "ocvar_hip_orient_camera",
     "ocvar_hip_warp", "ocvar_hip_warp_records", "ocvar_hip_board_plane_maps",
+    "ocvar_hip_levels_default_params", "ocvar_hip_levels",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -167,6 +168,31 @@ ORIENT_POSE = 1                                             # include/ocvar_hip.
 WARP_INTERPS = {"nearest": 0, "linear": 1}                  # include/ocvar_hip.h: OCVAR_WARP_NEAREST, OCVAR_WARP_LINEAR
 WARP_BORDERS = {"constant": 0, "replicate": 1}              # include/ocvar_hip.h: OCVAR_WARP_BORDER_*
 WARP_INVERSE_MAP, WARP_ONE_MAP, WARP_POSE = 1, 2, 4         # include/ocvar_hip.h: OCVAR_WARP_INVERSE_MAP ..
+LEVELS_MAX_TILES_AXIS, LEVELS_MAX_TILES, LEVELS_MAX_PPM = 16, 64, 500000   # include/ocvar_hip.h: OcvarLevelsParams' ranges
+
+
+class LevelsParams(C.Structure):  # OcvarLevelsParams
+    _fields_ = [("tiles_x", C.c_int), ("tiles_y", C.c_int), ("low_ppm", C.c_int), ("high_ppm", C.c_int), ("max_gain_q8", C.c_int)]
+
+
+def levels_params(tiles=(1, 1), low_ppm=10000, high_ppm=10000, max_gain=8.0):
+    """The parameters of Detector.levels (include/ocvar_hip.h: OcvarLevelsParams; the defaults are the library's), checked: tiles =
+    (tiles_x, tiles_y) of 1 .. 16 each and at most 64 in all (that neither exceeds the frame's side is the call's to check), low_ppm
+    and high_ppm the parts per million clipped at the dark and the bright end, 0 .. 500000, max_gain the largest gain, 1 .. 255
+    (stored in 1/256).  ValueError outside those."""
+    try:
+        tx, ty = tiles
+    except (TypeError, ValueError):
+        raise ValueError(f"tiles must be (tiles_x, tiles_y), got {tiles!r}") from None
+    for name, v, lo, hi in (("tiles_x", tx, 1, LEVELS_MAX_TILES_AXIS), ("tiles_y", ty, 1, LEVELS_MAX_TILES_AXIS),
+                            ("low_ppm", low_ppm, 0, LEVELS_MAX_PPM), ("high_ppm", high_ppm, 0, LEVELS_MAX_PPM)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an int in {lo} .. {hi}, got {v!r}")
+    if tx * ty > LEVELS_MAX_TILES:
+        raise ValueError(f"at most {LEVELS_MAX_TILES} tiles, got {tx} x {ty}")
+    if isinstance(max_gain, bool) or not isinstance(max_gain, (int, float, np.integer, np.floating)) or not 1.0 <= float(max_gain) <= 255.0:
+        raise ValueError(f"max_gain must be a number in 1 .. 255, got {max_gain!r}")
+    return LevelsParams(int(tx), int(ty), int(low_ppm), int(high_ppm), int(round(float(max_gain) * 256)))
 
 
 def perspective_map(src_quad, dst_quad):
@@ -424,6 +450,8 @@ def hip_lib():
         lib.ocvar_hip_warp.argtypes = [vp, vp, i, i, i, sz, vp, i, i, i, sz, i, i, vp, i, i, vp, i, vp, vp]
         lib.ocvar_hip_warp_records.argtypes = [vp, vp, vp, i, i, vp, i, vp, vp]
         lib.ocvar_hip_board_plane_maps.argtypes = [vp, vp, i, vp, i, i, vp, vp]
+        lib.ocvar_hip_levels_default_params.argtypes = [vp]
+        lib.ocvar_hip_levels.argtypes = [vp, vp, i, i, i, sz, i, vp, i, sz, i, vp, vp]
         _hip = lib
     return _hip
 
@@ -946,6 +974,23 @@ class Detector:
         per_frame = self.max_markers if per_frame is None else per_frame
         self._check(self._lib.ocvar_hip_orient_records(self._ctx, d_markers, d_counts, n_frames, per_frame, src_size[0], src_size[1],
                                                        orientation_code(orientation), ORIENT_POSE if pose else 0, d_out, stream), "orient_records")
+
+    def levels(self, d_src, d_dst, width, height, n_frames, params=None, fmt=None, src_row_stride=None, src_frame_stride=None,
+               dst_row_stride=None, dst_frame_stride=None, stream=None):
+        """n_frames device frames of width x height pixels at d_src in format fmt (default: the input format) with their grey levels
+        stretched into one GRAY plane per frame at d_dst: per tile of params' grid the grey values between the clipped ends of the
+        tile's histogram are spread over 0 .. 255 (the gain capped), and a pixel takes the blend of the maps of the four tiles
+        around it (params: levels_params(...); None: one map per frame, 1 % clipped at each end, a gain of at most 8).  Detected
+        with set_input_format('gray') the planes yield records in the source frames' own coordinates.  The sizes are not bound by
+        the detector's.  Source and destination must not overlap.  The first call allocates a workspace of 20 MiB.  Needs no batch,
+        does not wait (stream None: the detector's own stream)."""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        src_row_stride = src_row_stride or FORMAT_BPP[code] * width
+        src_frame_stride = src_frame_stride or src_row_stride * height
+        dst_row_stride = dst_row_stride or width
+        dst_frame_stride = dst_frame_stride or dst_row_stride * height
+        self._check(self._lib.ocvar_hip_levels(self._ctx, d_src, width, height, src_row_stride, src_frame_stride, code, d_dst, dst_row_stride,
+                                               dst_frame_stride, n_frames, None if params is None else C.byref(params), stream), "levels")
 
     def warp(self, d_src, src_width, src_height, d_dst, dst_width, dst_height, n_frames, d_maps, interp="linear", border="constant", fill=None,
              inverse_map=False, one_map=False, fmt=None, src_row_stride=None, src_frame_stride=None, dst_row_stride=None,

@@ -160,6 +160,7 @@ extern "C" void ocvar_hip_destroy(OcvarHip* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->ovl_used) (void)hipEventSynchronize(c->ovl_done);   // (a render_records in flight reads the overlay workspace and the images)
     if (c->anno_used) (void)hipEventSynchronize(c->anno_done);   // (an annotate_records in flight reads its workspace)
+    if (c->levels_used) (void)hipEventSynchronize(c->levels_done);   // (a levels call in flight uses its workspace)
     delete c;
 }
 
@@ -1307,6 +1308,61 @@ extern "C" int ocvar_hip_board_plane_maps(OcvarHip* c, const OcvarBoardPose* d_p
     launch_warp_board_maps(a, s);
     TRACE_LAUNCH("board_plane_maps", s);
     HIP_TRY(c, hipGetLastError());
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_levels_default_params(OcvarLevelsParams* params) {
+    if (!params) return OCVAR_E_ARG;
+    levels_default_params(params);
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_levels(OcvarHip* c, const uint8_t* d_src, int width, int height, int src_row_stride, size_t src_frame_stride, int format,
+                                uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride, int n_frames, const OcvarLevelsParams* params,
+                                void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    const auto refuse = [&](const char* text) {
+        c->err = std::string("levels: ") + text;
+        return OCVAR_E_ARG;
+    };
+    if (!d_src || !d_dst) return refuse("no source frames or no destination planes");
+    const int bpp = patch_bpp(format);
+    if (bpp == 0) return refuse("an unknown format");
+    if (width < 1 || width > LEVELS_MAX_SIDE || height < 1 || height > LEVELS_MAX_SIDE) return refuse("sides of 1 .. 32767 pixels");
+    if (n_frames < 1) return refuse("n_frames >= 1");
+    if ((long long)src_row_stride < (long long)bpp * width || dst_row_stride < width)
+        return refuse("a row stride below the bytes per pixel times width (the destination is GRAY: below width)");
+    if ((long long)(height - 1) * src_row_stride + (long long)bpp * width > 2147483647LL || (long long)(height - 1) * dst_row_stride + width > 2147483647LL)
+        return refuse("the rows of a frame span more than 2147483647 bytes");
+    const unsigned long long s0 = (unsigned long long)(uintptr_t)d_src, d0 = (unsigned long long)(uintptr_t)d_dst;
+    const unsigned long long s1 = s0 + frames_extent(width, height, bpp, src_row_stride, src_frame_stride, n_frames);
+    const unsigned long long d1 = d0 + frames_extent(width, height, 1, dst_row_stride, dst_frame_stride, n_frames);
+    if (s0 < d1 && d0 < s1) return refuse("the byte ranges of source and destination intersect (no levels in place)");
+    OcvarLevelsParams p;
+    levels_default_params(&p);
+    if (params) p = *params;
+    static const char* const why[] = {"", "tiles_x and tiles_y 1 .. 16, at most 64 tiles, no more tiles than pixels along an axis",
+                                      "low_ppm and high_ppm 0 .. 500000", "max_gain_q8 256 .. 65280"};
+    if (const int bad = levels_params_bad(p, width, height)) return refuse(why[bad]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
+    const bool fresh = c->levels_ws.bytes == 0;
+    HIP_TRY(c, c->levels_ws.reserve((size_t)LEVELS_WS_BYTES));
+    HIP_TRY(c, c->levels_done.ensure(hipEventDisableTiming));
+    // the histograms start as zeros; every round's LUT kernel leaves them so
+    if (fresh) HIP_TRY(c, hipMemsetAsync(c->levels_ws, 0, (size_t)LEVELS_WS_LUT_OFFSET, s));
+    if (c->levels_used && c->levels_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->levels_done, 0));
+    for (int f0 = 0; f0 < n_frames; f0 += LEVELS_WS_FRAMES) {     // the rounds share the workspace in stream order
+        const LevelsArgs a{d_src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, width, height,
+                           (long long)src_row_stride, (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride, p,
+                           reinterpret_cast<unsigned*>(c->levels_ws.p), c->levels_ws.p + LEVELS_WS_LUT_OFFSET};
+        launch_levels(a, std::min(LEVELS_WS_FRAMES, n_frames - f0), format, s);
+        TRACE_LAUNCH("levels", s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->levels_done, s));
+    c->levels_stream = s;
+    c->levels_used = true;
     return OCVAR_OK;
 }
 

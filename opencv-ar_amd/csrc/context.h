@@ -152,6 +152,11 @@ struct OcvarHip {
     ocvar::DeviceBuffer<ocvar::AnnoBox> anno_boxes;   // [max_batch][maxm]
     hipStream_t anno_stream = nullptr;
     bool anno_used = false;
+    // levels (ocvar_hip_levels): the tile histograms and LUTs' workspace is allocated, and cleared, by the first call
+    ocvar::Event levels_done;                      // behind the last use of the workspace, on levels_stream (created on first use)
+    ocvar::DeviceBuffer<uint8_t> levels_ws;        // levels_core.h: LEVELS_WS_BYTES
+    hipStream_t levels_stream = nullptr;
+    bool levels_used = false;
     std::string err;
 
     ~OcvarHip();   // (api.hip: the fixed arrays and the overlay images; the holders release the rest)

@@ -14,6 +14,7 @@
 #include "resize_core.h"
 #include "orient_core.h"
 #include "warp_core.h"
+#include "levels_core.h"
 #include "flow_core.h"
 #include "croplist_core.h"
 #include "ocvar_hip.h"
@@ -311,6 +312,11 @@ struct WarpBoardMapArgs {
     double K[9], rect[4];
 };
 void launch_warp_board_maps(const WarpBoardMapArgs& a, hipStream_t stream);
+
+// One round of the three levels kernels (levels.hip) on the n_frames (at most LEVELS_WS_FRAMES: the workspace's) frames in
+// `format` of a (levels_core.h: LevelsArgs), whose two sides do not overlap: histograms into a.hist, which must be all zeros and is
+// all zeros again afterwards (the LUT kernel clears what it has read), LUTs into a.luts, the blend into a.dst.
+void launch_levels(const LevelsArgs& a, int n_frames, int format, hipStream_t stream);
 
 // The pyramids of n_frames frames in `format` (flow.hip: flow_grey_kernel, then flow_down_kernel level by level): frame f's
 // levels 0 .. g.L go to pyr + f * slot_bytes, laid out as g says.
