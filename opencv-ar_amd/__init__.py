@@ -708,10 +708,16 @@ class Detector:
                 pm[f, k] = lst[k]
         return pm, pc
 
+    def _strides(self, fmt, width, height, row_stride, frame_stride, bpp=None):
+        """(format code, row stride, frame stride) of frames of width x height pixels in fmt (None: the input format): a stride
+        that is not given is that of packed rows or frames; bpp: the bytes per pixel where they are not the format's"""
+        code = self.input_format if fmt is None else input_format_code(fmt)
+        row_stride = row_stride or (bpp or FORMAT_BPP[code]) * width
+        return code, row_stride, frame_stride or row_stride * height
+
     def enqueue_device(self, d_ptr, width, height, n_frames, row_stride=None, frame_stride=None, grey_in_place=False,
                        prev=None, stream=None):
-        row_stride = row_stride or FORMAT_BPP[self.input_format] * width
-        frame_stride = frame_stride or row_stride * height
+        _, row_stride, frame_stride = self._strides(None, width, height, row_stride, frame_stride)
         pm, pc = self._prev_arrays(prev, n_frames)
         self._keep = (pm, pc)
         self._check(self._lib.ocvar_hip_enqueue(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames,
@@ -722,8 +728,7 @@ class Detector:
                         grey_in_place=False, stream=None):
         """enqueue with the previous markers in device memory: d_prev [n_frames, max_markers] records, d_prev_counts [n_frames]
         (ocvar_hip_enqueue_tracked); collect() as after enqueue_device"""
-        row_stride = row_stride or FORMAT_BPP[self.input_format] * width
-        frame_stride = frame_stride or row_stride * height
+        _, row_stride, frame_stride = self._strides(None, width, height, row_stride, frame_stride)
         self._check(self._lib.ocvar_hip_enqueue_tracked(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames,
                                                         int(grey_in_place), d_prev_ptr, d_prev_counts_ptr, stream), "enqueue_tracked")
         self._n = n_frames
@@ -803,19 +808,15 @@ class Detector:
         """between enqueue and collect: draws the overlays onto the enqueued batch's markers in the device frames at d_ptr (the
         frames detected, or another buffer of the batch's frame count and size) in format fmt (default: the input format);
         stream-ordered behind the batch, does not wait"""
-        code = self.input_format if fmt is None else input_format_code(fmt)
-        row_stride = row_stride or FORMAT_BPP[code] * width
-        frame_stride = frame_stride or row_stride * height
+        code, row_stride, frame_stride = self._strides(fmt, width, height, row_stride, frame_stride)
         self._check(self._lib.ocvar_hip_render(self._ctx, d_ptr, width, height, row_stride, frame_stride, code, stream), "render")
 
     def render_records(self, d_ptr, width, height, n_frames, d_markers_ptr, d_counts_ptr, per_frame=None, fmt=None, row_stride=None,
                        frame_stride=None, stream=None):
         """draws the overlays onto n_frames device frames under caller-supplied device records [n_frames, per_frame] (default
         per_frame: max_markers) and counts [n_frames]; needs no batch, does not wait (stream None: the detector's own stream)"""
-        code = self.input_format if fmt is None else input_format_code(fmt)
         per_frame = self.max_markers if per_frame is None else per_frame
-        row_stride = row_stride or FORMAT_BPP[code] * width
-        frame_stride = frame_stride or row_stride * height
+        code, row_stride, frame_stride = self._strides(fmt, width, height, row_stride, frame_stride)
         self._check(self._lib.ocvar_hip_render_records(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames, code,
                                                        d_markers_ptr, d_counts_ptr, per_frame, stream), "render_records")
 
@@ -824,9 +825,7 @@ class Detector:
         annotate_style(), asks for; default: the library's default style) of the enqueued batch's markers into the device frames
         at d_ptr (the frames detected, or another buffer of the batch's frame count and size) in format fmt (default: the input
         format); stream-ordered behind the batch -- and behind a render called before it -- does not wait"""
-        code = self.input_format if fmt is None else input_format_code(fmt)
-        row_stride = row_stride or FORMAT_BPP[code] * width
-        frame_stride = frame_stride or row_stride * height
+        code, row_stride, frame_stride = self._strides(fmt, width, height, row_stride, frame_stride)
         st = annotate_style() if style is None else AnnotateStyle.from_buffer_copy(bytes(style))
         self._check(self._lib.ocvar_hip_annotate(self._ctx, d_ptr, width, height, row_stride, frame_stride, code, C.byref(st), stream), "annotate")
 
@@ -834,10 +833,8 @@ class Detector:
                          row_stride=None, frame_stride=None, stream=None):
         """the same on n_frames device frames under caller-supplied device records [n_frames, per_frame] (default per_frame:
         max_markers) and counts [n_frames]; needs no batch, does not wait (stream None: the detector's own stream)"""
-        code = self.input_format if fmt is None else input_format_code(fmt)
         per_frame = self.max_markers if per_frame is None else per_frame
-        row_stride = row_stride or FORMAT_BPP[code] * width
-        frame_stride = frame_stride or row_stride * height
+        code, row_stride, frame_stride = self._strides(fmt, width, height, row_stride, frame_stride)
         st = annotate_style() if style is None else AnnotateStyle.from_buffer_copy(bytes(style))
         self._check(self._lib.ocvar_hip_annotate_records(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames, code,
                                                          d_markers_ptr, d_counts_ptr, per_frame, C.byref(st), stream), "annotate_records")
@@ -851,10 +848,8 @@ class Detector:
         bottom-left pixels (flip_rows: rows stored bottom-up, as the template's image file reads).  d_status_ptr: device ints
         [n, per_frame], 1 where the slot was written; slots that are not written keep their bytes (include/ocvar_hip.h has the
         rule).  matched_only: records with score > 0 only.  Stream-ordered behind the batch, does not wait."""
-        code = self.input_format if fmt is None else input_format_code(fmt)
         per_frame = self.max_markers if per_frame is None else per_frame
-        row_stride = row_stride or FORMAT_BPP[code] * width
-        frame_stride = frame_stride or row_stride * height
+        code, row_stride, frame_stride = self._strides(fmt, width, height, row_stride, frame_stride)
         flags = (PATCH_FLIP_ROWS if flip_rows else 0) | (PATCH_MATCHED_ONLY if matched_only else 0)
         self._check(self._lib.ocvar_hip_patches(self._ctx, d_ptr, width, height, row_stride, frame_stride, code, d_patches_ptr, patch_w,
                                                 patch_h, per_frame, flags, d_status_ptr, stream), "patches")
@@ -863,10 +858,8 @@ class Detector:
                         fmt=None, row_stride=None, frame_stride=None, flip_rows=False, matched_only=False, d_status_ptr=None, stream=None):
         """the same for n_frames device frames under caller-supplied device records [n_frames, per_frame] (default per_frame:
         max_markers) and counts [n_frames]; needs no batch, does not wait (stream None: the detector's own stream)"""
-        code = self.input_format if fmt is None else input_format_code(fmt)
         per_frame = self.max_markers if per_frame is None else per_frame
-        row_stride = row_stride or FORMAT_BPP[code] * width
-        frame_stride = frame_stride or row_stride * height
+        code, row_stride, frame_stride = self._strides(fmt, width, height, row_stride, frame_stride)
         flags = (PATCH_FLIP_ROWS if flip_rows else 0) | (PATCH_MATCHED_ONLY if matched_only else 0)
         self._check(self._lib.ocvar_hip_patches_records(self._ctx, d_ptr, width, height, row_stride, frame_stride, n_frames, code,
                                                         d_markers_ptr, d_counts_ptr, per_frame, d_patches_ptr, patch_w, patch_h, flags,
@@ -878,11 +871,8 @@ class Detector:
         device frames at d_dst as a pinhole camera with the same camera matrix sees them (OpenCV's undistort with newCameraMatrix =
         cameraMatrix; 0 where the source lies outside the frame).  Source and destination must not overlap.  Needs no batch, does
         not wait (stream None: the detector's own stream); the camera is the one set at the call."""
-        code = self.input_format if fmt is None else input_format_code(fmt)
-        src_row_stride = src_row_stride or FORMAT_BPP[code] * width
-        src_frame_stride = src_frame_stride or src_row_stride * height
-        dst_row_stride = dst_row_stride or FORMAT_BPP[code] * width
-        dst_frame_stride = dst_frame_stride or dst_row_stride * height
+        code, src_row_stride, src_frame_stride = self._strides(fmt, width, height, src_row_stride, src_frame_stride)
+        code, dst_row_stride, dst_frame_stride = self._strides(fmt, width, height, dst_row_stride, dst_frame_stride)
         self._check(self._lib.ocvar_hip_undistort(self._ctx, d_src, src_row_stride, src_frame_stride, d_dst, dst_row_stride, dst_frame_stride,
                                                   width, height, n_frames, code, stream), "undistort")
 
@@ -900,9 +890,7 @@ class Detector:
         fmt (default: the input format): OpenCV's cvtColor COLOR_YUV2BGR_NV12 and its relatives, limited range, the matrix yuv names.
         A four-channel destination gets byte 3 = 255, 'gray' the library's grey of the converted colour.  The two sides must not
         overlap.  Needs no batch, does not wait (stream None: the detector's own stream)."""
-        code = self.input_format if fmt is None else input_format_code(fmt)
-        dst_row_stride = dst_row_stride or FORMAT_BPP[code] * width
-        dst_frame_stride = dst_frame_stride or dst_row_stride * height
+        code, dst_row_stride, dst_frame_stride = self._strides(fmt, width, height, dst_row_stride, dst_frame_stride)
         self._check(self._lib.ocvar_hip_yuv_to_frames(self._ctx, C.byref(yuv), d_dst, dst_row_stride, dst_frame_stride, width, height, n_frames,
                                                       code, stream), "yuv_to_frames")
 
@@ -911,9 +899,7 @@ class Detector:
         frames yuv (a YuvFrames) describes: OpenCV's cvtColor COLOR_BGR2YUV_I420 and its relatives, limited range, a chroma sample from
         the mean colour of its 2 x 2 or 2 x 1 pixels.  The two sides must not overlap.  Needs no batch, does not wait (stream None:
         the detector's own stream)."""
-        code = self.input_format if fmt is None else input_format_code(fmt)
-        src_row_stride = src_row_stride or FORMAT_BPP[code] * width
-        src_frame_stride = src_frame_stride or src_row_stride * height
+        code, src_row_stride, src_frame_stride = self._strides(fmt, width, height, src_row_stride, src_frame_stride)
         self._check(self._lib.ocvar_hip_frames_to_yuv(self._ctx, d_src, src_row_stride, src_frame_stride, C.byref(yuv), width, height, n_frames,
                                                       code, stream), "frames_to_yuv")
 
@@ -927,11 +913,8 @@ class Detector:
         detector's own stream)."""
         if not (isinstance(interp, str) and interp.lower() in RESIZE_INTERPS):
             raise ValueError(f"unknown interpolation {interp!r}: one of {sorted(RESIZE_INTERPS)}")
-        code = self.input_format if fmt is None else input_format_code(fmt)
-        src_row_stride = src_row_stride or FORMAT_BPP[code] * src_width
-        src_frame_stride = src_frame_stride or src_row_stride * src_height
-        dst_row_stride = dst_row_stride or FORMAT_BPP[code] * dst_width
-        dst_frame_stride = dst_frame_stride or dst_row_stride * dst_height
+        code, src_row_stride, src_frame_stride = self._strides(fmt, src_width, src_height, src_row_stride, src_frame_stride)
+        code, dst_row_stride, dst_frame_stride = self._strides(fmt, dst_width, dst_height, dst_row_stride, dst_frame_stride)
         self._check(self._lib.ocvar_hip_resize(self._ctx, d_src, src_width, src_height, src_row_stride, src_frame_stride, d_dst, dst_width,
                                                dst_height, dst_row_stride, dst_frame_stride, n_frames, code, RESIZE_INTERPS[interp.lower()],
                                                stream), "resize")
@@ -955,12 +938,9 @@ class Detector:
         strides.  Source and destination must not overlap, 'identity' included.  Needs no batch, does not wait (stream None: the
         detector's own stream)."""
         o = orientation_code(orientation)
-        code = self.input_format if fmt is None else input_format_code(fmt)
         dst_width, dst_height = oriented_size((src_width, src_height), o)
-        src_row_stride = src_row_stride or FORMAT_BPP[code] * src_width
-        src_frame_stride = src_frame_stride or src_row_stride * src_height
-        dst_row_stride = dst_row_stride or FORMAT_BPP[code] * dst_width
-        dst_frame_stride = dst_frame_stride or dst_row_stride * dst_height
+        code, src_row_stride, src_frame_stride = self._strides(fmt, src_width, src_height, src_row_stride, src_frame_stride)
+        code, dst_row_stride, dst_frame_stride = self._strides(fmt, dst_width, dst_height, dst_row_stride, dst_frame_stride)
         self._check(self._lib.ocvar_hip_orient(self._ctx, d_src, src_width, src_height, src_row_stride, src_frame_stride, d_dst, dst_row_stride,
                                                dst_frame_stride, n_frames, code, o, stream), "orient")
 
@@ -984,11 +964,8 @@ class Detector:
         with set_input_format('gray') the planes yield records in the source frames' own coordinates.  The sizes are not bound by
         the detector's.  Source and destination must not overlap.  The first call allocates a workspace of 20 MiB.  Needs no batch,
         does not wait (stream None: the detector's own stream)."""
-        code = self.input_format if fmt is None else input_format_code(fmt)
-        src_row_stride = src_row_stride or FORMAT_BPP[code] * width
-        src_frame_stride = src_frame_stride or src_row_stride * height
-        dst_row_stride = dst_row_stride or width
-        dst_frame_stride = dst_frame_stride or dst_row_stride * height
+        code, src_row_stride, src_frame_stride = self._strides(fmt, width, height, src_row_stride, src_frame_stride)
+        _, dst_row_stride, dst_frame_stride = self._strides(fmt, width, height, dst_row_stride, dst_frame_stride, bpp=1)   # (GRAY)
         self._check(self._lib.ocvar_hip_levels(self._ctx, d_src, width, height, src_row_stride, src_frame_stride, code, d_dst, dst_row_stride,
                                                dst_frame_stride, n_frames, None if params is None else C.byref(params), stream), "levels")
 
@@ -1007,11 +984,8 @@ class Detector:
             raise ValueError(f"unknown interpolation {interp!r}: one of {sorted(WARP_INTERPS)}")
         if not (isinstance(border, str) and border.lower() in WARP_BORDERS):
             raise ValueError(f"unknown border {border!r}: one of {sorted(WARP_BORDERS)}")
-        code = self.input_format if fmt is None else input_format_code(fmt)
-        src_row_stride = src_row_stride or FORMAT_BPP[code] * src_width
-        src_frame_stride = src_frame_stride or src_row_stride * src_height
-        dst_row_stride = dst_row_stride or FORMAT_BPP[code] * dst_width
-        dst_frame_stride = dst_frame_stride or dst_row_stride * dst_height
+        code, src_row_stride, src_frame_stride = self._strides(fmt, src_width, src_height, src_row_stride, src_frame_stride)
+        code, dst_row_stride, dst_frame_stride = self._strides(fmt, dst_width, dst_height, dst_row_stride, dst_frame_stride)
         fill4 = None
         if fill is not None:
             f = [int(v) for v in np.atleast_1d(fill)]
@@ -1057,12 +1031,9 @@ class Detector:
         are not written.  params: flow_params(...), default the library's.  d_status_ptr: device ints [n_frames, per_frame];
         d_err_ptr: device floats [n_frames, per_frame, 4], the corners' mean absolute differences.  Needs no batch, does not wait
         (stream None: the detector's own stream); the frames are only read."""
-        code = self.input_format if fmt is None else input_format_code(fmt)
         per_frame = self.max_markers if per_frame is None else per_frame
-        prev_row_stride = prev_row_stride or FORMAT_BPP[code] * width
-        prev_frame_stride = prev_frame_stride or prev_row_stride * height
-        next_row_stride = next_row_stride or FORMAT_BPP[code] * width
-        next_frame_stride = next_frame_stride or next_row_stride * height
+        code, prev_row_stride, prev_frame_stride = self._strides(fmt, width, height, prev_row_stride, prev_frame_stride)
+        code, next_row_stride, next_frame_stride = self._strides(fmt, width, height, next_row_stride, next_frame_stride)
         p = flow_params() if params is None else FlowParams.from_buffer_copy(bytes(params))
         if pose:
             p.flags |= FLOW_POSE

@@ -4,6 +4,7 @@
 // per record slot: its primitives and boxes) and annotate_draw_kernel (by frame tile, as overlay.hip draws, so that overlapping
 // records neither race nor change their order).
 #include "kernels.h"
+#include "lane_run.h"
 
 namespace ocvar {
 
@@ -27,7 +28,6 @@ constexpr int ANNO_WAVE_ROWS = 4;                 // consecutive rows a wave own
 constexpr int ANNO_WAVES = 4;
 constexpr int ANNO_TILE_H = ANNO_WAVES * ANNO_WAVE_ROWS;
 
-OCVAR_D unsigned anno_get(const unsigned* q, int byte) { return (q[byte >> 2] >> (8 * (byte & 3))) & 255u; }
 OCVAR_D void anno_put(unsigned* q, int byte, unsigned v) {
     const int s = 8 * (byte & 3);
     q[byte >> 2] = (q[byte >> 2] & ~(255u << s)) | (v << s);
@@ -172,8 +172,8 @@ __global__ __launch_bounds__(64 * ANNO_WAVES) void annotate_draw_kernel(AnnoArgs
                 OCVAR_UNROLL
                 for (int i = 0; i < ANNO_LANE_PX; i++)
                     if (c[r][i] >> 24) {
-                        unsigned v[3] = {anno_get(q[r], i * BPP), NC > 1 ? anno_get(q[r], i * BPP + NC - 2) : 0u,
-                                         NC > 1 ? anno_get(q[r], i * BPP + NC - 1) : 0u};
+                        unsigned v[3] = {(unsigned)run_byte(q[r], i * BPP), NC > 1 ? (unsigned)run_byte(q[r], i * BPP + NC - 2) : 0u,
+                                         NC > 1 ? (unsigned)run_byte(q[r], i * BPP + NC - 1) : 0u};
                         overlay_blend_px(FMT, c[r][i], v);
                         OCVAR_UNROLL
                         for (int j = 0; j < NC; j++) anno_put(q[r], i * BPP + j, v[j]);
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(64 * ANNO_WAVES) void annotate_draw_kernel(AnnoArgs
             for (int i = 0; i < ANNO_LANE_PX; i++)
                 if ((dirty >> (4 * r + i)) & 1u) {
                     OCVAR_UNROLL
-                    for (int j = 0; j < NC; j++) p[i * BPP + j] = (uint8_t)anno_get(q[r], i * BPP + j);
+                    for (int j = 0; j < NC; j++) p[i * BPP + j] = (uint8_t)run_byte(q[r], i * BPP + j);
                 }
         }
     }
@@ -219,7 +219,7 @@ void launch_annotate(const AnnoArgs& aa, uint8_t* frames, int W, int H, long lon
     const long long lanes = (long long)n_frames * stride;
     hipLaunchKernelGGL(annotate_setup_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, aa, recs, counts, stride, n_frames, W, H,
                        st, cam);
-    const bool aligned = (((unsigned long long)(uintptr_t)frames | (unsigned long long)row_stride | (unsigned long long)frame_stride) & 3ull) == 0;
+    const bool aligned = frames_dwords(frames, row_stride, frame_stride);
     switch (format) {
         case OCVAR_FMT_BGR: launch_draw<OCVAR_FMT_BGR>(aa, frames, W, H, row_stride, frame_stride, n_frames, stride, aligned, stream); break;
         case OCVAR_FMT_RGB: launch_draw<OCVAR_FMT_RGB>(aa, frames, W, H, row_stride, frame_stride, n_frames, stride, aligned, stream); break;

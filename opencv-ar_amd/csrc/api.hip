@@ -1,6 +1,7 @@
-// api.hip -- the thin C ABI of include/ocvar_hip.h: context, device workspace, launch sequence, result copy-out and the work
-// that follows a batch.  (context.h: the context itself; plan_core.h: sizes and grids; gate.hip, host_transport.hip, debug.hip:
-// the gate and its lanes, frames in host memory, the debug entry points.)
+// api.hip -- the thin C ABI of include/ocvar_hip.h: context, device workspace, templates, camera and tuning, launch sequence,
+// result copy-out, board setup, timing and counters.  (context.h: the context itself; plan_core.h: sizes and grids; frame_ops.hip:
+// the opt-in operations on frames and records; gate.hip, host_transport.hip, debug.hip: the gate and its lanes, frames in host
+// memory, the debug entry points.)
 //
 // One batch = 12 kernel launches on one HIP stream, no host round trip in between (work counts stay in
 // device memory and the second-pass kernels are launched with fixed grids that read them):
@@ -8,10 +9,12 @@
 //   follow.hip), 3 (crops) -> decode -> finalise
 // There is deliberately no CPU path here: if the device or the code object is missing, create() fails.
 #include "context.h"
+#include "frames_core.h"
 #include "plan_core.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 
 using namespace ocvar;
@@ -22,15 +25,6 @@ static_assert(sizeof(CameraRec) == sizeof(OcvarCamera) && sizeof(CameraRec) == 2
 static_assert(sizeof(MarkerRec) == sizeof(OcvarMarker) && sizeof(MarkerRec) == 184, "CvarMarker layout");
 static_assert(sizeof(BoardEntry) == sizeof(OcvarBoardMarker) && sizeof(BoardEntry) == 72, "OcvarBoardMarker layout");
 static_assert(sizeof(BoardPose) == sizeof(OcvarBoardPose) && sizeof(BoardPose) == 192, "OcvarBoardPose layout");
-
-template <typename T>
-static int dev_alloc(OcvarHip* c, T** p, size_t n) {
-    void* q = nullptr;
-    HIP_TRY(c, hipMalloc(&q, n * sizeof(T) + 256));
-    c->allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return OCVAR_OK;
-}
 
 static int create_impl(OcvarHip** out, int device, int max_width, int max_height, int max_batch, int max_quads, int max_markers,
                        bool dense) {
@@ -158,9 +152,8 @@ extern "C" void ocvar_hip_destroy(OcvarHip* c) {
     (void)hipSetDevice(c->device);
     gate_detach(c);   // (waits for a batch on a lane of the gate)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->ovl_used) (void)hipEventSynchronize(c->ovl_done);   // (a render_records in flight reads the overlay workspace and the images)
-    if (c->anno_used) (void)hipEventSynchronize(c->anno_done);   // (an annotate_records in flight reads its workspace)
-    if (c->levels_used) (void)hipEventSynchronize(c->levels_done);   // (a levels call in flight uses its workspace)
+    // (a frame operation in flight uses its workspace; a render_records reads the overlay images too)
+    for (WorkspaceFence* f : {&c->ovl_fence, &c->anno_fence, &c->levels_fence, &c->flow_fence}) (void)f->drain();
     delete c;
 }
 
@@ -275,7 +268,7 @@ int ocvar::refuse_if_pending(OcvarHip* c) {
 // A frame whose rows reach further from its first byte than the frame binarise kernel addresses (hd.h::frame_src_addressable)
 // is refused: its lower rows would be read somewhere else, or as zeros, and the call would return a plausible, different result.
 int ocvar::frame_span_check(OcvarHip* c, int width, int height, int row_stride, int format) {
-    const int bpp = input_format_bpp(format);
+    const int bpp = format_bpp(format);
     if (frame_src_addressable(width, height, row_stride, bpp)) return OCVAR_OK;
     c->err = "the rows of a frame span more than the frame kernel addresses: ((height & ~1) - 1) * row_stride + bytes per pixel * "
              "(width & ~1) must not exceed 2147483647 (got " +
@@ -296,8 +289,8 @@ int ocvar::enqueue_impl(OcvarHip* c, const BatchRequest& r, hipStream_t s, hipSt
     const int n_frames = r.n_frames;
     int stages = r.stages;
     if (!r.frames || r.width < 16 || r.height < 16 || r.width > w.max_w || r.height > w.max_h || n_frames < 1 || n_frames > w.max_batch ||
-        (size_t)r.width * r.height > (size_t)w.max_w * w.max_h || input_format_bpp(r.format) == 0 ||
-        (long long)r.row_stride < (long long)input_format_bpp(r.format) * r.width)
+        (size_t)r.width * r.height > (size_t)w.max_w * w.max_h || format_bpp(r.format) == 0 ||
+        (long long)r.row_stride < (long long)format_bpp(r.format) * r.width)
         return OCVAR_E_ARG;
     if (int rc = frame_span_check(c, r.width, r.height, r.row_stride, r.format)) return rc;
     if (int rc = refuse_if_pending(c)) return rc;
@@ -509,7 +502,7 @@ extern "C" int ocvar_hip_enqueue_tracked(OcvarHip* c, uint8_t* d_bgr, int width,
 // need a wait for the batch's last event -- a barrier in a hardware queue that stream shares with a lane, which holds up the
 // other contexts' batches queued there until this one has finished: bench.py's multi-rank path lost a sixth of its rate to it.)
 // Any other stream the caller names waits for the batch's last event.
-static int follow_begin(OcvarHip* c, void* stream, hipStream_t* s) {
+int ocvar::follow_begin(OcvarHip* c, void* stream, hipStream_t* s) {
     *s = (!stream || (c->on_lane && (hipStream_t)stream == c->stream)) ? c->last_stream : (hipStream_t)stream;
     if (*s != c->last_stream) HIP_TRY(c, hipStreamWaitEvent(*s, c->ev[EV_LAST], 0));
     return OCVAR_OK;
@@ -517,7 +510,7 @@ static int follow_begin(OcvarHip* c, void* stream, hipStream_t* s) {
 
 // follow_end: behind work put on a lane collect waits for it too (it waits for events there; in front of the lanes collect's
 // wait for the batch's stream covered a results copy, and bench.py's gather reads the block right after collect).
-static int follow_end(OcvarHip* c, hipStream_t s) {
+int ocvar::follow_end(OcvarHip* c, hipStream_t s) {
     if (!c->on_lane || s != c->last_stream) return OCVAR_OK;
     HIP_TRY(c, c->copied.ensure(hipEventDisableTiming));
     c->copy_pending = true;
@@ -526,7 +519,7 @@ static int follow_end(OcvarHip* c, hipStream_t s) {
 }
 
 // what the entry points that work on the frames of the batch in flight refuse alike: no batch, or frames of another size
-static bool batch_frames_ok(OcvarHip* c, const char* who, int width, int height) {
+bool ocvar::batch_frames_ok(OcvarHip* c, const char* who, int width, int height) {
     if (!c->pending) c->err = std::string(who) + ": nothing enqueued";
     else if (width != c->ws.W || height != c->ws.H) c->err = std::string(who) + ": the frames are not of the batch's size";
     else return true;
@@ -592,7 +585,7 @@ extern "C" int ocvar_hip_set_result_limit(OcvarHip* c, int max_per_frame) {
 
 extern "C" int ocvar_hip_set_input_format(OcvarHip* c, int format) {
     if (!c) return OCVAR_E_ARG;
-    if (input_format_bpp(format) == 0) {
+    if (format_bpp(format) == 0) {
         c->err = "unknown input format";
         return OCVAR_E_ARG;
     }
@@ -665,782 +658,6 @@ extern "C" int ocvar_hip_board_poses_to_device(OcvarHip* c, OcvarBoardPose* d_po
     if (int rc = follow_begin(c, stream, &s)) return rc;
     HIP_TRY(c, hipMemcpyAsync(d_poses, c->d_board_poses, (size_t)c->ws.n_frames * sizeof(BoardPose), hipMemcpyDeviceToDevice, s));
     return follow_end(c, s);
-}
-
-extern "C" int ocvar_hip_set_overlay(OcvarHip* c, int template_id, const uint8_t* h_rgba, int width, int height, int row_stride) {
-    if (!c) return OCVAR_E_ARG;
-    if (template_id < -1 || template_id >= MAXT) {
-        c->err = "ocvar_hip_set_overlay: template id outside -1 .. 4095";
-        return OCVAR_E_ARG;
-    }
-    if (h_rgba && (width < 2 || height < 2 || width > OVL_MAX_SIDE || height > OVL_MAX_SIDE || (long long)row_stride < 4ll * width)) {
-        c->err = "ocvar_hip_set_overlay: sides 2 .. 1024 texels, row_stride >= 4 width";
-        return OCVAR_E_ARG;
-    }
-    if (int rc = refuse_if_pending(c)) return rc;
-    OverlayTable* t = c->h_overlays;
-    int slot = !t ? -1 : (template_id < 0 ? t->dflt : t->map[template_id]);
-    if (!h_rgba && slot < 0) return OCVAR_OK;   // (nothing to remove)
-    if (h_rgba && slot < 0 && c->n_overlays >= OVL_MAX) {
-        c->err = "ocvar_hip_set_overlay: the context has OCVAR_MAX_OVERLAYS overlays";
-        return OCVAR_E_ARG;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!t) {   // (the host table last: its presence says that the device blocks exist)
-        const size_t recs = (size_t)c->ws.max_batch * c->ws.maxm;
-        int rc = dev_alloc(c, &c->d_overlays, 1);
-        if (!rc) rc = dev_alloc(c, &c->d_ovl_draws, recs);
-        if (!rc) rc = dev_alloc(c, &c->d_ovl_boxes, recs);
-        if (rc) return rc;
-        HIP_TRY(c, c->ovl_done.ensure(hipEventDisableTiming));
-        t = new (std::nothrow) OverlayTable();
-        if (!t) return OCVAR_E_HIP;
-        for (auto& x : t->tex) x = OverlayTex{nullptr, 0, 0};
-        t->dflt = -1;
-        for (auto& m : t->map) m = -1;
-        c->h_overlays = t;
-    }
-    if (c->ovl_used) HIP_TRY(c, hipEventSynchronize(c->ovl_done));   // (a render_records in flight reads the table and the images)
-    if (slot >= 0) {   // removed, or replaced below
-        HIP_TRY(c, hipFree(const_cast<uint32_t*>(t->tex[slot].px)));
-        t->tex[slot] = OverlayTex{nullptr, 0, 0};
-        (template_id < 0 ? t->dflt : t->map[template_id]) = -1;
-        c->n_overlays--;
-    }
-    if (h_rgba) {
-        for (slot = 0; slot < OVL_MAX && t->tex[slot].px; slot++) {}
-        void* d = nullptr;
-        HIP_TRY(c, hipMalloc(&d, (size_t)width * height * 4));
-        const hipError_t e = hipMemcpy2D(d, (size_t)width * 4, h_rgba, (size_t)row_stride, (size_t)width * 4, (size_t)height, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            c->err = std::string("ocvar_hip_set_overlay: ") + hipGetErrorString(e);
-            return OCVAR_E_HIP;
-        }
-        t->tex[slot] = OverlayTex{static_cast<const uint32_t*>(d), width, height};
-        (template_id < 0 ? t->dflt : t->map[template_id]) = slot;
-        c->n_overlays++;
-    }
-    HIP_TRY(c, hipMemcpy(c->d_overlays, t, sizeof(OverlayTable), hipMemcpyHostToDevice));
-    return OCVAR_OK;
-}
-
-// setup + draw of n_frames frames (chunks of the workspace's max_batch) on stream s, behind the workspace's last use
-static int overlay_launch(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int n_frames,
-                          int format, const MarkerRec* recs, const int* counts, int stride, hipStream_t s) {
-    if (c->ovl_used && c->ovl_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->ovl_done, 0));
-    const OverlayArgs oa{c->d_overlays, c->d_ovl_draws, c->d_ovl_boxes};
-    const int chunk = std::min(c->ws.max_batch, 32768);   // (frames are the grid's z)
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const int n = std::min(chunk, n_frames - f0);
-        launch_overlay(oa, d_frames + (size_t)f0 * frame_stride, width, height, row_stride, (long long)frame_stride, n, format,
-                       recs + (size_t)f0 * stride, counts + f0, stride, s);
-        TRACE_LAUNCH("overlay", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ovl_done, s));
-    c->ovl_stream = s;
-    c->ovl_used = true;
-    return OCVAR_OK;
-}
-
-static bool overlay_frames_ok(OcvarHip* c, const uint8_t* d_frames, int width, int row_stride, int format) {
-    if (!d_frames || input_format_bpp(format) == 0 || (long long)row_stride < (long long)input_format_bpp(format) * width) {
-        c->err = "render: no frames, an unknown format or a row_stride below the format's bytes per pixel times width";
-        return false;
-    }
-    if (c->n_overlays < 1) {
-        c->err = "render: no overlay is set";
-        return false;
-    }
-    return true;
-}
-
-extern "C" int ocvar_hip_render(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int format,
-                                void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    if (!batch_frames_ok(c, "render", width, height)) return OCVAR_E_ARG;
-    if (!overlay_frames_ok(c, d_frames, width, row_stride, format)) return OCVAR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s;
-    if (int rc = follow_begin(c, stream, &s)) return rc;
-    const int rc = overlay_launch(c, d_frames, width, height, row_stride, frame_stride, c->ws.n_frames, format, c->ws.markers,
-                                  c->ws.n_markers, c->ws.maxm, s);
-    if (rc) return rc;
-    return follow_end(c, s);
-}
-
-extern "C" int ocvar_hip_render_records(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride,
-                                        int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts,
-                                        int records_per_frame, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    if (!d_markers || !d_counts || n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm || width < 1 || height < 1 ||
-        width > c->ws.max_w || height > c->ws.max_h) {
-        c->err = "render_records: frames of 1 .. the context's size, n_frames >= 1, 1 .. M records per frame";
-        return OCVAR_E_ARG;
-    }
-    if (!overlay_frames_ok(c, d_frames, width, row_stride, format)) return OCVAR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return overlay_launch(c, d_frames, width, height, row_stride, frame_stride, n_frames, format,
-                          reinterpret_cast<const MarkerRec*>(d_markers), d_counts, records_per_frame, stream ? (hipStream_t)stream : c->stream.s);
-}
-
-extern "C" int ocvar_hip_annotate_default_style(OcvarAnnotateStyle* style) {
-    if (!style) return OCVAR_E_ARG;
-    anno_default_style(style);
-    return OCVAR_OK;
-}
-
-// what ocvar_hip_annotate and ocvar_hip_annotate_records refuse alike
-static bool annotate_args_ok(OcvarHip* c, const uint8_t* d_frames, int width, int row_stride, int format, const OcvarAnnotateStyle* style) {
-    static const char* const why[] = {"", "no style", "thickness 1 .. 16", "label_scale 0 .. 8", "axis_length and cube_height are finite numbers >= 0",
-                                      "unknown flag bits", "none of OUTLINE, CORNER0, AXES, CUBE and LABEL is set", "AXES or CUBE without a camera"};
-    if (!d_frames || input_format_bpp(format) == 0 || (long long)row_stride < (long long)input_format_bpp(format) * width) {
-        c->err = "annotate: no frames, an unknown format or a row_stride below the format's bytes per pixel times width";
-        return false;
-    }
-    if (const int bad = anno_style_bad(style, c->have_camera)) {
-        c->err = std::string("annotate: ") + why[bad];
-        return false;
-    }
-    return true;
-}
-
-// setup + draw of n_frames frames (chunks of the workspace's max_batch) on stream s, behind the workspace's last use
-static int annotate_launch(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int n_frames,
-                           int format, const MarkerRec* recs, const int* counts, int stride, const OcvarAnnotateStyle& st, hipStream_t s) {
-    const size_t slots = (size_t)c->ws.max_batch * c->ws.maxm;
-    HIP_TRY(c, c->anno_recs.reserve(slots * sizeof(AnnoRec)));
-    HIP_TRY(c, c->anno_boxes.reserve(slots * sizeof(AnnoBox)));
-    HIP_TRY(c, c->anno_done.ensure(hipEventDisableTiming));
-    if (c->anno_used && c->anno_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->anno_done, 0));
-    const AnnoArgs aa{c->anno_recs, c->anno_boxes};
-    const int chunk = std::min(c->ws.max_batch, 32768);   // (frames are the grid's z)
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const int n = std::min(chunk, n_frames - f0);
-        launch_annotate(aa, d_frames + (size_t)f0 * frame_stride, width, height, row_stride, (long long)frame_stride, n, format,
-                        recs + (size_t)f0 * stride, counts + f0, stride, st, c->h_camera, s);
-        TRACE_LAUNCH("annotate", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->anno_done, s));
-    c->anno_stream = s;
-    c->anno_used = true;
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_annotate(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int format,
-                                  const OcvarAnnotateStyle* style, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    if (!batch_frames_ok(c, "annotate", width, height)) return OCVAR_E_ARG;
-    if (!annotate_args_ok(c, d_frames, width, row_stride, format, style)) return OCVAR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s;
-    if (int rc = follow_begin(c, stream, &s)) return rc;
-    const int rc = annotate_launch(c, d_frames, width, height, row_stride, frame_stride, c->ws.n_frames, format, c->ws.markers,
-                                   c->ws.n_markers, c->ws.maxm, *style, s);
-    if (rc) return rc;
-    return follow_end(c, s);
-}
-
-extern "C" int ocvar_hip_annotate_records(OcvarHip* c, uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride,
-                                          int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts,
-                                          int records_per_frame, const OcvarAnnotateStyle* style, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    if (!d_markers || !d_counts || n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm || width < 1 || height < 1 ||
-        width > c->ws.max_w || height > c->ws.max_h) {
-        c->err = "annotate_records: frames of 1 .. the context's size, n_frames >= 1, 1 .. M records per frame";
-        return OCVAR_E_ARG;
-    }
-    if (!annotate_args_ok(c, d_frames, width, row_stride, format, style)) return OCVAR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return annotate_launch(c, d_frames, width, height, row_stride, frame_stride, n_frames, format,
-                           reinterpret_cast<const MarkerRec*>(d_markers), d_counts, records_per_frame, *style, stream ? (hipStream_t)stream : c->stream.s);
-}
-
-// what ocvar_hip_patches and ocvar_hip_patches_records refuse alike
-static bool patch_args_ok(OcvarHip* c, const uint8_t* d_frames, int width, int row_stride, int format, const uint8_t* d_patches, int patch_w,
-                          int patch_h, int records_per_frame, int flags) {
-    if (!d_frames || !d_patches) {
-        c->err = "patches: no frames or no patch buffer";
-    } else if (patch_bpp(format) == 0 || (long long)row_stride < (long long)patch_bpp(format) * width) {
-        c->err = "patches: an unknown format or a row_stride below the format's bytes per pixel times width";
-    } else if (patch_w < 2 || patch_h < 2 || patch_w > PATCH_MAX_SIDE || patch_h > PATCH_MAX_SIDE) {
-        c->err = "patches: patch sides of 2 .. " + std::to_string(PATCH_MAX_SIDE) + " pixels";
-    } else if (flags & ~PATCH_FLAGS) {
-        c->err = "patches: unknown flag bits";
-    } else if (records_per_frame < 1 || records_per_frame > c->ws.maxm) {
-        c->err = "patches: 1 .. M records per frame";
-    } else {
-        return true;
-    }
-    return false;
-}
-
-// n_frames frames on stream s, in chunks of the grid's z
-static int patch_launch(OcvarHip* c, const PatchArgs& all, int n_frames, int format, hipStream_t s) {
-    const int chunk = 32768;
-    const size_t frame_patches = (size_t)all.slots * all.ph * all.pw * patch_bpp(format);
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        PatchArgs a = all;
-        a.frames += (size_t)f0 * a.frame_stride;
-        a.recs += (size_t)f0 * a.rec_stride;
-        a.counts += f0;
-        a.patches += (size_t)f0 * frame_patches;
-        if (a.status) a.status += (size_t)f0 * a.slots;
-        launch_patches(a, std::min(chunk, n_frames - f0), format, s);
-        TRACE_LAUNCH("patches", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_patches(OcvarHip* c, const uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride, int format,
-                                 uint8_t* d_patches, int patch_w, int patch_h, int records_per_frame, int flags, int* d_status, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    if (!batch_frames_ok(c, "patches", width, height)) return OCVAR_E_ARG;
-    if (!patch_args_ok(c, d_frames, width, row_stride, format, d_patches, patch_w, patch_h, records_per_frame, flags)) return OCVAR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s;
-    if (int rc = follow_begin(c, stream, &s)) return rc;
-    const PatchArgs a{d_frames, width, height, (long long)row_stride, (long long)frame_stride, c->ws.markers, c->ws.n_markers, c->ws.maxm,
-                      d_patches, patch_w, patch_h, records_per_frame, flags, d_status};
-    const int rc = patch_launch(c, a, c->ws.n_frames, format, s);
-    if (rc) return rc;
-    return follow_end(c, s);
-}
-
-extern "C" int ocvar_hip_patches_records(OcvarHip* c, const uint8_t* d_frames, int width, int height, int row_stride, size_t frame_stride,
-                                         int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
-                                         uint8_t* d_patches, int patch_w, int patch_h, int flags, int* d_status, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    if (!d_markers || !d_counts || n_frames < 1 || width < 1 || height < 1 || width > c->ws.max_w || height > c->ws.max_h) {
-        c->err = "patches_records: records and counts, frames of 1 .. the context's size, n_frames >= 1";
-        return OCVAR_E_ARG;
-    }
-    if (!patch_args_ok(c, d_frames, width, row_stride, format, d_patches, patch_w, patch_h, records_per_frame, flags)) return OCVAR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const PatchArgs a{d_frames, width, height, (long long)row_stride, (long long)frame_stride, reinterpret_cast<const MarkerRec*>(d_markers),
-                      d_counts, records_per_frame, d_patches, patch_w, patch_h, records_per_frame, flags, d_status};
-    return patch_launch(c, a, n_frames, format, stream ? (hipStream_t)stream : c->stream.s);
-}
-
-// the context's camera as the undistort entry points take it; false (and the text) when there is none they can use
-static bool undistort_camera(OcvarHip* c, const char* what, UndistortCam* cam) {
-    if (!c->have_camera) {
-        c->err = std::string(what) + ": no camera set";
-        return false;
-    }
-    *cam = undistort_cam(c->h_camera);
-    if (!undistort_cam_ok(*cam)) {
-        c->err = std::string(what) + ": the camera's fx or fy is zero, or one of fx fy cx cy k1 k2 p1 p2 k3 is not finite";
-        return false;
-    }
-    return true;
-}
-
-// the bytes from a frame block's first to its last pixel byte
-static unsigned long long frames_extent(int width, int height, int bpp, long long row_stride, size_t frame_stride, int n_frames) {
-    return (unsigned long long)(n_frames - 1) * frame_stride + (unsigned long long)(height - 1) * (unsigned long long)row_stride +
-           (unsigned long long)bpp * width;
-}
-
-extern "C" int ocvar_hip_undistort(OcvarHip* c, const uint8_t* d_src, int src_row_stride, size_t src_frame_stride, uint8_t* d_dst,
-                                   int dst_row_stride, size_t dst_frame_stride, int width, int height, int n_frames, int format, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    const int bpp = patch_bpp(format);
-    if (!d_src || !d_dst) {
-        c->err = "undistort: no source or no destination frames";
-        return OCVAR_E_ARG;
-    }
-    if (n_frames < 1 || width < 1 || height < 1 || width > c->ws.max_w || height > c->ws.max_h) {
-        c->err = "undistort: frames of 1 .. the context's size, n_frames >= 1";
-        return OCVAR_E_ARG;
-    }
-    if (bpp == 0 || (long long)src_row_stride < (long long)bpp * width || (long long)dst_row_stride < (long long)bpp * width) {
-        c->err = "undistort: an unknown format or a row stride below the format's bytes per pixel times width";
-        return OCVAR_E_ARG;
-    }
-    if (int rc = frame_span_check(c, width, height, src_row_stride, format)) return rc;
-    if (int rc = frame_span_check(c, width, height, dst_row_stride, format)) return rc;
-    const unsigned long long s0 = (unsigned long long)(uintptr_t)d_src, d0 = (unsigned long long)(uintptr_t)d_dst;
-    const unsigned long long s1 = s0 + frames_extent(width, height, bpp, src_row_stride, src_frame_stride, n_frames);
-    const unsigned long long d1 = d0 + frames_extent(width, height, bpp, dst_row_stride, dst_frame_stride, n_frames);
-    if (s0 < d1 && d0 < s1) {
-        c->err = "undistort: the byte ranges of source and destination frames intersect (no undistortion in place)";
-        return OCVAR_E_ARG;
-    }
-    UndistortCam cam;
-    if (!undistort_camera(c, "undistort", &cam)) return OCVAR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    const int chunk = 65535;
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const UndistortArgs a{d_src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, width, height,
-                              (long long)src_row_stride, (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride, cam};
-        launch_undistort(a, std::min(chunk, n_frames - f0), format, s);
-        TRACE_LAUNCH("undistort", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_undistort_records(OcvarHip* c, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
-                                           OcvarMarker* d_out, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    if (!d_markers || !d_counts || !d_out) {
-        c->err = "undistort_records: no records, no counts or no output";
-        return OCVAR_E_ARG;
-    }
-    if (n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm) {
-        c->err = "undistort_records: n_frames >= 1, 1 .. M records per frame";
-        return OCVAR_E_ARG;
-    }
-    UndistortCam cam;
-    if (!undistort_camera(c, "undistort_records", &cam)) return OCVAR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    const int chunk = 65535;
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const UndistortRecArgs a{reinterpret_cast<const MarkerRec*>(d_markers) + (size_t)f0 * records_per_frame,
-                                 reinterpret_cast<MarkerRec*>(d_out) + (size_t)f0 * records_per_frame, d_counts + f0, records_per_frame, cam};
-        launch_undistort_records(a, std::min(chunk, n_frames - f0), s);
-        TRACE_LAUNCH("undistort_records", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-// What ocvar_hip_yuv_to_frames and ocvar_hip_frames_to_yuv refuse alike, and the launches: yuv describes one side, pix the other.
-static int yuv_convert(OcvarHip* c, const char* what, const OcvarYuvFrames* yuv, const uint8_t* pix, int row_stride, size_t frame_stride,
-                       int width, int height, int n_frames, int format, bool to_frames, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    const std::string w = std::string(what) + ": ";
-    const auto refuse = [&](const std::string& text) {
-        c->err = w + text;
-        return OCVAR_E_ARG;
-    };
-    if (!yuv || !pix) return refuse("no YUV frames or no frames");
-    if (!yuv_layout_ok(yuv->layout) || !yuv_matrix_ok(yuv->matrix) || patch_bpp(format) == 0) return refuse("an unknown layout, matrix or format");
-    const bool s420 = yuv_is_420(yuv->layout);
-    if (!yuv->y || (s420 && !yuv->c0) || (yuv->layout == OCVAR_YUV_I420 && !yuv->c1)) return refuse("a plane the layout uses is NULL");
-    if (n_frames < 1 || width < 1 || height < 1 || width > c->ws.max_w || height > c->ws.max_h)
-        return refuse("frames of 1 .. the context's size, n_frames >= 1");
-    if ((width & 1) || (s420 && (height & 1))) return refuse("an odd width, or an odd height with NV12 or I420");
-    const int bpp = patch_bpp(format);
-    // the planes: first byte, bytes per row, rows, pitch
-    struct Plane { const uint8_t* p; long long row_bytes, rows, pitch; };
-    Plane planes[3];
-    int n_planes = 0;
-    planes[n_planes++] = Plane{yuv->y, s420 ? (long long)width : 2LL * width, height, yuv->y_pitch};
-    if (yuv->layout == OCVAR_YUV_NV12) planes[n_planes++] = Plane{yuv->c0, width, height / 2, yuv->c_pitch};
-    if (yuv->layout == OCVAR_YUV_I420) {
-        planes[n_planes++] = Plane{yuv->c0, width / 2, height / 2, yuv->c_pitch};
-        planes[n_planes++] = Plane{yuv->c1, width / 2, height / 2, yuv->c_pitch};
-    }
-    for (int i = 0; i < n_planes; i++)
-        if (planes[i].pitch < planes[i].row_bytes) return refuse("a pitch below the plane's bytes per row");
-    if ((long long)row_stride < (long long)bpp * width) return refuse("a row stride below the format's bytes per pixel times width");
-    const auto span = [](long long rows, long long stride, long long row_bytes) { return (rows - 1) * stride + row_bytes; };
-    const long long pix_span = span(height, row_stride, (long long)bpp * width);
-    bool spans_ok = pix_span <= 2147483647LL;
-    for (int i = 0; i < n_planes; i++) spans_ok = spans_ok && span(planes[i].rows, planes[i].pitch, planes[i].row_bytes) <= 2147483647LL;
-    if (!spans_ok) return refuse("the rows of a plane or of a frame span more than 2147483647 bytes");
-    const unsigned long long p0 = (unsigned long long)(uintptr_t)pix;
-    const unsigned long long p1 = p0 + (unsigned long long)(n_frames - 1) * frame_stride + (unsigned long long)pix_span;
-    for (int i = 0; i < n_planes; i++) {
-        const unsigned long long q0 = (unsigned long long)(uintptr_t)planes[i].p;
-        const unsigned long long q1 = q0 + (unsigned long long)(n_frames - 1) * yuv->frame_stride +
-                                      (unsigned long long)span(planes[i].rows, planes[i].pitch, planes[i].row_bytes);
-        if (p0 < q1 && q0 < p1) return refuse("the byte ranges of a YUV plane and of the frames intersect (no conversion in place)");
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    for (int f0 = 0; f0 < n_frames; f0 += YUV_CHUNK_FRAMES) {
-        const size_t yo = (size_t)f0 * yuv->frame_stride;
-        const YuvArgs a{yuv->y + yo, yuv->c0 ? yuv->c0 + yo : nullptr, yuv->c1 ? yuv->c1 + yo : nullptr, (long long)yuv->y_pitch,
-                        (long long)yuv->c_pitch, (long long)yuv->frame_stride, const_cast<uint8_t*>(pix) + (size_t)f0 * frame_stride,
-                        (long long)row_stride, (long long)frame_stride, width, height, yuv->layout, format, yuv_coef(yuv->matrix)};
-        launch_yuv(a, std::min(YUV_CHUNK_FRAMES, n_frames - f0), to_frames, s);
-        TRACE_LAUNCH(what, s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_yuv_to_frames(OcvarHip* c, const OcvarYuvFrames* src, uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride,
-                                       int width, int height, int n_frames, int format, void* stream) {
-    return yuv_convert(c, "yuv_to_frames", src, d_dst, dst_row_stride, dst_frame_stride, width, height, n_frames, format, true, stream);
-}
-
-extern "C" int ocvar_hip_frames_to_yuv(OcvarHip* c, const uint8_t* d_src, int src_row_stride, size_t src_frame_stride, const OcvarYuvFrames* dst,
-                                       int width, int height, int n_frames, int format, void* stream) {
-    return yuv_convert(c, "frames_to_yuv", dst, d_src, src_row_stride, src_frame_stride, width, height, n_frames, format, false, stream);
-}
-
-extern "C" int ocvar_hip_resize(OcvarHip* c, const uint8_t* d_src, int src_width, int src_height, int src_row_stride, size_t src_frame_stride,
-                                uint8_t* d_dst, int dst_width, int dst_height, int dst_row_stride, size_t dst_frame_stride, int n_frames,
-                                int format, int interpolation, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    const auto refuse = [&](const char* text) {
-        c->err = std::string("resize: ") + text;
-        return OCVAR_E_ARG;
-    };
-    if (!d_src || !d_dst) return refuse("no source or no destination frames");
-    const int bpp = patch_bpp(format);
-    if (bpp == 0 || !resize_interp_ok(interpolation)) return refuse("an unknown format or interpolation");
-    const auto side_ok = [](int v) { return v >= 1 && v <= RESIZE_MAX_SIDE; };
-    if (!side_ok(src_width) || !side_ok(src_height) || !side_ok(dst_width) || !side_ok(dst_height)) return refuse("sides of 1 .. 32767 pixels");
-    if (n_frames < 1) return refuse("n_frames >= 1");
-    if ((long long)src_row_stride < (long long)bpp * src_width || (long long)dst_row_stride < (long long)bpp * dst_width)
-        return refuse("a row stride below the format's bytes per pixel times width");
-    const auto span = [&](int width, int height, int row_stride) { return (long long)(height - 1) * row_stride + (long long)bpp * width; };
-    if (span(src_width, src_height, src_row_stride) > 2147483647LL || span(dst_width, dst_height, dst_row_stride) > 2147483647LL)
-        return refuse("the rows of a frame span more than 2147483647 bytes");
-    const unsigned long long s0 = (unsigned long long)(uintptr_t)d_src, d0 = (unsigned long long)(uintptr_t)d_dst;
-    const unsigned long long s1 = s0 + frames_extent(src_width, src_height, bpp, src_row_stride, src_frame_stride, n_frames);
-    const unsigned long long d1 = d0 + frames_extent(dst_width, dst_height, bpp, dst_row_stride, dst_frame_stride, n_frames);
-    if (s0 < d1 && d0 < s1) return refuse("the byte ranges of source and destination frames intersect (no resizing in place)");
-    if (interpolation == OCVAR_RESIZE_AREA && !resize_area_ok(src_width, src_height, dst_width, dst_height))
-        return refuse("AREA shrinks only, by at most OCVAR_MAX_RESIZE_RATIO per axis");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    const ResizePlan plan = resize_plan(src_width, src_height, dst_width, dst_height, interpolation);
-    for (int f0 = 0; f0 < n_frames; f0 += RESIZE_CHUNK_FRAMES) {
-        const ResizeArgs a{d_src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, src_width, src_height, dst_width, dst_height,
-                           (long long)src_row_stride, (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride, plan};
-        launch_resize(a, std::min(RESIZE_CHUNK_FRAMES, n_frames - f0), format, s);
-        TRACE_LAUNCH("resize", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_scale_records(OcvarHip* c, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
-                                       int src_width, int src_height, int dst_width, int dst_height, int flags, OcvarMarker* d_out, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    if (!d_markers || !d_counts || !d_out) {
-        c->err = "scale_records: no records, no counts or no output";
-        return OCVAR_E_ARG;
-    }
-    if (n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm) {
-        c->err = "scale_records: n_frames >= 1, 1 .. M records per frame";
-        return OCVAR_E_ARG;
-    }
-    const auto side_ok = [](int v) { return v >= 1 && v <= RESIZE_MAX_SIDE; };
-    if (!side_ok(src_width) || !side_ok(src_height) || !side_ok(dst_width) || !side_ok(dst_height)) {
-        c->err = "scale_records: sides of 1 .. 32767 pixels";
-        return OCVAR_E_ARG;
-    }
-    if (flags & ~RESIZE_FLAGS) {
-        c->err = "scale_records: unknown flag bits";
-        return OCVAR_E_ARG;
-    }
-    if ((flags & OCVAR_SCALE_POSE) && !c->have_camera) {
-        c->err = "scale_records: OCVAR_SCALE_POSE without a camera";
-        return OCVAR_E_ARG;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    const int chunk = 65535;
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const ScaleRecArgs a{reinterpret_cast<const MarkerRec*>(d_markers) + (size_t)f0 * records_per_frame,
-                       reinterpret_cast<MarkerRec*>(d_out) + (size_t)f0 * records_per_frame, d_counts + f0, records_per_frame,
-                       src_width, src_height, dst_width, dst_height, flags, c->h_camera};
-        launch_scale_records(a, std::min(chunk, n_frames - f0), s);
-        TRACE_LAUNCH("scale_records", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_orient(OcvarHip* c, const uint8_t* d_src, int src_width, int src_height, int src_row_stride, size_t src_frame_stride,
-                                uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride, int n_frames, int format, int orientation, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    const auto refuse = [&](const char* text) {
-        c->err = std::string("orient: ") + text;
-        return OCVAR_E_ARG;
-    };
-    if (!d_src || !d_dst) return refuse("no source or no destination frames");
-    const int bpp = patch_bpp(format);
-    if (bpp == 0 || !orient_ok(orientation)) return refuse("an unknown format or orientation");
-    const auto side_ok = [](int v) { return v >= 1 && v <= ORIENT_MAX_SIDE; };
-    if (!side_ok(src_width) || !side_ok(src_height)) return refuse("sides of 1 .. 32767 pixels");
-    if (n_frames < 1) return refuse("n_frames >= 1");
-    const int dst_width = orient_dst_width(orientation, src_width, src_height), dst_height = orient_dst_height(orientation, src_width, src_height);
-    if ((long long)src_row_stride < (long long)bpp * src_width || (long long)dst_row_stride < (long long)bpp * dst_width)
-        return refuse("a row stride below the format's bytes per pixel times the width of that side");
-    const auto span = [&](int width, int height, int row_stride) { return (long long)(height - 1) * row_stride + (long long)bpp * width; };
-    if (span(src_width, src_height, src_row_stride) > 2147483647LL || span(dst_width, dst_height, dst_row_stride) > 2147483647LL)
-        return refuse("the rows of a frame span more than 2147483647 bytes");
-    const unsigned long long s0 = (unsigned long long)(uintptr_t)d_src, d0 = (unsigned long long)(uintptr_t)d_dst;
-    const unsigned long long s1 = s0 + frames_extent(src_width, src_height, bpp, src_row_stride, src_frame_stride, n_frames);
-    const unsigned long long d1 = d0 + frames_extent(dst_width, dst_height, bpp, dst_row_stride, dst_frame_stride, n_frames);
-    if (s0 < d1 && d0 < s1) return refuse("the byte ranges of source and destination frames intersect (no turning in place)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    for (int f0 = 0; f0 < n_frames; f0 += ORIENT_CHUNK_FRAMES) {
-        const OrientArgs a{d_src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, src_width, src_height,
-                           (long long)src_row_stride, (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride, orientation};
-        launch_orient(a, std::min(ORIENT_CHUNK_FRAMES, n_frames - f0), format, s);
-        TRACE_LAUNCH("orient", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_orient_records(OcvarHip* c, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
-                                        int src_width, int src_height, int orientation, int flags, OcvarMarker* d_out, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    const auto refuse = [&](const char* text) {
-        c->err = std::string("orient_records: ") + text;
-        return OCVAR_E_ARG;
-    };
-    if (!d_markers || !d_counts || !d_out) return refuse("no records, no counts or no output");
-    if (n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm) return refuse("n_frames >= 1, 1 .. M records per frame");
-    if (src_width < 1 || src_width > ORIENT_MAX_SIDE || src_height < 1 || src_height > ORIENT_MAX_SIDE) return refuse("sides of 1 .. 32767 pixels");
-    if (!orient_ok(orientation)) return refuse("an unknown orientation");
-    if (flags & ~ORIENT_FLAGS) return refuse("unknown flag bits");
-    if ((flags & OCVAR_ORIENT_POSE) && orient_mirrors(orientation)) return refuse("OCVAR_ORIENT_POSE with a mirroring orientation: a reflected view has no rigid pose");
-    if ((flags & OCVAR_ORIENT_POSE) && !c->have_camera) return refuse("OCVAR_ORIENT_POSE without a camera");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    const int chunk = 65535;
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const OrientRecArgs a{reinterpret_cast<const MarkerRec*>(d_markers) + (size_t)f0 * records_per_frame,
-                              reinterpret_cast<MarkerRec*>(d_out) + (size_t)f0 * records_per_frame, d_counts + f0, records_per_frame,
-                              src_width, src_height, orientation, flags, c->h_camera};
-        launch_orient_records(a, std::min(chunk, n_frames - f0), s);
-        TRACE_LAUNCH("orient_records", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_orient_camera(const OcvarCamera* in, int orientation, OcvarCamera* out) {
-    static_assert(sizeof(OcvarCamera) == sizeof(CameraRec), "the same 248 bytes");
-    if (!in || !out) return OCVAR_E_ARG;
-    return orient_camera(*reinterpret_cast<const CameraRec*>(in), orientation, reinterpret_cast<CameraRec*>(out)) ? OCVAR_OK : OCVAR_E_ARG;
-}
-
-extern "C" int ocvar_hip_warp(OcvarHip* c, const uint8_t* d_src, int src_width, int src_height, int src_row_stride, size_t src_frame_stride,
-                              uint8_t* d_dst, int dst_width, int dst_height, int dst_row_stride, size_t dst_frame_stride, int n_frames, int format,
-                              const double* d_maps, int interpolation, int border, const uint8_t* fill, int flags, int* d_status, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    const auto refuse = [&](const char* text) {
-        c->err = std::string("warp: ") + text;
-        return OCVAR_E_ARG;
-    };
-    if (!d_src || !d_dst || !d_maps) return refuse("no source frames, no destination frames or no maps");
-    const int bpp = patch_bpp(format);
-    if (bpp == 0 || !warp_interp_ok(interpolation) || !warp_border_ok(border)) return refuse("an unknown format, interpolation or border");
-    if (flags & ~WARP_FLAGS) return refuse("unknown flag bits");
-    const auto side_ok = [](int v) { return v >= 1 && v <= WARP_MAX_SIDE; };
-    if (!side_ok(src_width) || !side_ok(src_height) || !side_ok(dst_width) || !side_ok(dst_height)) return refuse("sides of 1 .. 32767 pixels");
-    if (n_frames < 1) return refuse("n_frames >= 1");
-    if ((long long)src_row_stride < (long long)bpp * src_width || (long long)dst_row_stride < (long long)bpp * dst_width)
-        return refuse("a row stride below the format's bytes per pixel times width");
-    const auto span = [&](int width, int height, int row_stride) { return (long long)(height - 1) * row_stride + (long long)bpp * width; };
-    if (span(src_width, src_height, src_row_stride) > 2147483647LL || span(dst_width, dst_height, dst_row_stride) > 2147483647LL)
-        return refuse("the rows of a frame span more than 2147483647 bytes");
-    const unsigned long long s0 = (unsigned long long)(uintptr_t)d_src, d0 = (unsigned long long)(uintptr_t)d_dst;
-    const unsigned long long s1 = s0 + frames_extent(src_width, src_height, bpp, src_row_stride, src_frame_stride, n_frames);
-    const unsigned long long d1 = d0 + frames_extent(dst_width, dst_height, bpp, dst_row_stride, dst_frame_stride, n_frames);
-    if (s0 < d1 && d0 < s1) return refuse("the byte ranges of source and destination frames intersect (no warping in place)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    const bool one = (flags & OCVAR_WARP_ONE_MAP) != 0;
-    for (int f0 = 0; f0 < n_frames; f0 += WARP_CHUNK_FRAMES) {
-        WarpArgs a{d_src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, src_width, src_height, dst_width, dst_height,
-                   (long long)src_row_stride, (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride,
-                   one ? d_maps : d_maps + 9 * (size_t)f0, d_status ? d_status + f0 : nullptr, interpolation, border, flags,
-                   c->tune[OCVAR_TUNE_WARP_DIRECT] == 1, {0, 0, 0, 0}};
-        for (int k = 0; k < 4; k++) a.fill[k] = fill ? fill[k] : 0;
-        launch_warp(a, std::min(WARP_CHUNK_FRAMES, n_frames - f0), format, s);
-        TRACE_LAUNCH("warp", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_warp_records(OcvarHip* c, const OcvarMarker* d_markers, const int* d_counts, int n_frames, int records_per_frame,
-                                      const double* d_maps, int flags, OcvarMarker* d_out, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    const auto refuse = [&](const char* text) {
-        c->err = std::string("warp_records: ") + text;
-        return OCVAR_E_ARG;
-    };
-    if (!d_markers || !d_counts || !d_maps || !d_out) return refuse("no records, no counts, no maps or no output");
-    if (n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm) return refuse("n_frames >= 1, 1 .. M records per frame");
-    if (flags & ~WARP_REC_FLAGS) return refuse("unknown flag bits");
-    if (flags & OCVAR_WARP_INVERSE_MAP) return refuse("OCVAR_WARP_INVERSE_MAP: the records need the forward map");
-    if ((flags & OCVAR_WARP_POSE) && !c->have_camera) return refuse("OCVAR_WARP_POSE without a camera");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    const int chunk = 65535;
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const WarpRecArgs a{reinterpret_cast<const MarkerRec*>(d_markers) + (size_t)f0 * records_per_frame,
-                            reinterpret_cast<MarkerRec*>(d_out) + (size_t)f0 * records_per_frame, d_counts + f0, records_per_frame,
-                            (flags & OCVAR_WARP_ONE_MAP) ? d_maps : d_maps + 9 * (size_t)f0, flags, c->h_camera};
-        launch_warp_records(a, std::min(chunk, n_frames - f0), s);
-        TRACE_LAUNCH("warp_records", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_board_plane_maps(OcvarHip* c, const OcvarBoardPose* d_poses, int n_frames, const double* rect, int dst_width,
-                                          int dst_height, double* d_maps, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    const auto refuse = [&](const char* text) {
-        c->err = std::string("board_plane_maps: ") + text;
-        return OCVAR_E_ARG;
-    };
-    if (!d_poses || !rect || !d_maps) return refuse("no poses, no rectangle or no maps");
-    if (n_frames < 1) return refuse("n_frames >= 1");
-    if (dst_width < 1 || dst_width > WARP_MAX_SIDE || dst_height < 1 || dst_height > WARP_MAX_SIDE) return refuse("sides of 1 .. 32767 pixels");
-    if (!c->have_camera) return refuse("no camera set");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    WarpBoardMapArgs a{d_poses, d_maps, n_frames, dst_width, dst_height, {}, {}};
-    for (int i = 0; i < 9; i++) a.K[i] = c->h_camera.cameraMatrix[i];
-    for (int i = 0; i < 4; i++) a.rect[i] = rect[i];
-    launch_warp_board_maps(a, s);
-    TRACE_LAUNCH("board_plane_maps", s);
-    HIP_TRY(c, hipGetLastError());
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_levels_default_params(OcvarLevelsParams* params) {
-    if (!params) return OCVAR_E_ARG;
-    levels_default_params(params);
-    return OCVAR_OK;
-}
-
-extern "C" int ocvar_hip_levels(OcvarHip* c, const uint8_t* d_src, int width, int height, int src_row_stride, size_t src_frame_stride, int format,
-                                uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride, int n_frames, const OcvarLevelsParams* params,
-                                void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    const auto refuse = [&](const char* text) {
-        c->err = std::string("levels: ") + text;
-        return OCVAR_E_ARG;
-    };
-    if (!d_src || !d_dst) return refuse("no source frames or no destination planes");
-    const int bpp = patch_bpp(format);
-    if (bpp == 0) return refuse("an unknown format");
-    if (width < 1 || width > LEVELS_MAX_SIDE || height < 1 || height > LEVELS_MAX_SIDE) return refuse("sides of 1 .. 32767 pixels");
-    if (n_frames < 1) return refuse("n_frames >= 1");
-    if ((long long)src_row_stride < (long long)bpp * width || dst_row_stride < width)
-        return refuse("a row stride below the bytes per pixel times width (the destination is GRAY: below width)");
-    if ((long long)(height - 1) * src_row_stride + (long long)bpp * width > 2147483647LL || (long long)(height - 1) * dst_row_stride + width > 2147483647LL)
-        return refuse("the rows of a frame span more than 2147483647 bytes");
-    const unsigned long long s0 = (unsigned long long)(uintptr_t)d_src, d0 = (unsigned long long)(uintptr_t)d_dst;
-    const unsigned long long s1 = s0 + frames_extent(width, height, bpp, src_row_stride, src_frame_stride, n_frames);
-    const unsigned long long d1 = d0 + frames_extent(width, height, 1, dst_row_stride, dst_frame_stride, n_frames);
-    if (s0 < d1 && d0 < s1) return refuse("the byte ranges of source and destination intersect (no levels in place)");
-    OcvarLevelsParams p;
-    levels_default_params(&p);
-    if (params) p = *params;
-    static const char* const why[] = {"", "tiles_x and tiles_y 1 .. 16, at most 64 tiles, no more tiles than pixels along an axis",
-                                      "low_ppm and high_ppm 0 .. 500000", "max_gain_q8 256 .. 65280"};
-    if (const int bad = levels_params_bad(p, width, height)) return refuse(why[bad]);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    const bool fresh = c->levels_ws.bytes == 0;
-    HIP_TRY(c, c->levels_ws.reserve((size_t)LEVELS_WS_BYTES));
-    HIP_TRY(c, c->levels_done.ensure(hipEventDisableTiming));
-    // the histograms start as zeros; every round's LUT kernel leaves them so
-    if (fresh) HIP_TRY(c, hipMemsetAsync(c->levels_ws, 0, (size_t)LEVELS_WS_LUT_OFFSET, s));
-    if (c->levels_used && c->levels_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->levels_done, 0));
-    for (int f0 = 0; f0 < n_frames; f0 += LEVELS_WS_FRAMES) {     // the rounds share the workspace in stream order
-        const LevelsArgs a{d_src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, width, height,
-                           (long long)src_row_stride, (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride, p,
-                           reinterpret_cast<unsigned*>(c->levels_ws.p), c->levels_ws.p + LEVELS_WS_LUT_OFFSET};
-        launch_levels(a, std::min(LEVELS_WS_FRAMES, n_frames - f0), format, s);
-        TRACE_LAUNCH("levels", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->levels_done, s));
-    c->levels_stream = s;
-    c->levels_used = true;
-    return OCVAR_OK;
-}
-
-// a parameter of ocvar_hip_flow_records that must be a finite number >= 0
-static bool flow_number_ok(float v) { return v >= 0.0f && v <= 3.0e38f; }
-
-extern "C" int ocvar_hip_flow_records(OcvarHip* c, const uint8_t* d_prev_frames, int prev_row_stride, size_t prev_frame_stride,
-                                      const uint8_t* d_next_frames, int next_row_stride, size_t next_frame_stride, int width, int height,
-                                      int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
-                                      const OcvarFlowParams* params, OcvarMarker* d_out, int* d_status, float* d_err, void* stream) {
-    if (!c) return OCVAR_E_ARG;
-    const OcvarFlowParams p = params ? *params : OcvarFlowParams{10, 3, 30, 0, 0.03f, 1e-3f, 0.0f, 0.0f};
-    const int bpp = patch_bpp(format);
-    if (!d_prev_frames || !d_next_frames || !d_markers || !d_counts || !d_out) {
-        c->err = "flow_records: no frames, no records, no counts or no output";
-        return OCVAR_E_ARG;
-    }
-    if (p.half_win < 1 || p.half_win > OCVAR_MAX_FLOW_HALF_WIN || p.levels < 0 || p.levels > OCVAR_MAX_FLOW_LEVELS || p.max_iter < 1 ||
-        p.max_iter > 100) {
-        c->err = "flow_records: half_win 1 .. " + std::to_string(OCVAR_MAX_FLOW_HALF_WIN) + ", levels 0 .. " +
-                 std::to_string(OCVAR_MAX_FLOW_LEVELS) + ", max_iter 1 .. 100";
-        return OCVAR_E_ARG;
-    }
-    if (!flow_number_ok(p.eps) || !flow_number_ok(p.min_eig) || !flow_number_ok(p.max_err) || !flow_number_ok(p.fb_max)) {
-        c->err = "flow_records: eps, min_eig, max_err and fb_max are finite numbers >= 0";
-        return OCVAR_E_ARG;
-    }
-    if (p.flags & ~FLOW_FLAGS) {
-        c->err = "flow_records: unknown flag bits";
-        return OCVAR_E_ARG;
-    }
-    if (n_frames < 1 || records_per_frame < 1 || records_per_frame > c->ws.maxm) {
-        c->err = "flow_records: n_frames >= 1, 1 .. M records per frame";
-        return OCVAR_E_ARG;
-    }
-    const int side = 2 * p.half_win + 3;
-    if (width < side || height < side || width > c->ws.max_w || height > c->ws.max_h) {
-        c->err = "flow_records: frames of 2 half_win + 3 pixels each way .. the context's size";
-        return OCVAR_E_ARG;
-    }
-    if (bpp == 0 || (long long)prev_row_stride < (long long)bpp * width || (long long)next_row_stride < (long long)bpp * width) {
-        c->err = "flow_records: an unknown format or a row stride below the format's bytes per pixel times width";
-        return OCVAR_E_ARG;
-    }
-    if (int rc = frame_span_check(c, width, height, prev_row_stride, format)) return rc;
-    if (int rc = frame_span_check(c, width, height, next_row_stride, format)) return rc;
-    if ((p.flags & OCVAR_FLOW_POSE) && !c->have_camera) {
-        c->err = "flow_records: OCVAR_FLOW_POSE without a camera";
-        return OCVAR_E_ARG;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int chunk = std::min(c->ws.max_batch, 32);
-    const size_t slot = (size_t)flow_geom(c->ws.max_w, c->ws.max_h, 1, 0).bytes;
-    HIP_TRY(c, c->flow_ws.reserve(2 * (size_t)chunk * slot));
-    HIP_TRY(c, c->flow_done.ensure(hipEventDisableTiming));
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream.s;
-    if (c->flow_used && c->flow_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->flow_done, 0));
-    const FlowGeom g = flow_geom(width, height, p.half_win, p.levels);
-    uint8_t* pyr_a = c->flow_ws;
-    uint8_t* pyr_b = pyr_a + (size_t)chunk * slot;
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const int n = std::min(chunk, n_frames - f0);
-        launch_flow_pyramids(FlowPyrArgs{d_prev_frames + (size_t)f0 * prev_frame_stride, (long long)prev_row_stride, (long long)prev_frame_stride,
-                                         pyr_a, (long long)slot, g}, n, format, s);
-        launch_flow_pyramids(FlowPyrArgs{d_next_frames + (size_t)f0 * next_frame_stride, (long long)next_row_stride, (long long)next_frame_stride,
-                                         pyr_b, (long long)slot, g}, n, format, s);
-        TRACE_LAUNCH("flow_pyramids", s);
-        const size_t r0 = (size_t)f0 * records_per_frame;
-        launch_flow_track(FlowTrackArgs{pyr_a, pyr_b, (long long)slot, g, flow_args_make(p), c->h_camera,
-                                        reinterpret_cast<const MarkerRec*>(d_markers) + r0, d_counts + f0, reinterpret_cast<MarkerRec*>(d_out) + r0,
-                                        d_status ? d_status + r0 : nullptr, d_err ? d_err + 4 * r0 : nullptr, records_per_frame, n}, s);
-        TRACE_LAUNCH("flow_track", s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->flow_done, s));
-    c->flow_stream = s;
-    c->flow_used = true;
-    return OCVAR_OK;
 }
 
 extern "C" int ocvar_hip_detect_device(OcvarHip* c, uint8_t* d_bgr, int width, int height, int row_stride, size_t frame_stride,

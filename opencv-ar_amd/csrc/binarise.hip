@@ -132,7 +132,9 @@ struct MarchOut {
 // Sources of march_unit: the caller's frame in one of the formats of include/ocvar_hip.h (OCVAR_FMT_*: frame mode, which
 // also writes the grey plane), or SRC_CROP, a crop of the frame's panelled grey plane (hd.h::gray_col).
 constexpr int SRC_CROP = 5;
+// (the kernels' own constant form of frames_core.h::format_bpp, and 1 for SRC_CROP, which is no format)
 constexpr int src_bpp(int src) { return src == OCVAR_FMT_BGR || src == OCVAR_FMT_RGB ? 3 : src == OCVAR_FMT_BGRA || src == OCVAR_FMT_RGBA ? 4 : 1; }
+static_assert(src_bpp(0) == format_bpp(0) && src_bpp(1) == format_bpp(1) && src_bpp(2) == format_bpp(2) && src_bpp(3) == format_bpp(3) && src_bpp(4) == format_bpp(4), "one table");
 
 // One work unit: strip `strip` of an (sw x sh) ROI, output rows [Y0, Y1).
 // SRC: what `src` holds (above).  BGR / RGB: one 12-byte load per lane and row; BGRA / RGBA: one 16-byte load (four whole
@@ -783,8 +785,6 @@ __global__ __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(OCVAR_W
         march_unit<SRC_CROP, true>(src, pitch, r.x0, r.sw, r.sh, td.x0, td.y0, Y1, o, stage[wave], rowbuf[wave]);
     }
 }
-
-int input_format_bpp(int format) { return format >= OCVAR_FMT_BGR && format <= OCVAR_FMT_GRAY ? src_bpp(format) : 0; }
 
 void launch_binarise_frames(const Workspace& ws, const uint8_t* d_bgr, int row_stride, size_t frame_stride, int grey_in_place,
                             int format, hipStream_t stream) {

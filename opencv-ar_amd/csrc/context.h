@@ -1,5 +1,6 @@
-// context.h -- private to the host files of the C ABI (api.hip, gate.hip, host_transport.hip, debug.hip): the context and the
-// gate, the owners of their HIP resources, and the few functions those files share.
+// context.h -- private to the host files of the C ABI (api.hip, frame_ops.hip, gate.hip, host_transport.hip, debug.hip): the
+// context and the gate, the owners of their HIP resources, the fence of a workspace shared by calls on any stream, and the few
+// functions those files share.
 #pragma once
 #include "kernels.h"
 #include "lanes_core.h"
@@ -28,6 +29,25 @@ struct Event {
     ~Event() { if (e) (void)hipEventDestroy(e); }
     hipError_t ensure(unsigned flags) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }   // created on first use
     operator hipEvent_t() const { return e; }
+};
+
+// Orders the uses of a workspace shared by calls on any stream: a use lies between enter(s) and leave(s), and waits (on its
+// stream) for the last one when that ran on another stream.  drain(): the host waits for the last use, before the workspace or
+// what its kernels read is freed or rewritten.
+struct WorkspaceFence {
+    Event done;                  // behind the last use, on `last` (created on first use)
+    hipStream_t last = nullptr;
+    bool used = false;
+    hipError_t enter(hipStream_t s) {
+        const hipError_t e = done.ensure(hipEventDisableTiming);
+        return e == hipSuccess && used && last != s ? hipStreamWaitEvent(s, done, 0) : e;
+    }
+    hipError_t leave(hipStream_t s) {
+        const hipError_t e = hipEventRecord(done, s);
+        if (e == hipSuccess) last = s, used = true;
+        return e;
+    }
+    hipError_t drain() const { return used ? hipEventSynchronize(done) : hipSuccess; }
 };
 
 // Device memory, or page-locked host memory, that grows on demand: reserve(n) leaves at least n bytes -- a larger request
@@ -105,7 +125,8 @@ struct OcvarHip {
     ocvar::Event copied;               // (created on first use)
     bool copy_pending = false;
     ocvar::Event h2d_done[2];          // host transport: a staging slot's upload (created on first use)
-    ocvar::Event ovl_done;             // behind the last use of the overlay workspace, on ovl_stream
+    // the workspaces of the frame operations (frame_ops.hip): render_records reads the overlay table and images too
+    ocvar::WorkspaceFence ovl_fence, anno_fence, levels_fence, flow_fence;
     std::vector<void*> allocs;         // the workspace's arrays of fixed size (dev_alloc), freed with the context
     ocvar::DeviceBuffer<long long> sq_codes;   // ws.sq_codes / ws.sq_match, which mirror them: they grow with the library
     ocvar::DeviceBuffer<int> sq_match;
@@ -139,24 +160,13 @@ struct OcvarHip {
     ocvar::OverlayDraw* d_ovl_draws = nullptr;     // [max_batch][maxm]
     ocvar::OverlayBox* d_ovl_boxes = nullptr;      // [max_batch][maxm]
     int n_overlays = 0;
-    hipStream_t ovl_stream = nullptr;
-    bool ovl_used = false;
     // flow tracking (ocvar_hip_flow_records): the pyramids' workspace is allocated by the first call
-    ocvar::Event flow_done;                        // behind the last use of the workspace, on flow_stream (created on first use)
     ocvar::DeviceBuffer<uint8_t> flow_ws;          // [2][min(max_batch, 32)] pyramids of a max_w x max_h frame (flow_core.h: flow_geom)
-    hipStream_t flow_stream = nullptr;
-    bool flow_used = false;
     // annotation (ocvar_hip_annotate / ocvar_hip_annotate_records): the primitive records' workspace is allocated by the first call
-    ocvar::Event anno_done;                        // behind the last use of the workspace, on anno_stream (created on first use)
     ocvar::DeviceBuffer<ocvar::AnnoRec> anno_recs; // [max_batch][maxm]
     ocvar::DeviceBuffer<ocvar::AnnoBox> anno_boxes;   // [max_batch][maxm]
-    hipStream_t anno_stream = nullptr;
-    bool anno_used = false;
     // levels (ocvar_hip_levels): the tile histograms and LUTs' workspace is allocated, and cleared, by the first call
-    ocvar::Event levels_done;                      // behind the last use of the workspace, on levels_stream (created on first use)
     ocvar::DeviceBuffer<uint8_t> levels_ws;        // levels_core.h: LEVELS_WS_BYTES
-    hipStream_t levels_stream = nullptr;
-    bool levels_used = false;
     std::string err;
 
     ~OcvarHip();   // (api.hip: the fixed arrays and the overlay images; the holders release the rest)
@@ -206,6 +216,19 @@ int frame_span_check(OcvarHip* c, int width, int height, int row_stride, int for
 int enqueue_impl(OcvarHip* c, const BatchRequest& r, hipStream_t s, hipStream_t after);
 hipError_t batch_wait(OcvarHip* c);
 int wait_impl(OcvarHip* c);
+// Work that follows the batch in flight lies between follow_begin (the stream it goes to, ordered behind the batch) and follow_end
+int follow_begin(OcvarHip* c, void* stream, hipStream_t* s);
+int follow_end(OcvarHip* c, hipStream_t s);
+bool batch_frames_ok(OcvarHip* c, const char* who, int width, int height);   // false and the text: no batch, or frames of another size
+// n elements (and a margin) of device memory that live as long as the context
+template <typename T>
+int dev_alloc(OcvarHip* c, T** p, size_t n) {
+    void* q = nullptr;
+    HIP_TRY(c, hipMalloc(&q, n * sizeof(T) + 256));
+    c->allocs.push_back(q);
+    *p = static_cast<T*>(q);
+    return OCVAR_OK;
+}
 // gate.hip
 void gate_detach(OcvarHip* c);
 void lane_release(OcvarHip* c);

@@ -4,7 +4,7 @@
 // launch reads it: stream order, no flags between workgroups), flow_track_kernel.  Parameters, pyramid layout and camera travel by
 // value in the launch arguments.
 #include "kernels.h"
-#include <cstddef>
+#include "lane_run.h"
 
 namespace ocvar {
 
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(64) void flow_grey_kernel(FlowPyrArgs a, int fmt) {
         for (int i = 0; i < FLOW_LANE_PX; i++) {
             uint8_t px[BPP];
             OCVAR_UNROLL
-            for (int c = 0; c < BPP; c++) px[c] = (uint8_t)(q[(i * BPP + c) >> 2] >> (8 * ((i * BPP + c) & 3)));
+            for (int c = 0; c < BPP; c++) px[c] = (uint8_t)run_byte(q, i * BPP + c);
             out |= (unsigned)flow_grey(px, fmt) << (8 * i);
         }
     } else {
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64) void flow_down_kernel(uint8_t* pyr, long long s
             const unsigned* r4 = reinterpret_cast<const unsigned*>(r + 2 * x0 - 4);
             const unsigned q[4] = {r4[0], r4[1], r4[2], r4[3]};
             OCVAR_UNROLL
-            for (int t = 0; t < 11; t++) c[t] = (int)((q[(t + 2) >> 2] >> (8 * ((t + 2) & 3))) & 255u);
+            for (int t = 0; t < 11; t++) c[t] = run_byte(q, t + 2);
         } else {
             OCVAR_UNROLL
             for (int t = 0; t < 11; t++) c[t] = r[flow_reflect(2 * x0 - 2 + t, Ws)];
@@ -90,8 +90,8 @@ static void launch_grey(const FlowPyrArgs& a, int n_frames, int format, bool ali
 
 void launch_flow_pyramids(const FlowPyrArgs& a, int n_frames, int format, hipStream_t stream) {
     if (n_frames <= 0 || a.g.w[0] <= 0 || a.g.h[0] <= 0) return;
-    const bool aligned = (((unsigned long long)(uintptr_t)a.frames | (unsigned long long)a.row_stride | (unsigned long long)a.frame_stride) & 3ull) == 0;
-    switch (patch_bpp(format)) {
+    const bool aligned = frames_dwords(a.frames, a.row_stride, a.frame_stride);
+    switch (format_bpp(format)) {
         case 1: launch_grey<1>(a, n_frames, format, aligned, stream); break;
         case 3: launch_grey<3>(a, n_frames, format, aligned, stream); break;
         case 4: launch_grey<4>(a, n_frames, format, aligned, stream); break;

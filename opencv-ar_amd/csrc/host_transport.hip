@@ -68,7 +68,7 @@ extern "C" int ocvar_hip_detect_host(OcvarHip* c, uint8_t* h_bgr, int width, int
                                      int n_frames, int grey_in_place, const OcvarMarker* prev, const int* prev_counts,
                                      OcvarMarker* markers, int* counts, int max_per_frame) {
     if (!c || !h_bgr || n_frames < 1 || height < 1 || row_stride < 1) return OCVAR_E_ARG;
-    if ((long long)row_stride < (long long)input_format_bpp(c->input_format) * width) return OCVAR_E_ARG;
+    if ((long long)row_stride < (long long)format_bpp(c->input_format) * width) return OCVAR_E_ARG;
     // (the device slots keep the caller's strides, so the frame kernel's addressing limit is the host frames' too: refused here,
     // before anything is staged, not by the first sub-batch's enqueue after its upload)
     if (int rc = frame_span_check(c, width, height, row_stride, c->input_format)) return rc;

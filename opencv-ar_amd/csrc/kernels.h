@@ -1,6 +1,7 @@
 // kernels.h -- device workspace layout and launch entry points shared by the .hip translation units.
 #pragma once
 #include "hd.h"
+#include "frames_core.h"
 #include "decode_core.h"
 #include "pose_core.h"
 #include "tail_core.h"
@@ -143,9 +144,6 @@ struct Workspace {
     CameraRec* camera;
     int* counters;          // [CNT_COUNT]
 };
-
-// bytes per pixel of an input format (OCVAR_FMT_*: 3, 3, 4, 4, 1), 0 for anything else
-int input_format_bpp(int format);
 
 // launchers (each enqueues on `stream`, no synchronisation)
 // d_bgr holds frames in `format` (OCVAR_FMT_*); grey_in_place is not launched for OCVAR_FMT_GRAY (nothing to write)

@@ -1,12 +1,12 @@
-// lane_run.h -- a lane's run of consecutive bytes of one row, held in registers: what the streaming frame kernels (resize.hip,
-// orient.hip) load and store.  Byte j of a run lives in bits 8 (j & 3) of dword j >> 2 (constant indices once unrolled).
+// lane_run.h -- a lane's run of consecutive bytes of one row, held in registers: what the frame kernels (overlay, annotate, patch,
+// undistort, yuv, resize, orient, warp, levels, flow) load, unpack, pack and store; the only place that does.  Byte j of a run
+// lives in bits 8 (j & 3) of dword j >> 2 (constant indices once unrolled).
 #pragma once
 #include "hd.h"
 
 namespace ocvar {
 
-template <int ND>
-OCVAR_D int run_byte(const unsigned (&q)[ND], int j) { return (int)((q[j >> 2] >> (8 * (j & 3))) & 255u); }
+OCVAR_D int run_byte(const unsigned* q, int j) { return (int)((q[j >> 2] >> (8 * (j & 3))) & 255u); }
 template <int ND>
 OCVAR_D void run_put(unsigned (&q)[ND], int j, int b) { q[j >> 2] |= (unsigned)b << (8 * (j & 3)); }
 

@@ -190,22 +190,21 @@ __global__ __launch_bounds__(LEVELS_THREADS) void levels_apply_kernel(LevelsArgs
 
 template <int BPP>
 static void launch_bpp(const LevelsArgs& a, int n_frames, int format, hipStream_t stream) {
-    const unsigned long long sbits = (unsigned long long)(uintptr_t)a.src | (unsigned long long)a.src_row_stride | (unsigned long long)a.src_frame_stride;
-    const unsigned long long dbits = (unsigned long long)(uintptr_t)a.dst | (unsigned long long)a.dst_row_stride | (unsigned long long)a.dst_frame_stride;
+    const bool src_dwords = frames_dwords(a.src, a.src_row_stride, a.src_frame_stride), dst_dwords = frames_dwords(a.dst, a.dst_row_stride, a.dst_frame_stride);
     const int tiles = a.p.tiles_x * a.p.tiles_y;
     const int tallest = (a.h + a.p.tiles_y - 1) / a.p.tiles_y;
     const dim3 hgrid((tallest + LEVELS_SLAB_ROWS - 1) / LEVELS_SLAB_ROWS, tiles, n_frames);
-    if ((sbits & 3ull) == 0) hipLaunchKernelGGL((levels_hist_kernel<BPP, true>), hgrid, dim3(LEVELS_THREADS), 0, stream, a, format);
+    if (src_dwords) hipLaunchKernelGGL((levels_hist_kernel<BPP, true>), hgrid, dim3(LEVELS_THREADS), 0, stream, a, format);
     else hipLaunchKernelGGL((levels_hist_kernel<BPP, false>), hgrid, dim3(LEVELS_THREADS), 0, stream, a, format);
     hipLaunchKernelGGL(levels_lut_kernel, dim3(tiles, n_frames), dim3(64), 0, stream, a);
     const dim3 agrid(levels_segments(a.w, a.p.tiles_x, LEVELS_SEG_W), levels_segments(a.h, a.p.tiles_y, LEVELS_SEG_H), n_frames);
-    if (((sbits | dbits) & 3ull) == 0) hipLaunchKernelGGL((levels_apply_kernel<BPP, true>), agrid, dim3(LEVELS_THREADS), 0, stream, a, format);
+    if (src_dwords && dst_dwords) hipLaunchKernelGGL((levels_apply_kernel<BPP, true>), agrid, dim3(LEVELS_THREADS), 0, stream, a, format);
     else hipLaunchKernelGGL((levels_apply_kernel<BPP, false>), agrid, dim3(LEVELS_THREADS), 0, stream, a, format);
 }
 
 void launch_levels(const LevelsArgs& a, int n_frames, int format, hipStream_t stream) {
     if (n_frames <= 0 || n_frames > LEVELS_WS_FRAMES || a.w <= 0 || a.h <= 0 || levels_params_bad(a.p, a.w, a.h)) return;
-    switch (patch_bpp(format)) {
+    switch (format_bpp(format)) {
         case 1: launch_bpp<1>(a, n_frames, format, stream); break;
         case 3: launch_bpp<3>(a, n_frames, format, stream); break;
         case 4: launch_bpp<4>(a, n_frames, format, stream); break;

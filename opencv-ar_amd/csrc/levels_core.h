@@ -205,7 +205,7 @@ struct LevelsArgs {
 // The host reference: frame f of the call in format fmt, sequentially.  luts_out (may be nullptr) gets the frame's tiles_y tiles_x
 // LUTs of 256 bytes, hist_out (may be nullptr) their histograms.
 inline void levels_frame(const LevelsArgs& a, int fmt, int f, uint8_t* luts_out, unsigned* hist_out) {
-    const int bpp = patch_bpp(fmt), tx = a.p.tiles_x, ty = a.p.tiles_y;
+    const int bpp = format_bpp(fmt), tx = a.p.tiles_x, ty = a.p.tiles_y;
     const uint8_t* src = a.src + (long long)f * a.src_frame_stride;
     uint8_t* dst = a.dst + (long long)f * a.dst_frame_stride;
     static thread_local unsigned hist[LEVELS_MAX_TILES][256];

@@ -234,15 +234,13 @@ static void launch_aligned(const OrientArgs& a, int n_frames, hipStream_t stream
 
 template <int BPP>
 static void launch_bpp(const OrientArgs& a, int n_frames, hipStream_t stream) {
-    const unsigned long long bits = (unsigned long long)(uintptr_t)a.src | (unsigned long long)a.src_row_stride | (unsigned long long)a.src_frame_stride |
-                                    (unsigned long long)(uintptr_t)a.dst | (unsigned long long)a.dst_row_stride | (unsigned long long)a.dst_frame_stride;
-    if ((bits & 3ull) == 0) launch_aligned<BPP, true>(a, n_frames, stream);
+    if (frames_dwords(a.src, a.src_row_stride, a.src_frame_stride) && frames_dwords(a.dst, a.dst_row_stride, a.dst_frame_stride)) launch_aligned<BPP, true>(a, n_frames, stream);
     else launch_aligned<BPP, false>(a, n_frames, stream);
 }
 
 void launch_orient(const OrientArgs& a, int n_frames, int format, hipStream_t stream) {
     if (n_frames <= 0 || a.sw <= 0 || a.sh <= 0 || !orient_ok(a.orientation)) return;
-    switch (patch_bpp(format)) {
+    switch (format_bpp(format)) {
         case 1: launch_bpp<1>(a, n_frames, stream); break;
         case 3: launch_bpp<3>(a, n_frames, stream); break;
         case 4: launch_bpp<4>(a, n_frames, stream); break;

@@ -101,7 +101,7 @@ struct OrientArgs {
 
 // The host reference of the frame call: frame f of the launch in format fmt, sequentially.
 inline void orient_frame(const OrientArgs& a, int fmt, int f) {
-    const int bpp = patch_bpp(fmt);
+    const int bpp = format_bpp(fmt);
     const int dw = orient_dst_width(a.orientation, a.sw, a.sh), dh = orient_dst_height(a.orientation, a.sw, a.sh);
     const uint8_t* src = a.src + (long long)f * a.src_frame_stride;
     uint8_t* dst = a.dst + (long long)f * a.dst_frame_stride;

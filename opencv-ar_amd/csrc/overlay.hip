@@ -3,6 +3,7 @@
 // kernels' bytes.  Two launches per chunk of frames: overlay_setup_kernel (one lane per record: map, overlay, box) and
 // overlay_draw_kernel (by frame tile, so that overlapping markers neither race nor change their order).
 #include "kernels.h"
+#include "lane_run.h"
 
 namespace ocvar {
 
@@ -33,8 +34,6 @@ constexpr int OVL_WAVE_ROWS = 4;                 // consecutive rows a wave owns
 constexpr int OVL_WAVES = 4;
 constexpr int OVL_TILE_H = OVL_WAVES * OVL_WAVE_ROWS;
 
-template <int BPP>
-OCVAR_D unsigned ovl_get(const unsigned* q, int byte) { return (q[byte >> 2] >> (8 * (byte & 3))) & 255u; }
 template <int BPP>
 OCVAR_D void ovl_put(unsigned* q, int byte, unsigned v) {
     const int s = 8 * (byte & 3);
@@ -124,8 +123,8 @@ __global__ __launch_bounds__(64 * OVL_WAVES) void overlay_draw_kernel(OverlayArg
                 OCVAR_UNROLL
                 for (int i = 0; i < OVL_LANE_PX; i++)
                     if (c[i] >> 24) {   // (a covered pixel lies in the record's box, and the box in the frame)
-                        unsigned v[3] = {ovl_get<BPP>(q, i * BPP), NC > 1 ? ovl_get<BPP>(q, i * BPP + NC - 2) : 0u,
-                                         NC > 1 ? ovl_get<BPP>(q, i * BPP + NC - 1) : 0u};
+                        unsigned v[3] = {(unsigned)run_byte(q, i * BPP), NC > 1 ? (unsigned)run_byte(q, i * BPP + NC - 2) : 0u,
+                                         NC > 1 ? (unsigned)run_byte(q, i * BPP + NC - 1) : 0u};
                         overlay_blend_px(FMT, c[i], v);
                         OCVAR_UNROLL
                         for (int j = 0; j < NC; j++) ovl_put<BPP>(q, i * BPP + j, v[j]);
@@ -143,7 +142,7 @@ __global__ __launch_bounds__(64 * OVL_WAVES) void overlay_draw_kernel(OverlayArg
             for (int i = 0; i < OVL_LANE_PX; i++)
                 if ((dirty >> i) & 1u) {
                     OCVAR_UNROLL
-                    for (int j = 0; j < NC; j++) p[i * BPP + j] = (uint8_t)ovl_get<BPP>(q, i * BPP + j);
+                    for (int j = 0; j < NC; j++) p[i * BPP + j] = (uint8_t)run_byte(q, i * BPP + j);
                 }
         }
     }
@@ -164,7 +163,7 @@ void launch_overlay(const OverlayArgs& oa, uint8_t* frames, int W, int H, long l
     if (n_frames <= 0 || stride <= 0) return;
     const long long lanes = (long long)n_frames * stride;
     hipLaunchKernelGGL(overlay_setup_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, oa, recs, counts, stride, n_frames, W, H);
-    const bool aligned = (((unsigned long long)(uintptr_t)frames | (unsigned long long)row_stride | (unsigned long long)frame_stride) & 3ull) == 0;
+    const bool aligned = frames_dwords(frames, row_stride, frame_stride);
     switch (format) {
         case OCVAR_FMT_BGR: launch_draw<OCVAR_FMT_BGR>(oa, frames, W, H, row_stride, frame_stride, n_frames, stride, aligned, stream); break;
         case OCVAR_FMT_RGB: launch_draw<OCVAR_FMT_RGB>(oa, frames, W, H, row_stride, frame_stride, n_frames, stride, aligned, stream); break;

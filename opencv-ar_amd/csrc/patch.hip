@@ -2,6 +2,7 @@
 // ocvar_hip_patches_records).  The definition is patch_core.h's; its host build (tests/emul/patch_emul.cpp) gives this
 // kernel's bytes.  One launch per chunk of frames, no workspace: every wave recomputes its record's map.
 #include "kernels.h"
+#include "lane_run.h"
 
 namespace ocvar {
 
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(64) void patch_kernel(PatchArgs a) {
             OCVAR_UNROLL
             for (int c = 0; c < BPP; c++) {
                 const unsigned v = (unsigned)patch_sample(frame, a.W, a.H, a.row_stride, BPP, c, M, sx, y) & 255u;
-                q[(i * BPP + c) >> 2] |= v << (8 * ((i * BPP + c) & 3));
+                run_put(q, i * BPP + c, (int)v);
             }
         }
         if (++sx == a.pw) {
@@ -48,15 +49,13 @@ __global__ __launch_bounds__(64) void patch_kernel(PatchArgs a) {
         }
     }
     if (ALIGNED && q0 + PATCH_LANE_PX <= npx) {
-        unsigned* o = reinterpret_cast<unsigned*>(out);
-        OCVAR_UNROLL
-        for (int j = 0; j < BPP; j++) o[j] = q[j];
-    } else {
+        run_store(q, out, true, 0);
+    } else {   // (pixel by pixel: a lane's pixels end where the patch does)
         OCVAR_UNROLL
         for (int i = 0; i < PATCH_LANE_PX; i++)
             if (q0 + i < npx) {
                 OCVAR_UNROLL
-                for (int c = 0; c < BPP; c++) out[i * BPP + c] = (uint8_t)(q[(i * BPP + c) >> 2] >> (8 * ((i * BPP + c) & 3)));
+                for (int c = 0; c < BPP; c++) out[i * BPP + c] = (uint8_t)run_byte(q, i * BPP + c);
             }
     }
 }
@@ -72,8 +71,8 @@ static void launch_bpp(const PatchArgs& a, int n_frames, bool aligned, hipStream
 
 void launch_patches(const PatchArgs& a, int n_frames, int format, hipStream_t stream) {
     if (n_frames <= 0 || a.slots <= 0) return;
-    const int bpp = patch_bpp(format);
-    const bool aligned = (((unsigned long long)(uintptr_t)a.patches | ((unsigned long long)a.pw * a.ph * bpp)) & 3ull) == 0;
+    const int bpp = format_bpp(format);
+    const bool aligned = frames_dwords(a.patches, (long long)a.pw * a.ph * bpp, 0);   // (the "rows": the slots' patches)
     switch (bpp) {
         case 1: launch_bpp<1>(a, n_frames, aligned, stream); break;
         case 3: launch_bpp<3>(a, n_frames, aligned, stream); break;

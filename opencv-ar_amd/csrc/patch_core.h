@@ -23,6 +23,7 @@
 // the kernel (patch.hip).  patch_extract_frame is that host reference, sequential.
 #pragma once
 #include "hd.h"
+#include "frames_core.h"
 #include "ocvar_hip.h"
 #include "decode_core.h"
 #include "tail_core.h"
@@ -33,11 +34,6 @@ namespace ocvar {
 constexpr int PATCH_MAX_SIDE = OCVAR_MAX_PATCH_SIDE;
 constexpr float PATCH_MAX_COORD = 1e6f;   // OCVAR_PATCH_MAX_COORD
 constexpr int PATCH_FLAGS = OCVAR_PATCH_FLIP_ROWS | OCVAR_PATCH_MATCHED_ONLY;
-
-// bytes per pixel of a frame format, 0: unknown
-OCVAR_HD int patch_bpp(int fmt) {
-    return (fmt == OCVAR_FMT_BGR || fmt == OCVAR_FMT_RGB) ? 3 : ((fmt == OCVAR_FMT_BGRA || fmt == OCVAR_FMT_RGBA) ? 4 : (fmt == OCVAR_FMT_GRAY ? 1 : 0));
-}
 
 // The status rule for a record inside its frame's count, and the record's map M (patch pixels -> frame pixels); false: the
 // slot is not written.
@@ -60,7 +56,7 @@ OCVAR_HD int patch_sample(const uint8_t* frame, int W, int H, long long row_stri
 // recs[0 .. min(count, slots) - 1], sequentially.  status may be nullptr.  Returns the number of slots written.
 inline int patch_extract_frame(const uint8_t* frame, int W, int H, long long row_stride, int fmt, const MarkerRec* recs, int count, int slots,
                                uint8_t* patches, int pw, int ph, int flags, int* status) {
-    const int bpp = patch_bpp(fmt), n = count < slots ? count : slots;
+    const int bpp = format_bpp(fmt), n = count < slots ? count : slots;
     int written = 0;
     for (int k = 0; k < slots; k++) {
         double M[9];

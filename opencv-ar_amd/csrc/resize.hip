@@ -141,17 +141,15 @@ static void launch_aligned(const ResizeArgs& a, const dim3& grid, hipStream_t st
 template <int BPP>
 static void launch_bpp(const ResizeArgs& a, int n_frames, hipStream_t stream) {
     const dim3 grid((a.dw + RESIZE_WAVE_PX - 1) / RESIZE_WAVE_PX, a.dh, n_frames);
-    unsigned long long bits = (unsigned long long)(uintptr_t)a.dst | (unsigned long long)a.dst_row_stride | (unsigned long long)a.dst_frame_stride;
     // (the two box kernels load whole dwords too; the gathering ones read bytes wherever they lie)
-    if (a.p.kind == RESIZE_KIND_BOX && a.p.kx == a.p.ky && (a.p.kx == 2 || a.p.kx == 3))
-        bits |= (unsigned long long)(uintptr_t)a.src | (unsigned long long)a.src_row_stride | (unsigned long long)a.src_frame_stride;
-    if ((bits & 3ull) == 0) launch_aligned<BPP, true>(a, grid, stream);
+    const bool box = a.p.kind == RESIZE_KIND_BOX && a.p.kx == a.p.ky && (a.p.kx == 2 || a.p.kx == 3);
+    if (frames_dwords(a.dst, a.dst_row_stride, a.dst_frame_stride) && (!box || frames_dwords(a.src, a.src_row_stride, a.src_frame_stride))) launch_aligned<BPP, true>(a, grid, stream);
     else launch_aligned<BPP, false>(a, grid, stream);
 }
 
 void launch_resize(const ResizeArgs& a, int n_frames, int format, hipStream_t stream) {
     if (n_frames <= 0 || a.sw <= 0 || a.sh <= 0 || a.dw <= 0 || a.dh <= 0) return;
-    switch (patch_bpp(format)) {
+    switch (format_bpp(format)) {
         case 1: launch_bpp<1>(a, n_frames, stream); break;
         case 3: launch_bpp<3>(a, n_frames, stream); break;
         case 4: launch_bpp<4>(a, n_frames, stream); break;

@@ -209,7 +209,7 @@ OCVAR_HD void resize_pixel(const ResizeArgs& a, const uint8_t* src, int bpp, int
 
 // The host reference of the frame call: frame f of the launch in format fmt, sequentially.
 inline void resize_frame(const ResizeArgs& a, int fmt, int f) {
-    const int bpp = patch_bpp(fmt);
+    const int bpp = format_bpp(fmt);
     const uint8_t* src = a.src + (long long)f * a.src_frame_stride;
     uint8_t* dst = a.dst + (long long)f * a.dst_frame_stride;
     for (int y = 0; y < a.dh; y++)

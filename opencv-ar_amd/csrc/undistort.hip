@@ -4,6 +4,7 @@
 // model of its pixels in FP64 (about 40 operations per pixel against the 8 bytes per pixel a map would add to the traffic).  The
 // camera travels by value in the launch arguments, so a later ocvar_hip_set_camera cannot race a queued launch.
 #include "kernels.h"
+#include "lane_run.h"
 
 namespace ocvar {
 
@@ -31,21 +32,18 @@ __global__ __launch_bounds__(64) void undistort_kernel(UndistortArgs a) {
             undistort_source_fixed(a.cam, u0 + i, v, &X, &Y);
             OCVAR_UNROLL
             for (int c = 0; c < BPP; c++) {
-                const unsigned b = (unsigned)undistort_sample(src, a.W, a.H, a.src_row_stride, BPP, c, X, Y) & 255u;
-                q[(i * BPP + c) >> 2] |= b << (8 * ((i * BPP + c) & 3));
+                run_put(q, i * BPP + c, undistort_sample(src, a.W, a.H, a.src_row_stride, BPP, c, X, Y) & 255);
             }
         }
     }
     if (ALIGNED && u0 + UNDIST_LANE_PX <= a.W) {
-        unsigned* o = reinterpret_cast<unsigned*>(out);
-        OCVAR_UNROLL
-        for (int j = 0; j < BPP; j++) o[j] = q[j];
-    } else {
+        run_store(q, out, true, 0);
+    } else {   // (pixel by pixel: a lane's pixels end where the row does)
         OCVAR_UNROLL
         for (int i = 0; i < UNDIST_LANE_PX; i++)
             if (u0 + i < a.W) {
                 OCVAR_UNROLL
-                for (int c = 0; c < BPP; c++) out[i * BPP + c] = (uint8_t)(q[(i * BPP + c) >> 2] >> (8 * ((i * BPP + c) & 3)));
+                for (int c = 0; c < BPP; c++) out[i * BPP + c] = (uint8_t)run_byte(q, i * BPP + c);
             }
     }
 }
@@ -61,8 +59,8 @@ static void launch_bpp(const UndistortArgs& a, int n_frames, bool aligned, hipSt
 
 void launch_undistort(const UndistortArgs& a, int n_frames, int format, hipStream_t stream) {
     if (n_frames <= 0 || a.W <= 0 || a.H <= 0) return;
-    const int bpp = patch_bpp(format);
-    const bool aligned = (((unsigned long long)(uintptr_t)a.dst | (unsigned long long)a.dst_row_stride | (unsigned long long)a.dst_frame_stride) & 3ull) == 0;
+    const int bpp = format_bpp(format);
+    const bool aligned = frames_dwords(a.dst, a.dst_row_stride, a.dst_frame_stride);
     switch (bpp) {
         case 1: launch_bpp<1>(a, n_frames, aligned, stream); break;
         case 3: launch_bpp<3>(a, n_frames, aligned, stream); break;

@@ -117,7 +117,7 @@ OCVAR_HD void undistort_square(const UndistortCam& c, const float* sq, float* ou
 // The host reference of the frame map: one W x H frame in format fmt from src to dst (which do not overlap), sequentially.
 inline void undistort_frame(const uint8_t* src, int W, int H, long long src_row_stride, int fmt, const UndistortCam& cam, uint8_t* dst,
                             long long dst_row_stride) {
-    const int bpp = patch_bpp(fmt);
+    const int bpp = format_bpp(fmt);
     for (int v = 0; v < H; v++)
         for (int u = 0; u < W; u++) {
             int X, Y;

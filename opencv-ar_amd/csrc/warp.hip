@@ -70,7 +70,7 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_kernel(WarpArgs a) {
     const uint8_t* src = a.src + (long long)f * a.src_frame_stride;
     const long long rs = a.src_row_stride;
     if (p.staged) {            // (the same for every lane of the workgroup)
-        const bool src_dwords = (((unsigned long long)(uintptr_t)a.src | (unsigned long long)a.src_row_stride | (unsigned long long)a.src_frame_stride) & 3ull) == 0;
+        const bool src_dwords = frames_dwords(a.src, a.src_row_stride, a.src_frame_stride);
         const int row_bytes = a.sw * BPP;
         const unsigned recip = tile.recip;
         // the window's dwords, row after row, dealt to the 256 lanes in turn, WARP_STAGE_LOADS per lane in flight before the first
@@ -175,14 +175,14 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_kernel(WarpArgs a) {
 template <int BPP>
 static void launch_bpp(const WarpArgs& a, int n_frames, hipStream_t stream) {
     const dim3 grid((a.dw + WARP_TILE_W - 1) / WARP_TILE_W, (a.dh + warp_tile_h(BPP) - 1) / warp_tile_h(BPP), n_frames);
-    const bool aligned = (((unsigned long long)(uintptr_t)a.dst | (unsigned long long)a.dst_row_stride | (unsigned long long)a.dst_frame_stride) & 3ull) == 0;
+    const bool aligned = frames_dwords(a.dst, a.dst_row_stride, a.dst_frame_stride);
     if (aligned) hipLaunchKernelGGL((warp_kernel<BPP, true>), grid, dim3(WARP_THREADS), 0, stream, a);
     else hipLaunchKernelGGL((warp_kernel<BPP, false>), grid, dim3(WARP_THREADS), 0, stream, a);
 }
 
 void launch_warp(const WarpArgs& a, int n_frames, int format, hipStream_t stream) {
     if (n_frames <= 0 || a.sw <= 0 || a.sh <= 0 || a.dw <= 0 || a.dh <= 0) return;
-    switch (patch_bpp(format)) {
+    switch (format_bpp(format)) {
         case 1: launch_bpp<1>(a, n_frames, stream); break;
         case 3: launch_bpp<3>(a, n_frames, stream); break;
         case 4: launch_bpp<4>(a, n_frames, stream); break;

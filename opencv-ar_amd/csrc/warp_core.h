@@ -221,7 +221,7 @@ OCVAR_HD WarpPlan warp_tile_plan(const double* M, int tx0, int ty0, int tw, int 
 
 // Frame f of the launch in format fmt, sequentially: its status (when asked for) and, unless it is skipped, its pixels.
 inline int warp_frame(const WarpArgs& a, int fmt, int f) {
-    const int bpp = patch_bpp(fmt);
+    const int bpp = format_bpp(fmt);
     double M[9];
     const bool ok = warp_map(warp_frame_map(a, f), a.flags, M);
     if (a.status) a.status[f] = ok ? 1 : 0;

@@ -4,46 +4,12 @@
 // other, with about 17 integer operations per pixel; no workspace.  The coefficient table travels by value in the launch
 // arguments; the kernels are templates of the bytes per pixel, the alignment and the chroma subsampling, not of the table.
 #include "kernels.h"
+#include "lane_run.h"
 
 namespace ocvar {
 
 constexpr int YUV_LANE_PX = 8;                      // consecutive pixels of a row a lane owns (of two rows in 4:2:0)
 constexpr int YUV_WAVE_PX = 64 * YUV_LANE_PX;       // pixels of one wave's span
-
-// A lane's bytes live in registers, byte j of a run in bits 8 (j & 3) of dword j >> 2 (constant indices once unrolled).
-template <int ND>
-OCVAR_D int reg_byte(const unsigned (&q)[ND], int j) { return (int)((q[j >> 2] >> (8 * (j & 3))) & 255u); }
-template <int ND>
-OCVAR_D void reg_put(unsigned (&q)[ND], int j, int b) { q[j >> 2] |= (unsigned)b << (8 * (j & 3)); }
-
-// The lane's run of bytes at p: whole dwords (p is a multiple of 4 then, and all ND dwords belong to the lane), or the first
-// nbytes of them byte by byte, the others read as 0 / not written.
-template <int ND>
-OCVAR_D void lane_load(unsigned (&q)[ND], const uint8_t* p, bool dwords, int nbytes) {
-    if (dwords) {
-        const unsigned* w = reinterpret_cast<const unsigned*>(p);
-        OCVAR_UNROLL
-        for (int j = 0; j < ND; j++) q[j] = w[j];
-    } else {
-        OCVAR_UNROLL
-        for (int j = 0; j < ND; j++) q[j] = 0;
-        OCVAR_UNROLL
-        for (int b = 0; b < 4 * ND; b++)
-            if (b < nbytes) q[b >> 2] |= (unsigned)p[b] << (8 * (b & 3));
-    }
-}
-template <int ND>
-OCVAR_D void lane_store(const unsigned (&q)[ND], uint8_t* p, bool dwords, int nbytes) {
-    if (dwords) {
-        unsigned* w = reinterpret_cast<unsigned*>(p);
-        OCVAR_UNROLL
-        for (int j = 0; j < ND; j++) w[j] = q[j];
-    } else {
-        OCVAR_UNROLL
-        for (int b = 0; b < 4 * ND; b++)
-            if (b < nbytes) p[b] = (uint8_t)(q[b >> 2] >> (8 * (b & 3)));
-    }
-}
 
 // bytes 0 2 of lo and 0 2 of hi; bytes 1 3 of lo and 1 3 of hi; the two interleaved again
 OCVAR_D unsigned even_bytes(unsigned lo, unsigned hi) {
@@ -76,20 +42,20 @@ __global__ __launch_bounds__(64) void yuv_to_frames_kernel(YuvArgs a) {
     unsigned yq[ROWS][2], uq[1], vq[1];
     if (S420) {
         OCVAR_UNROLL
-        for (int r = 0; r < ROWS; r++) lane_load(yq[r], a.y + fo + (long long)(y0 + r) * a.y_pitch + x0, dwords, npx);
+        for (int r = 0; r < ROWS; r++) run_load(yq[r], a.y + fo + (long long)(y0 + r) * a.y_pitch + x0, dwords, npx);
         const long long co = fo + (long long)blockIdx.y * a.c_pitch;
         if (a.layout == OCVAR_YUV_NV12) {
             unsigned w[2];
-            lane_load(w, a.c0 + co + x0, dwords, npx);
+            run_load(w, a.c0 + co + x0, dwords, npx);
             uq[0] = even_bytes(w[0], w[1]);
             vq[0] = odd_bytes(w[0], w[1]);
         } else {
-            lane_load(uq, a.c0 + co + (x0 >> 1), dwords, npx >> 1);
-            lane_load(vq, a.c1 + co + (x0 >> 1), dwords, npx >> 1);
+            run_load(uq, a.c0 + co + (x0 >> 1), dwords, npx >> 1);
+            run_load(vq, a.c1 + co + (x0 >> 1), dwords, npx >> 1);
         }
     } else {
         unsigned w[4];
-        lane_load(w, a.y + fo + (long long)y0 * a.y_pitch + 2 * x0, dwords, 2 * npx);
+        run_load(w, a.y + fo + (long long)y0 * a.y_pitch + 2 * x0, dwords, 2 * npx);
         if (a.layout == OCVAR_YUV_UYVY) {
             OCVAR_UNROLL
             for (int j = 0; j < 4; j++) w[j] = swap_halfword_bytes(w[j]);
@@ -110,28 +76,28 @@ __global__ __launch_bounds__(64) void yuv_to_frames_kernel(YuvArgs a) {
     OCVAR_UNROLL
     for (int j = 0; j < YUV_LANE_PX / 2; j++) {
         int t[3];
-        yuv_terms(a.k, reg_byte(uq, j), reg_byte(vq, j), rgb, t);
+        yuv_terms(a.k, run_byte(uq, j), run_byte(vq, j), rgb, t);
         OCVAR_UNROLL
         for (int r = 0; r < ROWS; r++) {
             OCVAR_UNROLL
             for (int d = 0; d < 2; d++) {
                 const int i = 2 * j + d;
-                const int y = yuv_y_term(a.k, reg_byte(yq[r], i));
+                const int y = yuv_y_term(a.k, run_byte(yq[r], i));
                 const int p0 = yuv_channel(y, t[0]), p1 = yuv_channel(y, t[1]), p2 = yuv_channel(y, t[2]);
                 if (BPP == 1) {
-                    reg_put(q[r], i, yuv_grey(p0, p1, p2));   // (never rgb: p0 p1 p2 are B G R)
+                    run_put(q[r], i, yuv_grey(p0, p1, p2));   // (never rgb: p0 p1 p2 are B G R)
                 } else {
-                    reg_put(q[r], i * BPP, p0);
-                    reg_put(q[r], i * BPP + 1, p1);
-                    reg_put(q[r], i * BPP + 2, p2);
-                    if (BPP == 4) reg_put(q[r], i * BPP + 3, 255);
+                    run_put(q[r], i * BPP, p0);
+                    run_put(q[r], i * BPP + 1, p1);
+                    run_put(q[r], i * BPP + 2, p2);
+                    if (BPP == 4) run_put(q[r], i * BPP + 3, 255);
                 }
             }
         }
     }
     uint8_t* out = a.pix + (long long)blockIdx.z * a.pix_frame_stride + (long long)y0 * a.pix_row_stride + (long long)x0 * BPP;
     OCVAR_UNROLL
-    for (int r = 0; r < ROWS; r++) lane_store(q[r], out + (long long)r * a.pix_row_stride, dwords, npx * BPP);
+    for (int r = 0; r < ROWS; r++) run_store(q[r], out + (long long)r * a.pix_row_stride, dwords, npx * BPP);
 }
 
 // The other direction with the same ownership: a lane reads its 8 pixels of one row or of two, writes their 8 Y bytes per row
@@ -148,7 +114,7 @@ __global__ __launch_bounds__(64) void frames_to_yuv_kernel(YuvArgs a) {
     const uint8_t* in = a.pix + (long long)blockIdx.z * a.pix_frame_stride + (long long)y0 * a.pix_row_stride + (long long)x0 * BPP;
     unsigned q[ROWS][2 * BPP];
     OCVAR_UNROLL
-    for (int r = 0; r < ROWS; r++) lane_load(q[r], in + (long long)r * a.pix_row_stride, dwords, npx * BPP);
+    for (int r = 0; r < ROWS; r++) run_load(q[r], in + (long long)r * a.pix_row_stride, dwords, npx * BPP);
     const YuvCoef k = yuv_coef_in_memory_order(a.k, yuv_fmt_rgb(a.format));   // (uniform: scalar registers)
     unsigned yq[ROWS][2], uq[1] = {0}, vq[1] = {0};
     OCVAR_UNROLL
@@ -161,10 +127,10 @@ __global__ __launch_bounds__(64) void frames_to_yuv_kernel(YuvArgs a) {
             OCVAR_UNROLL
             for (int d = 0; d < 2; d++) {
                 const int i = 2 * j + d;
-                const int p0 = reg_byte(q[r], i * BPP);
-                const int p1 = BPP == 1 ? p0 : reg_byte(q[r], i * BPP + (BPP == 1 ? 0 : 1));
-                const int p2 = BPP == 1 ? p0 : reg_byte(q[r], i * BPP + (BPP == 1 ? 0 : 2));
-                reg_put(yq[r], i, yuv_luma(k, p0, p1, p2));
+                const int p0 = run_byte(q[r], i * BPP);
+                const int p1 = BPP == 1 ? p0 : run_byte(q[r], i * BPP + (BPP == 1 ? 0 : 1));
+                const int p2 = BPP == 1 ? p0 : run_byte(q[r], i * BPP + (BPP == 1 ? 0 : 2));
+                run_put(yq[r], i, yuv_luma(k, p0, p1, p2));
                 s0 += p0;
                 s1 += p1;
                 s2 += p2;
@@ -172,19 +138,19 @@ __global__ __launch_bounds__(64) void frames_to_yuv_kernel(YuvArgs a) {
         }
         int U, V;
         yuv_chroma(k, s0, s1, s2, ROWS, &U, &V);   // 2^ROWS pixels: 4 in 4:2:0, 2 in 4:2:2
-        reg_put(uq, j, U);
-        reg_put(vq, j, V);
+        run_put(uq, j, U);
+        run_put(vq, j, V);
     }
     if (S420) {
         OCVAR_UNROLL
-        for (int r = 0; r < ROWS; r++) lane_store(yq[r], a.y + fo + (long long)(y0 + r) * a.y_pitch + x0, dwords, npx);
+        for (int r = 0; r < ROWS; r++) run_store(yq[r], a.y + fo + (long long)(y0 + r) * a.y_pitch + x0, dwords, npx);
         const long long co = fo + (long long)blockIdx.y * a.c_pitch;
         if (a.layout == OCVAR_YUV_NV12) {
             const unsigned w[2] = {interleave_bytes(uq[0], vq[0], 0), interleave_bytes(uq[0], vq[0], 1)};
-            lane_store(w, a.c0 + co + x0, dwords, npx);
+            run_store(w, a.c0 + co + x0, dwords, npx);
         } else {
-            lane_store(uq, a.c0 + co + (x0 >> 1), dwords, npx >> 1);
-            lane_store(vq, a.c1 + co + (x0 >> 1), dwords, npx >> 1);
+            run_store(uq, a.c0 + co + (x0 >> 1), dwords, npx >> 1);
+            run_store(vq, a.c1 + co + (x0 >> 1), dwords, npx >> 1);
         }
     } else {
         const unsigned c01 = interleave_bytes(uq[0], vq[0], 0), c23 = interleave_bytes(uq[0], vq[0], 1);   // U V U V
@@ -194,7 +160,7 @@ __global__ __launch_bounds__(64) void frames_to_yuv_kernel(YuvArgs a) {
             OCVAR_UNROLL
             for (int j = 0; j < 4; j++) w[j] = swap_halfword_bytes(w[j]);
         }
-        lane_store(w, a.y + fo + (long long)y0 * a.y_pitch + 2 * x0, dwords, 2 * npx);
+        run_store(w, a.y + fo + (long long)y0 * a.y_pitch + 2 * x0, dwords, 2 * npx);
     }
 }
 
@@ -218,12 +184,10 @@ static void launch_bpp(const YuvArgs& a, int n_frames, bool to_frames, bool alig
 
 void launch_yuv(const YuvArgs& a, int n_frames, bool to_frames, hipStream_t stream) {
     if (n_frames <= 0 || a.W <= 0 || a.H <= 0) return;
-    unsigned long long bits = (unsigned long long)(uintptr_t)a.y | (unsigned long long)a.y_pitch | (unsigned long long)a.yuv_frame_stride |
-                              (unsigned long long)(uintptr_t)a.pix | (unsigned long long)a.pix_row_stride | (unsigned long long)a.pix_frame_stride;
-    if (yuv_is_420(a.layout)) bits |= (unsigned long long)(uintptr_t)a.c0 | (unsigned long long)a.c_pitch;
-    if (a.layout == OCVAR_YUV_I420) bits |= (unsigned long long)(uintptr_t)a.c1;
-    const bool aligned = (bits & 3ull) == 0;
-    switch (patch_bpp(a.format)) {
+    bool aligned = frames_dwords(a.y, a.y_pitch, a.yuv_frame_stride) && frames_dwords(a.pix, a.pix_row_stride, a.pix_frame_stride);
+    if (yuv_is_420(a.layout)) aligned = aligned && frames_dwords(a.c0, a.c_pitch, 0);
+    if (a.layout == OCVAR_YUV_I420) aligned = aligned && frames_dwords(a.c1, 0, 0);
+    switch (format_bpp(a.format)) {
         case 1: launch_bpp<1>(a, n_frames, to_frames, aligned, stream); break;
         case 3: launch_bpp<3>(a, n_frames, to_frames, aligned, stream); break;
         case 4: launch_bpp<4>(a, n_frames, to_frames, aligned, stream); break;

@@ -182,7 +182,7 @@ OCVAR_HD void yuv_uv_at(const YuvArgs& a, long long fo, int x, int y, uint8_t** 
 
 // The host reference of YUV to colour: frame f of the launch, sequentially.
 inline void yuv_to_frame(const YuvArgs& a, int f) {
-    const int bpp = patch_bpp(a.format);
+    const int bpp = format_bpp(a.format);
     const bool rgb = yuv_fmt_rgb(a.format);
     const long long fo = (long long)f * a.yuv_frame_stride;
     for (int y = 0; y < a.H; y++)
@@ -198,7 +198,7 @@ inline void yuv_to_frame(const YuvArgs& a, int f) {
 
 // The host reference of colour to YUV: frame f of the launch, sequentially.
 inline void frame_to_yuv(const YuvArgs& a, int f) {
-    const int bpp = patch_bpp(a.format);
+    const int bpp = format_bpp(a.format);
     const bool rgb = yuv_fmt_rgb(a.format);
     const long long fo = (long long)f * a.yuv_frame_stride;
     const int bh = yuv_is_420(a.layout) ? 2 : 1;   // rows of a chroma sample's block
