@@ -394,29 +394,43 @@ __device__ void march_unit(const uint8_t* src, long long src_stride, int x_org /
     };
     auto to_grey = [&](const Raw& r) -> unsigned {
         if constexpr (BPP == 1) return r.d0;   // (grey frames: BGR2GRAY of B = G = R = g is g)
-        // (1868 B + 9617 G + 4899 R + 8192) >> 14 with everything times four: (7472 B + 38468 G + 19596 R + 32768) >> 16 -- the
-        // grey value is then BYTE 2 of the sum (< 2^24), which a byte permute picks: no shift per pixel.  Coefficient halves for
-        // v_dot4_u32_u8 (hd.h::GREY_KH_BGR ...): 7472 = 29*256+48, 38468 = 150*256+68, 19596 = 76*256+140; in reverse byte order
-        // for RGB sources; 0 on byte 3 (a four-channel pixel's alpha).
+        // (1868 B + 9617 G + 4899 R + 8192) >> 14 with everything times four: (7472 B + 38468 G + 19596 R + 32768) >> 16.  Coefficient
+        // halves for v_dot4_u32_u8 (hd.h::GREY_KH_BGR ...): 7472 = 29*256+48, 38468 = 150*256+68, 19596 = 76*256+140; in reverse
+        // byte order for RGB sources; 0 on byte 3 (a four-channel pixel's alpha).  The grey value is byte 1 of hd.h::grey_sum16,
+        // T = (dot4(KH) + 128) + byte 1 of dot4(KL) < 2^16: three instructions per pixel, the add picking the byte itself -- and the
+        // add of every second pixel writes the upper word of the register of the pixel before it, so that the four grey values
+        // are bytes 1 and 3 of two registers and ONE byte permute packs them (no shift per pixel, no OR).
         constexpr bool REV = SRC == OCVAR_FMT_RGB || SRC == OCVAR_FMT_RGBA;
         const unsigned KH = REV ? GREY_KH_RGB : GREY_KH_BGR, KL = REV ? GREY_KL_RGB : GREY_KL_BGR;
-        if constexpr (FOUR) {   // a dword per pixel: one dot4 pair each, no byte alignment
-            const unsigned s0 = (dot4(r.d0, KH, 0u) << 8) + dot4(r.d0, KL, 32768u);
-            const unsigned s1 = (dot4(r.d1, KH, 0u) << 8) + dot4(r.d1, KL, 32768u);
-            const unsigned s2 = (dot4(r.d2, KH, 0u) << 8) + dot4(r.d2, KL, 32768u);
-            const unsigned s3 = (dot4(r.d3, KH, 0u) << 8) + dot4(r.d3, KL, 32768u);
-            const unsigned g01 = __builtin_amdgcn_perm(s1, s0, 0x0c0c0602u);
-            const unsigned g23 = __builtin_amdgcn_perm(s3, s2, 0x0c0c0602u);
-            return g01 | (g23 << 16);
-        }
-        const unsigned s0 = (dot4(r.d0, KH, 0u) << 8) + dot4(r.d0, KL, 32768u);                          // bytes b0 g0 r0 (x)
-        const unsigned w1 = alignb(r.d1, r.d0, 3), w2 = alignb(r.d2, r.d1, 2);
-        const unsigned s1 = (dot4(w1, KH, 0u) << 8) + dot4(w1, KL, 32768u);                              // b1 g1 r1 (x)
-        const unsigned s2 = (dot4(w2, KH, 0u) << 8) + dot4(w2, KL, 32768u);                              // b2 g2 r2 (x)
-        const unsigned s3 = (dot4(r.d2, KH << 8, 0u) << 8) + dot4(r.d2, KL << 8, 32768u);                // (x) b3 g3 r3
-        const unsigned g01 = __builtin_amdgcn_perm(s1, s0, 0x0c0c0602u);   // byte 2 of s0, byte 2 of s1, 0, 0
-        const unsigned g23 = __builtin_amdgcn_perm(s3, s2, 0x0c0c0602u);
-        return g01 | (g23 << 16);
+        // The four pixels' twelve instructions are one block, in an order of its own.  On this hardware a dot product's result may
+        // be read by another kind of vector instruction only three instructions later, and a register of which an instruction
+        // wrote one half only one wait state later; the compiler keeps both distances in its own code and cannot see into a
+        // block -- so all eight products come first, then the four sums in the products' order (the last sum reads the eighth
+        // product with three sums between them), then the wait state.  (Left to the compiler with only the sums as blocks, the
+        // products of two rows went above the row loop's branch, where sixteen of them stayed live: spills.)  The permute is the
+        // compiler's own: it knows what the lane shifts that read the result next have to wait for.
+        auto grey4 = [](unsigned w0, unsigned w1, unsigned w2, unsigned w3, unsigned kh, unsigned kl, unsigned kh3, unsigned kl3) -> unsigned {
+            unsigned g, t, l0, h1, l1, l2, h3, l3;   // g, t: high sums of pixels 0 and 2, then the sums of pixels 0 | 1 and 2 | 3
+            asm("v_dot4_u32_u8 %0, %8, %12, %16\n\t"
+                "v_dot4_u32_u8 %2, %8, %13, 0\n\t"
+                "v_dot4_u32_u8 %3, %9, %12, %16\n\t"
+                "v_dot4_u32_u8 %4, %9, %13, 0\n\t"
+                "v_dot4_u32_u8 %1, %10, %12, %16\n\t"
+                "v_dot4_u32_u8 %5, %10, %13, 0\n\t"
+                "v_dot4_u32_u8 %6, %11, %14, %16\n\t"
+                "v_dot4_u32_u8 %7, %11, %15, 0\n\t"
+                "v_add_u32_sdwa %0, %0, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
+                "v_add_u32_sdwa %0, %3, %4 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_1\n\t"
+                "v_add_u32_sdwa %1, %1, %5 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
+                "v_add_u32_sdwa %1, %6, %7 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_1\n\t"
+                "s_nop 0"
+                : "=&v"(g), "=&v"(t), "=&v"(l0), "=&v"(h1), "=&v"(l1), "=&v"(l2), "=&v"(h3), "=&v"(l3)
+                : "v"(w0), "v"(w1), "v"(w2), "v"(w3), "s"(kh), "s"(kl), "s"(kh3), "s"(kl3), "v"(128u));
+            return __builtin_amdgcn_perm(t, g, 0x07050301u);   // bytes 1 and 3 of g, bytes 1 and 3 of t
+        };
+        if constexpr (FOUR) return grey4(r.d0, r.d1, r.d2, r.d3, KH, KL, KH, KL);   // a dword per pixel: no byte alignment
+        // bytes b0 g0 r0 (x) | b1 g1 r1 (x) | b2 g2 r2 (x) | (x) b3 g3 r3
+        return grey4(r.d0, alignb(r.d1, r.d0, 3), alignb(r.d2, r.d1, 2), r.d2, KH, KL, KH << 8, KL << 8);
     };
 
     // Pyramid rows the unit needs: from qa (two rows before the first pyrUp row, Y0 - 4, that its first threshold row reads) to qb.

@@ -586,48 +586,85 @@ __global__ __launch_bounds__(FOLLOW_THREADS) void follow_kernel(Workspace ws) {
 // the longest dependent chain of the whole call.  If the ring of pixels next to the zeroed frame (rows 1 and sh-2, columns 1 and sw-2)
 // is all set, that border is exactly the rectangle (1,1) (1,sh-2) (sw-2,sh-2) (sw-2,1) -- the follower keeps the zeroed frame on one
 // side and the next ring pixel is always there, whatever lies inside -- with these four corner points in this order (the walk runs
-// down the left side first).  One wave per ROI checks the ring on the bit plane: a handful of independent loads instead of a
-// dependent chain; lane 0 then runs the same approximation and filter on the four points as on any stored border and publishes the quad if it is one.  ring[roi] tells tier 1
+// down the left side first).  The ring is checked on the bit plane -- independent loads instead of a dependent chain -- and the same
+// approximation and filter as on any stored border run on the four points and publish the quad if it is one.  ring[roi] tells tier 1
 // to drop the start.  A ring with a hole in it: ring[roi] = 0, the border is walked as before.
+// A wave takes RING_GROUP consecutive ROIs.  It checks their rings one after the other with all its lanes, each ROI's verdict
+// staying in the lane of the ROI's place in the group; then every lane with a clean ring approximates and publishes for its own
+// ROI, all at once: the approximation is ~600 instructions of one lane's work, which a wave of its own per ROI spent with 63 lanes
+// waiting.  Crops: 64 per wave (some 36 crops per frame).  Frames: one per wave -- a batch has few frames and their rings are
+// long (1300 loads against a crop's 200): 64 of them in a row would be the batch's longest chain, to save 60 approximations.
+// The quads are the same set whatever the grouping (their order is settled later by the rank sort on the discovery position,
+// a crop's winner by atomicMin in emit_quad).
+// The ring of an ROI as work items: item i < 2 tiles is tile i (i - tiles) of row 1 (row sh-2) -- pixel x in [1, sw-2] is bit
+// x % 16 + 1 of its row's dword in tile x >> 4, so the ring's rows are runs of set bits, one dword per tile --, item 2 tiles + j
+// is row 1 + j of columns 1 and sw-2.  Every item is two dwords and the bits needed of each (a row item: the same dword twice).
+// Four rounds of 64 items are loaded before the first is looked at: a crop's ring (~200 items) costs one memory latency.
 template <bool CROP>
 __global__ __launch_bounds__(64) void ring_quads_kernel(Workspace ws) {
+    constexpr int RING_GROUP = CROP ? 64 : 1, ROUNDS = 4;
     int n = CROP ? ws.counters[CNT_CROP_ROIS] : ws.n_frames;
     if (CROP && n > ws.cap_crop_rois) n = ws.cap_crop_rois;
     int* ring = CROP ? ws.ring_crop : ws.ring_frame;
     const int lane = threadIdx.x;
-    for (int roi = blockIdx.x; roi < n; roi += gridDim.x) {
-        const PlaneRef pl = plane_of<CROP>(ws, roi);
-        const int ns = uni(pl.ns), sh = uni(pl.sh), sw = uni(pl.img_w) & ~1;
-        bool bad = sw < 8 || sh < 8;
-        if (!bad) {
-            // rows 1 and sh-2: pixel x in [1, sw-2] is bit x % 16 + 1 of its row's dword in tile x >> 4: the ring's rows are runs of
-            // set bits, one dword per tile
-            const int tiles = ns >> 4;
-            for (int i = lane; i < 2 * tiles; i += 64) {
-                const int y = i < tiles ? 1 : sh - 2, xt = i < tiles ? i : i - tiles;
-                const unsigned v = *reinterpret_cast<const unsigned*>(pl.nbr + nbr_win_off(xt << 4, y, ns) + 4);
-                const int lo = (xt << 4) > 1 ? (xt << 4) : 1, hi = (xt << 4) + 15 < sw - 2 ? (xt << 4) + 15 : sw - 2;   // columns of the ring in this tile
-                if (lo <= hi) {
-                    const unsigned need = ((2u << (hi - lo)) - 1u) << (lo - (xt << 4) + 1);
-                    if ((v & need) != need) bad = true;
+    for (int roi0 = blockIdx.x * RING_GROUP; roi0 < n; roi0 += gridDim.x * RING_GROUP) {
+        const int cnt = n - roi0 < RING_GROUP ? n - roi0 : RING_GROUP;   // ROIs of this group: lane k < cnt keeps ROI roi0 + k
+        const int roi = roi0 + (lane < cnt ? lane : 0);
+        const PlaneRef mine = plane_of<CROP>(ws, roi);
+        const unsigned long long mine_nbr = (unsigned long long)reinterpret_cast<uintptr_t>(mine.nbr);
+        bool clean = false;
+        for (int k = 0; k < cnt; k++) {
+            // ROI roi0 + k's geometry from its lane
+            const int ns = __builtin_amdgcn_readlane(mine.ns, k), sh = __builtin_amdgcn_readlane(mine.sh, k), sw = __builtin_amdgcn_readlane(mine.img_w, k) & ~1;
+            const uint8_t* nbr = reinterpret_cast<const uint8_t*>((uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(mine_nbr >> 32), k) << 32)
+                                                                              | (unsigned)__builtin_amdgcn_readlane((int)(unsigned)mine_nbr, k)));
+            bool bad = sw < 8 || sh < 8;
+            if (!bad) {
+                const int tiles = ns >> 4, items = 2 * tiles + sh - 2;
+                const unsigned last_tile = (unsigned)(sw - 2) >> 4, last_bit = 1u << (((unsigned)(sw - 2) & 15u) + 1u);
+                for (int base = 0; base < items; base += 64 * ROUNDS) {
+                    unsigned va[ROUNDS], vb[ROUNDS], na[ROUNDS], nb[ROUNDS];
+#pragma unroll
+                    for (int r = 0; r < ROUNDS; r++) {
+                        const int i = base + 64 * r + lane;
+                        const bool valid = i < items;
+                        const int ic = valid ? i : 0;   // (a lane without an item loads item 0's dword -- tile 0 of row 1 -- and needs no bit of it)
+                        const bool row_item = ic < 2 * tiles;
+                        const int xt = ic < tiles ? ic : ic - tiles;
+                        const int y = row_item ? (ic < tiles ? 1 : sh - 2) : 1 + ic - 2 * tiles;
+                        const int lo = (xt << 4) > 1 ? (xt << 4) : 1, hi = (xt << 4) + 15 < sw - 2 ? (xt << 4) + 15 : sw - 2;   // columns of the ring in tile xt
+                        const unsigned run = row_item && lo <= hi ? ((2u << (hi - lo)) - 1u) << (lo - (xt << 4) + 1) : 0u;
+                        const unsigned row_off = nbr_win_off(0, y, ns) + 4u;   // the dword of row y in tile 0
+                        const unsigned ta = row_item ? (unsigned)xt : 0u, tb = row_item ? (unsigned)xt : last_tile;
+                        na[r] = !valid ? 0u : row_item ? run : 1u << 2;   // column 1: bit 2 of tile 0
+                        nb[r] = !valid ? 0u : row_item ? run : last_bit;
+                        va[r] = *reinterpret_cast<const unsigned*>(nbr + row_off + ta * (unsigned)NBR_TILE_BYTES);
+                        vb[r] = *reinterpret_cast<const unsigned*>(nbr + row_off + tb * (unsigned)NBR_TILE_BYTES);
+                    }
+#pragma unroll
+                    for (int r = 0; r < ROUNDS; r++)
+                        if ((va[r] & na[r]) != na[r] || (vb[r] & nb[r]) != nb[r]) bad = true;
                 }
             }
-            // columns 1 and sw-2, rows 1 .. sh-2
-            for (int y = 1 + lane; y <= sh - 2; y += 64)
-                if (!nbr_bit(pl.nbr, 1, y, ns) || !nbr_bit(pl.nbr, sw - 2, y, ns)) bad = true;
+            const bool roi_clean = __ballot(bad) == 0;
+            if (lane == k) clean = roi_clean;
         }
-        const bool clean = __ballot(bad) == 0;
-        if (lane == 0) {
+        if (lane < cnt) {
             ring[roi] = clean ? 1 : 0;
-            if (clean && (long long)(sw - 3) * (sh - 3) > 500) {   // (worth_approximating: the quad filter needs |area| > 500)
+            const int sw = mine.img_w & ~1, sh = mine.sh;
+            // (worth_approximating: the quad filter needs |area| > 500.  It also needs the result's first vertex inside the 2-px
+            // inset of the ROI's image, 2 < x < img_w - 2 and 2 < y < img_h - 2; a vertex is one of the four points, and of those only
+            // (sw-2, sh-2) can be, when img_w and img_h are both odd: sw - 2 < img_w - 2 means sw < img_w.  Any other ROI's rectangle
+            // is rejected whatever the approximation gives, so it is not approximated.)
+            if (clean && (long long)(sw - 3) * (sh - 3) > 500 && (mine.img_w & 1) && (mine.img_h & 1)) {
                 const int pts[8] = {1, 1, 1, sh - 2, sw - 2, sh - 2, sw - 2, 1};
                 const TraceStats st = stats_of_points(pts, 4);
                 StartCand c;
                 c.roi = roi;
-                c.pos = ns + 1;
+                c.pos = mine.ns + 1;
                 c.is_hole = 0;
                 DpSlice stack[DP_STACK];
-                approximate_and_emit<CROP>(ws, c, pl, pts, 4, st.perimeter, stack);
+                approximate_and_emit<CROP>(ws, c, mine, pts, 4, st.perimeter, stack);
             }
         }
     }

@@ -16,6 +16,13 @@
 #define OCVAR_D inline
 #define OCVAR_UNROLL
 #endif
+// OCVAR_OPAQUE(v): the optimiser is to take the per-lane value v as given and not look through it to the expression it came
+// from (where it would otherwise compute a variant of that expression again for each use); costs no instruction
+#if defined(__HIP_DEVICE_COMPILE__)
+#define OCVAR_OPAQUE(v) asm("" : "+v"(v))
+#else
+#define OCVAR_OPAQUE(v) ((void)0)
+#endif
 
 namespace ocvar {
 
@@ -28,10 +35,26 @@ struct Pt { int x, y; };
 
 // BGR2GRAY, (1868 B + 9617 G + 4899 R + 8192) >> 14, as the frame kernel computes it: times four, (7472 B + 38468 G + 19596 R
 // + 32768) >> 16, with each coefficient split into a high and a low byte for v_dot4_u32_u8 -- the grey value is byte 2 of
-// (dot4(pixel, KH) << 8) + dot4(pixel, KL) + 32768.  One word per byte order of the source pixel (B G R x / R G B x); byte 3
-// is 0, so a four-channel pixel's fourth byte does not count.  (tests/test_input_formats_cpu.py checks all 2^24 pixels.)
+// (dot4(pixel, KH) << 8) + dot4(pixel, KL) + 32768 (the kernel takes it from a 16-bit form of that sum: grey_sum16 below).  One
+// word per byte order of the source pixel (B G R x / R G B x); byte 3 is 0, so a four-channel pixel's fourth byte does not
+// count.  (tests/test_input_formats_cpu.py checks all 2^24 pixels.)
 constexpr unsigned GREY_KH_BGR = 29u | (150u << 8) | (76u << 16), GREY_KL_BGR = 48u | (68u << 8) | (140u << 16);
 constexpr unsigned GREY_KH_RGB = 76u | (150u << 8) | (29u << 16), GREY_KL_RGB = 140u | (68u << 8) | (48u << 16);
+// c + the sum of the four byte products of a and b (v_dot4_u32_u8)
+OCVAR_HD unsigned dot4_u8(unsigned a, unsigned b, unsigned c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_udot4(a, b, c, false);
+#else
+    for (int j = 0; j < 4; j++) c += ((a >> (8 * j)) & 255u) * ((b >> (8 * j)) & 255u);
+    return c;
+#endif
+}
+// The same grey value as byte 1 of a sum that fits 16 bits, which is how the kernel keeps it (two pixels per register):
+// with H = dot4(pixel, KH) (<= 65025) and L = dot4(pixel, KL) (<= 65280), (256 H + L + 32768) >> 16 = (H + ((L + 32768) >> 8)) >> 8
+// and (L + 32768) >> 8 = (L >> 8) + 128 exactly, so grey = T >> 8 with T = (H + 128) + (L >> 8) <= 65408.  L >> 8 is byte 1 of L:
+// the add picks it itself.  (tests/test_grey_pack_cpu.py: all 2^24 pixels in both byte orders, and the two bounds.)
+OCVAR_HD unsigned grey_low16(unsigned pixel, unsigned kl) { return dot4_u8(pixel, kl, 0u); }
+OCVAR_HD unsigned grey_sum16(unsigned pixel, unsigned kh, unsigned kl) { return dot4_u8(pixel, kh, 128u) + ((grey_low16(pixel, kl) >> 8) & 255u); }
 
 // The neighbour plane of a binary image (sw x sh, row stride ns: sw rounded up to a multiple of 16).
 //

@@ -40,25 +40,50 @@ OCVAR_HD unsigned starts_own_bits(int col0, int sw) {
     return n <= 0 ? 0u : n >= NBR_TILE_W ? STARTS_OWN_BITS : ((1u << n) - 1u) << STARTS_WORD_LEAD;
 }
 
+// the own columns (bits 8 .. 23; the other bits are 0) of two rows' words in one word: the first row's in the low half
+OCVAR_HD unsigned starts_pack2(unsigned lo, unsigned hi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, 0x06050201u);
+#else
+    return (lo >> STARTS_WORD_LEAD) | (hi << (16 - STARTS_WORD_LEAD));
+#endif
+}
+
 // The starts of one lane's four rows.  w: the row words, already zero for rows that are not in the ring (rows outside [0, Y1])
 // and masked with starts_word_bits; above: the word of the row before w[0] (the quad neighbour's w[3]; not read for q = 0, whose
 // w[0] is the apron row); qrow = 4 q - 1: w[0]'s row within the tile row; nrows: the tile row's rows that belong to the unit,
 // min(14, Y1 - 14 ty) -- a start row belongs to exactly one unit, its row above may be the unit's apron row Y0 - 1; own:
 // starts_own_bits.  any / hole: bit 16 i + k = column 16 tx + k of row i is a start / a hole start.
+//
+// starts_outer and starts_hole are spelt out here with the shifts shared: a row's a is the row before's c, so a << 1, a >> 1 and
+// a >> 2 are that row's c << 1, c >> 1 and c >> 2 -- a row costs three new shifts (two for the last), the first row takes its
+// three from above; and the logic is five operations of three inputs each, the form the device has an instruction for, and two
+// more for sel.  (Written as calls of the two one-line functions, each row's five shifts were computed anew and in merged forms
+// -- (a | c) >> 1 -- that nothing could share: 14 vector instructions per row where 10 do.)  Every shifted word below has more
+// than one use, which is also what keeps a compiler from merging them again.  tests/test_starts_words_cpu.py holds this
+// against the two functions row by row.
 OCVAR_HD void starts_of_lane(const unsigned w[4], unsigned above, int qrow, int nrows, unsigned own, unsigned long long& any, unsigned long long& hole) {
     unsigned m[4], h[4];
-    unsigned a = above;
+    unsigned a = above, al = above << 1, ar = above >> 1, ar2 = above >> 2;
+    OCVAR_UNROLL
     for (int i = 0; i < 4; i++) {
-        const unsigned c = w[i];
+        const unsigned c = w[i], cl = c << 1, cr = c >> 1;
         const unsigned sel = (unsigned)(qrow + i) < (unsigned)nrows ? own : 0u;
-        h[i] = starts_hole(c, a) & sel;
-        m[i] = (starts_outer(c, a) & sel) | h[i];
+        const unsigned n = al | a | ar;                 // NW, N or NE set
+        const unsigned o1 = c & ~cl & ~n;
+        const unsigned out = o1 & ~(cr & ar2);          // starts_outer(c, a)
+        const unsigned h1 = cl & ~c & a;
+        unsigned hs = h1 & (cr | ar);                   // starts_hole(c, a)
+        OCVAR_OPAQUE(hs);                               // (else both uses below get a chain of their own from h1 on: two more per row)
+        h[i] = hs & sel;
+        m[i] = (out | hs) & sel;
         a = c;
+        al = cl;
+        ar = cr;
+        if (i < 3) ar2 = c >> 2;
     }
-    const unsigned m01 = (m[0] >> STARTS_WORD_LEAD) | (m[1] << (16 - STARTS_WORD_LEAD)), m23 = (m[2] >> STARTS_WORD_LEAD) | (m[3] << (16 - STARTS_WORD_LEAD));
-    const unsigned h01 = (h[0] >> STARTS_WORD_LEAD) | (h[1] << (16 - STARTS_WORD_LEAD)), h23 = (h[2] >> STARTS_WORD_LEAD) | (h[3] << (16 - STARTS_WORD_LEAD));
-    any = (unsigned long long)m01 | ((unsigned long long)m23 << 32);
-    hole = (unsigned long long)h01 | ((unsigned long long)h23 << 32);
+    any = (unsigned long long)starts_pack2(m[0], m[1]) | ((unsigned long long)starts_pack2(m[2], m[3]) << 32);
+    hole = (unsigned long long)starts_pack2(h[0], h[1]) | ((unsigned long long)starts_pack2(h[2], h[3]) << 32);
 }
 
 }  // namespace ocvar
