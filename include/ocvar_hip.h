@@ -817,6 +817,15 @@ typedef struct OcvarStart {
 } OcvarStart;
 int ocvar_hip_debug_starts(OcvarHip* ctx, int crop_pass, OcvarStart* starts, int max_starts, int* n_starts);
 
+/* The ring verdicts of the last collected batch, one int per frame (crop_pass == 0, indexed by the frame's place in the batch)
+ * or per crop ROI (crop_pass != 0, indexed like ocvar_hip_debug_crop_rois' `index`): 1 where the ring of pixels next to the zeroed
+ * 1-px frame of the frame's or crop's binary image -- rows 1 and sh-2, columns 1 and sw-2 -- is all set and both sides are at
+ * least 8, so that the border which begins at (1, 1) is dropped without a walk; else 0.  Only batches of more than 8 frames
+ * judge their rings: a batch of at most 8 frames gives all zeros.  Writes the first max_flags values and stores the full count
+ * (the batch's frames, or its crop ROIs).  Copies out of the workspace and launches nothing; valid and refused like
+ * ocvar_hip_debug_starts. */
+int ocvar_hip_debug_rings(OcvarHip* ctx, int crop_pass, int* flags, int max_flags, int* n_flags);
+
 /* Measurement aid: runs a dword-per-lane copy of `bytes` bytes (the binarise kernel's access widths) so that a
  * rocprofv3 PMC pass can calibrate FETCH_SIZE / WRITE_SIZE for that pattern (tools/collect_traffic.py). */
 int ocvar_hip_debug_calibrate(OcvarHip* ctx, size_t bytes);

@@ -27,7 +27,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_pipe_detect_device", "ocvar_hip_pipe_track_device", "ocvar_hip_pipe_submit", "ocvar_hip_pipe_collect", "ocvar_hip_pipe_in_flight", "ocvar_hip_pipe_set_result_limit", "ocvar_hip_set_input_format", "ocvar_hip_pipe_set_input_format", "ocvar_hip_set_corner_refine", "ocvar_hip_pipe_set_corner_refine", "ocvar_hip_enqueue_tracked", "ocvar_hip_build_info", "ocvar_hip_set_tuning", "ocvar_hip_destroy", "ocvar_hip_last_error", "ocvar_hip_set_templates", "ocvar_hip_set_camera",
     "ocvar_hip_detect_device", "ocvar_hip_enqueue", "ocvar_hip_collect", "ocvar_hip_detect_host", "ocvar_hip_find_squares",
     "ocvar_hip_debug_gray", "ocvar_hip_debug_binary", "ocvar_hip_debug_masks", "ocvar_hip_debug_frame_quads", "ocvar_hip_debug_candidates",
-    "ocvar_hip_debug_crop_rois", "ocvar_hip_debug_crop_plane", "ocvar_hip_debug_starts",
+    "ocvar_hip_debug_crop_rois", "ocvar_hip_debug_crop_plane", "ocvar_hip_debug_starts", "ocvar_hip_debug_rings",
     "ocvar_hip_stage_ms", "ocvar_hip_stream", "ocvar_hip_stage_stamps", "ocvar_hip_counters", "ocvar_hip_results_to_device", "ocvar_hip_results_to_device_ex", "ocvar_hip_debug_calibrate",
     "ocvar_hip_set_board", "ocvar_hip_board_poses", "ocvar_hip_board_poses_to_device",
     "ocvar_hip_set_overlay", "ocvar_hip_render", "ocvar_hip_render_records",
@@ -418,6 +418,7 @@ def hip_lib():
         lib.ocvar_hip_debug_crop_rois.argtypes = [vp, vp, i, vp]
         lib.ocvar_hip_debug_crop_plane.argtypes = [vp, i, i, vp]
         lib.ocvar_hip_debug_starts.argtypes = [vp, i, vp, i, vp]
+        lib.ocvar_hip_debug_rings.argtypes = [vp, i, vp, i, vp]
         lib.ocvar_hip_stage_ms.argtypes = [vp, vp, i]
         lib.ocvar_hip_counters.argtypes = [vp, vp, i]
         lib.ocvar_hip_stage_stamps.argtypes = [vp, vp, vp, i]
@@ -1161,6 +1162,16 @@ class Detector:
         self._check(self._lib.ocvar_hip_debug_starts(self._ctx, int(bool(crop_pass)), None, 0, C.byref(n)), "debug_starts")
         out = np.zeros(max(n.value, 1), START_DTYPE)
         self._check(self._lib.ocvar_hip_debug_starts(self._ctx, int(bool(crop_pass)), _ptr(out), n.value, C.byref(n)), "debug_starts")
+        return out[:n.value]
+
+    def debug_rings(self, crop_pass=False):
+        """the ring verdicts of the last collected batch, int32 [frames of the batch], or [len(debug_crops())] indexed like its
+        `index`: 1 where ring_quads_kernel found the ring next to the ROI's zeroed frame all set (tier 1 then drops the border that
+        begins at (1, 1)); all zeros after a batch of at most 8 frames"""
+        n = C.c_int(0)
+        self._check(self._lib.ocvar_hip_debug_rings(self._ctx, int(bool(crop_pass)), None, 0, C.byref(n)), "debug_rings")
+        out = np.zeros(max(n.value, 1), np.int32)
+        self._check(self._lib.ocvar_hip_debug_rings(self._ctx, int(bool(crop_pass)), _ptr(out), n.value, C.byref(n)), "debug_rings")
         return out[:n.value]
 
     def stage_ms(self):

@@ -131,6 +131,20 @@ extern "C" int ocvar_hip_debug_starts(OcvarHip* c, int crop_pass, OcvarStart* st
     return OCVAR_OK;
 }
 
+// The ring verdicts of the last collected batch (follow.hip::ring_quads_kernel: 1 where the ROI's own frame border is the rectangle
+// that needs no walk), one int per frame or per crop ROI.  Batches of at most 8 frames run no ring kernel: api.hip and order.hip
+// have cleared the flags.
+extern "C" int ocvar_hip_debug_rings(OcvarHip* c, int crop_pass, int* flags, int max_flags, int* n_flags) {
+    if (!c || c->pending || !n_flags || max_flags < 0 || (max_flags > 0 && !flags) || c->ws.n_frames < 1 || !c->h_counters.p) return OCVAR_E_ARG;
+    const int n = crop_pass ? crop_count(c) : c->ws.n_frames;
+    if (n < 0) return OCVAR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int k = n < max_flags ? n : max_flags;
+    if (k > 0) HIP_TRY(c, hipMemcpy(flags, crop_pass ? c->ws.ring_crop : c->ws.ring_frame, (size_t)k * sizeof(int), hipMemcpyDeviceToHost));
+    *n_flags = n;
+    return OCVAR_OK;
+}
+
 extern "C" int ocvar_hip_debug_candidates(OcvarHip* c, int frame, OcvarCandidate* cands, int max_cands, int* n_cands) {
     if (!c || !cands || !n_cands || frame < 0 || frame >= c->ws.n_frames) return OCVAR_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));

@@ -653,9 +653,9 @@ __global__ __launch_bounds__(64) void ring_quads_kernel(Workspace ws) {
             ring[roi] = clean ? 1 : 0;
             const int sw = mine.img_w & ~1, sh = mine.sh;
             // (worth_approximating: the quad filter needs |area| > 500.  It also needs the result's first vertex inside the 2-px
-            // inset of the ROI's image, 2 < x < img_w - 2 and 2 < y < img_h - 2; a vertex is one of the four points, and of those only
-            // (sw-2, sh-2) can be, when img_w and img_h are both odd: sw - 2 < img_w - 2 means sw < img_w.  Any other ROI's rectangle
-            // is rejected whatever the approximation gives, so it is not approximated.)
+            // inset of the ROI's image, 2 < x < img_w - 2 and 2 < y < img_h - 2; of the four points only (sw-2, sh-2) lies there, and
+            // only when img_w and img_h are both odd, so no other ROI is approximated.  The approximation never begins with that
+            // point, though: it gives 2 vertices, or 4 that begin with (1, 1) -- tests/test_rings_cpu.py, sides 8 .. 32766.)
             if (clean && (long long)(sw - 3) * (sh - 3) > 500 && (mine.img_w & 1) && (mine.img_h & 1)) {
                 const int pts[8] = {1, 1, 1, sh - 2, sw - 2, sh - 2, sw - 2, 1};
                 const TraceStats st = stats_of_points(pts, 4);

@@ -93,6 +93,30 @@ extern "C" int emul_approx_poly(const int* src, int n, double eps, int* dst) {
     return m;
 }
 
+// The ring rectangle of follow.hip::ring_quads_kernel for n ROIs of sw[i] x sh[i]: the four points (1,1) (1,sh-2) (sw-2,sh-2)
+// (sw-2,1) through stats_of_points and approx_poly_dp at 0.02 of the perimeter, as approximate_and_emit calls them.  m[i]: the
+// vertex count; pts + 8 i: the first four vertices.
+extern "C" void emul_ring_rects(int n, const int* sw, const int* sh, int* m, int* pts) {
+    for (int i = 0; i < n; i++) {
+        const int src[8] = {1, 1, 1, sh[i] - 2, sw[i] - 2, sh[i] - 2, sw[i] - 2, 1};
+        const TraceStats st = stats_of_points(src, 4);
+        DpSlice stack[DP_STACK];
+        int dst[2 * (DP_MAX_OUT + 1)] = {0};
+        m[i] = approx_poly_dp(src, 4, st.perimeter * 0.02, dst, stack);
+        memcpy(pts + 8 * (size_t)i, dst, sizeof(int) * 8);
+    }
+}
+
+// quad_filter on n approximation results (m[i] vertices, the first four at pts + 8 i) of ROIs of sw[i] x sh[i], for the images
+// such an ROI can be cut from: bit 2 a + b of accepted[i] is set if m[i] == 4 and the filter passes img_w = sw + a, img_h = sh + b.
+extern "C" void emul_quad_filter_rois(int n, const int* sw, const int* sh, const int* m, const int* pts, int* accepted) {
+    for (int i = 0; i < n; i++) {
+        accepted[i] = 0;
+        for (int k = 0; k < 4; k++)
+            if (m[i] == 4 && quad_filter(pts + 8 * (size_t)i, sw[i] + (k >> 1), sh[i] + (k & 1))) accepted[i] |= 1 << k;
+    }
+}
+
 // The K3 flow on one binary plane: candidates -> pass 1 (stats, first-check) -> prune -> pass 2 -> DP -> filter.
 // quads come out in the reference's push order (descending start).  stats: [0] candidates, [1] steps spent by
 // candidates that dropped out, [2] steps of surviving borders (pass 1), [3] borders, [4] borders approximated.
