@@ -652,6 +652,43 @@ int ocvar_hip_levels(OcvarHip* ctx, const uint8_t* d_src, int width, int height,
                      int format, uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride, int n_frames,
                      const OcvarLevelsParams* params, void* stream);
 
+/* Bayer: the raw mosaic of a machine-vision camera (GigE, USB3, CSI), in 8-bit bytes or in 16-bit words holding 9 .. 16 bits,
+ * demosaiced on the device into frames of any OCVAR_FMT_*, behind a black level and a white balance -- what render, annotate,
+ * patches, warp and ocvar_hip_frames_to_yuv need of such a camera's frames.  The definition, bit for bit and all integer, is
+ * opencv-ar_amd/csrc/bayer_core.h.  The call stands for OpenCV's cvtColor with COLOR_Bayer*2BGR and its relatives (bilinear); no
+ * OpenCV exists where this library is built and tested, so parity with an OpenCV build is unpinned and not claimed, and the border
+ * rule is the library's own.
+ *   pattern   named by the colours of the top-left 2 x 2 block, row by row: OCVAR_BAYER_RGGB, _GRBG, _GBRG, _BGGR.  (OpenCV names
+ *             its constants by the second row's 2 x 2: COLOR_BayerBG2BGR is RGGB.)  A source rectangle is d_src moved to its first
+ *             sample with the full frame's strides and the pattern ocvar_hip_bayer_pattern_at(pattern, x0, y0) of its origin.
+ *   bits      8: one byte per sample.  9 .. 16: one little-endian 16-bit word per sample, right-aligned, the sample being
+ *             word & (2^bits - 1); MSB-aligned data is read with bits = 16.  A 16-bit source has an even address and even strides.
+ *   black, gain_b, gain_g, gain_r   on each sample, with the gain of the sample's own colour (1024 = 1.0), before interpolation:
+ *             s' = min(2^bits - 1, (max(s - black, 0) gain + 512) >> 10); black 0 .. 2^bits - 1, gains 0 .. 16383.
+ *   interpolation  at an R or B site: own colour = the sample, G = (N + S + W + E + 2) >> 2, the opposite colour = (NW + NE + SW +
+ *             SE + 2) >> 2; at a G site: G = the sample, the colour of the row's other sites = (W + E + 1) >> 1, of the column's
+ *             = (N + S + 1) >> 1.  A coordinate outside the frame is reflected without repeating the edge (-1 -> 1, W -> W - 2),
+ *             which keeps the colour phase: a mosaic of one colour gives that colour everywhere.
+ *   reduction for bits > 8: v8 = min(255, (v + (1 << (bits - 9))) >> (bits - 8)).
+ *   d_dst     n_frames frames of width x height pixels in `format`; BGRA and RGBA get byte 3 = 255, GRAY the library's grey of the
+ *             demosaiced colour, (1868 B + 9617 G + 4899 R + 8192) >> 14: detection on it is detection on the demosaiced BGR frame.
+ * params NULL: the defaults (RGGB, 8 bits, black 0, gains 1024), which ocvar_hip_bayer_default_params (host only) writes.  Sides
+ * are 2 .. 32767, odd ones included, and are NOT bound by the context's max_width x max_height.  When every address, row stride and
+ * frame stride of both sides is a multiple of 4 the kernels move whole dwords; otherwise, and at the ends of rows, bytes -- with the
+ * same result.  No byte outside the destination's pixels is written; the source is never written.  No workspace: the call
+ * allocates nothing and does not wait.  More than 65535 frames go in several launches, in order.  stream NULL: the context's own
+ * stream.  OCVAR_E_ARG, before any device call and with a text in ocvar_hip_last_error, for a NULL pointer (params may be NULL), a
+ * side below 2 or above 32767, an unknown pattern or format, bits outside 8 .. 16, black or a gain out of range, a row stride below
+ * the row's bytes, rows that span more than 2^31 - 1 bytes, a 16-bit source at an odd address or with an odd stride, n_frames < 1,
+ * intersecting source and destination byte ranges. */
+enum { OCVAR_BAYER_RGGB = 0, OCVAR_BAYER_GRBG = 1, OCVAR_BAYER_GBRG = 2, OCVAR_BAYER_BGGR = 3 };
+typedef struct { int pattern, bits, black, gain_b, gain_g, gain_r; } OcvarBayerParams;   /* 24 bytes */
+int ocvar_hip_bayer_default_params(OcvarBayerParams* p);             /* host only: RGGB, 8, 0, 1024 x 3 */
+int ocvar_hip_bayer_pattern_at(int pattern, int x0, int y0);         /* host only; -1 for an unknown pattern */
+int ocvar_hip_bayer_to_frames(OcvarHip* ctx, const void* d_src, int src_row_stride, size_t src_frame_stride,
+                              uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride,
+                              int width, int height, int n_frames, int format, const OcvarBayerParams* params, void* stream);
+
 /* Batch detection on frames already resident in device memory.
  *   d_bgr        frames in the context's input format (default 8UC3 interleaved BGR: ocvar_hip_set_input_format), frame f
  *                starts at d_bgr + f*frame_stride, rows row_stride bytes apart
@@ -695,6 +732,7 @@ enum { OCVAR_TUNE_CROP_PHASES = 1, /* crop-pass tier 2 in 1 launch or 2 (exact p
        OCVAR_TUNE_GATE_MODE = 8,   /* which of a context's two binarise kernels wait at its gate: 0 both (default), 1 the frames
                                     * kernel only, 2 the crops kernel only */
        OCVAR_TUNE_WARP_DIRECT = 9, /* 1: every tile of ocvar_hip_warp reads the source directly, none is staged through LDS */
+       OCVAR_TUNE_BAYER_PAIRS = 10, /* row pairs a lane of ocvar_hip_bayer_to_frames marches down, 1 .. 64 (default 4) */
        OCVAR_TUNE_HP_MASK = 7 };   /* kernels launched on the context's high-priority stream, one bit per launch: 1 tier 1
                                     * (frames), 2 tier 2, 4 tier 3, 8 order/crops, 16 tier 1 (crops), 32 tier 2, 64 tier 3,
                                     * 128 decode, 256 dedupe+pose; ocvar_hip_set_tuning(ctx, OCVAR_TUNE_HP_MASK, m) sets mask m

@@ -40,6 +40,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_orient", "ocvar_hip_orient_records", "ocvar_hip_orient_camera",
     "ocvar_hip_warp", "ocvar_hip_warp_records", "ocvar_hip_board_plane_maps",
     "ocvar_hip_levels_default_params", "ocvar_hip_levels",
+    "ocvar_hip_bayer_default_params", "ocvar_hip_bayer_pattern_at", "ocvar_hip_bayer_to_frames",
 ]
 # input formats (include/ocvar_hip.h: OCVAR_FMT_*) and their bytes per pixel
 INPUT_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "gray": 4}
@@ -193,6 +194,51 @@ def levels_params(tiles=(1, 1), low_ppm=10000, high_ppm=10000, max_gain=8.0):
     if isinstance(max_gain, bool) or not isinstance(max_gain, (int, float, np.integer, np.floating)) or not 1.0 <= float(max_gain) <= 255.0:
         raise ValueError(f"max_gain must be a number in 1 .. 255, got {max_gain!r}")
     return LevelsParams(int(tx), int(ty), int(low_ppm), int(high_ppm), int(round(float(max_gain) * 256)))
+
+
+BAYER_PATTERNS = {"rggb": 0, "grbg": 1, "gbrg": 2, "bggr": 3}   # include/ocvar_hip.h: OCVAR_BAYER_RGGB .. (the top-left 2 x 2, row by row)
+BAYER_MAX_GAIN = 16383                                          # include/ocvar_hip.h: OcvarBayerParams' gains, 1024 = 1.0
+
+
+class BayerParams(C.Structure):  # OcvarBayerParams
+    _fields_ = [("pattern", C.c_int), ("bits", C.c_int), ("black", C.c_int), ("gain_b", C.c_int), ("gain_g", C.c_int), ("gain_r", C.c_int)]
+
+
+def _bayer_pattern_code(pattern):
+    if isinstance(pattern, str) and pattern.lower() in BAYER_PATTERNS:
+        return BAYER_PATTERNS[pattern.lower()]
+    if not isinstance(pattern, bool) and isinstance(pattern, (int, np.integer)) and int(pattern) in BAYER_PATTERNS.values():
+        return int(pattern)
+    raise ValueError(f"unknown Bayer pattern {pattern!r}: one of {sorted(BAYER_PATTERNS)}")
+
+
+def bayer_params(pattern="rggb", bits=8, black=0, gains=(1.0, 1.0, 1.0)):
+    """The parameters of Detector.bayer_to_frames (include/ocvar_hip.h: OcvarBayerParams; the defaults are the library's), checked:
+    pattern a name of BAYER_PATTERNS (the colours of the top-left 2 x 2 block, row by row; OpenCV's COLOR_BayerBG2BGR is 'rggb') or
+    its code, bits 8 .. 16 (8: bytes; more: 16-bit words, right-aligned), black 0 .. 2^bits - 1, gains = (blue, green, red) as
+    numbers of 0 .. 16383 / 1024 (stored in 1/1024).  ValueError outside those."""
+    code = _bayer_pattern_code(pattern)
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 8 <= bits <= 16:
+        raise ValueError(f"bits must be an int in 8 .. 16, got {bits!r}")
+    if isinstance(black, bool) or not isinstance(black, (int, np.integer)) or not 0 <= black <= (1 << int(bits)) - 1:
+        raise ValueError(f"black must be an int in 0 .. {(1 << int(bits)) - 1}, got {black!r}")
+    try:
+        gb, gg, gr = gains
+    except (TypeError, ValueError):
+        raise ValueError(f"gains must be (blue, green, red), got {gains!r}") from None
+    q = []
+    for name, g in (("blue", gb), ("green", gg), ("red", gr)):
+        if isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating)) or not 0 <= int(round(float(g) * 1024)) <= BAYER_MAX_GAIN:
+            raise ValueError(f"the {name} gain must be a number in 0 .. {BAYER_MAX_GAIN / 1024:.3f}, got {g!r}")
+        q.append(int(round(float(g) * 1024)))
+    return BayerParams(code, int(bits), int(black), q[0], q[1], q[2])
+
+
+def bayer_pattern_at(pattern, x0, y0):
+    """the name of the pattern of a source rectangle whose origin is sample (x0, y0) of a mosaic in `pattern` (a name or a code):
+    pass it with the pointer moved to that sample and the full frame's strides.  No device call."""
+    code = hip_lib().ocvar_hip_bayer_pattern_at(_bayer_pattern_code(pattern), int(x0), int(y0))
+    return {v: k for k, v in BAYER_PATTERNS.items()}[code]
 
 
 def perspective_map(src_quad, dst_quad):
@@ -453,6 +499,9 @@ def hip_lib():
         lib.ocvar_hip_board_plane_maps.argtypes = [vp, vp, i, vp, i, i, vp, vp]
         lib.ocvar_hip_levels_default_params.argtypes = [vp]
         lib.ocvar_hip_levels.argtypes = [vp, vp, i, i, i, sz, i, vp, i, sz, i, vp, vp]
+        lib.ocvar_hip_bayer_default_params.argtypes = [vp]
+        lib.ocvar_hip_bayer_pattern_at.argtypes = [i, i, i]
+        lib.ocvar_hip_bayer_to_frames.argtypes = [vp, vp, i, sz, vp, i, sz, i, i, i, i, vp, vp]
         _hip = lib
     return _hip
 
@@ -970,6 +1019,22 @@ class Detector:
         self._check(self._lib.ocvar_hip_levels(self._ctx, d_src, width, height, src_row_stride, src_frame_stride, code, d_dst, dst_row_stride,
                                                dst_frame_stride, n_frames, None if params is None else C.byref(params), stream), "levels")
 
+    def bayer_to_frames(self, d_src, d_dst, width, height, n_frames, params=None, fmt=None, src_row_stride=None, src_frame_stride=None,
+                        dst_row_stride=None, dst_frame_stride=None, stream=None):
+        """n_frames raw Bayer mosaics of width x height samples at d_src (bytes, or 16-bit words when params.bits > 8) demosaiced
+        into the device frames at d_dst in format fmt (default: the input format): black level and white balance on each sample,
+        bilinear interpolation at full depth with reflected borders, the reduction to 8 bits (params: bayer_params(...); None: RGGB,
+        8 bits, black 0, gains 1).  A four-channel destination gets byte 3 = 255, 'gray' the library's grey of the demosaiced
+        colour.  Sides are 2 .. 32767, odd ones included, and are not bound by the detector's.  A source rectangle is d_src moved
+        to its first sample with the full frame's strides and the pattern bayer_pattern_at(pattern, x0, y0).  The two sides must
+        not overlap.  Needs no batch, allocates nothing, does not wait (stream None: the detector's own stream)."""
+        sb = 2 if params is not None and params.bits > 8 else 1
+        _, src_row_stride, src_frame_stride = self._strides(fmt, width, height, src_row_stride, src_frame_stride, bpp=sb)
+        code, dst_row_stride, dst_frame_stride = self._strides(fmt, width, height, dst_row_stride, dst_frame_stride)
+        self._check(self._lib.ocvar_hip_bayer_to_frames(self._ctx, d_src, src_row_stride, src_frame_stride, d_dst, dst_row_stride,
+                                                        dst_frame_stride, width, height, n_frames, code,
+                                                        None if params is None else C.byref(params), stream), "bayer_to_frames")
+
     def warp(self, d_src, src_width, src_height, d_dst, dst_width, dst_height, n_frames, d_maps, interp="linear", border="constant", fill=None,
              inverse_map=False, one_map=False, fmt=None, src_row_stride=None, src_frame_stride=None, dst_row_stride=None,
              dst_frame_stride=None, d_status_ptr=None, stream=None):
@@ -1043,7 +1108,7 @@ class Detector:
                                                      C.byref(p), d_out, d_status_ptr, d_err_ptr, stream), "flow_records")
 
     TUNE = {"crop_phases": 1, "mid_steps": 2, "mid_blocks": 3, "long_blocks": 4, "short_blocks": 5, "min_units": 6, "hp_mask": 7, "gate_mode": 8,
-            "warp_direct": 9}
+            "warp_direct": 9, "bayer_pairs": 10}
 
     def set_tuning(self, **kw):
         """result-invariant launch parameters (include/ocvar_hip.h: OCVAR_TUNE_*); 0 restores a default"""

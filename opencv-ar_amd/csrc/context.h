@@ -84,7 +84,7 @@ template <typename T> using PinnedBuffer = Buffer<T, true>;
 // reports the EV_STAGES intervals ev[k] .. ev[k + 1] one by one, then the whole batch ev[0] .. ev[EV_LAST].
 constexpr int EV_COUNT = 13, EV_LAST = EV_COUNT - 1, EV_STAGES = EV_LAST - 1;
 // ocvar_hip_set_tuning's knobs are 1 .. TUNE_KNOBS - 1 (OCVAR_TUNE_*)
-constexpr int TUNE_KNOBS = OCVAR_TUNE_WARP_DIRECT + 1;
+constexpr int TUNE_KNOBS = OCVAR_TUNE_BAYER_PAIRS + 1;
 
 }  // namespace ocvar
 

@@ -1,5 +1,5 @@
 // frame_ops.hip -- the opt-in operations of the C ABI on frames and marker records in device memory: overlays, annotation,
-// patches, undistortion, YUV conversion, resizing, turning, warping, levels and flow tracking.  An entry point is its own
+// patches, undistortion, YUV conversion, resizing, turning, warping, levels, demosaic and flow tracking.  An entry point is its own
 // parameter checks, the shared checks of its frame blocks (frames_core.h; here they get their error texts), and its launches in
 // chunks of frames.  Every refusal (OCVAR_E_ARG and a text that begins with the operation's name) comes before any device call.
 #include "context.h"
@@ -593,6 +593,49 @@ extern "C" int ocvar_hip_levels(OcvarHip* c, const uint8_t* d_src, int width, in
     if (rc) return rc;
     HIP_TRY(c, c->levels_fence.leave(s));
     return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_bayer_default_params(OcvarBayerParams* p) {
+    if (!p) return OCVAR_E_ARG;
+    bayer_default_params(p);
+    return OCVAR_OK;
+}
+
+extern "C" int ocvar_hip_bayer_pattern_at(int pattern, int x0, int y0) { return bayer_pattern_at(pattern, x0, y0); }
+
+extern "C" int ocvar_hip_bayer_to_frames(OcvarHip* c, const void* d_src, int src_row_stride, size_t src_frame_stride, uint8_t* d_dst,
+                                         int dst_row_stride, size_t dst_frame_stride, int width, int height, int n_frames, int format,
+                                         const OcvarBayerParams* params, void* stream) {
+    static_assert(sizeof(OcvarBayerParams) == 24, "the 24 bytes of the header");
+    if (!c) return OCVAR_E_ARG;
+    const char* const who = "bayer_to_frames";
+    if (!d_src || !d_dst) return refuse(c, who, "no source mosaics or no destination frames");
+    OcvarBayerParams p;
+    bayer_default_params(&p);
+    if (params) p = *params;
+    constexpr const char* UNKNOWN = "an unknown pattern or format";
+    static const char* const why[] = {"", UNKNOWN, "bits 8 .. 16", "black 0 .. 2^bits - 1", "gains 0 .. 16383"};
+    if (const int bad = bayer_params_bad(p)) return refuse(c, who, why[bad]);
+    constexpr FrameTexts texts = with(with(with(TEXTS, FRAMES_FORMAT, UNKNOWN), FRAMES_SIDE, "sides of 2 .. 32767 pixels"), FRAMES_ROW_STRIDE,
+                                      "a row stride below the row's bytes (the source: the sample's bytes times width)");
+    if (width < 2 || height < 2) return refuse(c, who, texts.why[FRAMES_SIDE]);
+    const int sb = bayer_sample_bytes(p.bits);
+    if (sb == 2 && (((uintptr_t)d_src | (uintptr_t)src_row_stride | (uintptr_t)src_frame_stride) & 1))
+        return refuse(c, who, "a 16-bit source at an odd address or with an odd stride");
+    const uint8_t* src = static_cast<const uint8_t*>(d_src);
+    // (the destination first: of the two blocks it alone can have an unknown format)
+    if (int rc = pair_check(c, who, block_of(d_dst, width, height, format_bpp(format), dst_row_stride, dst_frame_stride, n_frames),
+                            block_of(src, width, height, sb, src_row_stride, src_frame_stride, n_frames), ANY_SIZE, texts, "demosaic", true,
+                            "source and destination"))
+        return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream_or_own(c, stream);
+    const int pairs = c->tune[OCVAR_TUNE_BAYER_PAIRS] > 0 ? std::min(c->tune[OCVAR_TUNE_BAYER_PAIRS], BAYER_MAX_PAIRS) : BAYER_PAIRS;
+    return run_chunks(c, who, n_frames, BAYER_CHUNK_FRAMES, s, [&](int f0, int n) {
+        const BayerArgs a{src + (size_t)f0 * src_frame_stride, d_dst + (size_t)f0 * dst_frame_stride, (long long)src_row_stride,
+                          (long long)src_frame_stride, (long long)dst_row_stride, (long long)dst_frame_stride, width, height, format, p, pairs};
+        launch_bayer(a, n, s);
+    });
 }
 
 // a parameter of ocvar_hip_flow_records that must be a finite number >= 0

@@ -16,6 +16,7 @@
 #include "orient_core.h"
 #include "warp_core.h"
 #include "levels_core.h"
+#include "bayer_core.h"
 #include "flow_core.h"
 #include "croplist_core.h"
 #include "ocvar_hip.h"
@@ -315,6 +316,11 @@ void launch_warp_board_maps(const WarpBoardMapArgs& a, hipStream_t stream);
 // `format` of a (levels_core.h: LevelsArgs), whose two sides do not overlap: histograms into a.hist, which must be all zeros and is
 // all zeros again afterwards (the LUT kernel clears what it has read), LUTs into a.luts, the blend into a.dst.
 void launch_levels(const LevelsArgs& a, int n_frames, int format, hipStream_t stream);
+
+// One launch of bayer_to_frames_kernel (bayer.hip) on the n_frames (at most BAYER_CHUNK_FRAMES: the grid's z) mosaics of a
+// (bayer_core.h: BayerArgs), whose two sides do not overlap.
+constexpr int BAYER_CHUNK_FRAMES = 65535;
+void launch_bayer(const BayerArgs& a, int n_frames, hipStream_t stream);
 
 // The pyramids of n_frames frames in `format` (flow.hip: flow_grey_kernel, then flow_down_kernel level by level): frame f's
 // levels 0 .. g.L go to pyr + f * slot_bytes, laid out as g says.
