@@ -1,30 +1,24 @@
 """Annotation for the annotate tests (ocvar_hip_annotate / ocvar_hip_annotate_records): the host build of
 opencv-ar_amd/csrc/annotate_core.h (tests/emul/annotate_emul.cpp), its stand-alone sanitizer program, a numpy float64 restatement
 of the stroke rule that shares no code with it (distance from a pixel centre to a segment), the font restated as pictures, guarded
-frames (overlay_chain.Frames) and hand-made records with poses.  Shared by tests/test_annotate_cpu.py and
+frames (frame_kit.Frames) and hand-made records with poses.  Shared by tests/test_annotate_cpu.py and
 tests/test_gpu_annotate.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import board_chain as BC
 import helpers as H
-import overlay_chain as OC
-from overlay_chain import BPP, FORMATS, GUARD, LEAD, MARKER_DTYPE, Frames  # noqa: F401
+from frame_kit import records
+from hostbuild import host_core
 
-FMTS = ["bgr", "rgb", "bgra", "rgba", "gray"]
 OUTLINE, CORNER0, AXES, CUBE, LABEL, UNMATCHED, COLOR_BY_TEMPLATE = 1, 2, 4, 8, 16, 32, 64
 DRAW_FLAGS = OUTLINE | CORNER0 | AXES | CUBE | LABEL
 ALL_FLAGS = DRAW_FLAGS | UNMATCHED | COLOR_BY_TEMPLATE
 MAX_COORD = 1048576
-E_ARG = -2
 # annotate.hip: a lane owns ANNO_LANE_PX = 4 pixels of a row, a wave 256 columns and 4 rows, a workgroup 16 rows; record slots are
 # balloted 64 at a time
 LANE_PX, TILE_W, WAVE_ROWS, TILE_H, BALLOT = 4, 256, 4, 16, 64
-EMUL_SRC = os.path.join(H.ROOT, "tests", "emul", "annotate_emul.cpp")
-EMUL_FLAGS = ["-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + OC.CSRC, "-I" + os.path.join(H.ROOT, "include")]
 
 
 class Style(C.Structure):  # OcvarAnnotateStyle, restated
@@ -64,10 +58,8 @@ def label_picture(number, scale):
     return np.kron(pic, np.ones((scale, scale), bool)).astype(bool)
 
 
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "libannotate_emul.so")
-    subprocess.check_call(["g++", "-O2"] + EMUL_FLAGS + ["-shared", "-o", so, EMUL_SRC])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("annotate_emul")
     vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
     L.annotate_frame_emul.argtypes = [vp, i, i, ll, i, vp, i, i, vp, vp]
     L.annotate_setup_emul.argtypes = [vp, vp, vp, i, i, vp, vp]
@@ -78,14 +70,6 @@ def build_emul(out_dir):
     L.annotate_palette_emul.argtypes = [i]
     L.annotate_palette_emul.restype = C.c_uint
     return L
-
-
-def build_sanitized_program(out_dir):
-    """the emulation with its stand-alone main under AddressSanitizer and UndefinedBehaviorSanitizer -> the program's path"""
-    exe = os.path.join(str(out_dir), "annotate_emul_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DANNOTATE_EMUL_MAIN"] +
-                          EMUL_FLAGS + ["-o", exe, EMUL_SRC])
-    return exe
 
 
 def style(L, flags=None, **kw):
@@ -177,7 +161,7 @@ def posed_record(cam, R, t, template_id=0, score=1.0, ratio=1.0):
     """a record whose square is the projection of the model rectangle (+-ratio, +-1) under (R, t) and whose glMatrix holds the pose"""
     K, dist = BC.cam_arrays(cam)
     quad = BC.project(K, dist, R, t, np.array([[-ratio, -1], [ratio, -1], [ratio, 1], [-ratio, 1]], np.float64))
-    r = OC.records([quad.reshape(8)], [template_id], [score])
+    r = records([quad.reshape(8)], [template_id], [score])
     r["glMatrix"][0] = glmatrix_of_pose(R, t)
     r["aspectRatio"] = ratio
     return r[0]

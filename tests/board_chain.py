@@ -13,8 +13,7 @@ import dense_synth as DS
 import helpers as H
 import refine_chain as RC
 from helpers import P
-
-CSRC = os.path.join(H.PKG, "csrc")
+from hostbuild import host_core
 
 
 class BoardMarker(C.Structure):
@@ -29,12 +28,8 @@ class BoardPose(C.Structure):
 assert C.sizeof(BoardMarker) == 72 and C.sizeof(BoardPose) == 192
 
 
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "libboard_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + CSRC,
-                           "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(H.ROOT, "tests", "emul", "board_emul.cpp")])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("board_emul")
     L.board_first_bad_emul.argtypes = [C.c_void_p, C.c_int]
     L.board_solve_obs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.board_solve_obs.restype = None

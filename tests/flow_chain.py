@@ -1,25 +1,22 @@
 """Flow tracking for the flow tests (ocvar_hip_flow_records): the host build of opencv-ar_amd/csrc/flow_core.h
 (tests/emul/flow_emul.cpp), a plain numpy float64 restatement of the equations -- written from the text of the definition
 (include/ocvar_hip.h and the head of flow_core.h), not from the code: the independent yardstick --, textured frames, exact shifts
-and rendered view pairs.  Frames, records and guard bytes are overlay_chain's.  Shared by tests/test_flow_cpu.py and
+and rendered view pairs.  Frames, records and guard bytes are frame_kit's.  Shared by tests/test_flow_cpu.py and
 tests/test_gpu_flow.py.
 
 The oracle has no pyrDown entry point of its own (orc_binarise returns only the threshold and the pyrUp of its pyrDown), so the
 pyramid is compared against the numpy restatement here."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
 import helpers as H
-import overlay_chain as OC
 import persp_synth as PS
+from frame_kit import FORMATS, GUARD, records
 from helpers import P
-from overlay_chain import BPP, FORMATS, GUARD, LEAD, MARKER_DTYPE, Frames, records  # noqa: F401
+from hostbuild import host_core
 
-FMTS = ["bgr", "rgb", "bgra", "rgba", "gray"]
 POSE = 1
 DEFAULTS = dict(half_win=10, levels=3, max_iter=30, flags=0, eps=0.03, min_eig=1e-3, max_err=0.0, fb_max=0.0)
 
@@ -38,12 +35,8 @@ def params(**kw):
     return FlowParams(**d)
 
 
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "libflow_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + OC.CSRC,
-                           "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(H.ROOT, "tests", "emul", "flow_emul.cpp")])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("flow_emul")
     vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
     L.flow_geom_emul.argtypes = [i, i, i, i, vp, vp]
     L.flow_grey_level_emul.argtypes = [vp, i, i, ll, i, vp, i]

@@ -1,28 +1,22 @@
 """Grey levels for the levels tests (ocvar_hip_levels): the host build of opencv-ar_amd/csrc/levels_core.h (tests/emul/levels_emul.cpp),
-a numpy restatement of the definition that shares no code with it, guarded frames (yuv_chain.pix_layout on overlay_chain.Frames), the
+a numpy restatement of the definition that shares no code with it, guarded frames (frame_kit.pix_layout), the
 cases the CPU and GPU tests share, and the exposure chain through the oracle on the library's own synthetic scenes.  Shared by
 tests/test_levels_cpu.py and tests/test_gpu_levels.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import helpers as H
 import overlay_chain as OC
-from overlay_chain import BPP, FORMATS, GUARD, LEAD  # noqa: F401
-from yuv_chain import pix_layout  # noqa: F401
+from frame_kit import FORMATS, GUARD, pix_layout
+from hostbuild import host_core
 
-FMTS = ["bgr", "rgb", "bgra", "rgba", "gray"]
 FMT_NAMES = {v: k for k, v in FORMATS.items()}
-E_ARG = -2
 # levels.hip: a workgroup of the histogram kernel counts SLAB_ROWS rows of a tile, one of the apply kernel a rectangle of at most
 # SEG_W x SEG_H pixels inside one cell of the tile-centre lattice; the workspace takes WS_FRAMES frames a round (levels_core.h;
 # tests/test_levels_cpu.py compares these with the core's)
 SLAB_ROWS, SEG_W, SEG_H, WS_FRAMES, MAX_TILES = 32, 256, 32, 256, 64
 WS_BYTES = WS_FRAMES * MAX_TILES * (1024 + 256)
-EMUL_SRC = os.path.join(H.ROOT, "tests", "emul", "levels_emul.cpp")
-EMUL_FLAGS = ["-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + OC.CSRC, "-I" + os.path.join(H.ROOT, "include")]
 
 
 class Params(C.Structure):  # OcvarLevelsParams
@@ -37,10 +31,8 @@ def as_tuple(p):
     return (p.tiles_x, p.tiles_y, p.low_ppm, p.high_ppm, p.max_gain_q8)
 
 
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "liblevels_emul.so")
-    subprocess.check_call(["g++", "-O2"] + EMUL_FLAGS + ["-shared", "-o", so, EMUL_SRC])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("levels_emul")
     vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
     L.levels_emul.argtypes = [vp, i, i, ll, ll, i, vp, ll, ll, i, vp, vp, vp]
     L.levels_default_params_emul.argtypes = [vp]
@@ -52,14 +44,6 @@ def build_emul(out_dir):
     L.levels_segments_emul.argtypes = [i, i, i, vp]
     L.levels_ws_bytes_emul.restype = ll
     return L
-
-
-def build_sanitized_program(out_dir):
-    """the emulation with its stand-alone main under AddressSanitizer and UndefinedBehaviorSanitizer -> the program's path"""
-    exe = os.path.join(str(out_dir), "levels_emul_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DLEVELS_EMUL_MAIN"] +
-                          EMUL_FLAGS + ["-o", exe, EMUL_SRC])
-    return exe
 
 
 def dst_layout(src, aligned, fill=GUARD, n=None):

@@ -1,21 +1,17 @@
 """Orientation for the orient tests (ocvar_hip_orient / ocvar_hip_orient_records / ocvar_hip_orient_camera): the host build of
 opencv-ar_amd/csrc/orient_core.h (tests/emul/orient_emul.cpp), a numpy restatement of the table that shares no code with it
 (numpy's own rot90 / slicing / transpose for frames, float64 for coordinates and the camera), guarded frames
-(yuv_chain.pix_layout on overlay_chain.Frames) and the single-marker scenes of resize_chain.  Shared by tests/test_orient_cpu.py
+(frame_kit.pix_layout) and the single-marker scenes of resize_chain.  Shared by tests/test_orient_cpu.py
 and tests/test_gpu_orient.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import helpers as H
-import overlay_chain as OC
-from overlay_chain import BPP, FORMATS, GUARD, LEAD, MARKER_DTYPE  # noqa: F401
+from frame_kit import FORMATS, GUARD, MARKER_DTYPE, pix_layout
+from hostbuild import host_core
 from resize_chain import chain_scenes, chain_templates, CHAIN_FULL  # noqa: F401
-from yuv_chain import pix_layout  # noqa: F401
 
-FMTS = ["bgr", "rgb", "bgra", "rgba", "gray"]
 ORIENTS = {"identity": 0, "rot90": 1, "rot180": 2, "rot270": 3, "flip_h": 4, "flip_v": 5, "transpose": 6, "transverse": 7}
 NAMES = list(ORIENTS)
 FMT_NAMES = {v: k for k, v in FORMATS.items()}
@@ -26,7 +22,6 @@ INVERSE = {0: 0, 1: 3, 2: 2, 3: 1, 4: 4, 5: 5, 6: 6, 7: 7}
 CLASS = {0: "rows kept", 5: "rows kept", 4: "rows reversed", 2: "rows reversed", 1: "transposing", 3: "transposing", 6: "transposing",
          7: "transposing"}
 ORIENT_POSE = 1
-E_ARG = -2
 # orient.hip: a lane of the row kernels owns ORIENT_LANE_PX = 8 destination pixels, a wave 512; the transposing kernel moves tiles
 # of ORIENT_TILE = 64 pixels a side, a lane assembling ORIENT_TILE_RUN = 4 destination pixels
 LANE_PX, WAVE_PX, TILE, TILE_RUN = 8, 512, 64, 4
@@ -36,29 +31,17 @@ SIDES = sorted({1, 2, 3, 7, 8, 9, 63, 64, 65, 129, TILE_RUN - 1, TILE_RUN, TILE_
                 2 * TILE + 1, ROW_GROUP - 1, ROW_GROUP, ROW_GROUP + 1})
 # widths that put both sides of a wave's span of the row kernels, and a second workgroup, into a row
 WIDE = [WAVE_PX - 1, WAVE_PX, WAVE_PX + 1]
-EMUL_SRC = os.path.join(H.ROOT, "tests", "emul", "orient_emul.cpp")
-EMUL_FLAGS = ["-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + OC.CSRC, "-I" + os.path.join(H.ROOT, "include")]
 NAN_BITS = 0x7FC00000
 
 
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "liborient_emul.so")
-    subprocess.check_call(["g++", "-O2"] + EMUL_FLAGS + ["-shared", "-o", so, EMUL_SRC])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("orient_emul")
     vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
     L.orient_emul.argtypes = [vp, i, i, ll, ll, vp, ll, ll, i, i, i]
     L.orient_source_index_emul.argtypes = [i, i, i, i, i, vp]
     L.orient_records_emul.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp]
     L.orient_camera_emul.argtypes = [vp, i, vp]
     return L
-
-
-def build_sanitized_program(out_dir):
-    """the emulation with its stand-alone main under AddressSanitizer and UndefinedBehaviorSanitizer -> the program's path"""
-    exe = os.path.join(str(out_dir), "orient_emul_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DORIENT_EMUL_MAIN"] +
-                          EMUL_FLAGS + ["-o", exe, EMUL_SRC])
-    return exe
 
 
 def code(o):

@@ -1,29 +1,23 @@
 """Patches for the patch tests (ocvar_hip_patches / ocvar_hip_patches_records): the host build of
 opencv-ar_amd/csrc/patch_core.h (tests/emul/patch_emul.cpp), guarded patch buffers, the random quads of the oracle parity test
 and the oracle chain (orc_get_perspective_transform + orc_warp_perspective_gray per channel plane).  Frames, records and guard
-bytes are overlay_chain's.  Shared by tests/test_patches_cpu.py and tests/test_gpu_patches.py."""
+bytes are frame_kit's.  Shared by tests/test_patches_cpu.py and tests/test_gpu_patches.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import helpers as H
-import overlay_chain as OC
+from frame_kit import GUARD, LEAD
 from helpers import P
-from overlay_chain import BPP, FORMATS, GUARD, LEAD, MARKER_DTYPE, Frames, axis_square, records  # noqa: F401
+from hostbuild import host_core
 
 MAX_PATCH_SIDE, FLIP_ROWS, MATCHED_ONLY = 256, 1, 2
 STATUS_FILL = -7   # what a status array holds before a call: every entry must be written
 SIZES = [(2, 2), (3, 5), (16, 16), (63, 17), (64, 64), (65, 33), (256, 2), (256, 256)]   # (patch_w, patch_h)
 
 
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "libpatch_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + OC.CSRC,
-                           "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(H.ROOT, "tests", "emul", "patch_emul.cpp")])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("patch_emul")
     L.patch_extract_frame_emul.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                            C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.patch_map32_emul.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]

@@ -2,23 +2,16 @@
 host build of opencv-ar_amd/csrc/refine_core.h (tests/emul/refine_emul.cpp) on every output square, and the oracle's pose of the
 refined square.  Shared by tests/test_corner_refine_cpu.py and tests/test_gpu_corner_refine.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import helpers as H
 from helpers import P
+from hostbuild import host_core
 
-CSRC = os.path.join(H.PKG, "csrc")
 
-
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "librefine_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + CSRC,
-                           "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(H.ROOT, "tests", "emul", "refine_emul.cpp")])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("refine_emul")
     L.refine_weights.argtypes = [C.c_int, C.c_void_p]
     L.refine_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]
     L.refine_points.restype = None

@@ -1,37 +1,28 @@
 """Resizing for the resize tests (ocvar_hip_resize / ocvar_hip_scale_records): the host build of
 opencv-ar_amd/csrc/resize_core.h (tests/emul/resize_emul.cpp), a numpy restatement of the rules that shares no code with it,
-guarded frames (yuv_chain.pix_layout on overlay_chain.Frames), and the single-marker scenes of the 4K-in, 1080p-detect chain at
+guarded frames (frame_kit.pix_layout), and the single-marker scenes of the 4K-in, 1080p-detect chain at
 a quarter of that size.  Shared by tests/test_resize_cpu.py and tests/test_gpu_resize.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import helpers as H
-import overlay_chain as OC
 import persp_synth as PS
-from overlay_chain import BPP, FORMATS, GUARD, LEAD, MARKER_DTYPE  # noqa: F401
-from yuv_chain import pix_layout  # noqa: F401
+from frame_kit import FORMATS
+from hostbuild import host_core
 
-FMTS = ["bgr", "rgb", "bgra", "rgba", "gray"]
 INTERPS = {"nearest": 0, "linear": 1, "area": 2}
 MAX_RATIO = 16
-E_ARG = -2
 KIND_NEAREST, KIND_LINEAR, KIND_BOX, KIND_TABLE = 0, 1, 2, 3
 # resize.hip: RESIZE_LANE_PX = 8 destination pixels per lane, 64 lanes per workgroup
 LANE_PX, WAVE_PX = 8, 512
 # destination widths: 1, 2, a lane's run, run + 1, both sides of a wave's span (513 starts a second workgroup), a third workgroup
 DST_WIDTHS = [1, 2, LANE_PX, LANE_PX + 1, WAVE_PX - 1, WAVE_PX, WAVE_PX + 1, 2 * WAVE_PX + 1]
 DST_HEIGHTS = [1, 2, 5]
-EMUL_SRC = os.path.join(H.ROOT, "tests", "emul", "resize_emul.cpp")
-EMUL_FLAGS = ["-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + OC.CSRC, "-I" + os.path.join(H.ROOT, "include")]
 
 
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "libresize_emul.so")
-    subprocess.check_call(["g++", "-O2"] + EMUL_FLAGS + ["-shared", "-o", so, EMUL_SRC])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("resize_emul")
     vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
     L.resize_emul.argtypes = [vp, i, i, ll, ll, vp, i, i, ll, ll, i, i, i]
     L.resize_plan_emul.argtypes = [i, i, i, i, i, vp]
@@ -40,14 +31,6 @@ def build_emul(out_dir):
     L.resize_coords_emul.argtypes = [vp, i, i, i, vp]
     L.scale_records_emul.argtypes = [vp, vp, i, i, i, i, i, i, i, vp, vp]
     return L
-
-
-def build_sanitized_program(out_dir):
-    """the emulation with its stand-alone main under AddressSanitizer and UndefinedBehaviorSanitizer -> the program's path"""
-    exe = os.path.join(str(out_dir), "resize_emul_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DRESIZE_EMUL_MAIN"] +
-                          EMUL_FLAGS + ["-o", exe, EMUL_SRC])
-    return exe
 
 
 def code(table, v):

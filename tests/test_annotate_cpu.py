@@ -6,24 +6,25 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import annotate_chain as AC
+import frame_kit as FK
 import helpers as H
 import overlay_chain as OC
 import persp_synth as PS
+from hostbuild import run_sanitized
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return AC.build_emul(tmp_path_factory.mktemp("annotate_emul"))
+def L():
+    return AC.build_emul()
 
 
 def one_frame(L, W, Hh, fmt, recs, st, cam=None, fill=0, row_pad=0, count=None):
-    fr = AC.Frames(1, W, Hh, fmt, row_pad=row_pad, fill=fill)
+    fr = FK.Frames(1, W, Hh, fmt, row_pad=row_pad, fill=fill)
     recs = np.asarray(recs).reshape(1, -1)
     out, drawn = AC.host_annotate(L, fr, recs, [recs.shape[1] if count is None else count], st, cam)
     return fr, out, drawn[0]
@@ -31,7 +32,7 @@ def one_frame(L, W, Hh, fmt, recs, st, cam=None, fill=0, row_pad=0, count=None):
 
 def segment_record(a, b):
     """a record whose outline is the stroke of the one segment a -- b: corners a, b, b, a (the edges b -- b and a -- a are its caps)"""
-    return OC.records([[a[0], a[1], b[0], b[1], b[0], b[1], a[0], a[1]]])
+    return FK.records([[a[0], a[1], b[0], b[1], b[0], b[1], a[0], a[1]]])
 
 
 # ---- coverage -----------------------------------------------------------------------------------------------------------------
@@ -78,7 +79,7 @@ def test_a_stroke_is_the_pixels_within_half_the_thickness_of_its_segment(L, name
 def test_the_corner_dot_is_a_disc_of_diameter_two_thickness_plus_one(L):
     for t, c in [(1, (20.0, 15.0)), (3, (20.3, 15.6)), (16, (33.0, 24.0))]:
         st = AC.style(L, AC.CORNER0, thickness=t, corner0=(255, 255, 255, 255))
-        fr, out, _ = one_frame(L, W0, H0, "gray", OC.records([[c[0], c[1], 50, 10, 50, 40, 10, 40]]), st)
+        fr, out, _ = one_frame(L, W0, H0, "gray", FK.records([[c[0], c[1], 50, 10, 50, 40, 10, 40]]), st)
         mask = fr.view(0, out)[..., 0] == 255
         d = AC.np_distance(W0, H0, np.float32(c).astype(np.float64), np.float32(c).astype(np.float64))
         r = (2 * t + 1) / 2
@@ -88,7 +89,7 @@ def test_the_corner_dot_is_a_disc_of_diameter_two_thickness_plus_one(L):
 def test_end_points_round_to_sixteenths_and_clamp(L):
     st = AC.style(L, AC.OUTLINE | AC.CORNER0, thickness=2)
     big = 3.0e7
-    ok, rec, box = AC.host_setup(L, OC.records([[10.03, 7.97, big, 5, -big, big, 3.0e38, -3.0e38]])[0], st, 640, 480)
+    ok, rec, box = AC.host_setup(L, FK.records([[10.03, 7.97, big, 5, -big, big, 3.0e38, -3.0e38]])[0], st, 640, 480)
     assert ok
     lim = 16 * AC.MAX_COORD
     assert rec["seg"][0]["a"].tolist() == [160, 128] and rec["seg"][0]["b"].tolist() == [lim, 80]
@@ -125,7 +126,7 @@ def test_joints_and_crossings_of_half_transparent_strokes_blend_once(L):
 
 
 def test_later_records_are_drawn_over_earlier_ones(L):
-    a = OC.records([OC.axis_square(10, 10, 30, 30), OC.axis_square(25, 10, 30, 30)], [3, 4])
+    a = FK.records([FK.axis_square(10, 10, 30, 30), FK.axis_square(25, 10, 30, 30)], [3, 4])
     st = AC.style(L, AC.OUTLINE | AC.COLOR_BY_TEMPLATE, thickness=3)
     pal = [L.annotate_palette_emul(t) for t in (3, 4)]
     assert pal[0] != pal[1]
@@ -143,15 +144,15 @@ def test_later_records_are_drawn_over_earlier_ones(L):
     assert px(out3, 32, 10) == OC.blend(rgb(pal[1]), 100, first).tolist()
 
 
-@pytest.mark.parametrize("fmt", AC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 def test_bytes_that_are_never_written(L, fmt):
     W, Hh = 70, 37
-    recs = OC.records([OC.axis_square(-4, -3, 40, 30), [60.5, 5, 75, 20, 66, 41, 50, 30]], [12, 345])
+    recs = FK.records([FK.axis_square(-4, -3, 40, 30), [60.5, 5, 75, 20, 66, 41, 50, 30]], [12, 345])
     st = AC.style(L, AC.OUTLINE | AC.CORNER0 | AC.LABEL, thickness=2, outline=(10, 200, 90, 255), label=(1, 2, 3, 77))
-    fr = AC.Frames(1, W, Hh, fmt, row_pad=5, seed=9)
+    fr = FK.Frames(1, W, Hh, fmt, row_pad=5, seed=9)
     out, drawn = AC.host_annotate(L, fr, recs[None], [2], st)
     assert drawn == [2] and (out != fr.buf).any()
-    assert (out[~fr.pixel_mask()] == AC.GUARD).all()            # row padding and the bytes around the frame
+    assert (out[~fr.pixel_mask()] == FK.GUARD).all()            # row padding and the bytes around the frame
     if fr.bpp == 4:
         assert (fr.view(0, out)[..., 3] == fr.view(0)[..., 3]).all()   # byte 3
     # alpha 0 touches nothing
@@ -163,9 +164,9 @@ def test_bytes_that_are_never_written(L, fmt):
 def test_byte_order_and_grey(L):
     colour = (201, 102, 53, 255)
     st = AC.style(L, AC.OUTLINE, thickness=1, outline=colour)
-    rec = OC.records([OC.axis_square(4, 4, 20, 10)])
+    rec = FK.records([FK.axis_square(4, 4, 20, 10)])
     got = {}
-    for fmt in AC.FMTS:
+    for fmt in FK.FMTS:
         fr, out, _ = one_frame(L, 32, 20, fmt, rec, st, fill=7)
         got[fmt] = fr.view(0, out)[4, 10].tolist()
     assert got["rgb"] == [201, 102, 53] and got["bgr"] == [53, 102, 201]
@@ -179,7 +180,7 @@ def test_byte_order_and_grey(L):
 
 def test_a_last_primitive_with_alpha_zero_leaves_the_pixel_alone(L):
     """the pixel takes the colour of the LAST primitive that covers it -- also when that colour is transparent"""
-    rec = OC.records([OC.axis_square(10, 10, 20, 20)], [8])
+    rec = FK.records([FK.axis_square(10, 10, 20, 20)], [8])
     st = AC.style(L, AC.OUTLINE | AC.CORNER0, thickness=3, outline=(255, 255, 255, 255), corner0=(9, 9, 9, 0))
     fr, out, _ = one_frame(L, 48, 40, "gray", rec, st)
     img = fr.view(0, out)[..., 0]
@@ -189,8 +190,8 @@ def test_a_last_primitive_with_alpha_zero_leaves_the_pixel_alone(L):
 # ---- which records draw -----------------------------------------------------------------------------------------------------------
 
 def test_counts_and_strides(L):
-    sq = [OC.axis_square(4 + 12 * k, 5, 9, 9) for k in range(4)]
-    recs = OC.records(sq)
+    sq = [FK.axis_square(4 + 12 * k, 5, 9, 9) for k in range(4)]
+    recs = FK.records(sq)
     st = AC.style(L, AC.OUTLINE)
     for count, want in [(0, 0), (1, 1), (3, 3), (4, 4), (5, 4), (10 ** 6, 4), (-1, 0)]:
         _, _, drawn = one_frame(L, 64, 24, "gray", recs, st, count=count)
@@ -199,18 +200,18 @@ def test_counts_and_strides(L):
 
 def test_records_that_are_not_finite_or_not_matched(L):
     W, Hh = 64, 48
-    base = OC.axis_square(10, 10, 20, 20)
+    base = FK.axis_square(10, 10, 20, 20)
     st = AC.style(L, AC.OUTLINE | AC.CORNER0 | AC.LABEL)
     for bad in (np.nan, np.inf, -np.inf):
         for slot in range(8):
             sq = np.array(base, np.float32)
             sq[slot] = bad
-            _, out, drawn = one_frame(L, W, Hh, "gray", OC.records([sq]), st, fill=3)
-            assert drawn == 0 and (out[AC.LEAD:-AC.LEAD] == 3).all(), (bad, slot)
+            _, out, drawn = one_frame(L, W, Hh, "gray", FK.records([sq]), st, fill=3)
+            assert drawn == 0 and (out[FK.LEAD:-FK.LEAD] == 3).all(), (bad, slot)
     un = AC.style(L, AC.OUTLINE | AC.CORNER0 | AC.LABEL | AC.UNMATCHED, unmatched=(77, 77, 77, 255), corner0=(200, 200, 200, 255),
                   outline=(255, 255, 255, 255), label=(150, 150, 150, 255))
     for score, with_flag, without in [(1.0, True, True), (0.0, True, False), (-3.0, True, False), (np.nan, False, False)]:
-        rec = OC.records([base], [5], [score])
+        rec = FK.records([base], [5], [score])
         fr, out, drawn = one_frame(L, W, Hh, "gray", rec, un)
         assert drawn == int(with_flag), score
         _, _, drawn2 = one_frame(L, W, Hh, "gray", rec, st)
@@ -269,7 +270,7 @@ def test_a_bow_tie_is_its_four_edges(L):
     W, Hh = 64, 48
     c = np.array([[10, 8], [50, 40], [50, 8], [10, 40]], np.float64)
     st = AC.style(L, AC.OUTLINE, thickness=2, outline=(255, 255, 255, 255))
-    fr, out, drawn = one_frame(L, W, Hh, "gray", OC.records([c.reshape(8)]), st)
+    fr, out, drawn = one_frame(L, W, Hh, "gray", FK.records([c.reshape(8)]), st)
     mask = fr.view(0, out)[..., 0] == 255
     d = np.min([AC.np_distance(W, Hh, c[k], c[(k + 1) % 4]) for k in range(4)], axis=0)
     assert drawn == 1 and mask[d <= 0.9].all() and not mask[d >= 1.1].any()
@@ -278,9 +279,9 @@ def test_a_bow_tie_is_its_four_edges(L):
 
 def test_a_record_wholly_outside_draws_nothing(L):
     st = AC.style(L, AC.OUTLINE | AC.CORNER0 | AC.LABEL, thickness=16)
-    for sq in (OC.axis_square(-60, 5, 30, 30), OC.axis_square(90, 5, 30, 30), OC.axis_square(5, -70, 30, 30), OC.axis_square(5, 80, 30, 30)):
-        _, out, drawn = one_frame(L, 64, 48, "bgr", OC.records([sq]), st, fill=1)
-        assert drawn == 0 and (out[AC.LEAD:-AC.LEAD] == 1).all()
+    for sq in (FK.axis_square(-60, 5, 30, 30), FK.axis_square(90, 5, 30, 30), FK.axis_square(5, -70, 30, 30), FK.axis_square(5, 80, 30, 30)):
+        _, out, drawn = one_frame(L, 64, 48, "bgr", FK.records([sq]), st, fill=1)
+        assert drawn == 0 and (out[FK.LEAD:-FK.LEAD] == 1).all()
 
 
 # ---- pose primitives --------------------------------------------------------------------------------------------------------------
@@ -347,7 +348,7 @@ def test_the_cube_stands_on_the_side_the_z_axis_points_to(L):
 
 def label_mask(L, W, Hh, square, tid, scale, fmt="gray"):
     st = AC.style(L, AC.LABEL, label_scale=scale, label=(255, 255, 255, 255))
-    fr, out, drawn = one_frame(L, W, Hh, fmt, OC.records([square], [tid]), st)
+    fr, out, drawn = one_frame(L, W, Hh, fmt, FK.records([square], [tid]), st)
     return fr.view(0, out)[..., 0] == 255, drawn
 
 
@@ -356,7 +357,7 @@ def test_every_glyph_is_the_font_table(L):
         bits = L.annotate_glyph_emul(d)
         table = np.array([[(bits >> (5 * r + 4 - c)) & 1 for c in range(5)] for r in range(7)], bool)
         assert (table == AC.glyph(d)).all(), d
-        mask, drawn = label_mask(L, 32, 24, OC.axis_square(10, 8, 9, 9), d, 1)   # centre (14, 12): columns 12 .. 16, rows 9 .. 15
+        mask, drawn = label_mask(L, 32, 24, FK.axis_square(10, 8, 9, 9), d, 1)   # centre (14, 12): columns 12 .. 16, rows 9 .. 15
         want = np.zeros((24, 32), bool)
         want[9:16, 12:17] = AC.glyph(d)
         assert drawn == 1 and (mask == want).all(), d
@@ -383,10 +384,10 @@ def test_the_automatic_scale_follows_the_shorter_side_and_clamps(L):
     st = AC.style(L, AC.LABEL, label_scale=0)
     for side, want in [(5, 1), (23.9, 1), (47.9, 1), (48, 2), (71.9, 2), (72, 3), (191.9, 7), (192, 8), (1000, 8)]:
         sq = [100, 100, 100 + 4 * side, 100, 100 + 4 * side, 100 + side, 100, 100 + side]
-        ok, s, _ = AC.host_setup(L, OC.records([sq], [42])[0], st, 4000, 1400)
+        ok, s, _ = AC.host_setup(L, FK.records([sq], [42])[0], st, 4000, 1400)
         assert ok and s["scale"] == want and s["n"] == 2 and s["digit"][:2].tolist() == [4, 2], (side, s["scale"])
     # a negative template id has no label
-    ok, s, _ = AC.host_setup(L, OC.records([OC.axis_square(10, 10, 50, 50)], [-1])[0], st, 100, 100)
+    ok, s, _ = AC.host_setup(L, FK.records([FK.axis_square(10, 10, 50, 50)], [-1])[0], st, 100, 100)
     assert not ok and s["n"] == 0
 
 
@@ -428,14 +429,11 @@ def test_the_style_validator(L):
 
 # ---- sanitizers -------------------------------------------------------------------------------------------------------------------
 
-def test_stand_alone_program_under_the_sanitizers(tmp_path):
+def test_stand_alone_program_under_the_sanitizers():
     """tests/emul/annotate_emul.cpp with its own main, built with -fsanitize=address,undefined and run as a program: frames 1x1, 3x2,
     257x17 and 70x37 in every format on heap blocks of exactly their size, records at, on and beyond every edge, thickness 16 at a
     corner, coordinates at and beyond the clamp range"""
-    exe = AC.build_sanitized_program(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert "bytes changed" in r.stdout and "runtime error" not in r.stderr
+    run_sanitized("annotate_emul", "ANNOTATE_EMUL_MAIN", "bytes changed", timeout=600)
 
 
 # ---- ABI --------------------------------------------------------------------------------------------------------------------------
@@ -455,7 +453,7 @@ def test_abi_surface(L):
     assert re.search(r"OCVAR_ANNO_MAX_COORD = %d\b" % AC.MAX_COORD, header) and oa.ANNO_MAX_COORD == AC.MAX_COORD
     # the library's default style is the core's
     a, b = oa.AnnotateStyle(), AC.Style()
-    assert lib.ocvar_hip_annotate_default_style(C.byref(a)) == 0 and lib.ocvar_hip_annotate_default_style(None) == AC.E_ARG
+    assert lib.ocvar_hip_annotate_default_style(C.byref(a)) == 0 and lib.ocvar_hip_annotate_default_style(None) == FK.E_ARG
     L.annotate_default_style_emul(C.byref(b))
     assert bytes(a) == bytes(b)
     # sizeof(OcvarAnnotateStyle) as the built library has it: it writes exactly 56 bytes
@@ -473,5 +471,5 @@ def test_abi_surface(L):
                dict(outline_color=(1, 2, 3)), dict(outline_color=(1, 2, 3, 256)), dict(colour=1), dict(outline=False, corner0=False, label=False)]:
         with pytest.raises(ValueError):
             oa.annotate_style(**kw)
-    assert lib.ocvar_hip_annotate(None, None, 0, 0, 0, 0, 0, None, None) == AC.E_ARG
-    assert lib.ocvar_hip_annotate_records(None, None, 0, 0, 0, 0, 0, 0, None, None, 0, None, None) == AC.E_ARG
+    assert lib.ocvar_hip_annotate(None, None, 0, 0, 0, 0, 0, None, None) == FK.E_ARG
+    assert lib.ocvar_hip_annotate_records(None, None, 0, 0, 0, 0, 0, 0, None, None, 0, None, None) == FK.E_ARG

@@ -2,13 +2,12 @@
 tests/emul/plan_emul.cpp): the numbers api.hip allocates and launches by, and the kernels rely on -- binarise.hip on work units
 of whole tile rows that cover the plane, the followers on grids within their slabs."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import helpers as H
+from hostbuild import host_core
 
 KNOBS = ("crop_phases", "mid_steps", "mid_blocks", "long_blocks", "short_blocks", "min_units")   # PlanOverrides' order
 SIDES = (16, 17, 239, 240, 241, 255, 256, 257, 32767)
@@ -26,12 +25,8 @@ class PlanOut(C.Structure):
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("plan_emul") / "libplan_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
-                           "-DOCVAR_NBR_TILED", "-I" + os.path.join(H.PKG, "csrc"), "-I" + os.path.join(H.ROOT, "include"),
-                           "-shared", "-o", so, os.path.join(H.ROOT, "tests", "emul", "plan_emul.cpp")])
-    L = C.CDLL(so)
+def lib():
+    L = host_core("plan_emul")
     L.plan_emul.argtypes = [C.c_int] * 10 + [C.c_void_p, C.c_void_p, C.POINTER(PlanOut)]
     L.plan_emul.restype = None
     assert L.plan_emul_march_strip() == 240 and L.plan_emul_tile_rows() == 14

@@ -4,22 +4,23 @@ black level, gain and border case with guard bytes around every row and frame; w
 gives that colour, sampled channels come back unchanged, rectangles, the arithmetic's range); and the chain through the oracle.
 tests/test_gpu_bayer.py holds the kernels to this build byte for byte."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
 
 import bayer_chain as BC
+import frame_kit as FK
 import helpers as H
 import levels_chain as LC
 import overlay_chain as OC
+from hostbuild import run_sanitized
 
 PATS = list(BC.PATTERNS)
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return BC.build_emul(tmp_path_factory.mktemp("bayer_emul"))
+def L():
+    return BC.build_emul()
 
 
 def test_the_defaults_and_the_parameter_ranges(L):
@@ -37,9 +38,9 @@ def test_the_defaults_and_the_parameter_ranges(L):
     for kw, why in bad:
         q = BC.params(**kw)
         assert L.bayer_params_bad_emul(C.addressof(q)) == why, kw
-        src, dst = np.zeros(16, np.uint8), np.full(48, BC.GUARD, np.uint8)
+        src, dst = np.zeros(16, np.uint8), np.full(48, FK.GUARD, np.uint8)
         assert L.bayer_to_frames_emul(src.ctypes.data, 4, 16, dst.ctypes.data, 12, 48, 4, 4, 0, 1, C.addressof(q)) == why
-        assert (dst == BC.GUARD).all()   # (refused: nothing written)
+        assert (dst == FK.GUARD).all()   # (refused: nothing written)
 
 
 def test_the_patterns_are_named_by_their_top_left_block(L):
@@ -56,7 +57,7 @@ def test_the_patterns_are_named_by_their_top_left_block(L):
     assert [L.bayer_reflect_emul(i, 5) for i in (-1, 0, 4, 5)] == [1, 0, 4, 3] and [L.bayer_reflect_emul(i, 2) for i in (-1, 2)] == [1, 0]
 
 
-@pytest.mark.parametrize("fmt", BC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 @pytest.mark.parametrize("pattern", PATS)
 def test_host_core_is_the_numpy_restatement(L, pattern, fmt):
     """the four depths, five settings of black level and gains each (a gain of 0, the largest gain, black = the largest sample among
@@ -66,10 +67,10 @@ def test_host_core_is_the_numpy_restatement(L, pattern, fmt):
             p = BC.params(pattern, bits, black, gains)
             for W, Hh in BC.SIZES:
                 raw = BC.Raw(2, W, Hh, bits, aligned=False, seed=W * 7 + Hh + bits + k)
-                dst = BC.pix_layout(2, W, Hh, fmt, aligned=False, fill=BC.GUARD)
+                dst = FK.pix_layout(2, W, Hh, fmt, aligned=False, fill=FK.GUARD)
                 out = BC.host_demosaic(L, raw, dst, p)
                 where = (bits, black, gains, W, Hh)
-                assert (out[~dst.pixel_mask()] == BC.GUARD).all(), where
+                assert (out[~dst.pixel_mask()] == FK.GUARD).all(), where
                 for f in range(2):
                     want = BC.np_demosaic_params(raw.words(f), p, fmt)
                     assert (dst.view(f, out) == want).all(), where + (f,)
@@ -81,7 +82,7 @@ def test_host_core_is_the_numpy_restatement(L, pattern, fmt):
 
 def test_params_null_are_the_defaults(L):
     raw = BC.Raw(1, 9, 7, 8, aligned=True, seed=3)
-    dst = BC.pix_layout(1, 9, 7, "bgr", aligned=True, fill=BC.GUARD)
+    dst = FK.pix_layout(1, 9, 7, "bgr", aligned=True, fill=FK.GUARD)
     assert (BC.host_demosaic(L, raw, dst, None) == BC.host_demosaic(L, raw, dst, BC.params())).all()
 
 
@@ -163,8 +164,8 @@ def test_the_other_formats_follow_from_bgr(L, pattern):
             raw = BC.Raw(1, W, Hh, bits, aligned=True, seed=W + Hh)
             p = BC.params(pattern, bits, 2, (1100, 1024, 1400))
             out = {}
-            for fmt in BC.FMTS:
-                dst = BC.pix_layout(1, W, Hh, fmt, aligned=True, fill=BC.GUARD)
+            for fmt in FK.FMTS:
+                dst = FK.pix_layout(1, W, Hh, fmt, aligned=True, fill=FK.GUARD)
                 out[fmt] = dst.view(0, BC.host_demosaic(L, raw, dst, p)).astype(np.int64)
             b = out["bgr"]
             assert (out["gray"][..., 0] == OC.grey_of(b[..., 0], b[..., 1], b[..., 2])).all()
@@ -173,14 +174,11 @@ def test_the_other_formats_follow_from_bgr(L, pattern):
             assert (out["rgba"][..., :3] == b[..., ::-1]).all() and (out["rgba"][..., 3] == 255).all()
 
 
-def test_the_emulation_is_clean_under_the_sanitizers(tmp_path):
+def test_the_emulation_is_clean_under_the_sanitizers():
     """tests/emul/bayer_emul.cpp with its own main -- every pattern, format, size and depth on heap blocks of exactly the bytes a
     conversion may touch, the sequential reference and the lanes -- built with AddressSanitizer and UndefinedBehaviorSanitizer and run
     as a program of its own"""
-    exe = BC.build_sanitized_program(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "640 cases, 0 bad" in r.stdout and "runtime error" not in r.stderr
+    run_sanitized("bayer_emul", "BAYER_EMUL_MAIN", "640 cases, 0 bad", timeout=300)
 
 
 # ---- the chain on the oracle ----------------------------------------------------------------------------------------------------------

@@ -3,27 +3,16 @@ border followers read.  tests/emul/bitplane_emul.cpp is built twice -- with the 
 emulation's raster byte plane -- and both builds read the same random binary images: every pixel's mask through the
 readers, and every plausible border start through the run test, the look behind and the walks of trace_core.h."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import helpers as H
 from helpers import P
-
-SRC = os.path.join(H.ROOT, "tests", "emul", "bitplane_emul.cpp")
-DEPS = [SRC, os.path.join(H.ROOT, "tests", "emul", "plane_writer.h")] + [os.path.join(H.PKG, "csrc", f) for f in ("hd.h", "trace_core.h")]
+from hostbuild import host_core
 
 
 def _lib(tiled):
-    so = os.path.join(H.ROOT, "tests", "emul", "libbitplane_%s.so" % ("tiled" if tiled else "raster"))
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in DEPS):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
-                              + (["-DOCVAR_NBR_TILED"] if tiled else [])
-                              + ["-I" + os.path.join(H.PKG, "csrc"), "-I" + os.path.join(H.ROOT, "include"),
-                                 "-shared", "-o", so, SRC])
-    lib = C.CDLL(so)
+    lib = host_core("bitplane_emul", tiled=tiled)
     lib.bp_plane_bytes.restype = C.c_longlong
     lib.bp_check_readers.restype = C.c_longlong
     return lib

@@ -16,13 +16,13 @@ SET5 = (5, 30, 0.1)
 
 
 @pytest.fixture(scope="module")
-def Lb(tmp_path_factory):
-    return BC.build_emul(tmp_path_factory.mktemp("board_emul"))
+def Lb():
+    return BC.build_emul()
 
 
 @pytest.fixture(scope="module")
-def Lr(tmp_path_factory):
-    return RC.build_emul(tmp_path_factory.mktemp("refine_emul"))
+def Lr():
+    return RC.build_emul()
 
 
 def camera(dist=False):

@@ -12,8 +12,8 @@ import refine_chain as RC
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return RC.build_emul(tmp_path_factory.mktemp("refine_emul"))
+def L():
+    return RC.build_emul()
 
 
 def restated(gray, c0, w, max_iter, eps):

@@ -6,13 +6,12 @@ The rules the lists must restate are those follow_mid_kernel applied at hand-out
 entry of mid_crop when pos == crop_min_rest[roi]; phase 2 when pos != crop_min_rest[roi] and not
 (best_crop[roi] >> 32) < pos (unsigned).  They are written out again below, in numpy."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import helpers as H
+from hostbuild import host_core
 
 KNOBS = ("crop_phases", "mid_steps", "mid_blocks", "long_blocks", "short_blocks", "min_units")   # PlanOverrides' order
 NO_START = 0x7fffffff
@@ -20,12 +19,8 @@ NO_QUAD = 0xffffffffffffffff
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("croplist_emul") / "libcroplist_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
-                           "-DOCVAR_NBR_TILED", "-I" + os.path.join(H.PKG, "csrc"), "-I" + os.path.join(H.ROOT, "include"),
-                           "-shared", "-o", so, os.path.join(H.ROOT, "tests", "emul", "croplist_emul.cpp")])
-    L = C.CDLL(so)
+def lib():
+    L = host_core("croplist_emul")
     L.croplist_emul_split.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
     L.croplist_emul_prune.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.croplist_emul_plan.argtypes = [C.c_int] * 5 + [C.c_void_p] * 3

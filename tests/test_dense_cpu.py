@@ -4,24 +4,18 @@ they replace, and the new entry points' argument checks, which run before any de
 import ctypes as C
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import helpers as H
 from helpers import P
-
-CSRC = os.path.join(H.PKG, "csrc")
+from hostbuild import host_core
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("dense_emul") / "libdense_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + CSRC,
-                           "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(H.ROOT, "tests", "emul", "dense_emul.cpp")])
-    L = C.CDLL(so)
+def lib():
+    L = host_core("dense_emul")
     L.dense_track_literal.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.dense_track_sparse.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_void_p]

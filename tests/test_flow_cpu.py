@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import flow_chain as FC
+import frame_kit as FK
 import helpers as H
 import overlay_chain as OC
 
@@ -27,8 +28,8 @@ LOST = 2.0
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return FC.build_emul(tmp_path_factory.mktemp("flow_emul"))
+def L():
+    return FC.build_emul()
 
 
 @pytest.fixture(scope="module")
@@ -93,7 +94,7 @@ def test_pyramid_sizes_and_level_rule(L):
     pyr = FC.np_pyramid(img, 1, 5)
     assert [p.shape for p in pyr] == [(29, 37), (15, 19), (8, 10)]
     # the whole pyramid of a colour frame: level 0 is the library's grey
-    fr = OC.Frames(1, 37, 29, "rgba", row_pad=3, seed=3)
+    fr = FK.Frames(1, 37, 29, "rgba", row_pad=3, seed=3)
     buf = np.zeros(total, np.uint8)
     L.flow_build_pyramid_emul(fr.buf.ctypes.data + fr.offset(0), 37, 29, fr.row_stride, fr.fmt, 1, 5, FC.P(buf))
     want = FC.np_pyramid(FC.np_grey(fr.view(0), "rgba"), 1, 5)
@@ -109,9 +110,9 @@ def test_identical_frames_return_every_record_bit_for_bit(L):
     """I - J is exactly 0 at d = 0, so the first step is exactly 0: status 1, error 0.0, the record's bytes"""
     rng = np.random.default_rng(7)
     n, slots, W, Hh = 2, 5, 96, 64
-    fr = FC.fill_frames(OC.Frames(n, W, Hh, "bgr", row_pad=2), [FC.texture(rng, W, Hh) for _ in range(n)])
+    fr = FC.fill_frames(FK.Frames(n, W, Hh, "bgr", row_pad=2), [FC.texture(rng, W, Hh) for _ in range(n)])
     quad = np.array([20, 10, 60, 12, 58, 50, 18, 48], np.float64)   # convex, and stays so under a jitter of 3 px
-    recs = OC.records(quad + rng.uniform(-3, 3, (n * slots, 8)) + np.tile(rng.uniform(-8, 30, (n * slots, 1)), (1, 8)) * ([1, 0] * 4)).reshape(n, slots)
+    recs = FK.records(quad + rng.uniform(-3, 3, (n * slots, 8)) + np.tile(rng.uniform(-8, 30, (n * slots, 1)), (1, 8)) * ([1, 0] * 4)).reshape(n, slots)
     recs["glMatrix"] = rng.normal(size=(n, slots, 16))
     for p in (FC.params(), FC.params(half_win=3, levels=0), FC.params(fb_max=0.5, max_err=0.5)):
         out, status, err = FC.host_flow(L, fr, fr, recs, [slots, 3], p)
@@ -228,16 +229,16 @@ def test_record_rules(L, scene):
     """the lowest failing corner wins, a folded quad is -6, failed records are copied unchanged, slots beyond the count keep
     their guard bytes"""
     s, W, Hh = scene, scene["W"], scene["H"]
-    fa = FC.fill_frames(OC.Frames(1, W, Hh, "gray"), [s["A"]])
-    fb = FC.fill_frames(OC.Frames(1, W, Hh, "gray"), [s["B"]])
+    fa = FC.fill_frames(FK.Frames(1, W, Hh, "gray"), [s["A"]])
+    fb = FC.fill_frames(FK.Frames(1, W, Hh, "gray"), [s["B"]])
     recs = FC.code_records(W)
-    guard = np.frombuffer(np.full(recs.nbytes, OC.GUARD, np.uint8).tobytes(), OC.MARKER_DTYPE).reshape(1, 6).copy()
+    guard = np.frombuffer(np.full(recs.nbytes, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(1, 6).copy()
     p = FC.params(half_win=5, levels=2)
     out, status, err = FC.host_flow(L, fa, fb, recs, [5], p, out=guard)
     assert status[0].tolist() == [1, -1, -2, -6, -6, 0], status
     assert out[0, 1:5].tobytes() == recs[0, 1:5].tobytes()             # failed: copied unchanged
     assert out[0, 5].tobytes() == guard[0, 5].tobytes()                 # not live: untouched
-    assert err[0, 5].tobytes() == bytes([OC.GUARD]) * 16
+    assert err[0, 5].tobytes() == bytes([FK.GUARD]) * 16
     assert np.abs(out["square"][0, 0] - (np.array(GOOD) + [3, 2] * 4)).max() < 0.05
     for name in ("glMatrix", "templateId", "markerId", "score", "aspectRatio"):
         assert out[name][0, 0].tobytes() == recs[name][0, 0].tobytes()

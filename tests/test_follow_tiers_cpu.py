@@ -15,27 +15,20 @@ Tier 3 and trace_border both count the pixel moves made, less the closing move. 
 the border closes inside a run, the move that entered the run (the loop's own, counted at the loop's end, which the closing
 `break` skips) is missing as well: one less.  trace_border reports no count for a walk that does not close, so nothing is
 asserted about tier 3's there."""
-import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import helpers as H
 from border_shapes import sawtooth_frame
 from helpers import P
+from hostbuild import host_core
 
 OK, NOT_FIRST, SINGLE, OVERRUN = 0, 1, 2, 3   # trace_core.h: TraceStatus
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("follow_emul") / "libfollow_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
-                           "-Wno-unknown-pragmas", "-DOCVAR_NBR_TILED", "-I" + os.path.join(H.PKG, "csrc"), "-I" + os.path.join(H.ROOT, "include"),
-                           "-shared", "-o", so, os.path.join(H.ROOT, "tests", "emul", "follow_emul.cpp")])
-    L = C.CDLL(so)
+def lib():
+    L = host_core("follow_emul")
     assert L.fe_row_ints() == 24
     return L
 

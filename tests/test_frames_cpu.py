@@ -5,11 +5,11 @@ import ctypes as C
 import itertools
 import os
 import re
-import subprocess
 
 import pytest
 
 import helpers as H
+from hostbuild import host_core
 
 OK, FORMAT, SIDE, COUNT, ROW_STRIDE, SPAN = range(6)     # frames_core.h: FramesBad
 MAX_SPAN = 2147483647
@@ -28,11 +28,8 @@ def block(width, height, bpp, row_stride, frame_stride=0, n_frames=1, p=BASE):
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("frames_emul") / "libframes_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-Wall", "-I" + os.path.join(H.PKG, "csrc"), "-shared", "-o", so,
-                           os.path.join(H.ROOT, "tests", "emul", "frames_emul.cpp")])
-    L = C.CDLL(so)
+def lib():
+    L = host_core("frames_emul")
     B = C.POINTER(Block)
     for name, res, args in (("bpp", C.c_int, [C.c_int]), ("row_span", C.c_longlong, [B]), ("extent", C.c_ulonglong, [B]),
                             ("intersect", C.c_int, [B, B]), ("check", C.c_int, [B, C.c_int, C.c_int]),

@@ -5,17 +5,14 @@ __umul24 / __mul24 and require them to be exact for every operand pair the call 
 
 The GPU side of the same limits is tests/test_gpu_geometry_limits.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import helpers as H
 from helpers import P
+from hostbuild import host_core
 
-SRC = os.path.join(H.ROOT, "tests", "emul", "geometry_emul.cpp")
-DEPS = [SRC] + [os.path.join(H.PKG, "csrc", f) for f in ("hd.h", "trace_core.h")]
 MAX_SIDE = 32767                          # api.hip::create_impl
 NS_MAX = ((MAX_SIDE & ~1) + 15) & ~15     # 32768 columns of the bit plane
 SH_MAX = MAX_SIDE & ~1                    # 32766 rows
@@ -24,12 +21,7 @@ INT_MAX = 2**31 - 1
 
 @pytest.fixture(scope="module")
 def G():
-    so = os.path.join(H.ROOT, "tests", "emul", "libgeometry_emul.so")
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in DEPS):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
-                               "-DOCVAR_NBR_TILED", "-I" + os.path.join(H.PKG, "csrc"), "-I" + os.path.join(H.ROOT, "include"),
-                               "-shared", "-o", so, SRC])
-    L = C.CDLL(so)
+    L = host_core("geometry_emul")
     L.geo_div14.restype = C.c_uint
     L.geo_div14.argtypes = [C.c_uint]
     L.geo_div14_range.argtypes = [C.c_uint, C.c_uint, C.c_void_p]

@@ -7,32 +7,23 @@ import numpy as np
 import pytest
 
 import annotate_chain as AC
+import frame_kit as FK
 import helpers as H
 import overlay_chain as OC
 import persp_synth as PS
-from yuv_chain import Pix
+from frame_kit import E_ARG, oa, same, to_device  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-E_ARG = AC.E_ARG
+
+@pytest.fixture(scope="module")
+def L():
+    return AC.build_emul()
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return AC.build_emul(tmp_path_factory.mktemp("annotate_emul"))
-
-
-@pytest.fixture(scope="module")
-def LO(tmp_path_factory):
-    return OC.build_emul(tmp_path_factory.mktemp("overlay_emul"))
+def LO():
+    return OC.build_emul()
 
 
 @pytest.fixture(scope="module")
@@ -48,19 +39,14 @@ def cam_of(W, Hh, lens):
     return PS.camera(W, Hh, lens=lens)
 
 
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to("cuda:0")
-
-
 def layout(n, W, Hh, fmt, aligned, seed=0):
     """guarded frames: aligned -- address and both strides multiples of 4; else the address is odd and so is the row stride"""
-    bpp = AC.BPP[AC.FORMATS[fmt]]
+    bpp = FK.BPP[FK.FORMATS[fmt]]
     if aligned:
-        p = Pix(n, W, Hh, fmt, row_pad=4 + (-W * bpp) % 4, frame_gap=8, lead=AC.LEAD, seed=seed)
+        p = FK.Frames(n, W, Hh, fmt, row_pad=4 + (-W * bpp) % 4, frame_gap=8, lead=FK.LEAD, seed=seed)
         assert p.row_stride % 4 == 0 and p.frame_stride % 4 == 0 and p.offset(0) % 4 == 0
     else:
-        p = Pix(n, W, Hh, fmt, row_pad=1 + (W * bpp) % 2, frame_gap=5, lead=AC.LEAD + 1, seed=seed)
+        p = FK.Frames(n, W, Hh, fmt, row_pad=1 + (W * bpp) % 2, frame_gap=5, lead=FK.LEAD + 1, seed=seed)
         assert p.row_stride % 2 == 1 and p.offset(0) % 2 == 1
     return p
 
@@ -77,23 +63,17 @@ def device_annotate_records(det, fr, recs, counts, per_frame, st, stream=None):
     return d.cpu().numpy()
 
 
-def same(got, want, fr, where):
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, "%s: %d bytes differ (%d of them guard bytes), first at %d: %d != %d" % (
-        where, bad.size, int((~fr.pixel_mask()[bad]).sum()), bad[0], got[bad[0]], want[bad[0]])
-
-
 def placed_records(W, Hh, cam, slots=8):
     """[2, slots] posed records of a W x Hh frame and their counts: on the corners of the kernel's tiles (256 columns, 16 rows, a
     wave's 4 rows), on the frame's edges, partly and wholly outside, a bow-tie, an unmatched one; frame 1 holds one record"""
     places = [(min(AC.TILE_W, W - 1), min(AC.TILE_H, Hh - 1), 22, 30, 20), (0.0, 0.0, 18, 0, 70), (W - 1.0, Hh - 1.0, 30, 55, 200),
               (W * 0.5, AC.WAVE_ROWS - 0.5, 12, 40, 100), (W + 6.0, Hh * 0.4, 26, 20, 300), (-60.0, -60.0, 16, 0, 0)]
-    recs = np.zeros((2, slots), AC.MARKER_DTYPE)
+    recs = np.zeros((2, slots), FK.MARKER_DTYPE)
     for k, (u, v, size, tilt, gamma) in enumerate(places):
         R, t = PS.pose(cam, u, v, size, tilt, gamma, 30 + 50 * k)
         recs[0, k] = AC.posed_record(cam, R, t, template_id=[0, 7, 10, 4095, 123, 5][k], ratio=1.0 if k != 2 else 1.4)
-    recs[0, 6] = OC.records([[W * 0.2, Hh * 0.2, W * 0.6, Hh * 0.9, W * 0.6, Hh * 0.2, W * 0.2, Hh * 0.9]], [31])[0]
-    recs[0, 7] = OC.records([OC.axis_square(W // 3, Hh // 3, 9, 7)], [2], [0.0])[0]
+    recs[0, 6] = FK.records([[W * 0.2, Hh * 0.2, W * 0.6, Hh * 0.9, W * 0.6, Hh * 0.2, W * 0.2, Hh * 0.9]], [31])[0]
+    recs[0, 7] = FK.records([FK.axis_square(W // 3, Hh // 3, 9, 7)], [2], [0.0])[0]
     R, t = PS.pose(cam, W * 0.5, Hh * 0.5, min(W, Hh) * 0.6, 35, 45, 10)
     recs[1, 0] = AC.posed_record(cam, R, t, template_id=88)
     return recs, [8, 1]
@@ -107,7 +87,7 @@ def full_style(L, **kw):
 
 
 @pytest.mark.parametrize("aligned", [True, False])
-@pytest.mark.parametrize("fmt", AC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 @pytest.mark.parametrize("size", [(70, 37), (257, 17), (300, 33)])
 def test_every_format_and_layout(oa, L, det320, size, fmt, aligned):
     W, Hh = size
@@ -117,7 +97,7 @@ def test_every_format_and_layout(oa, L, det320, size, fmt, aligned):
     st = full_style(L)
     want, drawn = AC.host_annotate(L, fr, recs, counts, st, cam)
     assert drawn == [7, 1], drawn     # (the one wholly outside draws nothing)
-    assert (want != fr.buf).any() and (want[~fr.pixel_mask()] == AC.GUARD).all()
+    assert (want != fr.buf).any() and (want[~fr.pixel_mask()] == FK.GUARD).all()
     got = device_annotate_records(det320, fr, recs, counts, 8, st)
     same(got, want, fr, "%dx%d %s %s" % (W, Hh, fmt, "aligned" if aligned else "unaligned"))
 
@@ -125,7 +105,7 @@ def test_every_format_and_layout(oa, L, det320, size, fmt, aligned):
 def scattered(rng, n, W, Hh, lo, hi, cam, n_tids=4096):
     """n posed records of lo .. hi px, turned and tilted at random, all over (and over the edges of) a W x Hh frame; every fifth
     one unmatched"""
-    recs = np.zeros(n, AC.MARKER_DTYPE)
+    recs = np.zeros(n, FK.MARKER_DTYPE)
     for k in range(n):
         R, t = PS.pose(cam, rng.uniform(-5, W + 5), rng.uniform(-5, Hh + 5), rng.uniform(lo, hi), rng.uniform(0, 60), rng.uniform(0, 360), rng.uniform(0, 360))
         recs[k] = AC.posed_record(cam, R, t, template_id=int(rng.integers(0, n_tids)), score=0.0 if k % 5 == 4 else 1.0)
@@ -137,7 +117,7 @@ def test_record_strides_and_counts(L, det320, stride):
     """counts 0, 1, the stride and above it, at strides on both sides of the 64 slots one ballot takes"""
     rng = np.random.default_rng(50 + stride)
     cam = cam_of(320, 240, True)
-    fr = AC.Frames(4, 200, 120, "bgr", seed=stride)
+    fr = FK.Frames(4, 200, 120, "bgr", seed=stride)
     recs = np.stack([scattered(rng, stride, 200, 120, 8, 40, cam) for _ in range(4)])
     st = full_style(L, thickness=1)
     given = [0, 1, stride, stride + 7]
@@ -150,11 +130,11 @@ def test_record_strides_and_counts(L, det320, stride):
 
 def test_overlapping_records_keep_their_order(L, det320):
     cam = cam_of(320, 240, True)
-    sq = [OC.axis_square(20 + 9 * k, 15 + 4 * k, 60, 50) for k in range(6)]
-    recs = OC.records(sq, [0, 1, 2, 3, 4, 5])[None]
+    sq = [FK.axis_square(20 + 9 * k, 15 + 4 * k, 60, 50) for k in range(6)]
+    recs = FK.records(sq, [0, 1, 2, 3, 4, 5])[None]
     st = AC.style(L, AC.OUTLINE | AC.CORNER0 | AC.LABEL | AC.COLOR_BY_TEMPLATE, thickness=5, outline=(0, 0, 0, 150), label_scale=3,
                   label=(255, 255, 255, 140), corner0=(200, 0, 100, 99))
-    fr = AC.Frames(1, 160, 100, "rgba", seed=3)
+    fr = FK.Frames(1, 160, 100, "rgba", seed=3)
     want, _ = AC.host_annotate(L, fr, recs, [6], st, cam)
     backwards, _ = AC.host_annotate(L, fr, recs[:, ::-1].copy(), [6], st, cam)
     assert (want != backwards).any()     # the order shows
@@ -186,7 +166,7 @@ def test_more_frames_than_the_context_holds_go_in_chunks(oa, L):
     cam = cam_of(64, 48, False)
     det.set_camera(oa.Camera.from_buffer_copy(bytes(cam)))
     rng = np.random.default_rng(70)
-    fr = AC.Frames(5, 64, 48, "rgb", row_pad=4, seed=70)
+    fr = FK.Frames(5, 64, 48, "rgb", row_pad=4, seed=70)
     recs = np.stack([scattered(rng, 64, 64, 48, 8, 30, cam) for _ in range(5)])
     counts = [3, 0, 64, 7, 1]
     st = full_style(L)
@@ -226,7 +206,7 @@ COLOUR = np.array([250, 10, 200, 180], np.uint8)   # R G B A
 def batch():
     """four 320 x 240 views of one marker each"""
     scenes = [PS.scene("annotate", "g%d" % g, 320, 240, [(150 + 5 * k, 120, 90, 15 * k, g, 40, TPL, None)]) for k, g in enumerate((10, 100, 190, 280))]
-    fr = AC.Frames(4, 320, 240, "bgr")
+    fr = FK.Frames(4, 320, 240, "bgr")
     for f, s in enumerate(scenes):
         fr.view(f)[...] = s.frame
     return dict(scenes=scenes, fr=fr, cam=scenes[0].cam)
@@ -304,7 +284,7 @@ def test_a_context_that_never_annotates_allocates_nothing(oa, L, batch):
     whole device's, so a difference is looked at again on a fresh context: another process's allocation does not repeat."""
     import torch
     fr = batch["fr"]
-    recs = OC.records([OC.axis_square(10, 10, 40, 40)] * 4).reshape(4, 1)
+    recs = FK.records([FK.axis_square(10, 10, 40, 40)] * 4).reshape(4, 1)
     d, dm, dc = to_device(fr.buf), to_device(recs), to_device(np.ones(4, np.int32))
     st = AC.style(L, AC.OUTLINE)
 
@@ -353,7 +333,7 @@ def test_refusals_leave_the_frames_alone(oa, L, batch):
     W, Hh = 320, 240
     frames = np.full((4, Hh, W, 3), 200, np.uint8)
     d = to_device(frames)
-    recs = to_device(OC.records([OC.axis_square(5, 5, 50, 50)] * 4).reshape(4, 1))
+    recs = to_device(FK.records([FK.axis_square(5, 5, 50, 50)] * 4).reshape(4, 1))
     cnt = to_device(np.ones(4, np.int32))
     torch.cuda.synchronize()
     fp, rp, cp = d.data_ptr(), recs.data_ptr(), cnt.data_ptr()

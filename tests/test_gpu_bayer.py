@@ -8,13 +8,14 @@ import pytest
 
 import annotate_chain as AC
 import bayer_chain as BC
+import frame_kit as FK
 import helpers as H
 import levels_chain as LC
+from frame_kit import E_ARG, oa, same, to_device  # noqa: F401
 from test_gpu_parity import OracleFrame, check_markers, make_detector
 
 pytestmark = pytest.mark.gpu
 
-E_ARG = -2
 PATS = list(BC.PATTERNS)
 # The kernel's seams: a lane's span of 8 pixels, a wave's span of 512, the even-aligned row pair, and the strip of BC.PAIRS = 4 row
 # pairs (8 rows) a lane marches down.  The widths are the two spans and their neighbours, 520 (a second workgroup of one full lane)
@@ -25,26 +26,13 @@ HEIGHTS = [2, 3, 4, 5, 17, 7, 8, 9, 10]
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return BC.build_emul(tmp_path_factory.mktemp("bayer_emul"))
+def L():
+    return BC.build_emul()
 
 
 @pytest.fixture(scope="module")
 def det(oa):
     return oa.Detector(64, 32, max_batch=1)   # (neither the sides nor n_frames are bound by the context)
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to("cuda:0")
 
 
 def lib_params(oa, p):
@@ -64,13 +52,6 @@ def device_demosaic(oa, det, raw, dst, p, buf=None):
     return dd.cpu().numpy(), d.cpu().numpy()
 
 
-def same(got, want, inside, where):
-    bad = np.flatnonzero(got != want)
-    if bad.size:
-        raise AssertionError("%s: %d bytes differ (%d of them guard bytes), first at byte %d of the buffer: %d != %d" % (
-            where, bad.size, int((~inside[bad]).sum()), int(bad[0]), got[bad[0]], want[bad[0]]))
-
-
 def test_the_python_parameters(oa):
     p = oa.bayer_params()
     q = oa.BayerParams()
@@ -87,13 +68,13 @@ def test_the_python_parameters(oa):
 
 # ---- the sweep --------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("fmt", BC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 @pytest.mark.parametrize("pattern", PATS)
 def test_sweep(oa, L, det, pattern, fmt):
     """every width, paired with a height that moves with the case, with 1 and 3 frames, from 8-bit and from 12-bit sources, on the
     dword path (everything a multiple of 4) and on the byte path (an odd lead and pitch; for words an even lead off a multiple of 4):
     the host core's buffer each time, the source unchanged, and the same pixels on both paths"""
-    turn = PATS.index(pattern) + BC.FMTS.index(fmt)
+    turn = PATS.index(pattern) + FK.FMTS.index(fmt)
     for i, W in enumerate(WIDTHS):
         Hh = HEIGHTS[(i + turn) % len(HEIGHTS)]
         for n in (1, 3):
@@ -102,9 +83,9 @@ def test_sweep(oa, L, det, pattern, fmt):
                 pixels = []
                 for aligned in (True, False):
                     raw = BC.Raw(n, W, Hh, bits, aligned=aligned, seed=W + Hh + bits)
-                    dst = BC.pix_layout(n, W, Hh, fmt, aligned, fill=BC.GUARD)
+                    dst = FK.pix_layout(n, W, Hh, fmt, aligned, fill=FK.GUARD)
                     want = BC.host_demosaic(L, raw, dst, p)
-                    assert (want[~dst.pixel_mask()] == BC.GUARD).all()
+                    assert (want[~dst.pixel_mask()] == FK.GUARD).all()
                     got, src_after = device_demosaic(oa, det, raw, dst, p)
                     assert (src_after == raw.buf).all()
                     same(got, want, dst.pixel_mask(), "%dx%d x %d %s %d bits -> %s aligned=%s" % (W, Hh, n, pattern, bits, fmt, aligned))
@@ -117,11 +98,11 @@ def test_black_levels_and_gains(oa, L, det, bits):
     """non-default black levels and gains (a gain of 0, the largest gain, black = the largest sample among them) at 10 and 16 bits"""
     for W, Hh in ((17, 6), (513, 5)):
         for k, (black, gains) in enumerate(BC.knobs(bits)):
-            pattern, fmt = PATS[k % 4], BC.FMTS[(k + W) % 5]
+            pattern, fmt = PATS[k % 4], FK.FMTS[(k + W) % 5]
             p = BC.params(pattern, bits, black, gains)
             for aligned in (True, False):
                 raw = BC.Raw(2, W, Hh, bits, aligned=aligned, seed=W + k)
-                dst = BC.pix_layout(2, W, Hh, fmt, aligned, fill=BC.GUARD)
+                dst = FK.pix_layout(2, W, Hh, fmt, aligned, fill=FK.GUARD)
                 got, src_after = device_demosaic(oa, det, raw, dst, p)
                 assert (src_after == raw.buf).all()
                 same(got, BC.host_demosaic(L, raw, dst, p), dst.pixel_mask(), "%dx%d %s %d bits black %d gains %s -> %s aligned=%s" % (
@@ -135,10 +116,10 @@ def test_any_strip_height_gives_the_same_bytes(oa, L):
     for pairs, heights in ((1, (2, 3, 5)), (2, (3, 4, 5, 9)), (3, (5, 6, 7, 13)), (64, (17, 127, 128, 129)), (1000, (129,)), (0, (9,))):
         det.set_tuning(bayer_pairs=pairs)
         for k, Hh in enumerate(heights):
-            W, bits, fmt, aligned = (17, 521)[k % 2], (8, 12)[(k + pairs) % 2], BC.FMTS[(k + pairs) % 5], bool((k + pairs) % 2)
+            W, bits, fmt, aligned = (17, 521)[k % 2], (8, 12)[(k + pairs) % 2], FK.FMTS[(k + pairs) % 5], bool((k + pairs) % 2)
             p = BC.params(PATS[(k + pairs) % 4], bits, 3, (1100, 1024, 1300))
             raw = BC.Raw(2, W, Hh, bits, aligned=aligned, seed=Hh + pairs)
-            dst = BC.pix_layout(2, W, Hh, fmt, aligned, fill=BC.GUARD)
+            dst = FK.pix_layout(2, W, Hh, fmt, aligned, fill=FK.GUARD)
             got, src_after = device_demosaic(oa, det, raw, dst, p)
             assert (src_after == raw.buf).all()
             same(got, BC.host_demosaic(L, raw, dst, p), dst.pixel_mask(), "%d pairs, %dx%d %d bits -> %s aligned=%s" % (pairs, W, Hh, bits, fmt, aligned))
@@ -146,7 +127,7 @@ def test_any_strip_height_gives_the_same_bytes(oa, L):
 
 def test_params_none_are_the_defaults(oa, L, det):
     raw = BC.Raw(2, 17, 6, 8, aligned=True, seed=4)
-    dst = BC.pix_layout(2, 17, 6, "bgra", True, fill=BC.GUARD)
+    dst = FK.pix_layout(2, 17, 6, "bgra", True, fill=FK.GUARD)
     got, _ = device_demosaic(oa, det, raw, dst, None)
     same(got, BC.host_demosaic(L, raw, dst, BC.params()), dst.pixel_mask(), "params None")
 
@@ -158,9 +139,9 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
     import torch
     n, lead = 65537, 64
     rng = np.random.default_rng(2)
-    raw = np.full(lead + 4 * n + lead, BC.GUARD, np.uint8)
+    raw = np.full(lead + 4 * n + lead, FK.GUARD, np.uint8)
     raw[lead:lead + 4 * n] = rng.integers(0, 256, 4 * n, dtype=np.uint8)
-    pix = np.full(lead + 12 * n + lead, BC.GUARD, np.uint8)
+    pix = np.full(lead + 12 * n + lead, FK.GUARD, np.uint8)
     want = pix.copy()
     p = BC.params("gbrg", 8, 5, (1200, 1024, 1600))
     assert L.bayer_to_frames_emul(raw.ctypes.data + lead, 2, 4, want.ctypes.data + lead, 6, 12, 2, 2, 0, n, C.addressof(p)) == 0
@@ -170,24 +151,24 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
     torch.cuda.synchronize()
     got = dd.cpu().numpy()
     assert (got == want).all(), np.flatnonzero(got != want)[:4].tolist()
-    assert (got[lead + 12 * 65535: lead + 12 * n] != BC.GUARD).any()   # (the frames of the second launch)
+    assert (got[lead + 12 * 65535: lead + 12 * n] != FK.GUARD).any()   # (the frames of the second launch)
     assert (d.cpu().numpy() == raw).all()
 
 
-def test_demosaic_detect_annotate_on_one_stream(oa, L, tmp_path_factory):
+def test_demosaic_detect_annotate_on_one_stream(oa, L):
     """demosaic -> enqueue -> annotate on the frames behind the batch -> a second demosaic of the same mosaics, all queued on the
     context's stream with nothing waited for before collect: the host cores of every step"""
     import torch
     cfg = H.synth_config(2)   # 640 x 480, four markers
     W, Hh, n = cfg.width, cfg.height, 2
     det, tpls, cam = make_detector(oa, cfg, None, n)
-    LA = AC.build_emul(tmp_path_factory.mktemp("annotate_emul"))
+    LA = AC.build_emul()
     st = AC.style(LA, thickness=2)
     raw = BC.Raw(n, W, Hh, 12, aligned=True)
     for f in range(n):
         raw.put(f, BC.mosaic(H.synth_frame(cfg, f)[0], "grbg", 12))
     p = BC.params("grbg", 12)
-    bgr, again = BC.pix_layout(n, W, Hh, "bgr", True, fill=BC.GUARD), BC.pix_layout(n, W, Hh, "rgba", False, fill=BC.GUARD)
+    bgr, again = FK.pix_layout(n, W, Hh, "bgr", True, fill=FK.GUARD), FK.pix_layout(n, W, Hh, "rgba", False, fill=FK.GUARD)
     want_bgr, want_again = BC.host_demosaic(L, raw, bgr, p), BC.host_demosaic(L, raw, again, p)
     d, db, da = to_device(raw.buf), to_device(bgr.buf), to_device(again.buf)
     torch.cuda.synchronize()
@@ -225,7 +206,7 @@ def test_the_chain_on_the_device(oa, L, size):
     det = oa.Detector(W, Hh, max_batch=n)
     det.set_templates([oa.Template.from_buffer_copy(bytes(t)) for t in tpls])
     det.set_camera(oa.Camera.from_buffer_copy(bytes(cam)))
-    bgr, gray = BC.pix_layout(n, W, Hh, "bgr", True, fill=BC.GUARD), BC.pix_layout(n, W, Hh, "gray", False, fill=BC.GUARD)
+    bgr, gray = FK.pix_layout(n, W, Hh, "bgr", True, fill=FK.GUARD), FK.pix_layout(n, W, Hh, "gray", False, fill=FK.GUARD)
     db, dg = to_device(bgr.buf), to_device(gray.buf)
     want = bgr.buf.copy()
     for f in range(n):   # (a pattern per frame: a call per frame)
@@ -233,7 +214,7 @@ def test_the_chain_on_the_device(oa, L, size):
         raw = BC.Raw(1, W, Hh, 8, aligned=True)
         raw.put(0, BC.mosaic(scenes[f], pattern))
         p = BC.params(pattern)
-        one = BC.pix_layout(1, W, Hh, "bgr", True, fill=BC.GUARD)
+        one = FK.pix_layout(1, W, Hh, "bgr", True, fill=FK.GUARD)
         bgr.view(f, want)[...] = one.view(0, BC.host_demosaic(L, raw, one, p))
         d = to_device(raw.buf)
         torch.cuda.synchronize()
@@ -263,7 +244,7 @@ def test_refusals_launch_nothing(oa, L):
     det = oa.Detector(64, 32, max_batch=1)
     ctx = det._ctx
     W, Hh, n = 64, 32, 2
-    pix_h = np.full(n * 4 * W * Hh + 64, BC.GUARD, np.uint8)
+    pix_h = np.full(n * 4 * W * Hh + 64, FK.GUARD, np.uint8)
     raw_h = np.full(n * 2 * W * Hh + 64, 77, np.uint8)
     dp, dr = to_device(pix_h), to_device(raw_h)
     torch.cuda.synchronize()

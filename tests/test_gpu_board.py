@@ -9,6 +9,7 @@ import pytest
 import board_chain as BC
 import dense_synth as DS
 import helpers as H
+from frame_kit import oa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -19,16 +20,8 @@ RTOL = 1e-6
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def Lb(tmp_path_factory):
-    return BC.build_emul(tmp_path_factory.mktemp("board_emul"))
+def Lb():
+    return BC.build_emul()
 
 
 @pytest.fixture(scope="module")

@@ -2,7 +2,6 @@
 oracle's registration, the host build of refine_core.h on every output square, the oracle's pose of the refined square.
 Squares bit-exact, poses within the 1e-4 bar, everything else as without refinement."""
 import ctypes as C
-import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
@@ -11,6 +10,8 @@ import pytest
 
 import helpers as H
 import refine_chain as RC
+from frame_kit import oa  # noqa: F401
+from hostbuild import host_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -19,16 +20,8 @@ N = 64
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return RC.build_emul(tmp_path_factory.mktemp("refine_emul"))
+def L():
+    return RC.build_emul()
 
 
 @pytest.fixture(scope="module")
@@ -286,11 +279,7 @@ def test_input_formats_give_the_bgr_result(oa, L, scene, fmt):
 
 
 def test_host_mirror_registration(oa, L, scene, tmp_path):
-    exe = str(tmp_path / "refine_registration_driver")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(H.ROOT, "include"),
-                           "-I" + os.path.join(H.ROOT, "include", "shim"), "-o", exe,
-                           os.path.join(H.ROOT, "tests", "emul", "refine_registration_driver.cpp"),
-                           "-L" + os.path.join(H.PKG, "lib"), "-lopencv-ar", "-Wl,-rpath," + os.path.join(H.PKG, "lib")])
+    exe = host_driver("refine_registration_driver")
     order = [0, 0, 4]   # a static step (tracked markers), then a new scene
     tpls, cam = scene["tpls"], scene["cam"]
     inp, out = tmp_path / "in.bin", tmp_path / "out.bin"

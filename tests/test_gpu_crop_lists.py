@@ -10,17 +10,10 @@ import pytest
 
 import helpers as H
 import test_gpu_parity as T
+from frame_kit import oa  # noqa: F401
 
 W, HH = 640, 480
 MID_STEPS, CAP, BLOCK = 1536, 3072, 32   # kernels.h: MID_STEPS, CROP_STEPS_CAP; follow.hip: MID_BLOCK
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 def budget(cw, ch):

@@ -13,20 +13,18 @@ import pytest
 
 import dense_synth as D
 import helpers as H
+from frame_kit import oa  # noqa: F401
+from hostbuild import host_core, host_driver
 
 pytestmark = pytest.mark.gpu
 
 LIB = os.path.join(H.PKG, "lib", "libopencv-ar.so.1.0.0")
-CSRC = os.path.join(H.PKG, "csrc")
 
 
 @pytest.fixture(scope="module")
-def emul(tmp_path_factory):
+def emul():
     """host build of the tracking cores (tests/emul/dense_emul.cpp): how many markers the literal loop tracks"""
-    so = str(tmp_path_factory.mktemp("dense_emul_gpu") / "libdense_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-I" + CSRC, "-I" + os.path.join(H.ROOT, "include"),
-                           "-shared", "-o", so, os.path.join(H.ROOT, "tests", "emul", "dense_emul.cpp")])
-    L = C.CDLL(so)
+    L = host_core("dense_emul")
     L.dense_track_literal.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     return L
 
@@ -56,15 +54,6 @@ def grid_of_squares(w, h, pitch=40, side=28):
         for x in range(20, w - side - 20, pitch):
             g[y:y + side, x:x + side] = 40
     return g
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    opencv_ar_amd.hip_lib()
-    return opencv_ar_amd
 
 
 def test_4k_grid_of_squares_through_find_squares(oa):
@@ -215,12 +204,7 @@ def test_tracking_with_hundreds_of_markers_carried_in(oa, scene, chain):
 
 
 def run_tracking_driver(oa, tmp_path, scene, initial, frame_ids, tag):
-    exe = str(tmp_path / "tracking_driver")
-    if not os.path.exists(exe):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(H.ROOT, "include"),
-                               "-I" + os.path.join(H.ROOT, "include", "shim"), "-o", exe,
-                               os.path.join(H.ROOT, "tests", "emul", "tracking_driver.cpp"),
-                               "-L" + os.path.join(H.PKG, "lib"), "-lopencv-ar", "-Wl,-rpath," + os.path.join(H.PKG, "lib")])
+    exe = host_driver("tracking_driver")
     inp, out = tmp_path / f"in_{tag}.bin", tmp_path / f"out_{tag}.bin"
     tpls = scene["tpls"]
     inp.write_bytes(np.array([1920, 1080, len(tpls), len(frame_ids), len(initial)], np.int32).tobytes() + bytes(tpls) +

@@ -13,6 +13,8 @@ import pytest
 
 import dense_synth as D
 import helpers as H
+from frame_kit import oa  # noqa: F401
+from hostbuild import host_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -20,15 +22,6 @@ FLAG_QUADS, FLAG_CROPS, FLAG_TILES, FLAG_MARKERS = 4, 16, 32, 128
 QS = [1, 63, 64, 65, 255, 256, 2047, 2048, 2049, 4097, 16384]
 MS = [1, 7, 64, 65]          # (4096: test_marker_cap_4096_through_tracked_markers)
 POOL = 16
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    opencv_ar_amd.hip_lib()
-    return opencv_ar_amd
 
 
 def pmap(fn, items):
@@ -523,12 +516,7 @@ def test_host_ladder_find_squares_top(oa, square_frames, tmp_path):
 
 
 def run_tracking_driver(oa, tmp_path, w, h, tpls, cam, initial, frames, tag):
-    exe = str(tmp_path / "tracking_driver")
-    if not os.path.exists(exe):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(H.ROOT, "include"),
-                               "-I" + os.path.join(H.ROOT, "include", "shim"), "-o", exe,
-                               os.path.join(H.ROOT, "tests", "emul", "tracking_driver.cpp"),
-                               "-L" + os.path.join(H.PKG, "lib"), "-lopencv-ar", "-Wl,-rpath," + os.path.join(H.PKG, "lib")])
+    exe = host_driver("tracking_driver")
     inp, out = tmp_path / f"in_{tag}.bin", tmp_path / f"out_{tag}.bin"
     inp.write_bytes(np.array([w, h, len(tpls), len(frames), len(initial)], np.int32).tobytes() + bytes(tpls) + bytes(cam) +
                     b"".join(bytes(m) for m in initial) + b"".join(f.tobytes() for f in frames))

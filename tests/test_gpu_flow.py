@@ -8,26 +8,18 @@ import numpy as np
 import pytest
 
 import flow_chain as FC
+import frame_kit as FK
 import helpers as H
-import overlay_chain as OC
+from frame_kit import E_ARG, oa, to_device  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-E_ARG = -2
 POSE_RTOL = 1e-4   # tests/test_gpu_parity.py
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return FC.build_emul(tmp_path_factory.mktemp("flow_emul"))
+def L():
+    return FC.build_emul()
 
 
 @pytest.fixture(scope="module")
@@ -36,19 +28,8 @@ def det128(oa):
     return oa.Detector(128, 96, max_batch=2)
 
 
-def to_device(a, odd=False):
-    """the bytes of a on the device; odd: one byte into an allocation (an odd address, allocations being aligned)"""
-    import torch
-    flat = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    if not odd:
-        return torch.from_numpy(flat).to("cuda:0")
-    t = torch.zeros(flat.size + 1, dtype=torch.uint8, device="cuda:0")
-    t[1:] = torch.from_numpy(flat).to("cuda:0")
-    return t[1:]
-
-
 def guard_like(recs):
-    return np.frombuffer(np.full(recs.nbytes, OC.GUARD, np.uint8).tobytes(), OC.MARKER_DTYPE).reshape(recs.shape).copy()
+    return np.frombuffer(np.full(recs.nbytes, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(recs.shape).copy()
 
 
 def device_flow(det, prev, nxt, recs, counts, p, in_place=False, with_status=True, with_err=True, odd=False, stream=None, out=None):
@@ -58,8 +39,8 @@ def device_flow(det, prev, nxt, recs, counts, p, in_place=False, with_status=Tru
     dp, dn = to_device(prev.buf, odd), to_device(nxt.buf, odd)
     dm, dc = to_device(recs), to_device(np.asarray(counts, np.int32))
     do = dm if in_place else to_device(guard_like(recs) if out is None else out)
-    ds = to_device(np.full(n * slots * 4, OC.GUARD, np.uint8)) if with_status else None
-    de = to_device(np.full(n * slots * 16, OC.GUARD, np.uint8)) if with_err else None
+    ds = to_device(np.full(n * slots * 4, FK.GUARD, np.uint8)) if with_status else None
+    de = to_device(np.full(n * slots * 16, FK.GUARD, np.uint8)) if with_err else None
     assert (dp.data_ptr() % 4 == 1) == odd
     torch.cuda.synchronize()
     det.flow_records(dp.data_ptr() + prev.offset(0), dn.data_ptr() + nxt.offset(0), prev.width, prev.height, n, dm.data_ptr(), dc.data_ptr(),
@@ -70,7 +51,7 @@ def device_flow(det, prev, nxt, recs, counts, p, in_place=False, with_status=Tru
     assert (dp.cpu().numpy() == prev.buf).all() and (dn.cpu().numpy() == nxt.buf).all()
     if not in_place:
         assert dm.cpu().numpy().tobytes() == recs.tobytes()
-    return (do.cpu().numpy().view(OC.MARKER_DTYPE).reshape(n, slots),
+    return (do.cpu().numpy().view(FK.MARKER_DTYPE).reshape(n, slots),
             ds.cpu().numpy().view(np.int32).reshape(n, slots) if with_status else None,
             de.cpu().numpy().view(np.float32).reshape(n, slots, 4) if with_err else None)
 
@@ -101,7 +82,7 @@ def quads(rng, n, slots, W, Hh, margin):
     ang = np.deg2rad([225, 315, 45, 135]) + rng.uniform(-0.3, 0.3, (n, slots, 4))
     rad = rng.uniform(0.6 * r, r, (n, slots, 4))
     sq = np.stack([np.clip(cx + rad * np.cos(ang), 0, W - 1), np.clip(cy + rad * np.sin(ang), 0, Hh - 1)], -1).reshape(n * slots, 8)
-    recs = OC.records(sq, template_ids=rng.integers(0, 9, n * slots), scores=rng.integers(0, 2, n * slots)).reshape(n, slots)
+    recs = FK.records(sq, template_ids=rng.integers(0, 9, n * slots), scores=rng.integers(0, 2, n * slots)).reshape(n, slots)
     recs["glMatrix"] = rng.normal(size=(n, slots, 16))
     recs["aspectRatio"] = rng.uniform(0.5, 2, (n, slots))
     recs["square"][-1, -1, 2] = W + 3.5
@@ -110,8 +91,8 @@ def quads(rng, n, slots, W, Hh, margin):
 
 def textured(rng, n, W, Hh, fmt, shift, row_pad=0, frame_gap=0, cell=6):
     """(prev, next): Frames blocks whose grey is a texture and its shift; in a colour format the channels differ"""
-    prev = OC.Frames(n, W, Hh, fmt, row_pad=row_pad, frame_gap=frame_gap, seed=1)
-    nxt = OC.Frames(n, W, Hh, fmt, row_pad=row_pad + 1, frame_gap=frame_gap + 3, seed=2)
+    prev = FK.Frames(n, W, Hh, fmt, row_pad=row_pad, frame_gap=frame_gap, seed=1)
+    nxt = FK.Frames(n, W, Hh, fmt, row_pad=row_pad + 1, frame_gap=frame_gap + 3, seed=2)
     for f in range(n):
         A, B = FC.shifted_pair(rng, W, Hh, shift[0] + f, shift[1], cell=cell)
         for fr, g in ((prev, A), (nxt, B)):
@@ -141,7 +122,7 @@ def guard_merge(want, recs, counts):
     return out
 
 
-@pytest.mark.parametrize("fmt", FC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 def test_formats_strides_counts_and_chunks(L, det128, fmt):
     """96 x 64, three frames on a context of two: padded rows, an odd base address, a gap between the frames; counts 0, 1 and one above
     records_per_frame"""
@@ -156,7 +137,7 @@ def test_formats_strides_counts_and_chunks(L, det128, fmt):
     same(device_flow(det128, prev, nxt, recs, counts, p, odd=True), (guard_merge(want, recs, counts),) + want[1:], fmt + " odd address")
     if fmt in ("bgr", "gray"):   # (the dword loads of the grey kernel need an aligned block: strides that are multiples of 4)
         pa, na = textured(rng, n, W, Hh, fmt, (2, 1), row_pad=4 if fmt == "gray" else 12, frame_gap=8)
-        na = OC.Frames(n, W, Hh, fmt, row_pad=pa.row_stride - W * pa.bpp, frame_gap=8, seed=5)
+        na = FK.Frames(n, W, Hh, fmt, row_pad=pa.row_stride - W * pa.bpp, frame_gap=8, seed=5)
         for f in range(n):
             na.view(f)[...] = np.roll(pa.view(f), (1, 2), (0, 1))
         assert pa.row_stride % 4 == 0 and pa.frame_stride % 4 == 0 and na.row_stride % 4 == 0 and na.frame_stride % 4 == 0
@@ -213,9 +194,9 @@ def test_in_place_and_without_status_and_errors(L, det128):
 def test_every_status_code(L, det128):
     s = FC.code_scene()
     W, Hh = s["W"], s["H"]
-    fa = FC.fill_frames(OC.Frames(1, W, Hh, "gray"), [s["A"]])
-    fb = FC.fill_frames(OC.Frames(1, W, Hh, "gray"), [s["B"]])
-    fo = FC.fill_frames(OC.Frames(1, W, Hh, "gray"), [s["occl"]])
+    fa = FC.fill_frames(FK.Frames(1, W, Hh, "gray"), [s["A"]])
+    fb = FC.fill_frames(FK.Frames(1, W, Hh, "gray"), [s["B"]])
+    fo = FC.fill_frames(FK.Frames(1, W, Hh, "gray"), [s["occl"]])
     recs = FC.code_records(W)
     p = FC.params(half_win=5, levels=2)
     want = FC.host_flow(L, fa, fb, recs, [5], p)
@@ -223,14 +204,14 @@ def test_every_status_code(L, det128):
     same(device_flow(det128, fa, fb, recs, [5], p), (guard_merge(want, recs, [5]),) + want[1:], "codes 1 -1 -2 -6 0")
     # -3: a shift that carries corners out of the frame, at level 0 alone
     A2, B2 = FC.shifted_pair(np.random.default_rng(13), W, Hh, -3, -2)
-    f2a, f2b = FC.fill_frames(OC.Frames(1, W, Hh, "gray"), [A2]), FC.fill_frames(OC.Frames(1, W, Hh, "gray"), [B2])
-    r3 = OC.records([[2, 40, 40, 40, 40, 70, 4, 70], [20, 40, 60, 1, 60, 60, 20, 60]]).reshape(1, 2)
+    f2a, f2b = FC.fill_frames(FK.Frames(1, W, Hh, "gray"), [A2]), FC.fill_frames(FK.Frames(1, W, Hh, "gray"), [B2])
+    r3 = FK.records([[2, 40, 40, 40, 40, 70, 4, 70], [20, 40, 60, 1, 60, 60, 20, 60]]).reshape(1, 2)
     p0 = FC.params(half_win=5, levels=0)
     want = FC.host_flow(L, f2a, f2b, r3, [2], p0)
     assert want[1][0].tolist() == [-3, -3] and want[2][0, 0].tolist()[0] == -1.0 and (want[2][0, 0, 1:3] >= 0).all()
     same(device_flow(det128, f2a, f2b, r3, [2], p0), want, "code -3")
     # -4 and -5 on the occluded frame: error limits around a measured error, the forward-backward check on and off
-    r4 = OC.records([[40, 56, 100, 50, 100, 85, 20, 85], [75, 50, 115, 52, 113, 88, 73, 86]]).reshape(1, 2)   # corner 0 of the first under the occluder
+    r4 = FK.records([[40, 56, 100, 50, 100, 85, 20, 85], [75, 50, 115, 52, 113, 88, 73, 86]]).reshape(1, 2)   # corner 0 of the first under the occluder
     base = FC.host_flow(L, fa, fo, r4, [2], p)
     assert base[1][0].tolist() == [1, 1]
     e = float(base[2][0, 0].max())
@@ -260,8 +241,8 @@ def test_the_pose_flag_takes_the_camera_of_the_call(oa, L):
     s = FC.code_scene()
     W, Hh = s["W"], s["H"]
     det = oa.Detector(W, Hh, max_batch=1)
-    fa = FC.fill_frames(OC.Frames(1, W, Hh, "gray"), [s["A"]])
-    fb = FC.fill_frames(OC.Frames(1, W, Hh, "gray"), [s["B"]])
+    fa = FC.fill_frames(FK.Frames(1, W, Hh, "gray"), [s["A"]])
+    fb = FC.fill_frames(FK.Frames(1, W, Hh, "gray"), [s["B"]])
     recs = FC.code_records(W)
     cam_a, cam_b = H.oracle_camera(W, Hh), H.oracle_camera(W, Hh)
     cam_b.cameraMatrix[0] *= 1.7
@@ -279,14 +260,14 @@ def test_the_pose_flag_takes_the_camera_of_the_call(oa, L):
                      fmt="gray", params=p, d_status_ptr=ds.data_ptr())
     set_camera(oa, det, cam_b)
     torch.cuda.synchronize()
-    got = dm.cpu().numpy().view(OC.MARKER_DTYPE).reshape(1, 6)
+    got = dm.cpu().numpy().view(FK.MARKER_DTYPE).reshape(1, 6)
     same((got, ds.cpu().numpy().view(np.int32).reshape(1, 6), None), want_a, "camera by value", pose=True)
     # the pose keyword of the binding sets the flag
     dm2 = to_device(recs)
     det.flow_records(dp.data_ptr() + fa.offset(0), dn.data_ptr() + fb.offset(0), W, Hh, 1, dm2.data_ptr(), dc.data_ptr(), dm2.data_ptr(), per_frame=6,
                      fmt="gray", params=FC.params(half_win=5, levels=2), pose=True)
     torch.cuda.synchronize()
-    same((dm2.cpu().numpy().view(OC.MARKER_DTYPE).reshape(1, 6), None, None), want_b, "pose keyword", pose=True)
+    same((dm2.cpu().numpy().view(FK.MARKER_DTYPE).reshape(1, 6), None, None), want_b, "pose keyword", pose=True)
     det.close()
 
 
@@ -331,7 +312,7 @@ def test_a_fast_marker_keeps_its_record_with_flow(oa, moving):
     assert np.abs(stateless[1]["square"] - stateless[0]["square"]).max() > 20
 
     def first_records():
-        recs = np.zeros((1, M), OC.MARKER_DTYPE)
+        recs = np.zeros((1, M), FK.MARKER_DTYPE)
         recs[0, 0] = stateless[0]
         recs["score"][0, 0] = SENTINEL
         return to_device(recs), to_device(np.array([1], np.int32))
@@ -370,7 +351,7 @@ def test_device_stream_tracker(oa, moving, predict):
     assert c[0] == 1
     torch.cuda.synchronize()
     first = m[0, 0].copy()
-    recs = trk.recs.cpu().numpy().view(OC.MARKER_DTYPE).copy()
+    recs = trk.recs.cpu().numpy().view(FK.MARKER_DTYPE).copy()
     recs["score"][0] = SENTINEL
     trk.recs.copy_(to_device(recs))
     torch.cuda.synchronize()
@@ -428,7 +409,7 @@ def test_beside_a_batch_in_flight_under_a_gate_and_on_two_streams(oa, L, moving)
     flow(2, 0, 1, prev, nxt, s2)
     torch.cuda.synchronize()
     for k, w in ((0, want), (1, want2), (2, want)):
-        got = (outs[k].cpu().numpy().view(OC.MARKER_DTYPE).reshape(1, slots), sts[k].cpu().numpy().view(np.int32).reshape(1, slots), None)
+        got = (outs[k].cpu().numpy().view(FK.MARKER_DTYPE).reshape(1, slots), sts[k].cpu().numpy().view(np.int32).reshape(1, slots), None)
         same(got, w, "call %d" % k)
     assert (dev[0].cpu().numpy() == prev.buf).all() and (d.cpu().numpy().reshape(-1) == mv["frames"][0].reshape(-1)).all()
     det.close()
@@ -443,12 +424,12 @@ def test_refusals_launch_nothing(oa, L):
     ctx = det._ctx
     W, Hh, M = 128, 96, det.max_markers
     s = FC.code_scene()
-    fa = FC.fill_frames(OC.Frames(2, W, Hh, "bgr"), [s["A"], s["A"]])
-    fb = FC.fill_frames(OC.Frames(2, W, Hh, "bgr"), [s["B"], s["B"]])
-    recs = OC.records([FC.GOOD] * 2).reshape(2, 1)
+    fa = FC.fill_frames(FK.Frames(2, W, Hh, "bgr"), [s["A"], s["A"]])
+    fb = FC.fill_frames(FK.Frames(2, W, Hh, "bgr"), [s["B"], s["B"]])
+    recs = FK.records([FC.GOOD] * 2).reshape(2, 1)
     dp, dn, dm, dc = to_device(fa.buf), to_device(fb.buf), to_device(recs), to_device(np.array([1, 1], np.int32))
     out_h = guard_like(recs)
-    do, ds, de = to_device(out_h), to_device(np.full(8, OC.GUARD, np.uint8)), to_device(np.full(32, OC.GUARD, np.uint8))
+    do, ds, de = to_device(out_h), to_device(np.full(8, FK.GUARD, np.uint8)), to_device(np.full(32, FK.GUARD, np.uint8))
     torch.cuda.synchronize()
     pp, np_ = dp.data_ptr() + fa.offset(0), dn.data_ptr() + fb.offset(0)
 
@@ -473,12 +454,12 @@ def test_refusals_launch_nothing(oa, L):
         assert call(**kw) == E_ARG, kw
         assert lib.ocvar_hip_last_error(ctx), kw
     torch.cuda.synchronize()
-    assert do.cpu().numpy().tobytes() == out_h.tobytes() and (ds.cpu().numpy() == OC.GUARD).all() and (de.cpu().numpy() == OC.GUARD).all()
+    assert do.cpu().numpy().tobytes() == out_h.tobytes() and (ds.cpu().numpy() == FK.GUARD).all() and (de.cpu().numpy() == FK.GUARD).all()
     # and after all that the context still tracks: the defaults of a NULL parameter block, sides of exactly 2 half_win + 3
     assert call(par=None) == 0
     torch.cuda.synchronize()
     want = FC.host_flow(L, fa, fb, recs, [1, 1], FC.params())
-    got = (do.cpu().numpy().view(OC.MARKER_DTYPE).reshape(2, 1), ds.cpu().numpy().view(np.int32).reshape(2, 1), de.cpu().numpy().view(np.float32).reshape(2, 1, 4))
+    got = (do.cpu().numpy().view(FK.MARKER_DTYPE).reshape(2, 1), ds.cpu().numpy().view(np.int32).reshape(2, 1), de.cpu().numpy().view(np.float32).reshape(2, 1, 4))
     same(got, want, "defaults")
     assert call(w=23, h=23, par=dict(half_win=10)) == 0
     set_camera(oa, det, H.oracle_camera(W, Hh))

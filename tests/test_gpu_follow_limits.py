@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import follow_limit_scenes as S
+from frame_kit import oa  # noqa: F401
 from test_follow_tiers_cpu import lib   # noqa: F401  (lib: the fixture that builds tests/emul/follow_emul.cpp)
 from test_gpu_parity import OracleFrame, check_candidates, check_markers, check_planes, make_detector
 from test_starts_cpu import build_lib
@@ -35,14 +36,6 @@ SETTINGS = {"defaults": dict(mid_steps=0, mid_blocks=0, long_blocks=0),
             "tier2": dict(mid_steps=2 ** 31 - 1, mid_blocks=0, long_blocks=0),
             "tier3": dict(mid_steps=64, mid_blocks=3, long_blocks=2)}
 BY_NAME = {s.name: s for s in S.SCENES}
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 @pytest.fixture(scope="module")

@@ -12,29 +12,21 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import geometry_scenes as GS
 import helpers as H
 import overlay_chain as OC
 import refine_chain as RC
+from frame_kit import E_ARG, FMTS, GUARD, oa  # noqa: F401
 from test_gpu_input_formats import as_format, grey_in_place_of
 from test_gpu_parity import OracleFrame, check_candidates, check_markers, check_planes
 
 pytestmark = pytest.mark.gpu
 
-E_ARG, E_CAPACITY = -2, -4
+E_CAPACITY = -4
 INT_MAX = 2**31 - 1
-FORMATS = ["bgr", "rgb", "bgra", "rgba", "gray"]
-BPP = {"bgr": 3, "rgb": 3, "bgra": 4, "rgba": 4, "gray": 1}
 SET5 = (5, 30, 0.1)
-GUARD, GUARD_BYTES = 0xA5, 64
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
+GUARD_BYTES = 64
 
 
 def detector(oa, w, h, tpls, cam, batch=1):
@@ -155,20 +147,20 @@ def test_one_marker_2500_pixels_on_its_side(oa):
     assert ((sq.max(0) - sq.min(0)) ** 2).sum() > 2**21 * 8
 
 
-def test_opt_in_stages_at_far_coordinates(oa, tmp_path_factory):
+def test_opt_in_stages_at_far_coordinates(oa):
     """Corner refinement (5 / 30 / 0.1) and the overlay renderer on the 32767 x 600 scene, whose records reach x = 32690:
     refined squares bit-exact against the host chain of tests/refine_chain.py (poses within the bar), and the frame rendered
     with a default overlay byte for byte against tests/overlay_chain.py's host renderer, guard bytes included."""
     import torch
     sc = long_scene(False)
     w, h, ref = sc["w"], sc["h"], sc["ref"]
-    Lr = RC.build_emul(tmp_path_factory.mktemp("refine_emul"))
-    Lo = OC.build_emul(tmp_path_factory.mktemp("overlay_emul"))
+    Lr = RC.build_emul()
+    Lo = OC.build_emul()
     overlay = OC.random_overlay(np.random.default_rng(9), 16, 16)
     det = detector(oa, w, h, sc["tpls"], sc["cam"])
     det.set_corner_refine(*SET5)
     det.set_overlay(-1, overlay)
-    fr = OC.Frames(1, w, h, "bgr", row_pad=5, fill=0)
+    fr = FK.Frames(1, w, h, "bgr", row_pad=5, fill=0)
     fr.view(0)[...] = sc["frame"]
     d = torch.from_numpy(fr.buf).cuda()
     clone = d.clone()
@@ -246,13 +238,13 @@ def raw_enqueue(oa, det, ptr, stride, frame_stride):
     return rc, lib.ocvar_hip_last_error(det._ctx).decode()
 
 
-@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("fmt", FMTS)
 def test_largest_row_span_the_rule_accepts(oa, fmt):
     """320 x 240 with the largest row_stride the rule accepts, in a device buffer of 2 GiB + slack of which only the 240 rows and
     64 guard bytes behind each are written: row 239 ends on the last byte the frame kernel's 2^31 - 1 byte resource covers, and
     all markers lie in the bottom 100 rows.  Results equal the oracle, the rows come back greyed, the guards are untouched."""
     src, tpls, cam, ref = small_scene(fmt)
-    bpp = BPP[fmt]
+    bpp = FK.bpp_of(fmt)
     stride = largest_stride(bpp)
     assert 239 * stride + bpp * 320 <= INT_MAX < 239 * (stride + 1) + bpp * 320
     assert 140 * stride > INT_MAX - 100 * stride             # the marker rows begin in the last 100 strides below 2^31
@@ -270,13 +262,13 @@ def test_largest_row_span_the_rule_accepts(oa, fmt):
         sp.free()
 
 
-@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("fmt", FMTS)
 def test_one_byte_more_of_row_stride_is_refused(oa, fmt):
     """row_stride one byte above the largest accepted: OCVAR_E_ARG with a text, nothing enqueued, the buffer -- row 239 and the
     guards included -- unchanged although grey_in_place was asked for; a legal call on the same context afterwards is right."""
     import torch
     src, tpls, cam, ref = small_scene(fmt)
-    stride = largest_stride(BPP[fmt]) + 1
+    stride = largest_stride(FK.bpp_of(fmt)) + 1
     sp = Spread(src, stride, (1 << 31) + 4096)
     try:
         det = detector(oa, 320, 240, tpls, cam)
@@ -293,7 +285,7 @@ def test_one_byte_more_of_row_stride_is_refused(oa, fmt):
         sp.free()
 
 
-@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("fmt", FMTS)
 def test_row_239_beyond_4_gib_is_refused(oa, fmt):
     """a row_stride that puts row 239 beyond 2^32 bytes (its offset wrapped to 32 bits would look like a small, legal one), in a
     buffer of 4 GiB + slack: OCVAR_E_ARG, the buffer unchanged"""

@@ -6,6 +6,7 @@ strips, so a wave of an edge strip (reflected columns, byte loads) and a wave of
 import numpy as np
 import pytest
 
+from frame_kit import oa  # noqa: F401
 from test_gpu_parity import make_detector
 from test_gpu_starts import size
 
@@ -13,14 +14,6 @@ pytestmark = pytest.mark.gpu
 
 W, HH, N = 512, 30, 3
 EXTREMES = ((0, 0, 0), (255, 255, 255), (255, 0, 0), (0, 255, 0), (0, 0, 255))   # (B, G, R)
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 @pytest.fixture(scope="module")

@@ -10,22 +10,15 @@ import os
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
+from frame_kit import oa  # noqa: F401
 from test_gpu_load import NAMES, distinct_frames, oracle_all
 from test_gpu_parity import OracleFrame, check_candidates, check_markers, check_planes, make_detector
 
 pytestmark = pytest.mark.gpu
 
-FORMATS = ["gray", "rgb", "bgra", "rgba"]
-BPP = {"bgr": 3, "gray": 1, "rgb": 3, "bgra": 4, "rgba": 4}
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
+NOT_BGR = ["gray", "rgb", "bgra", "rgba"]
 
 
 def unequal(bgr, seed):
@@ -86,7 +79,7 @@ def hd_scene(fmt):
     return cfg, src, refs
 
 
-@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("fmt", NOT_BGR)
 def test_planes_of_64_distinct_full_hd_frames_in_one_launch(oa, fmt):
     """every frame of a 64-frame 1080p launch, plane by plane (grey, binary, masks), frame quads, pre-elimination candidates,
     markers and poses"""
@@ -103,7 +96,7 @@ def test_planes_of_64_distinct_full_hd_frames_in_one_launch(oa, fmt):
         check_markers(f, refs[f], markers, counts, where=fmt)
 
 
-@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("fmt", NOT_BGR)
 def test_odd_panel_boundary_and_smallest_sizes(oa, fmt):
     """odd widths and heights (1921x1081, and the sizes whose last column or row begins a grey panel), and the smallest frames,
     which take the byte-wise generic path (sw < 32)"""
@@ -134,13 +127,13 @@ def test_odd_panel_boundary_and_smallest_sizes(oa, fmt):
             check_markers(f, ref, markers, counts, where=(fmt, w, h))
 
 
-@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("fmt", NOT_BGR)
 def test_padded_rows_gapped_frames_unaligned_base_and_grey_in_place(oa, fmt):
     """rows padded by 5 bytes, frames 77 bytes apart, the base pointer at an odd address; grey_in_place leaves a GRAY buffer as
     it was, makes bytes 0..2 of every other pixel the grey value and leaves the alpha bytes and the padding untouched"""
     import torch
     cfg = H.synth_config(2, width=644, height=482)
-    n, bpp = 3, BPP[fmt]
+    n, bpp = 3, FK.bpp_of(fmt)
     det, tpls, cam = make_detector(oa, cfg, ["2x2-01"], n)
     det.set_input_format(fmt)
     src, bgr = formatted_batch(cfg, n, fmt, ["2x2-01"], seed=3)
@@ -169,7 +162,7 @@ def test_padded_rows_gapped_frames_unaligned_base_and_grey_in_place(oa, fmt):
     assert out[0] == 0xA5 and (out[1 + (n - 1) * frame_stride + row_stride * h:] == 0xA5).all()
 
 
-@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("fmt", NOT_BGR)
 def test_4k_frame(oa, fmt):
     cfg = H.synth_config(5)
     det, tpls, cam = make_detector(oa, cfg, None, 1)
@@ -209,7 +202,7 @@ def test_nv12_luma_plane(oa):
     assert counts.sum() > 0
 
 
-@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("fmt", NOT_BGR)
 def test_entry_points(oa, fmt):
     """detect_device, detect_host from pageable and from caller-pinned memory (grey_in_place: GRAY copies nothing back), a
     tracked second call through enqueue_tracked with the first call's results_to_device block"""
@@ -244,7 +237,7 @@ def test_entry_points(oa, fmt):
     for f in range(n):
         assert blk[f, :c1[f]].tobytes() == m1[f, :c1[f]].tobytes()
     lib = det._lib
-    rc = lib.ocvar_hip_enqueue_tracked(det._ctx, C.c_void_p(d.data_ptr()), w, h, BPP[fmt] * w, BPP[fmt] * w * h, n, 0,
+    rc = lib.ocvar_hip_enqueue_tracked(det._ctx, C.c_void_p(d.data_ptr()), w, h, FK.bpp_of(fmt) * w, FK.bpp_of(fmt) * w * h, n, 0,
                                        C.c_void_p(d_m.data_ptr()), C.c_void_p(d_c.data_ptr()), None)
     assert rc == 0, rc
     det._n = n
@@ -315,10 +308,10 @@ def test_multi_detect_host_on_one_device(oa):
             src, bgr = formatted_batch(cfg, n, fmt, seed=41)
             markers = np.zeros((n, oa.MAX_MARKERS), oa.MARKER_DTYPE)
             counts = np.zeros(n, np.int32)
-            assert lib.ocvar_multi_detect_host(m, H.P(src), w, h, BPP[fmt] * w, src[0].nbytes, n, H.P(markers), H.P(counts), oa.MAX_MARKERS) == 0
+            assert lib.ocvar_multi_detect_host(m, H.P(src), w, h, FK.bpp_of(fmt) * w, src[0].nbytes, n, H.P(markers), H.P(counts), oa.MAX_MARKERS) == 0
             for f in range(n):
                 check_markers(f, OracleFrame(bgr[f], tpls, cam, planes=False), markers, counts, where=(fmt, "multi"))
-            assert lib.ocvar_multi_detect_host(m, H.P(src), w, h, BPP[fmt] * w - 1, src[0].nbytes, n, H.P(markers), H.P(counts), oa.MAX_MARKERS) == -2
+            assert lib.ocvar_multi_detect_host(m, H.P(src), w, h, FK.bpp_of(fmt) * w - 1, src[0].nbytes, n, H.P(markers), H.P(counts), oa.MAX_MARKERS) == -2
         assert lib.ocvar_multi_set_input_format(m, 5) == -2
     finally:
         lib.ocvar_multi_destroy(m)
@@ -355,11 +348,11 @@ def test_errors(oa):
     w, h = cfg.width, cfg.height
     det, tpls, cam = make_detector(oa, cfg, ["2x2-01"], 2)
     d = torch.zeros(2 * 4 * w * h, dtype=torch.uint8, device="cuda")
-    for fmt in ["bgr"] + FORMATS:
+    for fmt in ["bgr"] + NOT_BGR:
         det.set_input_format(fmt)
         with pytest.raises(oa.OcvarError, match=r"\(-2\)"):
-            det.detect_device(d.data_ptr(), w, h, 2, row_stride=BPP[fmt] * w - 1)
-        det.detect_device(d.data_ptr(), w, h, 2, row_stride=BPP[fmt] * w)
+            det.detect_device(d.data_ptr(), w, h, 2, row_stride=FK.bpp_of(fmt) * w - 1)
+        det.detect_device(d.data_ptr(), w, h, 2, row_stride=FK.bpp_of(fmt) * w)
     det.set_input_format("gray")
     with pytest.raises(ValueError):
         det.detect_host(np.zeros((2, h, w, 4), np.uint8))   # gray frames are [n, H, W]

@@ -4,36 +4,23 @@ source is read back untouched every time."""
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
 import levels_chain as LC
+from frame_kit import E_ARG, oa, same, to_device  # noqa: F401
 from test_gpu_parity import OracleFrame, check_markers
 
 pytestmark = pytest.mark.gpu
 
-E_ARG = LC.E_ARG
-
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return LC.build_emul(tmp_path_factory.mktemp("levels_emul"))
+def L():
+    return LC.build_emul()
 
 
 @pytest.fixture(scope="module")
 def det(oa):
     return oa.Detector(64, 32, max_batch=1)   # (neither the sizes nor n_frames are bound by the context's)
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to("cuda:0")
 
 
 def lib_params(oa, p):
@@ -56,18 +43,11 @@ def device_levels(oa, det, src, dst, p=None, stream=None, d_src=None, d_dst=None
     return dd.cpu().numpy(), d.cpu().numpy()
 
 
-def same(got, want, inside, where):
-    bad = np.flatnonzero(got != want)
-    if bad.size:
-        raise AssertionError("%s: %d bytes differ (%d of them guard bytes), first at byte %d of the buffer: %d != %d" % (
-            where, bad.size, int((~inside[bad]).sum()), int(bad[0]), got[bad[0]], want[bad[0]]))
-
-
 def check(oa, L, det, src, p, aligned, where, stream=None):
     """one call against the host core: the whole destination buffer, the source untouched -> the destination buffer"""
     dst = LC.dst_layout(src, aligned)
     rc, want = LC.host_levels(L, src, dst, p)
-    assert rc == 0 and (want[~dst.pixel_mask()] == LC.GUARD).all()
+    assert rc == 0 and (want[~dst.pixel_mask()] == FK.GUARD).all()
     got, src_after = device_levels(oa, det, src, dst, p, stream=stream)
     assert (src_after == src.buf).all(), where
     same(got, want, dst.pixel_mask(), where)
@@ -76,7 +56,7 @@ def check(oa, L, det, src, p, aligned, where, stream=None):
 
 # ---- the shapes ---------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("fmt", LC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 def test_shapes_against_the_host_core(oa, L, det, fmt):
     """the CPU test's shapes and grids (37 x 23 under three grids, 1 x 1, 2 x 1, 5 x 3, one-pixel tiles, 8 x 8 on 16 x 16) under every
     setting of the knobs, 3 frames and one frame alone, on the dword path (everything a multiple of 4) and on the byte path (an odd
@@ -87,7 +67,7 @@ def test_shapes_against_the_host_core(oa, L, det, fmt):
             n = 1 if (k + q) % 3 == 0 else 3
             pixels = []
             for aligned in (True, False):
-                src = LC.pix_layout(n, w, h, fmt, aligned, seed=k + 1)
+                src = FK.pix_layout(n, w, h, fmt, aligned, seed=k + 1)
                 got = check(oa, L, det, src, p, aligned, "%s %dx%d %s %s x %d aligned=%s" % (fmt, w, h, tiles, LC.KNOBS[q], n, aligned))
                 dst = LC.dst_layout(src, aligned)
                 pixels.append(np.stack([dst.view(f, got) for f in range(n)]))
@@ -95,7 +75,7 @@ def test_shapes_against_the_host_core(oa, L, det, fmt):
 
 
 def test_default_params_are_the_null_pointer(oa, L, det):
-    src = LC.pix_layout(2, 37, 23, "bgr", True, seed=3)
+    src = FK.pix_layout(2, 37, 23, "bgr", True, seed=3)
     a = check(oa, L, det, src, None, True, "params None")
     b = check(oa, L, det, src, LC.params(), True, "the defaults")
     assert (a == b).all()
@@ -109,7 +89,7 @@ def test_special_frames(oa, L, det, name):
         g = LC.special_frames(w, h)[name]
         for fmt in ("gray", "bgr"):
             for lo, hi, gain in [LC.KNOBS[0], LC.KNOBS[2], LC.KNOBS[3]]:
-                src = LC.pix_layout(2, w, h, fmt, True)
+                src = FK.pix_layout(2, w, h, fmt, True)
                 for f in range(2):
                     src.view(f)[...] = g[:, :, None]
                 check(oa, L, det, src, LC.params(tiles, lo, hi, gain), True, "%s %s %dx%d %s" % (name, fmt, w, h, tiles))
@@ -122,14 +102,14 @@ def test_a_tile_of_several_row_slabs(oa, L, det, fmt):
     assert -(-300 // LC.SLAB_ROWS) >= 3 and 300 % LC.SLAB_ROWS != 0
     for tiles in ((1, 1), (1, 2)):
         for aligned in (True, False):
-            check(oa, L, det, LC.pix_layout(2, 64, 300, fmt, aligned, seed=4), LC.params(tiles), aligned, "slabs %s %s aligned=%s" % (fmt, tiles, aligned))
+            check(oa, L, det, FK.pix_layout(2, 64, 300, fmt, aligned, seed=4), LC.params(tiles), aligned, "slabs %s %s aligned=%s" % (fmt, tiles, aligned))
 
 
 @pytest.mark.parametrize("tiles", [(4, 3), (8, 8)])
 def test_grids_on_67_by_41(oa, L, det, tiles):
-    for fmt in LC.FMTS:
+    for fmt in FK.FMTS:
         for aligned in (True, False):
-            check(oa, L, det, LC.pix_layout(3, 67, 41, fmt, aligned, seed=5), LC.params(tiles), aligned, "67x41 %s %s aligned=%s" % (fmt, tiles, aligned))
+            check(oa, L, det, FK.pix_layout(3, 67, 41, fmt, aligned, seed=5), LC.params(tiles), aligned, "67x41 %s %s aligned=%s" % (fmt, tiles, aligned))
 
 
 def test_wider_than_one_segment(oa, L, det):
@@ -137,7 +117,7 @@ def test_wider_than_one_segment(oa, L, det):
     one tile and with a grid whose cells are cut too"""
     for tiles in ((1, 1), (2, 2), (3, 1)):
         for fmt, aligned in (("gray", True), ("bgr", False), ("bgra", True)):
-            check(oa, L, det, LC.pix_layout(2, 521, 70, fmt, aligned, seed=6), LC.params(tiles), aligned, "521x70 %s %s" % (fmt, tiles))
+            check(oa, L, det, FK.pix_layout(2, 521, 70, fmt, aligned, seed=6), LC.params(tiles), aligned, "521x70 %s %s" % (fmt, tiles))
 
 
 # ---- rounds, streams, reuse ---------------------------------------------------------------------------------------------------------
@@ -146,14 +126,14 @@ def test_more_frames_than_one_round_takes(oa, L, det):
     """257 frames of 8 x 4: the workspace takes LC.WS_FRAMES = 256 a round"""
     assert LC.WS_FRAMES == 256
     for fmt, tiles in (("gray", (1, 1)), ("bgr", (2, 2))):
-        check(oa, L, det, LC.pix_layout(257, 8, 4, fmt, True, seed=7), LC.params(tiles), True, "257 frames %s" % fmt)
+        check(oa, L, det, FK.pix_layout(257, 8, 4, fmt, True, seed=7), LC.params(tiles), True, "257 frames %s" % fmt)
 
 
 def test_on_a_stream_of_the_caller(oa, L):
     import torch
     det = oa.Detector(64, 32, max_batch=1)
     s = torch.cuda.Stream()
-    src = LC.pix_layout(3, 67, 41, "bgr", True, seed=8)
+    src = FK.pix_layout(3, 67, 41, "bgr", True, seed=8)
     check(oa, L, det, src, LC.params((4, 3)), True, "caller's stream", stream=s.cuda_stream)
     # two calls on two streams back to back: the library orders them on its workspace
     dst = LC.dst_layout(src, True)
@@ -174,7 +154,7 @@ def test_two_calls_back_to_back_with_different_grids(oa, L):
     leaves every histogram it has read zeroed, so each call counts from zero"""
     import torch
     det = oa.Detector(64, 32, max_batch=1)
-    a, b = LC.pix_layout(3, 67, 41, "bgr", True, seed=9), LC.pix_layout(2, 37, 23, "gray", False, seed=10)
+    a, b = FK.pix_layout(3, 67, 41, "bgr", True, seed=9), FK.pix_layout(2, 37, 23, "gray", False, seed=10)
     calls = [(a, LC.params((8, 8)), True), (a, LC.params((1, 1)), True), (b, LC.params((4, 3)), False), (a, LC.params((8, 8)), True)]
     outs = [device_levels(oa, det, src, LC.dst_layout(src, al), p, sync=False)[0] for src, p, al in calls]
     torch.cuda.synchronize()
@@ -191,7 +171,7 @@ def test_a_context_that_never_calls_levels_allocates_nothing(oa, L):
     levels call of a context takes the workspace of 20 MiB (so the counter would have shown one), the second nothing.  The figure is
     the whole device's, so a difference is looked at again on a fresh context: another process's allocation does not repeat."""
     import torch
-    src = LC.pix_layout(2, 64, 48, "bgr", True, seed=11)
+    src = FK.pix_layout(2, 64, 48, "bgr", True, seed=11)
     dst = LC.dst_layout(src, True)
     d, dd, turned = to_device(src.buf), to_device(dst.buf), to_device(np.zeros(2 * 64 * 48 * 3, np.uint8))
     warm = oa.Detector(64, 48, max_batch=1)      # (the process's first launches load the code object)
@@ -230,7 +210,7 @@ def test_refusals_launch_nothing(oa, L):
     ctx = det._ctx
     W, Hh, n = 64, 32, 2
     src_h = np.full(n * 4 * W * Hh + 64, 77, np.uint8)
-    dst_h = np.full(n * 4 * W * Hh + 64, LC.GUARD, np.uint8)
+    dst_h = np.full(n * 4 * W * Hh + 64, FK.GUARD, np.uint8)
     ds, dd = to_device(src_h), to_device(dst_h)
     torch.cuda.synchronize()
     free_before = torch.cuda.mem_get_info()[0]
@@ -291,7 +271,7 @@ def test_the_chain_on_the_device(oa, L, size):
     det.set_camera(oa.Camera.from_buffer_copy(bytes(cam)))
     det.set_input_format("gray")
     d_src = to_device(np.stack(frames))
-    d_planes = to_device(np.full(n * w * h, LC.GUARD, np.uint8))
+    d_planes = to_device(np.full(n * w * h, FK.GUARD, np.uint8))
     torch.cuda.synchronize()
     for f0, k, p in groups:
         det.levels(d_src.data_ptr() + f0 * w * h * 3, d_planes.data_ptr() + f0 * w * h, w, h, k, params=lib_params(oa, p), fmt="bgr")

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+from frame_kit import oa  # noqa: F401
 from test_gpu_parity import OracleFrame, check_candidates, check_markers, check_planes
 
 pytestmark = pytest.mark.gpu
@@ -90,14 +91,6 @@ class Scene:
         del self.d, self.d_base
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 @pytest.mark.parametrize("w,h,launch,U", [(1920, 1080, 1638, 64), (3840, 2160, 410, 16)], ids=["1080p-1638", "2160p-410"])

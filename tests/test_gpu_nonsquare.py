@@ -10,20 +10,14 @@ import pytest
 
 import helpers as H
 import nonsquare_scenes as NS
+from frame_kit import oa  # noqa: F401
+from hostbuild import host_driver
 
 pytestmark = pytest.mark.gpu
 
 POSE_RTOL = NS.POSE_RTOL
 CAND = np.dtype(H.Candidate)
 CAND_FIELDS = ["markerId", "templateId", "orient", "bit", "square", "patPoint"]
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 def detector(oa, which, cam, batch=16, **kw):
@@ -153,11 +147,11 @@ def test_dense_context_gives_the_same_records(oa):
         assert m0[f, :c0[f]].tobytes() == m1[f, :c1[f]].tobytes(), f
 
 
-def test_corner_refinement_on(oa, tmp_path):
+def test_corner_refinement_on(oa):
     """refinement (5, 30, 0.1) against the host chain of tests/refine_chain.py, which solves the pose of the refined square at
     the record's aspectRatio: squares bit-exact, poses where the reference defines them for the refined square"""
     import refine_chain as RC
-    L = RC.build_emul(tmp_path)
+    L = RC.build_emul()
     runs = NS.runs("A", "pinhole")
     cam = runs[0].scene.cam
     exp = [RC.refined_markers(L, r.ref, r.gray, cam, (5, 30, 0.1)) for r in runs]
@@ -215,11 +209,7 @@ def test_host_mirror_registration_with_templates_from_png(oa, tmp_path):
     loaded = NS.templates_from_png(host, tmp_path)
     tpls = (H.Template * len(loaded))(*loaded)
     assert bytes(tpls) == bytes(NS.library("A")[1])
-    exe = str(tmp_path / "registration_driver")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(H.ROOT, "include"),
-                           "-I" + os.path.join(H.ROOT, "include", "shim"), "-o", exe,
-                           os.path.join(H.ROOT, "tests", "emul", "registration_driver.cpp"),
-                           "-L" + os.path.join(H.PKG, "lib"), "-lopencv-ar", "-Wl,-rpath," + os.path.join(H.PKG, "lib")])
+    exe = host_driver("registration_driver")
     for f, r in enumerate(NS.runs("A", "pinhole")[:2]):
         inp, out = tmp_path / ("in%d.bin" % f), tmp_path / ("out%d.bin" % f)
         inp.write_bytes(np.array([NS.WIDTH, NS.HEIGHT, len(tpls)], np.int32).tobytes() + bytes(tpls) + bytes(r.scene.cam) +

@@ -6,15 +6,16 @@ import itertools
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
 import orient_chain as OR
 import overlay_chain as OC
 import persp_synth as PS
+from frame_kit import E_ARG, hand_made_records, oa, same, to_device  # noqa: F401
 from test_gpu_parity import OracleFrame, check_markers
 
 pytestmark = pytest.mark.gpu
 
-E_ARG = OR.E_ARG
 POSE_RTOL = 1e-4   # tests/test_gpu_parity.py: check_markers
 # widths and heights that straddle the transposing kernel's run (4), the row kernels' run (8), the tile (64), two tiles; the widths
 # also a wave's span of the row kernels (512)
@@ -23,26 +24,13 @@ HEIGHTS = [1, OR.ROW_GROUP + 1, 2 * OR.ROW_GROUP, OR.TILE, OR.TILE + 1, 2 * OR.T
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return OR.build_emul(tmp_path_factory.mktemp("orient_emul"))
+def L():
+    return OR.build_emul()
 
 
 @pytest.fixture(scope="module")
 def det(oa):
     return oa.Detector(64, 32, max_batch=1)   # (neither the sizes nor n_frames are bound by the context's)
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to("cuda:0")
 
 
 def device_orient(det, src, dst, o, buf=None, src_offset=None, src_size=None):
@@ -58,16 +46,9 @@ def device_orient(det, src, dst, o, buf=None, src_offset=None, src_size=None):
     return dd.cpu().numpy(), d.cpu().numpy()
 
 
-def same(got, want, inside, where):
-    bad = np.flatnonzero(got != want)
-    if bad.size:
-        raise AssertionError("%s: %d bytes differ (%d of them guard bytes), first at byte %d of the buffer: %d != %d" % (
-            where, bad.size, int((~inside[bad]).sum()), int(bad[0]), got[bad[0]], want[bad[0]]))
-
-
 # ---- the sweep ----------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("fmt", OR.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 def test_orient_sweep(oa, L, det, fmt):
     """every orientation on every width x height, 1 and 3 frames, on the dword path (everything a multiple of 4) and on the byte path
     (an odd lead, odd paddings, a frame gap of 5): the host core's buffer each time, the same pixels on both paths, the source
@@ -78,10 +59,10 @@ def test_orient_sweep(oa, L, det, fmt):
         where = "%s %s %dx%d x %d" % (OR.NAMES[o], fmt, w, h, n)
         pixels = []
         for aligned in (True, False):
-            src = OR.pix_layout(n, w, h, fmt, aligned, seed=w + k)
+            src = FK.pix_layout(n, w, h, fmt, aligned, seed=w + k)
             dst = OR.dst_layout(src, o, aligned)
             rc, want = OR.host_orient(L, src, dst, o)
-            assert rc == 0 and (want[~dst.pixel_mask()] == OR.GUARD).all()
+            assert rc == 0 and (want[~dst.pixel_mask()] == FK.GUARD).all()
             got, src_after = device_orient(det, src, dst, o)
             assert (src_after == src.buf).all(), where
             same(got, want, dst.pixel_mask(), where + " aligned=%s" % aligned)
@@ -96,7 +77,7 @@ def test_reversed_rows_whose_width_is_no_multiple_of_four(oa, L, det):
     per pixel whose rows are not, next to ones whose rows are"""
     for fmt, w in [("gray", 30), ("gray", 32), ("gray", 521), ("bgr", 30), ("bgr", 32), ("bgr", 523)]:
         for o in ("flip_h", "rot180"):
-            src = OR.pix_layout(2, w, 3, fmt, True, seed=w)
+            src = FK.pix_layout(2, w, 3, fmt, True, seed=w)
             dst = OR.dst_layout(src, o, True)
             rc, want = OR.host_orient(L, src, dst, o)
             got, _ = device_orient(det, src, dst, o)
@@ -110,10 +91,10 @@ def test_source_rectangle(oa, L, det, aligned):
     """a rectangle inside a larger guarded frame, as a pointer offset with the full frame's strides, into a padded destination: the
     bytes of the cropped copy, for every orientation"""
     n, fmt = 2, "bgr"
-    big = OR.pix_layout(n, 150, 90, fmt, aligned, seed=11)
+    big = FK.pix_layout(n, 150, 90, fmt, aligned, seed=11)
     x0, y0, rw, rh = (8 if aligned else 7), 5, 96, 70     # (8 pixels of 3 bytes keep the aligned case aligned)
     off = big.offset(0) + y0 * big.row_stride + x0 * big.bpp
-    crop = OR.pix_layout(n, rw, rh, fmt, aligned)
+    crop = FK.pix_layout(n, rw, rh, fmt, aligned)
     for f in range(n):
         crop.view(f)[...] = big.view(f)[y0:y0 + rh, x0:x0 + rw]
     for o in range(8):
@@ -134,11 +115,11 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
     import torch
     n, lead = 65537, 64
     rng = np.random.default_rng(2)
-    src = np.full(lead + 2 * n + lead, OR.GUARD, np.uint8)
+    src = np.full(lead + 2 * n + lead, FK.GUARD, np.uint8)
     src[lead:lead + 2 * n] = rng.integers(0, 256, 2 * n, dtype=np.uint8)
-    dst = np.full(lead + 2 * n + lead, OR.GUARD, np.uint8)
+    dst = np.full(lead + 2 * n + lead, FK.GUARD, np.uint8)
     want = dst.copy()
-    assert L.orient_emul(src.ctypes.data + lead, 2, 1, 2, 2, want.ctypes.data + lead, 1, 2, n, OR.FORMATS["gray"], 1) == 0
+    assert L.orient_emul(src.ctypes.data + lead, 2, 1, 2, 2, want.ctypes.data + lead, 1, 2, n, FK.FORMATS["gray"], 1) == 0
     assert (want[lead:lead + 2 * n] == src[lead:lead + 2 * n]).all()    # (a 2 x 1 row turned clockwise is the same two bytes as a column)
     d, dd = to_device(src), to_device(dst)
     torch.cuda.synchronize()
@@ -146,7 +127,7 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
     torch.cuda.synchronize()
     got = dd.cpu().numpy()
     assert (got == want).all(), np.flatnonzero(got != want)[:4].tolist()
-    assert (got[lead + 2 * 65535: lead + 2 * n] != OR.GUARD).any()   # (the frames of the second launch)
+    assert (got[lead + 2 * 65535: lead + 2 * n] != FK.GUARD).any()   # (the frames of the second launch)
     # and under ROT270_CW every frame's two bytes are swapped
     dd = to_device(dst)
     det.orient(d.data_ptr() + lead, 2, 1, dd.data_ptr() + lead, n, "rot270", fmt="gray")
@@ -163,7 +144,7 @@ def test_refusals_launch_nothing(oa, L):
     ctx = det._ctx
     SW, SH, n = 64, 32, 2
     src_h = np.full(n * 4 * SW * SH + 64, 77, np.uint8)
-    dst_h = np.full(n * 4 * SW * SH + 64, OR.GUARD, np.uint8)
+    dst_h = np.full(n * 4 * SW * SH + 64, FK.GUARD, np.uint8)
     ds, dd = to_device(src_h), to_device(dst_h)
     torch.cuda.synchronize()
     sp, dp = ds.data_ptr(), dd.data_ptr()
@@ -205,7 +186,7 @@ def test_refusals_launch_nothing(oa, L):
         assert (dd.cpu().numpy() == want).all()
 
     # orient_records
-    recs = to_device(np.zeros(2 * 4, OC.MARKER_DTYPE))
+    recs = to_device(np.zeros(2 * 4, FK.MARKER_DTYPE))
     counts = to_device(np.array([4, 4], np.int32))
     before = recs.cpu().numpy().copy()
 
@@ -238,21 +219,6 @@ def test_refusals_launch_nothing(oa, L):
 
 # ---- orient_records -------------------------------------------------------------------------------------------------------------------
 
-def hand_made_records(rng, n, slots, W, Hh):
-    """[n, slots] records with every field filled: convex squares in and around the frame and the frame's corners"""
-    sq = np.zeros((n * slots, 4, 2), np.float32)
-    for k in range(n * slots):
-        s, a = rng.uniform(8, 0.4 * Hh), rng.uniform(0, 2 * np.pi)
-        c = np.array([rng.uniform(-5, W + 5), rng.uniform(-5, Hh + 5)])
-        ang = a + np.arange(4) * np.pi / 2
-        sq[k] = c + s / np.sqrt(2) * np.stack([np.cos(ang), np.sin(ang)], 1)
-    r = OC.records(sq, template_ids=rng.integers(0, 9, n * slots), scores=rng.integers(0, 2, n * slots))
-    r["glMatrix"] = rng.normal(size=(n * slots, 16))
-    r["aspectRatio"] = rng.uniform(0.5, 2, n * slots)
-    r["square"][0] = [0, 0, W - 1, 0, W - 1, Hh - 1, 0, Hh - 1]
-    return r.reshape(n, slots)
-
-
 @pytest.mark.parametrize("pose", [False, True])
 @pytest.mark.parametrize("slots,in_place", [(1, True), (5, False), ("all", True), ("all", False)])
 def test_orient_records(oa, L, pose, slots, in_place):
@@ -277,7 +243,7 @@ def test_orient_records(oa, L, pose, slots, in_place):
         rc, want_new = OR.host_orient_records(L, recs, live, size, o, pose=pose, cam=cam_o)
         assert rc == 0
         written = np.arange(slots)[None, :] < live[:, None]
-        guard = np.frombuffer(np.full(recs.nbytes, OR.GUARD, np.uint8).tobytes(), OC.MARKER_DTYPE).reshape(n, slots)
+        guard = np.frombuffer(np.full(recs.nbytes, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(n, slots)
         before = recs.copy() if in_place else guard.copy()
         want = before.copy()
         want[written] = want_new[written]
@@ -287,7 +253,7 @@ def test_orient_records(oa, L, pose, slots, in_place):
         torch.cuda.synchronize()
         det.orient_records(dm.data_ptr(), dc.data_ptr(), n, do.data_ptr(), size, o, per_frame=slots, pose=pose)
         torch.cuda.synchronize()
-        got = do.cpu().numpy().view(OC.MARKER_DTYPE).reshape(n, slots)
+        got = do.cpu().numpy().view(FK.MARKER_DTYPE).reshape(n, slots)
         if pose:
             g, w = got["glMatrix"][written], want["glMatrix"][written]
             for a, b in zip(g, w):
@@ -304,7 +270,7 @@ def test_orient_records(oa, L, pose, slots, in_place):
 COLOUR = np.array([250, 10, 200, 255], np.uint8)   # R G B A
 
 
-def test_the_chain_on_the_device(oa, L, tmp_path_factory):
+def test_the_chain_on_the_device(oa, L):
     """the feature end to end: the CPU chain's 1280 x 960 scenes delivered turned by ROT90_CW (960 x 1280), turned upright on the
     device (ROT270_CW), detected there with the upright camera, the records handed over on the device, carried back with ROT90_CW and
     drawn on the frames as they were delivered -- the oracle's markers on the upright frames, the upright frames themselves, the
@@ -323,16 +289,16 @@ def test_the_chain_on_the_device(oa, L, tmp_path_factory):
     painter = oa.Detector(TW, TH, max_batch=1)     # render_records is bound by its context's size: a context for the turned frames
     overlay = np.broadcast_to(COLOUR, (4, 4, 4)).copy()
     painter.set_overlay(-1, overlay)
-    upright = OR.pix_layout(n, FW, FH, "bgr", True)
-    delivered = OR.pix_layout(n, TW, TH, "bgr", True)
+    upright = FK.pix_layout(n, FW, FH, "bgr", True)
+    delivered = FK.pix_layout(n, TW, TH, "bgr", True)
     for f, sc in enumerate(scenes):
         upright.view(f)[...] = sc.frame
         delivered.view(f)[...] = OR.np_orient(sc.frame, "rot90")
-    blank = OR.pix_layout(n, FW, FH, "bgr", True, fill=OR.GUARD)
+    blank = FK.pix_layout(n, FW, FH, "bgr", True, fill=FK.GUARD)
     M = det.max_markers
     d_delivered, d_upright = to_device(delivered.buf), to_device(blank.buf)
-    d_recs, d_counts = to_device(np.full(n * M * OC.MARKER_DTYPE.itemsize, OR.GUARD, np.uint8)), to_device(np.zeros(n, np.int32))
-    d_back = to_device(np.full(n * M * OC.MARKER_DTYPE.itemsize, OR.GUARD, np.uint8))
+    d_recs, d_counts = to_device(np.full(n * M * FK.MARKER_DTYPE.itemsize, FK.GUARD, np.uint8)), to_device(np.zeros(n, np.int32))
+    d_back = to_device(np.full(n * M * FK.MARKER_DTYPE.itemsize, FK.GUARD, np.uint8))
     torch.cuda.synchronize()
     # one stream, nothing waited for in between
     s = det.stream_ptr()
@@ -351,22 +317,22 @@ def test_the_chain_on_the_device(oa, L, tmp_path_factory):
         ref = OracleFrame(np.ascontiguousarray(scenes[f].frame), tpls, cam, planes=False)
         assert len(ref.markers) == 1
         check_markers(f, ref, markers, counts, where="chain")
-    recs = d_recs.cpu().numpy().view(OC.MARKER_DTYPE).reshape(n, M)
+    recs = d_recs.cpu().numpy().view(FK.MARKER_DTYPE).reshape(n, M)
     assert all(recs[f, :counts[f]].tobytes() == markers[f, :counts[f]].tobytes() for f in range(n))
-    want_back = np.frombuffer(np.full(recs.nbytes, OR.GUARD, np.uint8).tobytes(), OC.MARKER_DTYPE).reshape(n, M).copy()
+    want_back = np.frombuffer(np.full(recs.nbytes, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(n, M).copy()
     for f in range(n):
         want_back[f, :counts[f]] = recs[f, :counts[f]]
         want_back["square"][f, :counts[f]] = OR.np_orient_squares(recs["square"][f, :counts[f]], (FW, FH), "rot90")
     rc, host_back = OR.host_orient_records(L, recs, counts, (FW, FH), "rot90", out=want_back)
     assert rc == 0 and host_back.tobytes() == want_back.tobytes()
-    got_back = d_back.cpu().numpy().view(OC.MARKER_DTYPE).reshape(n, M)
+    got_back = d_back.cpu().numpy().view(FK.MARKER_DTYPE).reshape(n, M)
     assert got_back.tobytes() == want_back.tobytes()
     for f in range(n):
         p = scenes[f].markers[0]
         truth = PS.PlantedMarker(OR.np_orient_points(p.quad, (FW, FH), "rot90"), p.R, p.t, p.template, p.tilt, p.size)
         m, kk, d = PS.match(got_back[f, 0]["square"], [truth])
         assert m is truth and kk is not None, (f, d)
-    LO = OC.build_emul(tmp_path_factory.mktemp("overlay_emul"))
+    LO = OC.build_emul()
     rendered, drawn = OC.host_render(LO, delivered, want_back, counts, {-1: overlay})
     assert min(drawn) >= 1 and (rendered != delivered.buf).any()
     same(d_delivered.cpu().numpy(), rendered, delivered.pixel_mask(), "rendered")

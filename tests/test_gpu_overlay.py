@@ -7,27 +7,20 @@ import numpy as np
 import pytest
 
 import dense_synth as DS
+import frame_kit as FK
 import helpers as H
 import overlay_chain as OC
 import persp_synth as PS
+from frame_kit import E_ARG, oa, same, to_device  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SET5 = (5, 30, 0.1)
-E_ARG = -2
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return OC.build_emul(tmp_path_factory.mktemp("overlay_emul"))
+def L():
+    return OC.build_emul()
 
 
 @pytest.fixture(scope="module")
@@ -45,11 +38,6 @@ def det320(oa, overlays):
     return det
 
 
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to("cuda:0")
-
-
 def device_render_records(det, fr, recs, counts, per_frame, buf=None):
     """det.render_records on a device copy of fr.buf (or buf) -> the buffer afterwards"""
     import torch
@@ -60,12 +48,6 @@ def device_render_records(det, fr, recs, counts, per_frame, buf=None):
                        fmt=fr.fmt, row_stride=fr.row_stride, frame_stride=fr.frame_stride)
     torch.cuda.synchronize()
     return d.cpu().numpy()
-
-
-def same(got, want, fr, where):
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, "%s: %d bytes differ (%d of them guard bytes), first at %d: %d != %d" % (
-        where, bad.size, int((~fr.pixel_mask()[bad]).sum()), bad[0], got[bad[0]], want[bad[0]])
 
 
 def six_records(W, Hh):
@@ -79,9 +61,9 @@ def six_records(W, Hh):
     degenerate = [3, 3, 9, 9, 15, 15, 21, 21]
     whole = [-3, -2, W + 2, -3, W + 3, Hh + 2, -2, Hh + 3]
     tiny = [9.75, 9.8, 10.3, 9.75, 10.35, 10.3, 9.8, 10.25]
-    recs = np.zeros((3, 8), OC.MARKER_DTYPE)
-    recs[1, :1] = OC.records([tiny], [1])
-    recs[2, :6] = OC.records([whole, pair_a, pair_b, corner, outside, degenerate], [0, 2, 3, 1, 2, 3])
+    recs = np.zeros((3, 8), FK.MARKER_DTYPE)
+    recs[1, :1] = FK.records([tiny], [1])
+    recs[2, :6] = FK.records([whole, pair_a, pair_b, corner, outside, degenerate], [0, 2, 3, 1, 2, 3])
     return recs, [0, 1, 6]
 
 
@@ -90,11 +72,11 @@ def six_records(W, Hh):
 @pytest.mark.parametrize("size", [(61, 37), (64, 64), (257, 131)])
 def test_render_records_on_hand_made_records(L, det320, overlays, size, fmt, row_pad):
     W, Hh = size
-    fr = OC.Frames(3, W, Hh, fmt, row_pad=row_pad, frame_gap=12, seed=W + row_pad)
+    fr = FK.Frames(3, W, Hh, fmt, row_pad=row_pad, frame_gap=12, seed=W + row_pad)
     recs, counts = six_records(W, Hh)
     want, drawn = OC.host_render(L, fr, recs, counts, overlays)
     assert drawn == [0, 1, 4]   # (outside and degenerate draw nothing)
-    assert (want != fr.buf).any() and (want[~fr.pixel_mask()] == OC.GUARD).all()
+    assert (want != fr.buf).any() and (want[~fr.pixel_mask()] == FK.GUARD).all()
     got = device_render_records(det320, fr, recs, counts, 8)
     same(got, want, fr, "%dx%d %s pad %d" % (W, Hh, fmt, row_pad))
 
@@ -107,13 +89,13 @@ def scattered(rng, n, W, Hh, lo, hi, n_tids):
         c = np.array([rng.uniform(-5, W + 5), rng.uniform(-5, Hh + 5)])
         ang = a + np.arange(4) * np.pi / 2
         sq[k] = c + s / np.sqrt(2) * np.stack([np.cos(ang), np.sin(ang)], 1)
-    return OC.records(sq, rng.integers(0, n_tids, n))
+    return FK.records(sq, rng.integers(0, n_tids, n))
 
 
 @pytest.mark.parametrize("stride", [1, 8, 64])
 def test_record_strides_and_counts_above_the_stride(L, det320, overlays, stride):
     rng = np.random.default_rng(50 + stride)
-    fr = OC.Frames(2, 200, 120, "bgr", row_pad=0, seed=stride)
+    fr = FK.Frames(2, 200, 120, "bgr", row_pad=0, seed=stride)
     recs = np.stack([scattered(rng, stride, 200, 120, 10, 60, 4) for _ in range(2)])
     given = [stride + 5, 10 ** 6]          # read as the stride
     want, drawn = OC.host_render(L, fr, recs, [stride, stride], overlays)
@@ -128,7 +110,7 @@ def test_dense_context_walks_its_list_beyond_64(oa, L, overlays):
     for t, o in overlays.items():
         det.set_overlay(t if t else -1, o)   # (the 2 x 2 one as the default overlay)
     rng = np.random.default_rng(60)
-    fr = OC.Frames(1, 320, 240, "rgba", seed=60)
+    fr = FK.Frames(1, 320, 240, "rgba", seed=60)
     recs = scattered(rng, 512, 320, 240, 4, 40, 6)[None]
     ovs = {(t if t else -1): o for t, o in overlays.items()}
     want, drawn = OC.host_render(L, fr, recs, [512], ovs)
@@ -141,7 +123,7 @@ def test_more_frames_than_the_context_holds_go_in_chunks(oa, L, overlays):
     det = oa.Detector(64, 64, max_batch=2)
     det.set_overlay(-1, overlays[2])
     rng = np.random.default_rng(70)
-    fr = OC.Frames(5, 64, 48, "rgb", row_pad=4, seed=70)
+    fr = FK.Frames(5, 64, 48, "rgb", row_pad=4, seed=70)
     recs = np.stack([scattered(rng, 64, 64, 48, 8, 30, 1) for _ in range(5)])
     counts = [3, 0, 64, 7, 1]
     want, drawn = OC.host_render(L, fr, recs, counts, {-1: overlays[2]})
@@ -182,7 +164,7 @@ def e2e_detector(oa, sc, refine=None, overlay=True, gate=None):
 
 
 def frames_of(sc):
-    fr = OC.Frames(N_E2E, sc["cfg"].width, sc["cfg"].height, "bgr")
+    fr = FK.Frames(N_E2E, sc["cfg"].width, sc["cfg"].height, "bgr")
     for f in range(N_E2E):
         fr.view(f)[...] = sc["frames"][f]
     return fr
@@ -291,7 +273,7 @@ def test_refusals_leave_the_frames_alone(oa, overlays):
     W, Hh = 320, 240
     frames = np.full((2, Hh, W, 3), 200, np.uint8)
     d = to_device(frames)
-    recs = to_device(OC.records([OC.axis_square(5, 5, 50, 50)] * 2).reshape(2, 1))
+    recs = to_device(FK.records([FK.axis_square(5, 5, 50, 50)] * 2).reshape(2, 1))
     cnt = to_device(np.array([1, 1], np.int32))
     torch.cuda.synchronize()
     fp, rp, cp = d.data_ptr(), recs.data_ptr(), cnt.data_ptr()

@@ -9,19 +9,12 @@ import pytest
 
 import helpers as H
 from border_shapes import sawtooth_frame
+from frame_kit import oa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 POSE_RTOL = 1e-4   # north_star: glMatrix within 1e-4 relative
 CORNER_TOL = 0.5   # north_star: quad corners within 0.5 px
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 def make_detector(oa, cfg, names, batch):

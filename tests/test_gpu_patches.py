@@ -5,45 +5,32 @@ included, and every status."""
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
 import overlay_chain as OC
 import patch_chain as PC
+from frame_kit import E_ARG, FMTS, oa, to_device  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SET5 = (5, 30, 0.1)
-E_ARG = -2
-FMTS = ["bgr", "rgb", "bgra", "rgba", "gray"]
 FRAME_SIZES = [(61, 37), (64, 64), (257, 131)]
 PATCH_SIZES = [s for s in PC.SIZES if s != (16, 16)]
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
+def L():
+    return PC.build_emul()
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return PC.build_emul(tmp_path_factory.mktemp("patch_emul"))
-
-
-@pytest.fixture(scope="module")
-def LO(tmp_path_factory):
-    return OC.build_emul(tmp_path_factory.mktemp("overlay_emul"))
+def LO():
+    return OC.build_emul()
 
 
 @pytest.fixture(scope="module")
 def det320(oa):
     return oa.Detector(320, 240, max_batch=2)
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to("cuda:0")
 
 
 def device_patches_records(det, fr, recs, counts, pt, flags=0, with_status=True, buf=None):
@@ -67,7 +54,7 @@ def device_patches_records(det, fr, recs, counts, pt, flags=0, with_status=True,
 def same(got, want, pt, where):
     bad = np.flatnonzero(got != want)
     if bad.size:
-        inside = (bad >= pt.lead) & (bad < got.size - PC.LEAD)
+        inside = (bad >= pt.lead) & (bad < got.size - FK.LEAD)
         slot = (bad[0] - pt.lead) // pt.slot_bytes
         raise AssertionError("%s: %d bytes differ (%d of them outside the block), first at %d (frame %d slot %d byte %d): %d != %d" % (
             where, bad.size, int((~inside).sum()), bad[0], slot // pt.slots, slot % pt.slots, (bad[0] - pt.lead) % pt.slot_bytes,
@@ -88,10 +75,10 @@ def hand_made_records(W, Hh):
     tiny = [9.75, 9.8, 10.3, 9.75, 10.35, 10.3, 9.8, 10.25]
     nan, inf, far = list(pair_a), list(pair_b), list(whole)
     nan[7], inf[0], far[2] = np.nan, np.inf, -2e6
-    recs = np.zeros((3, 12), OC.MARKER_DTYPE)
-    recs[0, :2] = OC.records([pair_a, pair_b])
-    recs[1, :3] = OC.records([tiny, pair_a, whole])
-    recs[2, :10] = OC.records([whole, pair_a, pair_b, corner, outside, degenerate, nan, inf, far, pair_b], scores=[1, 1, 1, 1, 1, 1, 1, 1, 1, 0])
+    recs = np.zeros((3, 12), FK.MARKER_DTYPE)
+    recs[0, :2] = FK.records([pair_a, pair_b])
+    recs[1, :3] = FK.records([tiny, pair_a, whole])
+    recs[2, :10] = FK.records([whole, pair_a, pair_b, corner, outside, degenerate, nan, inf, far, pair_b], scores=[1, 1, 1, 1, 1, 1, 1, 1, 1, 0])
     plain = [[0] * 12, [1] + [0] * 11, [1, 1, 1, 1, 1, 0, 0, 0, 0, 1, 0, 0]]
     matched = [[0] * 12, [1] + [0] * 11, [1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]]
     return recs, [0, 1, 10], plain, matched
@@ -111,12 +98,12 @@ def test_the_hand_made_cases_cover_every_value_with_every_format():
 def test_patches_records_on_hand_made_records(L, det320, fmt, size, row_pad, patch, flags):
     W, Hh = size
     pw, ph = patch
-    fr = OC.Frames(3, W, Hh, fmt, row_pad=row_pad, frame_gap=12, seed=W + row_pad)
+    fr = FK.Frames(3, W, Hh, fmt, row_pad=row_pad, frame_gap=12, seed=W + row_pad)
     recs, counts, plain, matched = hand_made_records(W, Hh)
     pt, want, want_status = PC.host_patches(L, fr, recs, counts, pw, ph, flags)
     assert (want_status == (matched if flags & PC.MATCHED_ONLY else plain)).all()
     v = pt.view(want)
-    assert (v[want_status == 0] == PC.GUARD).all() and (v[2, 4] == 0).all() and (v[2, 0] != v[2, 1]).any()
+    assert (v[want_status == 0] == FK.GUARD).all() and (v[2, 4] == 0).all() and (v[2, 0] != v[2, 1]).any()
     got, status, frames_after = device_patches_records(det320, fr, recs, counts, pt, flags)
     assert (frames_after == fr.buf).all()
     assert (status == want_status).all(), status.tolist()
@@ -124,7 +111,7 @@ def test_patches_records_on_hand_made_records(L, det320, fmt, size, row_pad, pat
 
 
 def scattered(rng, n, W, Hh):
-    return OC.records(PC.random_quads(rng, n, W, Hh), scores=rng.integers(0, 2, n))
+    return FK.records(PC.random_quads(rng, n, W, Hh), scores=rng.integers(0, 2, n))
 
 
 @pytest.mark.parametrize("stride,flags,with_status", [(1, PC.FLIP_ROWS, True), (8, PC.MATCHED_ONLY, False), (64, PC.FLIP_ROWS | PC.MATCHED_ONLY, True)])
@@ -132,10 +119,10 @@ def scattered(rng, n, W, Hh):
 def test_strides_chunks_an_odd_address_and_no_status(L, det320, stride, flags, with_status, fmt, patch):
     """three frames on a context of two; counts above the stride are read as it; the patch block at an odd byte address"""
     rng = np.random.default_rng(50 + stride)
-    fr = OC.Frames(3, 200, 120, fmt, row_pad=1, seed=stride)
+    fr = FK.Frames(3, 200, 120, fmt, row_pad=1, seed=stride)
     recs = np.stack([scattered(rng, stride, 200, 120) for _ in range(3)])
     given = [stride + 5, 10 ** 6, stride - 1 if stride > 1 else 1]
-    pt, want, want_status = PC.host_patches(L, fr, recs, np.minimum(given, stride), patch[0], patch[1], flags, lead=PC.LEAD + 1)
+    pt, want, want_status = PC.host_patches(L, fr, recs, np.minimum(given, stride), patch[0], patch[1], flags, lead=FK.LEAD + 1)
     assert want_status.sum() >= 1
     got, status, _ = device_patches_records(det320, fr, recs, given, pt, flags, with_status=with_status)
     if with_status:
@@ -147,9 +134,9 @@ def test_an_aligned_block_of_whole_dwords_next_to_an_unaligned_one(L, det320):
     """the same records into a block whose address and slot size are multiples of 4 (dword stores) and into one a byte further"""
     rng = np.random.default_rng(77)
     for fmt, (pw, ph) in (("gray", (64, 64)), ("bgr", (20, 7)), ("bgra", (65, 33)), ("gray", (66, 5))):   # (66 x 5: a tail of 2 px)
-        fr = OC.Frames(2, 257, 131, fmt, seed=3)
+        fr = FK.Frames(2, 257, 131, fmt, seed=3)
         recs = np.stack([scattered(rng, 8, 257, 131) for _ in range(2)])
-        for lead in (PC.LEAD, PC.LEAD + 1, PC.LEAD + 2):
+        for lead in (FK.LEAD, FK.LEAD + 1, FK.LEAD + 2):
             pt, want, want_status = PC.host_patches(L, fr, recs, [8, 6], pw, ph, 0, lead=lead)
             got, status, _ = device_patches_records(det320, fr, recs, [8, 6], pt)
             assert (status == want_status).all()
@@ -188,7 +175,7 @@ def e2e_detector(oa, sc, refine=None, gate=None, overlay=False):
 
 
 def frames_of(sc):
-    fr = OC.Frames(N_E2E, sc["cfg"].width, sc["cfg"].height, "bgr")
+    fr = FK.Frames(N_E2E, sc["cfg"].width, sc["cfg"].height, "bgr")
     for f in range(N_E2E):
         fr.view(f)[...] = sc["frames"][f]
     return fr
@@ -300,9 +287,9 @@ def test_refusals_launch_nothing(oa):
     ctx = det._ctx
     W, Hh, M = 320, 240, det.max_markers
     d = to_device(np.full((2, Hh, W, 3), 200, np.uint8))
-    recs = to_device(OC.records([OC.axis_square(5, 5, 50, 50)] * 2).reshape(2, 1))
+    recs = to_device(FK.records([FK.axis_square(5, 5, 50, 50)] * 2).reshape(2, 1))
     cnt = to_device(np.array([1, 1], np.int32))
-    out = np.full(2 * 256 * 256 * 4 + 64, PC.GUARD, np.uint8)
+    out = np.full(2 * 256 * 256 * 4 + 64, FK.GUARD, np.uint8)
     dp = to_device(out)
     ds = to_device(np.full(2 * M, PC.STATUS_FILL, np.int32))
     torch.cuda.synchronize()
@@ -339,5 +326,5 @@ def test_refusals_launch_nothing(oa):
     assert records_call() == 0
     torch.cuda.synchronize()
     got = dp.cpu().numpy()
-    assert (got[:2 * 16 * 16 * 3] == 200).all() and (got[2 * 16 * 16 * 3:] == PC.GUARD).all()
+    assert (got[:2 * 16 * 16 * 3] == 200).all() and (got[2 * 16 * 16 * 3:] == FK.GUARD).all()
     assert (ds.cpu().numpy().view(np.int32)[:2] == 1).all()

@@ -11,6 +11,7 @@ import persp_synth as PS
 import refine_chain as RC
 import test_gpu_parity as GP
 import test_perspective_cpu as TC
+from frame_kit import oa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -19,16 +20,8 @@ MIN_BATCH = 18   # scene frames also sit at batch positions >= 16
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return RC.build_emul(tmp_path_factory.mktemp("refine_emul"))
+def L():
+    return RC.build_emul()
 
 
 class Group:

@@ -6,39 +6,27 @@ import itertools
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
 import overlay_chain as OC
 import persp_synth as PS
 import resize_chain as RC
+from frame_kit import E_ARG, hand_made_records, oa, same, to_device  # noqa: F401
 from test_gpu_parity import OracleFrame, check_markers
 
 pytestmark = pytest.mark.gpu
 
-E_ARG = RC.E_ARG
 POSE_RTOL = 1e-4   # tests/test_gpu_parity.py: check_markers
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return RC.build_emul(tmp_path_factory.mktemp("resize_emul"))
+def L():
+    return RC.build_emul()
 
 
 @pytest.fixture(scope="module")
 def det(oa):
     return oa.Detector(64, 32, max_batch=1)   # (neither the sizes nor n_frames are bound by the context's)
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to("cuda:0")
 
 
 def device_resize(det, src, dst, interp, buf=None, src_offset=None, src_size=None):
@@ -55,13 +43,6 @@ def device_resize(det, src, dst, interp, buf=None, src_offset=None, src_size=Non
     return dd.cpu().numpy(), d.cpu().numpy()
 
 
-def same(got, want, inside, where):
-    bad = np.flatnonzero(got != want)
-    if bad.size:
-        raise AssertionError("%s: %d bytes differ (%d of them guard bytes), first at byte %d of the buffer: %d != %d" % (
-            where, bad.size, int((~inside[bad]).sum()), int(bad[0]), got[bad[0]], want[bad[0]]))
-
-
 # ---- the sweep ----------------------------------------------------------------------------------------------------------------------
 
 # the source side of a destination side d: ratio 2, ratio 3, 1.5, below 1, a source of 1; and blocks the two box kernels do not
@@ -71,7 +52,7 @@ RATIOS = [("x2", lambda d: 2 * d, lambda d: 2 * d), ("x3", lambda d: 3 * d, lamb
           ("one", lambda d: 1, lambda d: 1), ("x4", lambda d: 4 * d, lambda d: 4 * d), ("2x3", lambda d: 2 * d, lambda d: 3 * d)]
 
 
-@pytest.mark.parametrize("fmt", RC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 @pytest.mark.parametrize("interp", list(RC.INTERPS))
 def test_resize_sweep(oa, L, det, interp, fmt):
     """every destination width with every ratio, 1 and 3 frames, on the dword path (everything a multiple of 4) and on the byte path
@@ -85,8 +66,8 @@ def test_resize_sweep(oa, L, det, interp, fmt):
         where = "%s %s %dx%d -> %dx%d x %d" % (interp, fmt, sw, sh, dw, dh, n)
         pixels = []
         for aligned in (True, False):
-            src = RC.pix_layout(n, sw, sh, fmt, aligned, seed=dw + j)
-            dst = RC.pix_layout(n, dw, dh, fmt, aligned, fill=RC.GUARD)
+            src = FK.pix_layout(n, sw, sh, fmt, aligned, seed=dw + j)
+            dst = FK.pix_layout(n, dw, dh, fmt, aligned, fill=FK.GUARD)
             rc, want = RC.host_resize(L, src, dst, interp)
             if interp == "area" and not RC.area_ok(sw, sh, dw, dh):
                 assert rc == E_ARG
@@ -96,7 +77,7 @@ def test_resize_sweep(oa, L, det, interp, fmt):
                 assert lib.ocvar_hip_last_error(det._ctx)
                 assert (dd.cpu().numpy() == dst.buf).all()
                 continue
-            assert rc == 0 and (want[~dst.pixel_mask()] == RC.GUARD).all()
+            assert rc == 0 and (want[~dst.pixel_mask()] == FK.GUARD).all()
             got, src_after = device_resize(det, src, dst, interp)
             assert (src_after == src.buf).all(), where
             same(got, want, dst.pixel_mask(), where + " aligned=%s" % aligned)
@@ -114,8 +95,8 @@ def test_resize_sweep(oa, L, det, interp, fmt):
 def test_a_box_source_that_is_unaligned_under_an_aligned_destination(oa, L, det):
     """the box kernels load whole dwords only when the source is aligned too"""
     for k in (2, 3):
-        src = RC.pix_layout(2, k * 37, k * 3, "bgr", False, seed=k)
-        dst = RC.pix_layout(2, 37, 3, "bgr", True, fill=RC.GUARD)
+        src = FK.pix_layout(2, k * 37, k * 3, "bgr", False, seed=k)
+        dst = FK.pix_layout(2, 37, 3, "bgr", True, fill=FK.GUARD)
         rc, want = RC.host_resize(L, src, dst, "area")
         got, _ = device_resize(det, src, dst, "area")
         same(got, want, dst.pixel_mask(), "box %d" % k)
@@ -123,8 +104,8 @@ def test_a_box_source_that_is_unaligned_under_an_aligned_destination(oa, L, det)
 
 def test_the_largest_ratio_of_the_table(oa, L, det):
     """AREA at a ratio just below 16 on both axes: 18 x 18 taps at most"""
-    src = RC.pix_layout(1, 16 * 21 - 5, 16 * 3 - 1, "bgra", True, seed=3)
-    dst = RC.pix_layout(1, 21, 3, "bgra", True, fill=RC.GUARD)
+    src = FK.pix_layout(1, 16 * 21 - 5, 16 * 3 - 1, "bgra", True, seed=3)
+    dst = FK.pix_layout(1, 21, 3, "bgra", True, fill=FK.GUARD)
     rc, want = RC.host_resize(L, src, dst, "area")
     assert rc == 0
     got, _ = device_resize(det, src, dst, "area")
@@ -138,14 +119,14 @@ def test_the_largest_ratio_of_the_table(oa, L, det):
 def test_source_rectangle(oa, L, det, interp, aligned):
     """a rectangle inside a larger guarded frame, as a pointer offset with the full frame's strides: the bytes of the cropped copy"""
     n, fmt = 2, "bgr"
-    big = RC.pix_layout(n, 150, 40, fmt, aligned, seed=11)
+    big = FK.pix_layout(n, 150, 40, fmt, aligned, seed=11)
     x0, y0, rw, rh = (8 if aligned else 7), 5, 96, 30     # (8 pixels of 3 bytes keep the aligned case aligned)
     dw, dh = 48, 15
     off = big.offset(0) + y0 * big.row_stride + x0 * big.bpp
-    crop = RC.pix_layout(n, rw, rh, fmt, aligned)
+    crop = FK.pix_layout(n, rw, rh, fmt, aligned)
     for f in range(n):
         crop.view(f)[...] = big.view(f)[y0:y0 + rh, x0:x0 + rw]
-    dst = RC.pix_layout(n, dw, dh, fmt, aligned, fill=RC.GUARD)
+    dst = FK.pix_layout(n, dw, dh, fmt, aligned, fill=FK.GUARD)
     rc, want_crop = RC.host_resize(L, crop, dst, interp)
     rc2, want = RC.host_resize(L, big, dst, interp, src_offset=off, src_size=(rw, rh))
     assert rc == 0 and rc2 == 0 and (want == want_crop).all()
@@ -161,9 +142,9 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
     import torch
     n, lead = 65537, 64
     rng = np.random.default_rng(2)
-    src = np.full(lead + 12 * n + lead, RC.GUARD, np.uint8)
+    src = np.full(lead + 12 * n + lead, FK.GUARD, np.uint8)
     src[lead:lead + 12 * n] = rng.integers(0, 256, 12 * n, dtype=np.uint8)
-    dst = np.full(lead + 3 * n + lead, RC.GUARD, np.uint8)
+    dst = np.full(lead + 3 * n + lead, FK.GUARD, np.uint8)
     want = dst.copy()
     assert L.resize_emul(src.ctypes.data + lead, 2, 2, 6, 12, want.ctypes.data + lead, 1, 1, 3, 3, n, 0, 2) == 0
     d, dd = to_device(src), to_device(dst)
@@ -172,7 +153,7 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
     torch.cuda.synchronize()
     got = dd.cpu().numpy()
     assert (got == want).all(), np.flatnonzero(got != want)[:4].tolist()
-    assert (got[lead + 3 * 65535: lead + 3 * n] != RC.GUARD).any()   # (the frames of the second launch)
+    assert (got[lead + 3 * 65535: lead + 3 * n] != FK.GUARD).any()   # (the frames of the second launch)
 
 
 # ---- arguments ------------------------------------------------------------------------------------------------------------------------
@@ -184,7 +165,7 @@ def test_refusals_launch_nothing(oa, L):
     ctx = det._ctx
     SW, SH, DW, DH, n = 64, 32, 32, 16, 2
     src_h = np.full(n * 4 * SW * SH + 64, 77, np.uint8)
-    dst_h = np.full(n * 4 * SW * SH + 64, RC.GUARD, np.uint8)
+    dst_h = np.full(n * 4 * SW * SH + 64, FK.GUARD, np.uint8)
     ds, dd = to_device(src_h), to_device(dst_h)
     torch.cuda.synchronize()
     sp, dp = ds.data_ptr(), dd.data_ptr()
@@ -226,7 +207,7 @@ def test_refusals_launch_nothing(oa, L):
     torch.cuda.synchronize()
 
     # scale_records
-    recs = to_device(np.zeros(2 * 4, OC.MARKER_DTYPE))
+    recs = to_device(np.zeros(2 * 4, FK.MARKER_DTYPE))
     counts = to_device(np.array([4, 4], np.int32))
     before = recs.cpu().numpy().copy()
 
@@ -250,22 +231,6 @@ def test_refusals_launch_nothing(oa, L):
 
 # ---- scale_records --------------------------------------------------------------------------------------------------------------------
 
-def hand_made_records(rng, n, slots, W, Hh):
-    """[n, slots] records with every field filled: convex squares in and around the frame, the frame's corners, and (where there is
-    room) a NaN and a 1e30 coordinate"""
-    sq = np.zeros((n * slots, 4, 2), np.float32)
-    for k in range(n * slots):
-        s, a = rng.uniform(8, 0.4 * Hh), rng.uniform(0, 2 * np.pi)
-        c = np.array([rng.uniform(-5, W + 5), rng.uniform(-5, Hh + 5)])
-        ang = a + np.arange(4) * np.pi / 2
-        sq[k] = c + s / np.sqrt(2) * np.stack([np.cos(ang), np.sin(ang)], 1)
-    r = OC.records(sq, template_ids=rng.integers(0, 9, n * slots), scores=rng.integers(0, 2, n * slots))
-    r["glMatrix"] = rng.normal(size=(n * slots, 16))
-    r["aspectRatio"] = rng.uniform(0.5, 2, n * slots)
-    r["square"][0] = [0, 0, W - 1, 0, W - 1, Hh - 1, 0, Hh - 1]
-    return r.reshape(n, slots)
-
-
 @pytest.mark.parametrize("dense", [False, True])
 @pytest.mark.parametrize("pose", [False, True])
 @pytest.mark.parametrize("slots,in_place", [(1, True), (5, False), ("all", True), ("all", False)])
@@ -288,7 +253,7 @@ def test_scale_records(oa, L, dense, pose, slots, in_place):
     live = np.minimum(given, slots)
     want_new = RC.host_scale_records(L, recs, live, small, large, pose=pose, cam=cam)
     written = np.arange(slots)[None, :] < live[:, None]
-    guard = np.frombuffer(np.full(recs.nbytes, RC.GUARD, np.uint8).tobytes(), OC.MARKER_DTYPE).reshape(n, slots)
+    guard = np.frombuffer(np.full(recs.nbytes, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(n, slots)
     before = recs.copy() if in_place else guard.copy()
     want = before.copy()
     want[written] = want_new[written]
@@ -299,7 +264,7 @@ def test_scale_records(oa, L, dense, pose, slots, in_place):
     torch.cuda.synchronize()
     det.scale_records(dm.data_ptr(), dc.data_ptr(), n, do.data_ptr(), small, large, per_frame=slots, pose=pose)
     torch.cuda.synchronize()
-    got = do.cpu().numpy().view(OC.MARKER_DTYPE).reshape(n, slots)
+    got = do.cpu().numpy().view(FK.MARKER_DTYPE).reshape(n, slots)
     if pose:
         g, w = got["glMatrix"][written], want["glMatrix"][written]
         for a, b in zip(g, w):
@@ -327,7 +292,7 @@ def test_scale_records_takes_the_camera_of_the_call(oa, L):
     det.scale_records(dm.data_ptr(), dc.data_ptr(), 1, dm.data_ptr(), small, large, per_frame=6, pose=True)
     det.set_camera(oa.Camera.from_buffer_copy(bytes(cam_b)))
     torch.cuda.synchronize()
-    got = dm.cpu().numpy().view(OC.MARKER_DTYPE).reshape(1, 6)
+    got = dm.cpu().numpy().view(FK.MARKER_DTYPE).reshape(1, 6)
     for a, b in zip(got["glMatrix"][0], want_a["glMatrix"][0]):
         assert np.abs(a - b).max() <= POSE_RTOL * max(1.0, np.abs(b).max())
     assert got["square"].tobytes() == want_a["square"].tobytes()
@@ -338,7 +303,7 @@ def test_scale_records_takes_the_camera_of_the_call(oa, L):
 COLOUR = np.array([250, 10, 200, 255], np.uint8)   # R G B A
 
 
-def test_the_chain_on_the_device(oa, L, tmp_path_factory):
+def test_the_chain_on_the_device(oa, L):
     """the feature end to end: the CPU chain's 1280 x 960 scenes shrunk by 2 on the device (AREA), detected by a 640 x 480 context
     with the camera of that size, the records handed over on the device, scaled up with the pose of the large camera and drawn on
     the large frames -- the oracle's markers on the host core's small frames, the host core's scaled records bit for bit, the
@@ -356,16 +321,16 @@ def test_the_chain_on_the_device(oa, L, tmp_path_factory):
     overlay = np.broadcast_to(COLOUR, (4, 4, 4)).copy()
     painter.set_overlay(-1, overlay)
     painter.set_camera(oa.Camera.from_buffer_copy(bytes(cam_full)))
-    full = RC.pix_layout(n, FW, FH, "bgr", True)
+    full = FK.pix_layout(n, FW, FH, "bgr", True)
     for f, sc in enumerate(scenes):
         full.view(f)[...] = sc.frame
-    small = RC.pix_layout(n, W, Hh, "bgr", True, fill=RC.GUARD)
+    small = FK.pix_layout(n, W, Hh, "bgr", True, fill=FK.GUARD)
     rc, want_small = RC.host_resize(L, full, small, "area")
     assert rc == 0
     M = det.max_markers
     d_full, d_small = to_device(full.buf), to_device(small.buf)
-    d_recs, d_counts = to_device(np.full(n * M * OC.MARKER_DTYPE.itemsize, RC.GUARD, np.uint8)), to_device(np.zeros(n, np.int32))
-    d_up = to_device(np.full(n * M * OC.MARKER_DTYPE.itemsize, RC.GUARD, np.uint8))
+    d_recs, d_counts = to_device(np.full(n * M * FK.MARKER_DTYPE.itemsize, FK.GUARD, np.uint8)), to_device(np.zeros(n, np.int32))
+    d_up = to_device(np.full(n * M * FK.MARKER_DTYPE.itemsize, FK.GUARD, np.uint8))
     torch.cuda.synchronize()
     # one stream, nothing waited for in between
     s = det.stream_ptr()
@@ -384,10 +349,10 @@ def test_the_chain_on_the_device(oa, L, tmp_path_factory):
         ref = OracleFrame(np.ascontiguousarray(small.view(f, want_small)), tpls, cam_small, planes=False)
         assert len(ref.markers) == 1
         check_markers(f, ref, markers, counts, where="chain")
-    recs = d_recs.cpu().numpy().view(OC.MARKER_DTYPE).reshape(n, M)
+    recs = d_recs.cpu().numpy().view(FK.MARKER_DTYPE).reshape(n, M)
     assert all(recs[f, :counts[f]].tobytes() == markers[f, :counts[f]].tobytes() for f in range(n))
     want_up = RC.host_scale_records(L, recs, counts, (W, Hh), (FW, FH), pose=True, cam=cam_full)
-    got_up = d_up.cpu().numpy().view(OC.MARKER_DTYPE).reshape(n, M).copy()
+    got_up = d_up.cpu().numpy().view(FK.MARKER_DTYPE).reshape(n, M).copy()
     for f in range(n):
         for k in range(counts[f]):
             a, b = got_up[f, k]["glMatrix"], want_up[f, k]["glMatrix"]
@@ -395,11 +360,11 @@ def test_the_chain_on_the_device(oa, L, tmp_path_factory):
             got_up[f, k]["glMatrix"] = b
             m, kk, d = PS.match(got_up[f, k]["square"], scenes[f].markers)
             assert m is scenes[f].markers[0] and kk is not None, (f, d)
-    want_guarded = np.frombuffer(np.full(recs.nbytes, RC.GUARD, np.uint8).tobytes(), OC.MARKER_DTYPE).reshape(n, M).copy()
+    want_guarded = np.frombuffer(np.full(recs.nbytes, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(n, M).copy()
     for f in range(n):
         want_guarded[f, :counts[f]] = want_up[f, :counts[f]]
     assert got_up.tobytes() == want_guarded.tobytes()
-    LO = OC.build_emul(tmp_path_factory.mktemp("overlay_emul"))
+    LO = OC.build_emul()
     rendered, drawn = OC.host_render(LO, full, want_guarded, counts, {-1: overlay})
     assert min(drawn) >= 1 and (rendered != full.buf).any()
     same(d_full.cpu().numpy(), rendered, full.pixel_mask(), "rendered")

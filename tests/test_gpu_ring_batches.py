@@ -13,6 +13,7 @@ import pytest
 
 import helpers as H
 import ring_batch_scenes as R
+from frame_kit import oa  # noqa: F401
 from test_gpu_parity import OracleFrame, check_candidates, check_markers, make_detector
 from test_gpu_starts import size
 
@@ -22,14 +23,6 @@ GOLDEN = os.path.join(H.ROOT, "tests", "golden", "ring_batches_counters.json")
 # ocvar_hip_counters: frame starts, crop ROIs, crop tiles, crop starts, crop pixels, pool ints, tier-2 starts of the frame and the
 # crop pass, tier-3 starts of the frame and the crop pass
 N_COUNTERS = 10
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 @pytest.fixture(scope="module")

@@ -12,18 +12,11 @@ import pytest
 
 import helpers as H
 import ring_scenes as R
+from frame_kit import oa  # noqa: F401
 from test_gpu_parity import OracleFrame, check_candidates, check_markers, check_planes, make_detector
 from test_gpu_starts import size
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 def crop_plane(det, r):

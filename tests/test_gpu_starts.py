@@ -9,20 +9,13 @@ import pytest
 
 import helpers as H
 import work_cut_scenes as S
+from frame_kit import oa  # noqa: F401
 from helpers import P
 from test_batch_plan_cpu import lib, plan   # noqa: F401  (lib: the fixture that builds tests/emul/plan_emul.cpp)
 from test_gpu_parity import make_detector
 from test_starts_cpu import build_lib
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 @pytest.fixture(scope="module")

@@ -3,26 +3,18 @@ scenes whose markers are drawn from random code grids, against the oracle (which
 frame's markers (ids, score, corners bit-exact, pose within 1e-4) and every pre-elimination candidate must match, through
 Detector.detect_device, Pipe.submit/collect, Pipe.track_device and cvarArMultRegistration of libopencv-ar.so."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import helpers as H
+from frame_kit import E_ARG, oa  # noqa: F401
+from hostbuild import host_driver
 
 pytestmark = pytest.mark.gpu
 
 POSE_RTOL = 1e-4
-E_ARG = -2
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 _libraries = {}
@@ -204,11 +196,7 @@ def test_pipe_submit_collect_and_track_with_1024_templates(oa):
 def test_host_mirror_registration_with_100_templates(oa, tmp_path):
     names, tpls = library("r8", 100)
     cfg, frames = scenes(names, [[99, 0, 50, 0]])
-    exe = str(tmp_path / "registration_driver")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(H.ROOT, "include"),
-                           "-I" + os.path.join(H.ROOT, "include", "shim"), "-o", exe,
-                           os.path.join(H.ROOT, "tests", "emul", "registration_driver.cpp"),
-                           "-L" + os.path.join(H.PKG, "lib"), "-lopencv-ar", "-Wl,-rpath," + os.path.join(H.PKG, "lib")])
+    exe = host_driver("registration_driver")
     cam = H.oracle_camera(cfg.width, cfg.height)
     inp, out = tmp_path / "in.bin", tmp_path / "out.bin"
     inp.write_bytes(np.array([cfg.width, cfg.height, len(tpls)], np.int32).tobytes() + bytes(tpls) + bytes(cam) + frames[0].tobytes())

@@ -4,14 +4,14 @@ the frames and around the block included, and whole record blocks, the slots tha
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
-import overlay_chain as OC
 import persp_synth as PS
 import undistort_chain as UC
+from frame_kit import E_ARG, oa, same, to_device  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-E_ARG = -2
 SHAPES = [(33, 17), (259, 5), (320, 240)]   # a row that ends inside a lane; a row that crosses the 256-pixel span of a wave; many rows
 LENS_NAMES = ["BARREL", "PINCUSHION", "ZERO", "OFF_CENTRE", "WILD"]
 SRC_ROW_PAD = 3
@@ -19,26 +19,13 @@ N_FRAMES = 3   # on a context of max_batch 2
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return UC.build_emul(tmp_path_factory.mktemp("undistort_emul"))
+def L():
+    return UC.build_emul()
 
 
 @pytest.fixture(scope="module")
 def det320(oa):
     return oa.Detector(320, 240, max_batch=2)
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to("cuda:0")
 
 
 def set_camera(oa, det, cam):
@@ -48,13 +35,13 @@ def set_camera(oa, det, cam):
 def dst_layout(W, Hh, fmt, path):
     """the destination of a case: 'dword' -- address, row stride and frame stride multiples of 4 (row padding 4 .. 7 bytes); 'bytes'
     -- a row padding of 1 byte at an odd address"""
-    bpp = OC.BPP[OC.FORMATS[fmt]]
+    bpp = FK.BPP[FK.FORMATS[fmt]]
     if path == "dword":
         pad = 8 - (W * bpp) % 4 if (W * bpp) % 4 else 4
-        d = UC.Dst(N_FRAMES, W, Hh, fmt, row_pad=pad, frame_gap=8, lead=UC.LEAD)
+        d = UC.dst_frames(N_FRAMES, W, Hh, fmt, row_pad=pad, frame_gap=8, lead=FK.LEAD)
         assert d.row_stride % 4 == 0 and d.frame_stride % 4 == 0
     else:
-        d = UC.Dst(N_FRAMES, W, Hh, fmt, row_pad=1, frame_gap=5, lead=UC.LEAD + 1)
+        d = UC.dst_frames(N_FRAMES, W, Hh, fmt, row_pad=1, frame_gap=5, lead=FK.LEAD + 1)
     return d
 
 
@@ -72,22 +59,12 @@ def device_undistort(det, src, dst, buf=None):
     return dd.cpu().numpy(), d.cpu().numpy()
 
 
-def same(got, want, dst, where):
-    bad = np.flatnonzero(got != want)
-    if bad.size:
-        outside = ~dst.pixel_mask()[bad]
-        off = int(bad[0]) - dst.offset(0)
-        raise AssertionError("%s: %d bytes differ (%d of them guard bytes), first at frame %d row %d byte %d: %d != %d" % (
-            where, bad.size, int(outside.sum()), off // dst.frame_stride, off % dst.frame_stride // dst.row_stride,
-            off % dst.frame_stride % dst.row_stride, got[bad[0]], want[bad[0]]))
-
-
 # every lens with every format; shapes and lane-store paths rotate through them
-HAND_MADE = [(fmt, lens, SHAPES[(i + j) % 3], ("dword", "bytes")[(i + j) % 2]) for j, fmt in enumerate(UC.FMTS) for i, lens in enumerate(LENS_NAMES)]
+HAND_MADE = [(fmt, lens, SHAPES[(i + j) % 3], ("dword", "bytes")[(i + j) % 2]) for j, fmt in enumerate(FK.FMTS) for i, lens in enumerate(LENS_NAMES)]
 
 
 def test_the_hand_made_cases_cover_every_format_with_every_lens_shape_and_store_path():
-    for fmt in UC.FMTS:
+    for fmt in FK.FMTS:
         mine = [c for c in HAND_MADE if c[0] == fmt]
         assert {c[1] for c in mine} == set(LENS_NAMES) and {c[2] for c in mine} == set(SHAPES) and {c[3] for c in mine} == {"dword", "bytes"}
         for path in ("dword", "bytes"):   # (each path on a row that ends inside a lane, too)
@@ -100,10 +77,10 @@ def test_undistort_on_hand_made_shapes(oa, L, det320, fmt, lens, shape, path):
     stay"""
     W, Hh = shape
     cam = UC.camera(W, Hh, lens)
-    src = OC.Frames(N_FRAMES, W, Hh, fmt, row_pad=SRC_ROW_PAD, frame_gap=7, seed=W + len(lens))
+    src = FK.Frames(N_FRAMES, W, Hh, fmt, row_pad=SRC_ROW_PAD, frame_gap=7, seed=W + len(lens))
     dst = dst_layout(W, Hh, fmt, path)
     want = UC.host_undistort(L, src, cam, dst)
-    assert (want[~dst.pixel_mask()] == UC.GUARD).all()
+    assert (want[~dst.pixel_mask()] == FK.GUARD).all()
     set_camera(oa, det320, cam)
     got, src_after = device_undistort(det320, src, dst)
     assert (src_after == src.buf).all()
@@ -115,10 +92,10 @@ def test_undistort_on_hand_made_shapes(oa, L, det320, fmt, lens, shape, path):
 
 # ---- records ---------------------------------------------------------------------------------------------------------------------
 
-def hand_made_records(rng, n, slots, W, Hh):
+def lens_records(rng, n, slots, W, Hh):
     """[n, slots] records with every field filled: random squares in and around the frame, the frame's corners, a NaN and a 1e30
     coordinate (an infinite one would make new NaNs, whose sign is the processor's choice)"""
-    r = OC.records(rng.uniform(-30, max(W, Hh) + 30, (n * slots, 8)), template_ids=rng.integers(0, 9, n * slots), scores=rng.integers(0, 2, n * slots))
+    r = FK.records(rng.uniform(-30, max(W, Hh) + 30, (n * slots, 8)), template_ids=rng.integers(0, 9, n * slots), scores=rng.integers(0, 2, n * slots))
     r["glMatrix"] = rng.normal(size=(n * slots, 16))
     r["aspectRatio"] = rng.uniform(0.5, 2, n * slots)
     r["square"][0] = [0, 0, W - 1, 0, W - 1, Hh - 1, 0, Hh - 1]
@@ -135,11 +112,11 @@ def test_undistort_records(oa, L, det320, lens, slots, in_place):
     import torch
     W, Hh, n = 320, 240, 4
     cam = UC.camera(W, Hh, lens)
-    recs = hand_made_records(np.random.default_rng(slots), n, slots, W, Hh)
+    recs = lens_records(np.random.default_rng(slots), n, slots, W, Hh)
     given = [slots - 1, slots, slots + 3, 0]
     want_new = UC.host_records(L, cam, recs, np.minimum(given, slots))
     written = np.arange(slots)[None, :] < np.minimum(given, slots)[:, None]
-    before = recs.copy() if in_place else np.frombuffer(np.full(recs.nbytes, UC.GUARD, np.uint8).tobytes(), OC.MARKER_DTYPE).reshape(n, slots).copy()
+    before = recs.copy() if in_place else np.frombuffer(np.full(recs.nbytes, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(n, slots).copy()
     want = before.copy()
     want[written] = want_new[written]
     for name in ("glMatrix", "templateId", "markerId", "score", "aspectRatio"):   # (every other field as it was)
@@ -189,7 +166,7 @@ def test_the_camera_travels_by_value(oa, L, det960, views):
     import torch
     v = views
     n, W, Hh = 2, 960, 540
-    src, dst = OC.Frames(n, W, Hh, "bgr"), UC.Dst(n, W, Hh, "bgr")
+    src, dst = FK.Frames(n, W, Hh, "bgr"), UC.dst_frames(n, W, Hh, "bgr")
     for f in range(n):
         src.view(f)[...] = v["D"][f]
     want = UC.host_undistort(L, src, v["lens"], dst)
@@ -218,19 +195,19 @@ def test_records_of_the_distorted_frames(oa, L, det960, views):
     n, W, Hh = 2, 960, 540
     set_camera(oa, det960, v["lens"])
     d = to_device(v["D"])
-    dm = to_device(np.full(n * PER * 184, UC.GUARD, np.uint8))
+    dm = to_device(np.full(n * PER * 184, FK.GUARD, np.uint8))
     dc = to_device(np.zeros(n, np.int32))
-    do = to_device(np.full(n * PER * 184, UC.GUARD, np.uint8))
+    do = to_device(np.full(n * PER * 184, FK.GUARD, np.uint8))
     torch.cuda.synchronize()
     det960.enqueue_device(d.data_ptr(), W, Hh, n)
     det960.results_to_device(dm.data_ptr(), dc.data_ptr(), per_frame=PER)
     markers, counts = det960.collect(PER)
     det960.undistort_records(dm.data_ptr(), dc.data_ptr(), n, do.data_ptr(), per_frame=PER)
     torch.cuda.synchronize()
-    got = do.cpu().numpy().view(OC.MARKER_DTYPE).reshape(n, PER)
+    got = do.cpu().numpy().view(FK.MARKER_DTYPE).reshape(n, PER)
     assert (dc.cpu().numpy().view(np.int32) == counts).all() and (counts >= 1).all() and (counts <= PER).all()
-    block = dm.cpu().numpy().view(OC.MARKER_DTYPE).reshape(n, PER)
-    want = np.frombuffer(np.full(n * PER * 184, UC.GUARD, np.uint8).tobytes(), OC.MARKER_DTYPE).reshape(n, PER).copy()
+    block = dm.cpu().numpy().view(FK.MARKER_DTYPE).reshape(n, PER)
+    want = np.frombuffer(np.full(n * PER * 184, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(n, PER).copy()
     mapped = UC.host_records(L, v["lens"], block, counts)
     for f in range(n):
         want[f, :counts[f]] = mapped[f, :counts[f]]
@@ -238,7 +215,7 @@ def test_records_of_the_distorted_frames(oa, L, det960, views):
     for f in range(n):
         ref = H.oracle_registration(v["D"][f], v["tpls"], v["lens"])[0]
         assert counts[f] == len(ref)
-        orc = OC.records([list(r.square) for r in ref]).reshape(1, -1)
+        orc = FK.records([list(r.square) for r in ref]).reshape(1, -1)
         sq = UC.host_records(L, v["lens"], orc, [len(ref)])["square"][0]
         assert got["square"][f, :len(ref)].tobytes() == sq.tobytes()
         assert (sq != orc["square"][0]).any()
@@ -254,11 +231,11 @@ def test_refusals_launch_nothing(oa):
     W, Hh, M = 320, 240, det.max_markers
     frame = 3 * W * Hh
     d = to_device(np.full(3 * frame, 200, np.uint8))
-    out = np.full(2 * frame + 64, UC.GUARD, np.uint8)
+    out = np.full(2 * frame + 64, FK.GUARD, np.uint8)
     dd = to_device(out)
-    recs_h = OC.records([OC.axis_square(5, 5, 50, 50)] * 2).reshape(2, 1)
+    recs_h = FK.records([FK.axis_square(5, 5, 50, 50)] * 2).reshape(2, 1)
     recs, cnt = to_device(recs_h), to_device(np.array([1, 1], np.int32))
-    ro_h = np.full(2 * 184, UC.GUARD, np.uint8)
+    ro_h = np.full(2 * 184, FK.GUARD, np.uint8)
     ro = to_device(ro_h)
     torch.cuda.synchronize()
     sp, dp, rp, cp, op = d.data_ptr(), dd.data_ptr(), recs.data_ptr(), cnt.data_ptr(), ro.data_ptr()
@@ -305,5 +282,5 @@ def test_refusals_launch_nothing(oa):
     assert frames_call() == 0 and records_call() == 0
     torch.cuda.synchronize()
     got = dd.cpu().numpy()
-    assert (got[:2 * frame] == 200).all() and (got[2 * frame:] == UC.GUARD).all()   # (BARREL: nothing outside)
-    assert (ro.cpu().numpy().view(OC.MARKER_DTYPE)["templateId"] == 0).all()
+    assert (got[:2 * frame] == 200).all() and (got[2 * frame:] == FK.GUARD).all()   # (BARREL: nothing outside)
+    assert (ro.cpu().numpy().view(FK.MARKER_DTYPE)["templateId"] == 0).all()

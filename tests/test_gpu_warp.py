@@ -8,15 +8,15 @@ import numpy as np
 import pytest
 
 import board_chain as BC
+import frame_kit as FK
 import helpers as H
-import overlay_chain as OC
 import persp_synth as PS
 import undistort_chain as UC
 import warp_chain as WC
+from frame_kit import E_ARG, hand_made_records, oa, same, to_device  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-E_ARG = WC.E_ARG
 POSE_RTOL = 1e-4   # tests/test_gpu_parity.py: check_markers
 # destination widths and heights on both sides of the kernel's tile, and two tiles and a pixel
 WIDTHS = [WC.TILE_W - 1, WC.TILE_W, WC.TILE_W + 1, 2 * WC.TILE_W + 1]
@@ -26,26 +26,13 @@ FILL = [7, 130, 255, 66]
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return WC.build_emul(tmp_path_factory.mktemp("warp_emul"))
+def L():
+    return WC.build_emul()
 
 
 @pytest.fixture(scope="module")
 def det(oa):
     return oa.Detector(64, 32, max_batch=1)   # (neither the sizes nor n_frames are bound by the context's)
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to("cuda:0")
 
 
 def device_warp(det, src, dst, maps, interp=WC.LINEAR, border=WC.CONSTANT, fill=None, flags=0, with_status=True):
@@ -64,16 +51,9 @@ def device_warp(det, src, dst, maps, interp=WC.LINEAR, border=WC.CONSTANT, fill=
     return dd.cpu().numpy(), ds.cpu().numpy().view(np.int32), d.cpu().numpy()
 
 
-def same(got, want, inside, where):
-    bad = np.flatnonzero(got != want)
-    if bad.size:
-        raise AssertionError("%s: %d bytes differ (%d of them guard bytes), first at byte %d of the buffer: %d != %d" % (
-            where, bad.size, int((~inside[bad]).sum()), int(bad[0]), got[bad[0]], want[bad[0]]))
-
-
 def check(L, det, src, dst, maps, interp, border, fill, flags, where, want_status=None):
     rc, want, status = WC.host_warp(L, src, dst, maps, interp, border, fill, flags)
-    assert rc >= 0 and (want[~dst.pixel_mask()] == WC.GUARD).all()
+    assert rc >= 0 and (want[~dst.pixel_mask()] == FK.GUARD).all()
     if want_status is not None:
         assert status.tolist() == want_status, where
     got, got_status, src_after = device_warp(det, src, dst, maps, interp, border, fill, flags)
@@ -97,7 +77,7 @@ def inverse_maps(src_size, dst_size):
 
 # ---- the sweep ----------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("fmt", WC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 def test_warp_sweep(oa, L, det, fmt):
     """destination widths x heights around the tile, seven frames with a map each (one of them skipped), both interpolations and both
     borders in turn, on the dword path (everything a multiple of 4) and on the byte path (an odd lead, odd paddings, a frame gap of 5):
@@ -109,7 +89,7 @@ def test_warp_sweep(oa, L, det, fmt):
         where = "%s %dx%d interp %d border %d" % (fmt, dw, dh, interp, border)
         pixels = []
         for aligned in (True, False):
-            src = WC.pix_layout(len(maps), *src_size, fmt, aligned, seed=dw + k)
+            src = FK.pix_layout(len(maps), *src_size, fmt, aligned, seed=dw + k)
             dst = WC.dst_layout(src, (dw, dh), aligned)
             got = check(L, det, src, dst, maps, interp, border, FILL, WC.INVERSE_MAP, where + " aligned=%s" % aligned, status)
             pixels.append(np.stack([dst.view(f, got) for f in range(dst.n)]))
@@ -124,7 +104,7 @@ def test_forward_maps_and_one_map(oa, L, det, interp, border):
     shared = WC.shared_maps(src_size, dst_size)
     maps = [shared["mild"][0], WC.SKIPPED_MAPS["singular"], shared["magnify"][0], shared["shift"][0], shared["identity"][0]]
     for fmt, aligned in (("bgr", True), ("gray", False), ("rgba", False)):
-        src = WC.pix_layout(len(maps), *src_size, fmt, aligned, seed=3)
+        src = FK.pix_layout(len(maps), *src_size, fmt, aligned, seed=3)
         dst = WC.dst_layout(src, dst_size, aligned)
         check(L, det, src, dst, maps, interp, border, FILL, 0, "forward %s" % fmt, [1, 0, 1, 1, 1])
         got = check(L, det, src, dst, maps[0], interp, border, None, WC.ONE_MAP, "one map %s" % fmt, [1] * 5)
@@ -141,7 +121,7 @@ def test_smallest_frames_and_a_source_narrower_than_a_dword(oa, L, det):
         maps = [np.array([1, 0, 0, 0, 1, 0, 0, 0, 1.0]), np.array([0.5, 0, 0.25, 0, 0.5, 0.125, 0, 0, 1.0]), np.array([1, 0, -0.5, 0, 1, 0, 0.25, 0, 1.0])]
         for fmt, aligned in itertools.product(("gray", "bgr", "bgra"), (True, False)):
             for interp, border in COMBOS:
-                src = WC.pix_layout(len(maps), sw, sh, fmt, aligned, seed=sw + dw)
+                src = FK.pix_layout(len(maps), sw, sh, fmt, aligned, seed=sw + dw)
                 dst = WC.dst_layout(src, (dw, dh), aligned)
                 check(L, det, src, dst, maps, interp, border, [1, 2, 3, 4], WC.INVERSE_MAP, "%dx%d -> %dx%d %s %s" % (sw, sh, dw, dh, fmt, aligned), [1, 1, 1])
 
@@ -157,10 +137,10 @@ def test_both_classes_give_the_core_bytes(oa, L, case):
     m, flags = WC.shared_maps(src_size, dst_size)[name]
     det = oa.Detector(64, 32, max_batch=1)
     for fmt in ("bgr", "rgba", "gray"):
-        c = WC.plan_counts(L, m, src_size, dst_size, WC.BPP[WC.FORMATS[fmt]], WC.LINEAR, WC.CONSTANT, flags)
+        c = WC.plan_counts(L, m, src_size, dst_size, FK.BPP[FK.FORMATS[fmt]], WC.LINEAR, WC.CONSTANT, flags)
         assert (c["staged"] >= 1) == (classes in ("staged", "both")) and (c["direct"] >= 1) == (classes in ("direct", "both")), (case, fmt, c)
         for (interp, border), aligned in zip(COMBOS, (True, False, True, False)):
-            src = WC.pix_layout(2, *src_size, fmt, aligned, seed=5)
+            src = FK.pix_layout(2, *src_size, fmt, aligned, seed=5)
             dst = WC.dst_layout(src, dst_size, aligned)
             for direct in (0, 1):
                 det.set_tuning(warp_direct=direct)
@@ -176,14 +156,14 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
     import torch
     n, lead = 65537, 64
     rng = np.random.default_rng(2)
-    src = np.full(lead + 2 * n + lead, WC.GUARD, np.uint8)
+    src = np.full(lead + 2 * n + lead, FK.GUARD, np.uint8)
     src[lead:lead + 2 * n] = rng.integers(0, 256, 2 * n, dtype=np.uint8)
-    dst = np.full(lead + 2 * n + lead, WC.GUARD, np.uint8)
+    dst = np.full(lead + 2 * n + lead, FK.GUARD, np.uint8)
     maps = np.tile(np.array([-1, 0, 1, 0, 1, 0, 0, 0, 1.0]), (n, 1))
     maps[1::2] = [1, 0, 0, 0, 1, 0, 0, 0, 1.0]
     maps[::1000, 4] = np.nan
     want, want_status = dst.copy(), np.full(n, -7, np.int32)
-    assert L.warp_emul(src.ctypes.data + lead, 2, 1, 2, 2, want.ctypes.data + lead, 2, 1, 2, 2, n, WC.FORMATS["gray"], maps.ctypes.data, WC.LINEAR,
+    assert L.warp_emul(src.ctypes.data + lead, 2, 1, 2, 2, want.ctypes.data + lead, 2, 1, 2, 2, n, FK.FORMATS["gray"], maps.ctypes.data, WC.LINEAR,
                        WC.CONSTANT, None, WC.INVERSE_MAP, want_status.ctypes.data) == n - len(range(0, n, 1000))
     d, dd, dm, ds = to_device(src), to_device(dst), to_device(maps), to_device(np.full(n, -7, np.int32))
     torch.cuda.synchronize()
@@ -193,7 +173,7 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
     assert (got == want).all(), np.flatnonzero(got != want)[:4].tolist()
     assert (ds.cpu().numpy().view(np.int32) == want_status).all()
     pairs, spairs = got[lead:lead + 2 * n].reshape(n, 2), src[lead:lead + 2 * n].reshape(n, 2)
-    assert (pairs[65536] == spairs[65536][::-1]).all() and (pairs[65535] == spairs[65535]).all() and (pairs[65000] == WC.GUARD).all()
+    assert (pairs[65536] == spairs[65536][::-1]).all() and (pairs[65535] == spairs[65535]).all() and (pairs[65000] == FK.GUARD).all()
 
 
 # ---- arguments ------------------------------------------------------------------------------------------------------------------------
@@ -206,7 +186,7 @@ def test_refusals_launch_nothing(oa, L):
     ctx = det._ctx
     SW, SH, DW, DH, n = 64, 32, 48, 40, 2
     src_h = np.full(n * 4 * SW * SH + 64, 77, np.uint8)
-    dst_h = np.full(n * 4 * DW * DH + 64, WC.GUARD, np.uint8)
+    dst_h = np.full(n * 4 * DW * DH + 64, FK.GUARD, np.uint8)
     maps_h = np.tile(np.array([1, 0, 0, 0, 1, 0, 0, 0, 1.0]), (n, 1))
     ds, dd, dm, dst_ = to_device(src_h), to_device(dst_h), to_device(maps_h), to_device(np.full(n, -7, np.int32))
     torch.cuda.synchronize()
@@ -246,7 +226,7 @@ def test_refusals_launch_nothing(oa, L):
     assert (dd.cpu().numpy() == want).all() and dst_.cpu().numpy().view(np.int32).tolist() == [1, 1]
 
     # warp_records
-    recs = to_device(np.zeros(2 * 4, OC.MARKER_DTYPE))
+    recs = to_device(np.zeros(2 * 4, FK.MARKER_DTYPE))
     counts = to_device(np.array([4, 4], np.int32))
     before = recs.cpu().numpy().copy()
 
@@ -293,7 +273,7 @@ def test_a_context_that_never_warps_allocates_nothing(oa):
     n, W, Hh = 2, 64, 48
     src, dst = to_device(np.zeros(n * W * Hh * 3, np.uint8)), to_device(np.zeros(n * W * Hh * 3, np.uint8))
     maps = to_device(np.tile(np.array([1, 0, 0, 0, 1, 0, 0, 0, 1.0]), (n, 1)))
-    recs, counts = to_device(np.zeros(n * 4, OC.MARKER_DTYPE)), to_device(np.array([4, 4], np.int32))
+    recs, counts = to_device(np.zeros(n * 4, FK.MARKER_DTYPE)), to_device(np.array([4, 4], np.int32))
     poses = to_device(np.zeros(n, oa.BOARD_DTYPE))
 
     def run(det):
@@ -319,20 +299,6 @@ def test_a_context_that_never_warps_allocates_nothing(oa):
 
 # ---- warp_records -----------------------------------------------------------------------------------------------------------------------
 
-def hand_made_records(rng, n, slots, W, Hh):
-    """[n, slots] records with every field filled: convex squares in and around the frame"""
-    sq = np.zeros((n * slots, 4, 2), np.float32)
-    for k in range(n * slots):
-        s, a = rng.uniform(8, 0.4 * Hh), rng.uniform(0, 2 * np.pi)
-        c = np.array([rng.uniform(-5, W + 5), rng.uniform(-5, Hh + 5)])
-        ang = a + np.arange(4) * np.pi / 2
-        sq[k] = c + s / np.sqrt(2) * np.stack([np.cos(ang), np.sin(ang)], 1)
-    r = OC.records(sq, template_ids=rng.integers(0, 9, n * slots), scores=rng.integers(0, 2, n * slots))
-    r["glMatrix"] = rng.normal(size=(n * slots, 16))
-    r["aspectRatio"] = rng.uniform(0.5, 2, n * slots)
-    return r.reshape(n, slots)
-
-
 @pytest.mark.parametrize("pose", [False, True])
 @pytest.mark.parametrize("slots,in_place,one_map", [(1, True, False), (5, False, True), ("all", True, True), ("all", False, False)])
 def test_warp_records(oa, L, pose, slots, in_place, one_map):
@@ -353,7 +319,7 @@ def test_warp_records(oa, L, pose, slots, in_place, one_map):
         maps[1] = [2, 0, 1, 0, 2, 3, 1, 0, -0.25]
     if one_map:
         maps = maps[:1]
-    recs = hand_made_records(np.random.default_rng(slots), n, slots, *size)
+    recs = hand_made_records(np.random.default_rng(slots), n, slots, *size, frame_corners=False)
     if not pose:
         recs["square"][1, 0, :2] = [0.25, 9]        # on the horizon of maps[1]
         if slots >= 4:
@@ -365,7 +331,7 @@ def test_warp_records(oa, L, pose, slots, in_place, one_map):
     rc, want_new = WC.host_warp_records(L, recs, live, maps, flags, cam=cam)
     assert rc == 0
     written = np.arange(slots)[None, :] < live[:, None]
-    guard = np.frombuffer(np.full(recs.nbytes, WC.GUARD, np.uint8).tobytes(), OC.MARKER_DTYPE).reshape(n, slots)
+    guard = np.frombuffer(np.full(recs.nbytes, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(n, slots)
     before = recs.copy() if in_place else guard.copy()
     want = before.copy()
     want[written] = want_new[written]
@@ -376,7 +342,7 @@ def test_warp_records(oa, L, pose, slots, in_place, one_map):
     torch.cuda.synchronize()
     det.warp_records(dm.data_ptr(), dc.data_ptr(), n, do.data_ptr(), dmaps.data_ptr(), per_frame=slots, one_map=one_map, pose=pose)
     torch.cuda.synchronize()
-    got = do.cpu().numpy().view(OC.MARKER_DTYPE).reshape(n, slots)
+    got = do.cpu().numpy().view(FK.MARKER_DTYPE).reshape(n, slots)
     if pose:
         g, w = got["glMatrix"][written], want["glMatrix"][written]
         for a, b in zip(g, w):
@@ -427,7 +393,7 @@ def test_board_plane_maps_to_the_last_bit(oa, L):
 
 # ---- the chain on the device ------------------------------------------------------------------------------------------------------------
 
-def test_the_chain_on_the_device(oa, L, tmp_path_factory):
+def test_the_chain_on_the_device(oa, L):
     """the feature end to end on one stream, nothing waited for in between: frames of a camera with a lens undistorted, detected with
     the board by a context with the pinhole camera of the same matrix, the board poses handed over on the device, the plane maps, the
     warp to bird's-eye frames.  Against the CPU chain: the undistorted frames byte for byte, the device's poses within the board
@@ -441,18 +407,18 @@ def test_the_chain_on_the_device(oa, L, tmp_path_factory):
     n = len(sc)
     tpls = H.oracle_templates(names)
     rect, size = WC.chain_rect(board)
-    Lu, Lb = UC.build_emul(tmp_path_factory.mktemp("undistort_emul")), BC.build_emul(tmp_path_factory.mktemp("board_emul"))
+    Lu, Lb = UC.build_emul(), BC.build_emul()
     lens = oa.Detector(W, Hh, max_batch=1)      # (the context with the lens: undistort is bound by its context's size)
     lens.set_camera(oa.Camera.from_buffer_copy(bytes(lens_cam)))
     det = oa.Detector(W, Hh, max_batch=n)
     det.set_templates([oa.Template.from_buffer_copy(bytes(t)) for t in tpls])
     det.set_camera(oa.Camera.from_buffer_copy(bytes(cam)))
     det.set_board(board)
-    taken = WC.pix_layout(n, W, Hh, "bgr", True)
+    taken = FK.pix_layout(n, W, Hh, "bgr", True)
     for f in range(n):
         taken.view(f)[...] = sc[f][0]
-    flat = WC.pix_layout(n, W, Hh, "bgr", True, fill=WC.GUARD)
-    top = WC.pix_layout(n, size[0], size[1], "bgr", True, fill=WC.GUARD)
+    flat = FK.pix_layout(n, W, Hh, "bgr", True, fill=FK.GUARD)
+    top = FK.pix_layout(n, size[0], size[1], "bgr", True, fill=FK.GUARD)
     d_taken, d_flat, d_top = to_device(taken.buf), to_device(flat.buf), to_device(top.buf)
     d_poses, d_maps, d_status = to_device(np.zeros(n, oa.BOARD_DTYPE)), to_device(np.zeros(9 * n)), to_device(np.full(n, -7, np.int32))
     torch.cuda.synchronize()
@@ -477,7 +443,7 @@ def test_the_chain_on_the_device(oa, L, tmp_path_factory):
     want_maps = WC.host_plane_maps(L, poses, K, rect, size)
     got_maps = d_maps.cpu().numpy().view(np.float64).reshape(n, 9)
     assert (got_maps.view(np.uint64) == want_maps.view(np.uint64)).all()
-    flat_frames = WC.pix_layout(n, W, Hh, "bgr", True)
+    flat_frames = FK.pix_layout(n, W, Hh, "bgr", True)
     flat_frames.buf[...] = want_flat
     rc, want_top, status = WC.host_warp(L, flat_frames, top, want_maps, WC.LINEAR, WC.CONSTANT, [220, 220, 220], WC.INVERSE_MAP)
     assert rc == n and d_status.cpu().numpy().view(np.int32).tolist() == [1] * n

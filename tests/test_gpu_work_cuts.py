@@ -9,22 +9,13 @@ import pytest
 
 import helpers as H
 import work_cut_scenes as S
+from frame_kit import E_ARG, oa  # noqa: F401
 from geometry_scenes import pinhole_camera
 from test_batch_plan_cpu import lib, plan   # noqa: F401  (lib: the fixture that builds tests/emul/plan_emul.cpp)
 from test_gpu_input_formats import as_format
 from test_gpu_parity import OracleFrame, cand_array, check_candidates, check_markers, check_planes, make_detector
 
 pytestmark = pytest.mark.gpu
-
-E_ARG = -2   # include/ocvar_hip.h: OCVAR_E_ARG
-
-
-@pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
 
 
 def size(w, h):

@@ -6,38 +6,26 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
 import overlay_chain as OC
 import yuv_chain as YC
+from frame_kit import E_ARG, oa, same, to_device  # noqa: F401
 from test_gpu_parity import OracleFrame, check_markers, make_detector
 
 pytestmark = pytest.mark.gpu
 
-E_ARG = -2
 MATS = ["bt601", "bt709"]
 
 
 @pytest.fixture(scope="module")
-def oa():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a device"
-    import opencv_ar_amd
-    return opencv_ar_amd
-
-
-@pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return YC.build_emul(tmp_path_factory.mktemp("yuv_emul"))
+def L():
+    return YC.build_emul()
 
 
 @pytest.fixture(scope="module")
 def det(oa):
     return oa.Detector(1026, 16, max_batch=1)   # (n_frames is not bound by the batch)
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to("cuda:0")
 
 
 def yuv_struct(oa, yuv, base, matrix):
@@ -69,16 +57,9 @@ def device_to_yuv(oa, det, src, matrix, yuv, buf=None):
     return dd.cpu().numpy(), d.cpu().numpy()
 
 
-def same(got, want, inside, where):
-    bad = np.flatnonzero(got != want)
-    if bad.size:
-        raise AssertionError("%s: %d bytes differ (%d of them guard bytes), first at byte %d of the buffer: %d != %d" % (
-            where, bad.size, int((~inside[bad]).sum()), int(bad[0]), got[bad[0]], want[bad[0]]))
-
-
 # ---- the layout sweep ---------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("fmt", YC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 @pytest.mark.parametrize("layout", list(YC.LAYOUTS))
 def test_yuv_to_frames_sweep(oa, L, det, layout, fmt):
     """every size with 1 and 3 frames, on the dword path (everything a multiple of 4) and on the byte path (an odd lead, odd
@@ -89,9 +70,9 @@ def test_yuv_to_frames_sweep(oa, L, det, layout, fmt):
             pixels = []
             for aligned in (True, False):
                 yuv = YC.Yuv(n, W, Hh, layout, aligned=aligned, seed=W + Hh)
-                dst = YC.pix_layout(n, W, Hh, fmt, aligned, fill=YC.GUARD)
+                dst = FK.pix_layout(n, W, Hh, fmt, aligned, fill=FK.GUARD)
                 want = YC.host_to_frames(L, yuv, m, dst)
-                assert (want[~dst.pixel_mask()] == YC.GUARD).all()
+                assert (want[~dst.pixel_mask()] == FK.GUARD).all()
                 got, src_after = device_to_frames(oa, det, yuv, m, dst)
                 assert (src_after == yuv.buf).all()
                 same(got, want, dst.pixel_mask(), "%dx%d x %d %s -> %s %s aligned=%s" % (W, Hh, n, layout, fmt, m, aligned))
@@ -99,7 +80,7 @@ def test_yuv_to_frames_sweep(oa, L, det, layout, fmt):
             assert (pixels[0] == pixels[1]).all()
 
 
-@pytest.mark.parametrize("fmt", YC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 @pytest.mark.parametrize("layout", list(YC.LAYOUTS))
 def test_frames_to_yuv_sweep(oa, L, det, layout, fmt):
     for i, (W, Hh) in enumerate(YC.SIZES):
@@ -107,10 +88,10 @@ def test_frames_to_yuv_sweep(oa, L, det, layout, fmt):
         for n in (1, 3):
             samples = []
             for aligned in (True, False):
-                src = YC.pix_layout(n, W, Hh, fmt, aligned, seed=W * Hh)
+                src = FK.pix_layout(n, W, Hh, fmt, aligned, seed=W * Hh)
                 yuv = YC.Yuv(n, W, Hh, layout, aligned=aligned)
                 want = YC.host_to_yuv(L, src, m, yuv)
-                assert (want[~yuv.sample_mask()] == YC.GUARD).all()
+                assert (want[~yuv.sample_mask()] == FK.GUARD).all()
                 got, src_after = device_to_yuv(oa, det, src, m, yuv)
                 assert (src_after == src.buf).all()
                 same(got, want, yuv.sample_mask(), "%dx%d x %d %s -> %s %s aligned=%s" % (W, Hh, n, fmt, layout, m, aligned))
@@ -126,9 +107,9 @@ def test_there_and_back_on_one_stream(oa, L, det, aligned):
     """frames_to_yuv into NV12 and yuv_to_frames back, queued on the context's stream with nothing waited for in between"""
     import torch
     W, Hh, n = 514, 6, 3
-    src = YC.pix_layout(n, W, Hh, "bgr", aligned, seed=9)
+    src = FK.pix_layout(n, W, Hh, "bgr", aligned, seed=9)
     yuv = YC.Yuv(n, W, Hh, "nv12", aligned=aligned)
-    back = YC.pix_layout(n, W, Hh, "bgra", aligned, fill=YC.GUARD)
+    back = FK.pix_layout(n, W, Hh, "bgra", aligned, fill=FK.GUARD)
     want_yuv = YC.host_to_yuv(L, src, "bt709", yuv)
     want_back = YC.host_to_frames(L, yuv, "bt709", back, buf=want_yuv)
     d, dy, db = to_device(src.buf), to_device(yuv.buf), to_device(back.buf)
@@ -148,9 +129,9 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
     import torch
     n, lead = 65537, 64
     rng = np.random.default_rng(2)
-    yuv = np.full(lead + 6 * n + lead, YC.GUARD, np.uint8)     # per frame: Y Y / Y Y / U V
+    yuv = np.full(lead + 6 * n + lead, FK.GUARD, np.uint8)     # per frame: Y Y / Y Y / U V
     yuv[lead:lead + 6 * n] = rng.integers(0, 256, 6 * n, dtype=np.uint8)
-    pix = np.full(lead + 12 * n + lead, YC.GUARD, np.uint8)
+    pix = np.full(lead + 12 * n + lead, FK.GUARD, np.uint8)
     want = pix.copy()
     L.yuv_to_frames_emul(0, 0, yuv.ctypes.data + lead, yuv.ctypes.data + lead + 4, None, 2, 2, 6, want.ctypes.data + lead, 6, 12, 2, 2, 0, n)
     d, dd = to_device(yuv), to_device(pix)
@@ -159,8 +140,8 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
     torch.cuda.synchronize()
     got = dd.cpu().numpy()
     assert (got == want).all(), np.flatnonzero(got != want)[:4].tolist()
-    assert (got[lead + 12 * 65535: lead + 12 * n] != YC.GUARD).any()   # (the frames of the second launch)
-    back = np.full(yuv.size, YC.GUARD, np.uint8)
+    assert (got[lead + 12 * 65535: lead + 12 * n] != FK.GUARD).any()   # (the frames of the second launch)
+    back = np.full(yuv.size, FK.GUARD, np.uint8)
     want_back = back.copy()
     L.frames_to_yuv_emul(0, 1, want_back.ctypes.data + lead, want_back.ctypes.data + lead + 4, None, 2, 2, 6, want.ctypes.data + lead, 6, 12, 2, 2, 0, n)
     db = to_device(back)
@@ -175,7 +156,7 @@ def test_more_frames_than_one_launch_takes(oa, L, det):
 COLOUR = np.array([250, 10, 200, 255], np.uint8)   # R G B A
 
 
-def test_decoded_frames_are_detected_drawn_on_and_encoded(oa, L, tmp_path_factory):
+def test_decoded_frames_are_detected_drawn_on_and_encoded(oa, L):
     """the loop of a decoder's NV12 frames: converted on the device to BGR and to GRAY, each detected -- the oracle's registration on
     the host core's BGR bytes, and the same records from both; then the overlay drawn on the BGR frames and those converted to NV12
     -- the host cores of both steps"""
@@ -183,17 +164,17 @@ def test_decoded_frames_are_detected_drawn_on_and_encoded(oa, L, tmp_path_factor
     cfg = H.synth_config(2)   # 640 x 480, four markers: the size the synthetic scenes are made for
     W, Hh, n = cfg.width, cfg.height, 2
     det, tpls, cam = make_detector(oa, cfg, None, n)
-    src = YC.pix_layout(n, W, Hh, "bgr", True)
+    src = FK.pix_layout(n, W, Hh, "bgr", True)
     for f in range(n):
         src.view(f)[...] = H.synth_frame(cfg, f)[0]
     yuv = YC.Yuv(n, W, Hh, "nv12", aligned=True)
     nv12 = YC.host_to_yuv(L, src, "bt601", yuv)                 # what the decoder delivers
-    bgr, gray = YC.pix_layout(n, W, Hh, "bgr", True, fill=YC.GUARD), YC.pix_layout(n, W, Hh, "gray", False, fill=YC.GUARD)
+    bgr, gray = FK.pix_layout(n, W, Hh, "bgr", True, fill=FK.GUARD), FK.pix_layout(n, W, Hh, "gray", False, fill=FK.GUARD)
     want_bgr = YC.host_to_frames(L, yuv, "bt601", bgr, buf=nv12)
     d, db, dg = to_device(nv12), to_device(bgr.buf), to_device(gray.buf)
     torch.cuda.synchronize()
     st = yuv_struct(oa, yuv, d.data_ptr(), "bt601")
-    LO = OC.build_emul(tmp_path_factory.mktemp("overlay_emul"))
+    LO = OC.build_emul()
     overlay = np.broadcast_to(COLOUR, (4, 4, 4)).copy()
     det.set_overlay(-1, overlay)
     out = YC.Yuv(n, W, Hh, "nv12", aligned=True)
@@ -239,7 +220,7 @@ def test_refusals_launch_nothing(oa, L):
     det = oa.Detector(64, 32, max_batch=1)
     ctx = det._ctx
     W, Hh, n = 64, 32, 2
-    pix_h = np.full(n * 4 * W * Hh + 64, YC.GUARD, np.uint8)
+    pix_h = np.full(n * 4 * W * Hh + 64, FK.GUARD, np.uint8)
     yuv_h = np.full(n * 2 * W * Hh + 64, 77, np.uint8)
     dp, dy = to_device(pix_h), to_device(yuv_h)
     torch.cuda.synchronize()
@@ -273,7 +254,7 @@ def test_refusals_launch_nothing(oa, L):
     assert call(True, layout=2, yp=2 * W, h=Hh - 1, c0=None, c1=None) == 0
     torch.cuda.synchronize()
     pix_after = dp.cpu().numpy()
-    assert (pix_after[3 * W * (Hh - 1) * n:] == YC.GUARD).all() and (pix_after[:3 * W * (Hh - 1)] != YC.GUARD).any()
+    assert (pix_after[3 * W * (Hh - 1) * n:] == FK.GUARD).all() and (pix_after[:3 * W * (Hh - 1)] != FK.GUARD).any()
     dp.copy_(torch.from_numpy(pix_h))
     torch.cuda.synchronize()
     for to_frames in (True, False):

@@ -3,23 +3,14 @@
 the sum and its low part must fit 16 bits -- the kernel keeps two sums in one register and picks the grey bytes with one permute.
 tests/emul/grey_pack_emul.cpp builds the function for the host."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-import helpers as H
-
-SRC = os.path.join(H.ROOT, "tests", "emul", "grey_pack_emul.cpp")
-DEPS = [SRC, os.path.join(H.PKG, "csrc", "hd.h")]
+from hostbuild import host_core
 
 
 def build_lib():
-    so = os.path.join(H.ROOT, "tests", "emul", "libgrey_pack_emul.so")
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in DEPS):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-DOCVAR_NBR_TILED",
-                               "-I" + os.path.join(H.PKG, "csrc"), "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so, SRC])
-    l = C.CDLL(so)
+    l = host_core("grey_pack_emul")
     l.gp_sweep.restype = C.c_longlong
     l.gp_sweep.argtypes = [C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     return l

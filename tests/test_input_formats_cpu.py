@@ -8,9 +8,10 @@ import re
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
 
-FORMATS = {"OCVAR_FMT_BGR": 0, "OCVAR_FMT_RGB": 1, "OCVAR_FMT_BGRA": 2, "OCVAR_FMT_RGBA": 3, "OCVAR_FMT_GRAY": 4}
+HEADER_FORMATS = {"OCVAR_FMT_" + name.upper(): code for name, code in FK.FORMATS.items()}
 
 
 @pytest.fixture(scope="module")
@@ -30,7 +31,7 @@ def test_headers_declare_the_setters_and_the_formats():
     for name in ("ocvar_hip_set_input_format", "ocvar_hip_pipe_set_input_format"):
         assert re.search(r"\bint\s+%s\s*\(\s*Ocvar\w+\*\s*\w+\s*,\s*int\s+format\s*\)\s*;" % name, hip), name
     enum = dict((k, int(v)) for k, v in re.findall(r"\b(OCVAR_FMT_\w+)\s*=\s*(\d+)", hip))
-    assert enum == FORMATS
+    assert enum == HEADER_FORMATS
     multi = _header("ocvar_multi.h")
     inc = re.findall(r'#include\s+"(ocvar_multi\w*\.h)"', multi)
     decl = "".join(_header(x) for x in inc)

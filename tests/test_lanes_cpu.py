@@ -2,23 +2,16 @@
 on a simulated timeline: lanes are queues that run their entries in order, a gated segment starts when the launch its ticket
 names has finished, and the host collects and re-enqueues as bench.py does -- or in a random order."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import helpers as H
-
-CSRC = os.path.join(H.PKG, "csrc")
+from hostbuild import host_core
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("lanes_emul") / "liblanes_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-Wall", "-I" + CSRC, "-shared", "-o", so,
-                           os.path.join(H.ROOT, "tests", "emul", "lanes_emul.cpp")])
-    L = C.CDLL(so)
+def lib():
+    L = host_core("lanes_emul")
     vp, i = C.c_void_p, C.c_int
     L.lanes_emul_init.argtypes = [vp, i, i]
     L.lanes_emul_choose.argtypes = [vp]

@@ -5,18 +5,19 @@ for byte."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
 import levels_chain as LC
+from hostbuild import run_sanitized
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return LC.build_emul(tmp_path_factory.mktemp("levels_emul"))
+def L():
+    return LC.build_emul()
 
 
 def test_constants_agree_with_the_core(L):
@@ -29,7 +30,7 @@ def test_constants_agree_with_the_core(L):
 
 # ---- the step against numpy ------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("fmt", LC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 def test_frames_against_numpy(L, fmt):
     """guarded frames with padded rows, aligned and odd layouts, every shared shape and grid under every setting of the knobs: numpy's
     plane of the frame's grey, every guard byte kept, the source untouched"""
@@ -37,12 +38,12 @@ def test_frames_against_numpy(L, fmt):
         for q, (lo, hi, gain) in enumerate(LC.KNOBS):
             aligned = (k + q) % 2 == 0
             p = LC.params(tiles, lo, hi, gain)
-            src = LC.pix_layout(2, w, h, fmt, aligned, seed=k + 1)
+            src = FK.pix_layout(2, w, h, fmt, aligned, seed=k + 1)
             dst = LC.dst_layout(src, aligned)
             before = src.buf.copy()
             rc, got = LC.host_levels(L, src, dst, p)
             assert rc == 0 and (src.buf == before).all()
-            assert (got[~dst.pixel_mask()] == LC.GUARD).all()
+            assert (got[~dst.pixel_mask()] == FK.GUARD).all()
             for f in range(src.n):
                 want = LC.np_levels_params(LC.np_grey(src.view(f), fmt), p)
                 bad = np.argwhere(dst.view(f, got)[..., 0] != want)
@@ -120,7 +121,7 @@ def test_axis_against_numpy(L):
 def test_one_tile_is_the_lut_of_the_grey(L):
     rng = np.random.default_rng(5)
     g = rng.integers(30, 180, (23, 37), dtype=np.uint8)
-    src = LC.pix_layout(1, 37, 23, "gray", True)
+    src = FK.pix_layout(1, 37, 23, "gray", True)
     src.view(0)[..., 0] = g
     rc, got, luts = LC.host_levels(L, src, LC.dst_layout(src, True), LC.params(), want_luts=True)
     assert rc == 0 and (LC.dst_layout(src, True).view(0, got)[..., 0] == luts[0, 0][g]).all()
@@ -130,11 +131,11 @@ def test_one_tile_is_the_lut_of_the_grey(L):
 @pytest.mark.parametrize("fmt", ["bgr", "rgb", "bgra", "rgba"])
 def test_colour_formats_give_the_result_of_their_grey_plane(L, fmt):
     rng = np.random.default_rng(6)
-    px = rng.integers(0, 256, (23, 37, LC.BPP[LC.FORMATS[fmt]]), dtype=np.uint8)
+    px = rng.integers(0, 256, (23, 37, FK.BPP[FK.FORMATS[fmt]]), dtype=np.uint8)
     grey = LC.np_grey(px, fmt)
     for a, b, c in [(0, 0, 0), (255, 255, 255), (255, 0, 0), (0, 255, 0), (0, 0, 255), (17, 200, 90)]:
         order = (a, b, c) if fmt in ("bgr", "bgra") else (c, b, a)
-        assert L.levels_grey_emul(*order, LC.FORMATS[fmt]) == (1868 * a + 9617 * b + 4899 * c + 8192) >> 14
+        assert L.levels_grey_emul(*order, FK.FORMATS[fmt]) == (1868 * a + 9617 * b + 4899 * c + 8192) >> 14
     for p in (LC.params(), LC.params((4, 3)), LC.params((5, 2), 0, 50000, 1024)):
         assert (LC.host_levels_image(L, px, p, fmt=fmt) == LC.host_levels_image(L, grey, p)).all()
 
@@ -152,7 +153,7 @@ def test_no_clipping_on_a_full_range_frame_is_the_identity(L):
 
 
 def test_refusals_of_the_host_call(L):
-    px, out = np.zeros(64, np.uint8), np.full(64, LC.GUARD, np.uint8)
+    px, out = np.zeros(64, np.uint8), np.full(64, FK.GUARD, np.uint8)
 
     def call(w=4, h=4, srs=12, fmt=0, drs=4, n=1, p=None):
         return L.levels_emul(px.ctypes.data, w, h, srs, srs * max(h, 1), fmt, out.ctypes.data, drs, drs * max(h, 1), n, None if p is None else C.addressof(p),
@@ -162,8 +163,8 @@ def test_refusals_of_the_host_call(L):
     bad += [dict(p=LC.params(t)) for t in [(0, 1), (1, 0), (17, 1), (1, 17), (16, 5), (5, 1), (1, 5)]]
     bad += [dict(p=LC.params((1, 1), *k)) for k in [(-1, 0, 2048), (0, -1, 2048), (500001, 0, 2048), (0, 500001, 2048), (0, 0, 255), (0, 0, 65281)]]
     for kw in bad:
-        assert call(**kw) == LC.E_ARG, kw
-    assert (out == LC.GUARD).all()
+        assert call(**kw) == FK.E_ARG, kw
+    assert (out == FK.GUARD).all()
     assert call() == 0 and call(p=LC.params((4, 4), 0, 500000, 65280)) == 0
 
 
@@ -230,14 +231,11 @@ def test_the_exposure_chain_on_the_cpu(chain):
 
 # ---- sanitizers ------------------------------------------------------------------------------------------------------------------------
 
-def test_stand_alone_program_under_the_sanitizers(tmp_path):
+def test_stand_alone_program_under_the_sanitizers():
     """tests/emul/levels_emul.cpp with its own main, built with -fsanitize=address,undefined and run as a program: sides 1 .. 32767,
     every pixel size, grids up to 16 tiles an axis, the extremes of the knobs, random, constant and two-valued frames on heap blocks of
     exactly the bytes a call may touch"""
-    exe = LC.build_sanitized_program(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert ", 0 bad" in r.stdout and "runtime error" not in r.stderr
+    run_sanitized("levels_emul", "LEVELS_EMUL_MAIN", ", 0 bad", timeout=600)
 
 
 # ---- ABI -------------------------------------------------------------------------------------------------------------------------------
@@ -255,7 +253,7 @@ def test_abi_and_python_names():
     assert re.search(r"int tiles_x, tiles_y, low_ppm, high_ppm, max_gain_q8;", header)
     assert [f[0] for f in oa.LevelsParams._fields_] == [f[0] for f in LC.Params._fields_] and C.sizeof(oa.LevelsParams) == 20
     p = oa.LevelsParams(9, 9, 9, 9, 9)
-    assert lib.ocvar_hip_levels_default_params(C.byref(p)) == 0 and lib.ocvar_hip_levels_default_params(None) == LC.E_ARG
+    assert lib.ocvar_hip_levels_default_params(C.byref(p)) == 0 and lib.ocvar_hip_levels_default_params(None) == FK.E_ARG
     assert LC.as_tuple(p) == LC.as_tuple(oa.levels_params()) == (1, 1, 10000, 10000, 2048)
     assert LC.as_tuple(oa.levels_params((4, 3), 0, 500000, 1.0)) == (4, 3, 0, 500000, 256) and oa.levels_params(max_gain=255).max_gain_q8 == 65280
     assert hasattr(oa.Detector, "levels")

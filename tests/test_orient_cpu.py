@@ -6,23 +6,24 @@ stand-alone program under the sanitizers; the ABI.  tests/test_gpu_orient.py hol
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
 import orient_chain as OR
 import persp_synth as PS
 from helpers import P
+from hostbuild import run_sanitized
 
 CHANNELS = {"bgr": 3, "rgb": 3, "bgra": 4, "rgba": 4, "gray": 1}
 POSE_RTOL = 1e-4   # tests/test_gpu_parity.py: check_markers
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return OR.build_emul(tmp_path_factory.mktemp("orient_emul"))
+def L():
+    return OR.build_emul()
 
 
 def sweep_sizes():
@@ -30,7 +31,7 @@ def sweep_sizes():
     return [(w, h) for w in OR.SIDES for h in OR.SIDES] + [(w, h) for w in OR.WIDE for h in (1, 3, OR.TILE + 1)]
 
 
-@pytest.mark.parametrize("fmt", OR.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 def test_frame_sweep(L, fmt):
     """every orientation on guarded frames with padded rows, 1 and 2 frames, aligned and odd layouts: numpy's pixels, every guard byte
     kept"""
@@ -39,11 +40,11 @@ def test_frame_sweep(L, fmt):
     for j, (w, h) in enumerate(sweep_sizes()):
         for o in range(8):
             n = 1 + (j + o) % 2
-            src = OR.pix_layout(n, w, h, fmt, aligned=bool((j + o) & 2), seed=j)
+            src = FK.pix_layout(n, w, h, fmt, aligned=bool((j + o) & 2), seed=j)
             dst = OR.dst_layout(src, o, aligned=bool((j + o) & 4))
             rc, out = OR.host_orient(L, src, dst, o)
             assert rc == 0
-            assert (out[~dst.pixel_mask()] == OR.GUARD).all(), (o, w, h)
+            assert (out[~dst.pixel_mask()] == FK.GUARD).all(), (o, w, h)
             for f in range(n):
                 want = OR.np_orient(src.view(f), o)
                 got = dst.view(f, out)
@@ -117,8 +118,8 @@ def test_record_map_against_numpy(L):
     count untouched; into the block itself"""
     rng = np.random.default_rng(5)
     n, slots = 3, 6
-    raw = rng.integers(0, 256, n * slots * OR.MARKER_DTYPE.itemsize, dtype=np.uint8)
-    recs = np.frombuffer(raw.tobytes(), OR.MARKER_DTYPE).reshape(n, slots).copy()
+    raw = rng.integers(0, 256, n * slots * FK.MARKER_DTYPE.itemsize, dtype=np.uint8)
+    recs = np.frombuffer(raw.tobytes(), FK.MARKER_DTYPE).reshape(n, slots).copy()
     recs["square"] = rng.uniform(-50, 4000, (n, slots, 8)).astype(np.float32)
     recs["square"][0, 0] = [0.0, -0.5, 0.25, 1e30, -1e30, np.inf, -np.inf, np.nan]
     recs["square"][0, 1, 2] = np.array([0xFFC12345], np.uint32).view(np.float32)[0]     # a NaN with a payload and a sign
@@ -228,9 +229,9 @@ def test_camera_map_composes_and_refuses(L):
             if o == 0:   # everything but glProjection (the last 128 bytes) is kept
                 assert rc == 0 and bytes(out)[:-128] == bytes(bad)[:-128]
             else:
-                assert rc == OR.E_ARG and bytes(out) == b"\xa5" * C.sizeof(out), (idx, o)
+                assert rc == FK.E_ARG and bytes(out) == b"\xa5" * C.sizeof(out), (idx, o)
     out = H.Camera()
-    assert L.orient_camera_emul(C.addressof(cam), 8, C.addressof(out)) == OR.E_ARG and L.orient_camera_emul(C.addressof(cam), -1, C.addressof(out)) == OR.E_ARG
+    assert L.orient_camera_emul(C.addressof(cam), 8, C.addressof(out)) == FK.E_ARG and L.orient_camera_emul(C.addressof(cam), -1, C.addressof(out)) == FK.E_ARG
 
 
 # ---- the pose flag ---------------------------------------------------------------------------------------------------------------------
@@ -274,10 +275,10 @@ def test_pose_under_the_oriented_camera(L):
                 print("%s %s: reprojection %.4f px (original %.4f px), pose %.3g from the turned original" % (name, OR.NAMES[o], e_new, e_old, d))
                 assert e_new <= e_old + 0.01, (name, o, e_new, e_old)
                 assert d <= POSE_RTOL, (name, o, d)
-        guard = np.frombuffer(np.full(recs.nbytes, OR.GUARD, np.uint8).tobytes(), OR.MARKER_DTYPE).reshape(recs.shape)
+        guard = np.frombuffer(np.full(recs.nbytes, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(recs.shape)
         for o in OR.MIRRORING:
             rc, out = OR.host_orient_records(L, recs, [k], size, o, pose=True, cam=cam, out=guard)
-            assert rc == OR.E_ARG and out.tobytes() == guard.tobytes()
+            assert rc == FK.E_ARG and out.tobytes() == guard.tobytes()
     print("pose: at most %.3g relative from the turned pose, reprojection at most %.4f px worse" % (worst_gl, worst_px))
 
 
@@ -319,13 +320,10 @@ def test_the_chain_on_the_cpu(L):
 
 # ---- sanitizers ------------------------------------------------------------------------------------------------------------------------
 
-def test_stand_alone_program_under_the_sanitizers(tmp_path):
+def test_stand_alone_program_under_the_sanitizers():
     """tests/emul/orient_emul.cpp with its own main, built with -fsanitize=address,undefined and run as a program: sides 1 .. 32767,
     every pixel size and orientation, on heap blocks of exactly the bytes a call may touch"""
-    exe = OR.build_sanitized_program(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert ", 0 bad" in r.stdout and "runtime error" not in r.stderr
+    run_sanitized("orient_emul", "ORIENT_EMUL_MAIN", ", 0 bad", timeout=600)
 
 
 # ---- ABI -------------------------------------------------------------------------------------------------------------------------------

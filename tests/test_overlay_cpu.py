@@ -7,21 +7,22 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
 import overlay_chain as OC
 from helpers import P
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return OC.build_emul(tmp_path_factory.mktemp("overlay_emul"))
+def L():
+    return OC.build_emul()
 
 
 def render(L, fr, squares, overlays, tids=None, scores=None, count=None):
-    recs = OC.records(squares, tids, scores)[None]
+    recs = FK.records(squares, tids, scores)[None]
     out, drawn = OC.host_render(L, fr, recs, [len(recs[0]) if count is None else count], overlays)
     guards = ~fr.pixel_mask()
-    assert (out[guards] == OC.GUARD).all(), "guard bytes changed"
+    assert (out[guards] == FK.GUARD).all(), "guard bytes changed"
     return fr.view(0, out), drawn[0]
 
 
@@ -29,9 +30,9 @@ def render(L, fr, squares, overlays, tids=None, scores=None, count=None):
 def test_opaque_overlay_on_its_own_rectangle_is_an_exact_copy(L, ow, oh):
     rng = np.random.default_rng(ow * 100 + oh)
     ov = OC.random_overlay(rng, ow, oh, alpha=255)
-    fr = OC.Frames(1, 40, 30, "rgb", row_pad=5)
+    fr = FK.Frames(1, 40, 30, "rgb", row_pad=5)
     x0, y0 = 7, 11
-    got, drawn = render(L, fr, [OC.axis_square(x0, y0, ow, oh)], {0: ov})
+    got, drawn = render(L, fr, [FK.axis_square(x0, y0, ow, oh)], {0: ov})
     assert drawn == 1
     want = fr.view(0).copy()
     want[y0:y0 + oh, x0:x0 + ow] = ov[..., :3]
@@ -42,9 +43,9 @@ def test_cyclic_shifts_of_the_corners_give_the_four_quarter_turns(L):
     rng = np.random.default_rng(5)
     n = 6
     ov = OC.random_overlay(rng, n, n, alpha=255)
-    sq = np.array(OC.axis_square(10, 8, n, n), np.float32).reshape(4, 2)
+    sq = np.array(FK.axis_square(10, 8, n, n), np.float32).reshape(4, 2)
     for s in range(4):
-        fr = OC.Frames(1, 32, 24, "rgb")
+        fr = FK.Frames(1, 32, 24, "rgb")
         got, _ = render(L, fr, [np.roll(sq, -s, axis=0)], {0: ov})   # new corner i = old corner i + s
         want = fr.view(0).copy()
         want[8:8 + n, 10:10 + n] = np.rot90(ov[..., :3], -s)
@@ -56,8 +57,8 @@ def test_magnification_by_two_follows_the_weight_formula(L):
     ow, oh = 5, 4
     ov = OC.random_overlay(rng, ow, oh, alpha=255)
     W, Hh = 2 * (ow - 1) + 1, 2 * (oh - 1) + 1
-    fr = OC.Frames(1, 20, 16, "rgba", row_pad=3)
-    got, _ = render(L, fr, [OC.axis_square(3, 2, W, Hh)], {0: ov})
+    fr = FK.Frames(1, 20, 16, "rgba", row_pad=3)
+    got, _ = render(L, fr, [FK.axis_square(3, 2, W, Hh)], {0: ov})
     t = ov.astype(np.int64)
     want = np.zeros((Hh, W, 4), np.int64)
     want[0::2, 0::2] = t
@@ -77,9 +78,9 @@ def test_alpha_follows_the_blend_formula_in_every_format(L, fmt):
     ov = OC.random_overlay(rng, ow, oh, alpha=255)
     ov[:, 0:3, 3] = 0
     ov[:, 3:6, 3] = 128
-    fr = OC.Frames(1, 24, 20, fmt, row_pad=5, seed=3)
+    fr = FK.Frames(1, 24, 20, fmt, row_pad=5, seed=3)
     x0, y0 = 5, 6
-    got, _ = render(L, fr, [OC.axis_square(x0, y0, ow, oh)], {0: ov})
+    got, _ = render(L, fr, [FK.axis_square(x0, y0, ow, oh)], {0: ov})
     exp = fr.view(0).copy()
     region = exp[y0:y0 + oh, x0:x0 + ow]
     nc = 1 if fmt == "gray" else 3
@@ -101,8 +102,8 @@ def test_alpha_follows_the_blend_formula_in_every_format(L, fmt):
 def test_overlapping_records_compose_in_output_order(L):
     ca, cb = np.array([200, 30, 90, 128], np.uint8), np.array([10, 220, 160, 128], np.uint8)
     ovs = {0: np.broadcast_to(ca, (2, 2, 4)).copy(), 1: np.broadcast_to(cb, (2, 2, 4)).copy()}
-    fr = OC.Frames(1, 40, 30, "rgb", seed=8)
-    sa, sb = OC.axis_square(4, 4, 20, 16), OC.axis_square(14, 10, 20, 16)
+    fr = FK.Frames(1, 40, 30, "rgb", seed=8)
+    sa, sb = FK.axis_square(4, 4, 20, 16), FK.axis_square(14, 10, 20, 16)
     got, drawn = render(L, fr, [sa, sb], ovs, tids=[0, 1])
     assert drawn == 2
     exp = fr.view(0).astype(np.int64)
@@ -132,15 +133,15 @@ NOTHING = {
 def test_records_that_draw_nothing(L, case):
     sq, tid, score = NOTHING[case]
     ov = OC.random_overlay(np.random.default_rng(9), 4, 4, alpha=255)
-    fr = OC.Frames(1, 40, 30, "bgr", row_pad=2)
+    fr = FK.Frames(1, 40, 30, "bgr", row_pad=2)
     got, drawn = render(L, fr, [sq], {0: ov}, tids=[tid], scores=[score])
     assert drawn == 0 and (got == fr.view(0)).all()
 
 
 def test_count_zero_draws_nothing_and_the_default_overlay_serves_the_rest(L):
     ov = OC.random_overlay(np.random.default_rng(10), 4, 4, alpha=255)
-    fr = OC.Frames(1, 40, 30, "bgr")
-    sq = OC.axis_square(5, 5, 4, 4)
+    fr = FK.Frames(1, 40, 30, "bgr")
+    sq = FK.axis_square(5, 5, 4, 4)
     got, drawn = render(L, fr, [sq], {0: ov}, count=0)
     assert drawn == 0 and (got == fr.view(0)).all()
     got, drawn = render(L, fr, [sq], {-1: ov}, tids=[3])   # template 3 has none of its own
@@ -154,8 +155,8 @@ def test_count_zero_draws_nothing_and_the_default_overlay_serves_the_rest(L):
 def test_a_square_cut_by_the_frame_draws_only_inside(L, x0, y0):
     ow, oh = 16, 12
     ov = OC.random_overlay(np.random.default_rng(12), ow, oh, alpha=255)
-    fr = OC.Frames(1, 40, 30, "rgb", row_pad=5)
-    got, drawn = render(L, fr, [OC.axis_square(x0, y0, ow, oh)], {0: ov})
+    fr = FK.Frames(1, 40, 30, "rgb", row_pad=5)
+    got, drawn = render(L, fr, [FK.axis_square(x0, y0, ow, oh)], {0: ov})
     assert drawn == 1
     exp = fr.view(0).copy()
     xa, xb, ya, yb = max(x0, 0), min(x0 + ow, 40), max(y0, 0), min(y0 + oh, 30)
@@ -200,7 +201,7 @@ def test_perspective_quads_against_a_float64_homography(L):
     ys, xs = np.mgrid[0:Hh, 0:W]
     for n in range(20):
         q = random_convex_quad(rng, W, Hh)
-        fr = OC.Frames(1, W, Hh, "rgb", fill=0)
+        fr = FK.Frames(1, W, Hh, "rgb", fill=0)
         got, drawn = render(L, fr, [q.reshape(8)], {0: ov})
         assert drawn == 1
         Hm = homography(q.astype(np.float64), [(0, 0), (ow - 1, 0), (ow - 1, oh - 1), (0, oh - 1)])

@@ -49,8 +49,8 @@ TRUTH_WORST = {
 
 
 @pytest.fixture(scope="module")
-def Lr(tmp_path_factory):
-    return RC.build_emul(tmp_path_factory.mktemp("refine_emul"))
+def Lr():
+    return RC.build_emul()
 
 
 @pytest.fixture(scope="module")

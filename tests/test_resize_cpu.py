@@ -2,15 +2,16 @@
 restatement of the rules, byte for byte; what the rules promise (copies, constants, the exact factor 2, integer boxes, table
 weights); the record map against numpy float64; the chain "shrink by 2, detect, map the squares back up" through the oracle; and
 the stand-alone program under the sanitizers.  tests/test_gpu_resize.py holds the kernels to this build byte for byte."""
-import subprocess
 
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
 import persp_synth as PS
 import resize_chain as RC
 from helpers import P
+from hostbuild import run_sanitized
 
 SIDES = [1, 2, 3, 5, 8, 17, 64]
 PAIRS = [(64, 32), (96, 32), (48, 32), (33, 7), (7, 33), (1, 9)]
@@ -18,8 +19,8 @@ CHANNELS = {"bgr": 3, "rgb": 3, "bgra": 4, "rgba": 4, "gray": 1}
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return RC.build_emul(tmp_path_factory.mktemp("resize_emul"))
+def L():
+    return RC.build_emul()
 
 
 def sweep_sizes():
@@ -37,7 +38,7 @@ def sweep_sizes():
     return out
 
 
-@pytest.mark.parametrize("fmt", RC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 @pytest.mark.parametrize("interp", list(RC.INTERPS))
 def test_case_sweep(L, interp, fmt):
     """guarded frames with padded rows: the numpy restatement's pixels, every guard byte kept; AREA beyond its domain is refused
@@ -47,15 +48,15 @@ def test_case_sweep(L, interp, fmt):
     kinds = set()
     for j, (sw, sh, dw, dh) in enumerate(sweep_sizes()):
         n = 1 + j % 2
-        src = RC.pix_layout(n, sw, sh, fmt, aligned=bool(j & 2), seed=j)
-        dst = RC.pix_layout(n, dw, dh, fmt, aligned=bool(j & 4), fill=RC.GUARD)
+        src = FK.pix_layout(n, sw, sh, fmt, aligned=bool(j & 2), seed=j)
+        dst = FK.pix_layout(n, dw, dh, fmt, aligned=bool(j & 4), fill=FK.GUARD)
         rc, out = RC.host_resize(L, src, dst, interp)
         if interp == "area" and not RC.area_ok(sw, sh, dw, dh):
-            assert rc == RC.E_ARG and (out == RC.GUARD).all(), (sw, sh, dw, dh)
+            assert rc == FK.E_ARG and (out == FK.GUARD).all(), (sw, sh, dw, dh)
             refused += 1
             continue
         assert rc == 0
-        assert (out[~dst.pixel_mask()] == RC.GUARD).all(), (sw, sh, dw, dh)
+        assert (out[~dst.pixel_mask()] == FK.GUARD).all(), (sw, sh, dw, dh)
         plan = np.zeros(3, np.int32)
         L.resize_plan_emul(sw, sh, dw, dh, RC.INTERPS[interp], P(plan))
         assert tuple(plan) == RC.np_plan(sw, sh, dw, dh, interp), (sw, sh, dw, dh)
@@ -188,7 +189,7 @@ def test_record_map_against_numpy(L):
 
 def test_records_of_equal_sizes_are_copied_bit_for_bit(L):
     rng = np.random.default_rng(6)
-    recs = np.frombuffer(rng.integers(0, 256, 3 * 4 * RC.MARKER_DTYPE.itemsize, dtype=np.uint8).tobytes(), RC.MARKER_DTYPE).reshape(3, 4).copy()
+    recs = np.frombuffer(rng.integers(0, 256, 3 * 4 * FK.MARKER_DTYPE.itemsize, dtype=np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(3, 4).copy()
     out = RC.host_scale_records(L, recs, [4, 2, 0], (640, 480), (640, 480))
     assert out.tobytes() == recs.tobytes()
     # one axis equal: its coordinates are copied, the other axis moves, nothing else does
@@ -225,9 +226,9 @@ def chain_on_the_host(L):
         full, _, _ = H.oracle_registration(sc.frame, tpls, PS.camera(FW, FH))
         small_frame = RC.host_resize_image(L, sc.frame, W, Hh, "area")
         small, _, _ = H.oracle_registration(small_frame, tpls, PS.camera(W, Hh))
-        recs = np.zeros((1, max(len(small), 1)), RC.MARKER_DTYPE)
+        recs = np.zeros((1, max(len(small), 1)), FK.MARKER_DTYPE)
         for k, m in enumerate(small):
-            recs[0, k] = np.frombuffer(bytes(m), RC.MARKER_DTYPE)[0]
+            recs[0, k] = np.frombuffer(bytes(m), FK.MARKER_DTYPE)[0]
         up = RC.host_scale_records(L, recs, [len(small)], (W, Hh), (FW, FH))
         out.append((sc, full, small, up[0]))
     return out
@@ -258,10 +259,7 @@ def test_the_chain_on_the_cpu(L):
 
 # ---- sanitizers ------------------------------------------------------------------------------------------------------------------------
 
-def test_stand_alone_program_under_the_sanitizers(tmp_path):
+def test_stand_alone_program_under_the_sanitizers():
     """tests/emul/resize_emul.cpp with its own main, built with -fsanitize=address,undefined and run as a program: the sweep's
     extremes (sides 1 .. 32767, every pixel size and mode) on heap blocks of exactly the bytes a call may touch"""
-    exe = RC.build_sanitized_program(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert ", 0 bad" in r.stdout and "runtime error" not in r.stderr
+    run_sanitized("resize_emul", "RESIZE_EMUL_MAIN", ", 0 bad", timeout=600)

@@ -3,25 +3,16 @@ plane.  tests/emul/starts_emul.cpp builds the core for the host next to the rule
 on random row pairs, and on whole binary images walked as the kernel walks them (work units of whole tile rows, 240-column
 strips, four lanes per 16x14 tile), where the words' unreliable bits -- halo columns, stale ring rows -- are noise."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import helpers as H
 from helpers import P
-
-SRC = os.path.join(H.ROOT, "tests", "emul", "starts_emul.cpp")
-DEPS = [SRC] + [os.path.join(H.PKG, "csrc", f) for f in ("hd.h", "starts_core.h")]
+from hostbuild import host_core
 
 
 def build_lib():
-    so = os.path.join(H.ROOT, "tests", "emul", "libstarts_emul.so")
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in DEPS):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-DOCVAR_NBR_TILED",
-                               "-I" + os.path.join(H.PKG, "csrc"), "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so, SRC])
-    l = C.CDLL(so)
+    l = host_core("starts_emul")
     l.se_pairs.restype = C.c_longlong
     l.se_walk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int]
     return l

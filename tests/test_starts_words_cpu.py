@@ -6,28 +6,20 @@ tile (qrow = -1, 3, 7, 11) and tile rows of 1, 13 and 14 rows that belong to the
 both for the host."""
 import ctypes as C
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import helpers as H
 from helpers import P
+from hostbuild import host_core
 
-SRC = os.path.join(H.ROOT, "tests", "emul", "starts_words_emul.cpp")
-DEPS = [SRC] + [os.path.join(H.PKG, "csrc", f) for f in ("hd.h", "starts_core.h")]
 QROWS, NROWS = (-1, 3, 7, 11), (1, 13, 14)
 OWN_ALL = 0x00FFFF00
 SINGLE_BITS = (0, 7, 8, 23, 24, 25, 31)
 
 
 def build_lib():
-    so = os.path.join(H.ROOT, "tests", "emul", "libstarts_words_emul.so")
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in DEPS):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-DOCVAR_NBR_TILED",
-                               "-I" + os.path.join(H.PKG, "csrc"), "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so, SRC])
-    l = C.CDLL(so)
+    l = host_core("starts_words_emul")
     for f in (l.sw_lanes, l.sw_rows):
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]
         f.restype = None

@@ -3,25 +3,18 @@ for the host from tests/emul/library_emul.cpp: the code lookup against the refer
 rotation as a prefix shift against sequential rot_square, and the sparse survivors against the literal `||` loop."""
 import ctypes as C
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import helpers as H
 from helpers import P
-
-CSRC = os.path.join(H.PKG, "csrc")
+from hostbuild import host_core
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("library_emul") / "liblibrary_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + CSRC,
-                           "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(H.ROOT, "tests", "emul", "library_emul.cpp")])
-    L = C.CDLL(so)
+def lib():
+    L = host_core("library_emul")
     L.lib_set.argtypes = [C.c_void_p, C.c_int]
     L.lib_square_matches.argtypes = [C.c_void_p, C.c_void_p]
     L.lib_candidate_square.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]

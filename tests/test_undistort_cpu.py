@@ -5,8 +5,8 @@ view.  tests/test_gpu_undistort.py holds the kernels to this build byte for byte
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import helpers as H
-import overlay_chain as OC
 import persp_synth as PS
 import undistort_chain as UC
 
@@ -14,13 +14,13 @@ SIZES = [(33, 17), (320, 240)]
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return UC.build_emul(tmp_path_factory.mktemp("undistort_emul"))
+def L():
+    return UC.build_emul()
 
 
 def odd_records(rng, n, W, Hh):
     """n records with random squares around the frame, every field filled, one NaN and one 1e30 coordinate among them"""
-    r = OC.records(rng.uniform(-20, max(W, Hh) + 20, (n, 8)), template_ids=rng.integers(0, 9, n), scores=rng.integers(0, 2, n))
+    r = FK.records(rng.uniform(-20, max(W, Hh) + 20, (n, 8)), template_ids=rng.integers(0, 9, n), scores=rng.integers(0, 2, n))
     r["glMatrix"] = rng.normal(size=(n, 16))
     r["aspectRatio"] = rng.uniform(0.5, 2, n)
     if n >= 3:
@@ -29,17 +29,17 @@ def odd_records(rng, n, W, Hh):
     return r
 
 
-@pytest.mark.parametrize("fmt", UC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 @pytest.mark.parametrize("size", SIZES)
 def test_a_lens_of_zeros_copies_frames_and_records(L, fmt, size):
     W, Hh = size
     cam = UC.camera(W, Hh, "ZERO")
-    src = OC.Frames(2, W, Hh, fmt, row_pad=3, frame_gap=8, seed=W)
-    dst = UC.Dst(2, W, Hh, fmt, row_pad=1, lead=UC.LEAD + 1)
+    src = FK.Frames(2, W, Hh, fmt, row_pad=3, frame_gap=8, seed=W)
+    dst = UC.dst_frames(2, W, Hh, fmt, row_pad=1, lead=FK.LEAD + 1)
     out = UC.host_undistort(L, src, cam, dst)
     for f in range(2):
         assert (dst.view(f, out) == src.view(f)).all()
-    assert (out[~dst.pixel_mask()] == UC.GUARD).all()
+    assert (out[~dst.pixel_mask()] == FK.GUARD).all()
     recs = odd_records(np.random.default_rng(W), 6, W, Hh).reshape(2, 3)
     assert UC.host_records(L, cam, recs, [3, 2]).tobytes() == recs.tobytes()
 

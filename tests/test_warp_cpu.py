@@ -4,23 +4,23 @@ frames, the record map, the board's plane map, the tile plan, the bird's-eye cha
 the sanitizers, and the ABI.  tests/test_gpu_warp.py holds the kernels to this build byte for byte."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import board_chain as BC
+import frame_kit as FK
 import helpers as H
-import overlay_chain as OC
 import persp_synth as PS
 import warp_chain as WC
+from hostbuild import run_sanitized
 
 CHAIN_MEASURED_PX, CHAIN_BAR_PX, CHAIN_SCENES = WC.CHAIN_MEASURED_PX, WC.CHAIN_BAR_PX, WC.CHAIN_SCENES
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return WC.build_emul(tmp_path_factory.mktemp("warp_emul"))
+def L():
+    return WC.build_emul()
 
 
 def image(rng, w, h, ch):
@@ -34,7 +34,7 @@ def test_constants_agree_with_the_core(L):
 
 # ---- the sampler against numpy ---------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("fmt", WC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 def test_frames_against_numpy(L, fmt):
     """guarded frames with padded rows, aligned and odd layouts, every shared map, both interpolations, both borders, a fill that is
     not zero: numpy's pixels and status, every guard byte kept, the source untouched"""
@@ -46,11 +46,11 @@ def test_frames_against_numpy(L, fmt):
         aligned = k % 2 == 0
         for inverse in (0, WC.INVERSE_MAP):
             use = [n for n in names if maps[n][1] == inverse]
-            src = WC.pix_layout(len(use), *src_size, fmt, aligned, seed=k + 1)
+            src = FK.pix_layout(len(use), *src_size, fmt, aligned, seed=k + 1)
             dst = WC.dst_layout(src, dst_size, aligned)
             rc, got, status = WC.host_warp(L, src, dst, [maps[n][0] for n in use], interp, border, fill, inverse)
             assert rc == len(use) and status.tolist() == [1] * len(use)
-            assert (got[~dst.pixel_mask()] == WC.GUARD).all()
+            assert (got[~dst.pixel_mask()] == FK.GUARD).all()
             for f, n in enumerate(use):
                 want, st = WC.np_warp(src.view(f), maps[n][0], dst_size, interp, border, fill, inverse)
                 assert st == 1
@@ -109,13 +109,13 @@ def test_a_warp_is_the_patch_of_the_same_quad(L, fmt):
     of patch_extract_frame, for quads inside, across and outside the frame"""
     rng = np.random.default_rng(3)
     W, Hh = 160, 120
-    code, ch = WC.FORMATS[fmt], WC.BPP[WC.FORMATS[fmt]]
+    code, ch = FK.FORMATS[fmt], FK.BPP[FK.FORMATS[fmt]]
     img = np.ascontiguousarray(image(rng, W, Hh, ch))
     quads = [[20, 15, 90, 25, 100, 95, 12, 80], [-30, -20, 60, 10, 70, 70, -10, 90], [100, 60, 200, 50, 210, 160, 90, 150],
              [40.5, 30.25, 44.75, 31, 45, 36.5, 39, 35], [300, 300, 400, 300, 400, 400, 300, 400]]
     sizes = [(64, 64), (33, 17), (2, 2), (65, 129), (256, 3)]
     for q, (pw, ph) in zip(quads, sizes):
-        rec = OC.records([q])
+        rec = FK.records([q])
         patch = np.full((ph, pw, ch), 0x5A, np.uint8)
         m = np.zeros(9)
         st = L.warp_patch_reference_emul(img.ctypes.data, W, Hh, W * ch, code, rec.ctypes.data, pw, ph, patch.ctypes.data, m.ctypes.data)
@@ -133,27 +133,27 @@ def test_skipped_frames_keep_their_bytes(L):
     good = WC.about_centre((20, 12), (24, 10), 1.2, 8.0)
     maps = [good] + [WC.SKIPPED_MAPS[n] for n in names] + [good]
     for flags in (0, WC.INVERSE_MAP):
-        src = WC.pix_layout(len(maps), 20, 12, "bgr", False, seed=9)
+        src = FK.pix_layout(len(maps), 20, 12, "bgr", False, seed=9)
         dst = WC.dst_layout(src, (24, 10), False)
         rc, got, status = WC.host_warp(L, src, dst, maps, WC.LINEAR, WC.CONSTANT, [1, 2, 3], flags)
         skipped = [0] + [0 if (flags == 0 or not np.isfinite(WC.SKIPPED_MAPS[n]).all()) else 1 for n in names] + [0]
         skipped[0] = skipped[-1] = 1
         assert status.tolist() == skipped and rc == sum(skipped)
-        assert (got[~dst.pixel_mask()] == WC.GUARD).all()
+        assert (got[~dst.pixel_mask()] == FK.GUARD).all()
         for f in range(len(maps)):
             if status[f] == 0:
-                assert (dst.view(f, got) == WC.GUARD).all()
+                assert (dst.view(f, got) == FK.GUARD).all()
             else:
                 want, st = WC.np_warp(src.view(f), maps[f], (24, 10), WC.LINEAR, WC.CONSTANT, [1, 2, 3], flags)
                 assert st == 1 and (dst.view(f, got) == want).all()
         for n in names:
             ok, _ = WC.host_map(L, WC.SKIPPED_MAPS[n], 0)
             assert not ok and WC.np_invert(WC.SKIPPED_MAPS[n]) is None, n
-    assert L.warp_emul(None, 4, 4, 12, 48, None, 4, 4, 12, 48, 1, 0, None, 2, 0, None, 0, None) == WC.E_ARG
-    assert L.warp_emul(None, 4, 4, 12, 48, None, 4, 4, 12, 48, 1, 0, None, 1, 2, None, 0, None) == WC.E_ARG
-    assert L.warp_emul(None, 4, 4, 12, 48, None, 4, 4, 12, 48, 1, 0, None, 1, 0, None, 4, None) == WC.E_ARG
-    assert L.warp_emul(None, 4, 4, 12, 48, None, 4, 32768, 12, 48, 1, 0, None, 1, 0, None, 0, None) == WC.E_ARG
-    assert L.warp_emul(None, 4, 4, 12, 48, None, 4, 4, 12, 48, 1, 5, None, 1, 0, None, 0, None) == WC.E_ARG
+    assert L.warp_emul(None, 4, 4, 12, 48, None, 4, 4, 12, 48, 1, 0, None, 2, 0, None, 0, None) == FK.E_ARG
+    assert L.warp_emul(None, 4, 4, 12, 48, None, 4, 4, 12, 48, 1, 0, None, 1, 2, None, 0, None) == FK.E_ARG
+    assert L.warp_emul(None, 4, 4, 12, 48, None, 4, 4, 12, 48, 1, 0, None, 1, 0, None, 4, None) == FK.E_ARG
+    assert L.warp_emul(None, 4, 4, 12, 48, None, 4, 32768, 12, 48, 1, 0, None, 1, 0, None, 0, None) == FK.E_ARG
+    assert L.warp_emul(None, 4, 4, 12, 48, None, 4, 4, 12, 48, 1, 5, None, 1, 0, None, 0, None) == FK.E_ARG
 
 
 # ---- records --------------------------------------------------------------------------------------------------------------------------
@@ -166,7 +166,7 @@ def test_record_map_against_numpy(L):
     n, slots = 3, 6
     maps = np.stack([WC.about_centre((640, 480), (800, 600), 1.3, 20.0, 1e-4, -2e-4), np.array([2, 0, 1, 0, 2, 3, 1, 0, -0.25]),
                      np.array([1, 2, 3, 2, 4, 6, 0, 0, 1.0])])
-    recs = np.zeros((n, slots), OC.MARKER_DTYPE)
+    recs = np.zeros((n, slots), FK.MARKER_DTYPE)
     recs["square"] = rng.uniform(-50, 700, (n, slots, 8)).astype(np.float32)
     recs["glMatrix"] = rng.normal(size=(n, slots, 16))
     recs["templateId"] = rng.integers(0, 9, (n, slots))
@@ -180,7 +180,7 @@ def test_record_map_against_numpy(L):
     live = np.arange(slots)[None, :] < np.minimum(counts, slots)[:, None]
     want_sq = np.stack([WC.np_warp_squares(recs["square"][f], maps[f]) for f in range(n)])
     assert want_sq.view(np.uint32)[1, 0, 0] == WC.NAN_BITS and want_sq.view(np.uint32)[1, 1, 1] == WC.NAN_BITS and want_sq.view(np.uint32)[0, 0, 0] == WC.NAN_BITS
-    for out in (None, np.frombuffer(np.full(recs.nbytes, WC.GUARD, np.uint8).tobytes(), OC.MARKER_DTYPE).reshape(n, slots)):
+    for out in (None, np.frombuffer(np.full(recs.nbytes, FK.GUARD, np.uint8).tobytes(), FK.MARKER_DTYPE).reshape(n, slots)):
         rc, got = WC.host_warp_records(L, recs, counts, maps, 0, out=out)
         assert rc == 0
         want = (recs if out is None else out).copy()
@@ -192,7 +192,7 @@ def test_record_map_against_numpy(L):
     for flags in (WC.INVERSE_MAP, WC.POSE, 8, -1):     # (POSE: no camera given)
         before = recs.copy()
         rc, got = WC.host_warp_records(L, recs, counts, maps, flags)
-        assert rc == WC.E_ARG and got.tobytes() == before.tobytes()
+        assert rc == FK.E_ARG and got.tobytes() == before.tobytes()
 
 
 def test_records_follow_the_pixels_and_the_pose_flag(L):
@@ -205,7 +205,7 @@ def test_records_follow_the_pixels_and_the_pose_flag(L):
     K = np.array(list(cam.cameraMatrix)).reshape(3, 3)
     m = (K @ BC.rodrigues(np.array([0.05, -0.08, 0.2])) @ np.linalg.inv(K)).reshape(9)
     sq = PS.project(cam, *PS.pose(cam, 300, 250, 110, 25, 30, 40)).reshape(1, 8).astype(np.float32)
-    recs = OC.records(sq).reshape(1, 1)
+    recs = FK.records(sq).reshape(1, 1)
     recs["aspectRatio"] = 1.0
     rc, got = WC.host_warp_records(L, recs, [1], m, WC.POSE, cam=cam)
     assert rc == 0
@@ -344,13 +344,13 @@ def birds_eye(L, Lb, bgr, board, tpls, cam, rect, size, pose=None):
     return found, pose
 
 
-def test_the_birds_eye_chain_on_the_cpu(L, board_scenes, tmp_path_factory):
+def test_the_birds_eye_chain_on_the_cpu(L, board_scenes):
     """a board (markers turned by 25 degrees in its plane) seen by a pinhole camera at tilts of 0 .. 50 degrees: the host board
     core's pose from the oracle's records, the plane map of the board's rectangle, the host warp to a bird's-eye frame -- on which the
     oracle's registration finds every marker of the board with the right template, its corners within CHAIN_BAR_PX of where the board
     layout and the rectangle put them.  Measured: 1.07 px at most (0.49 .. 1.07 per scene; 0.49 .. 0.62 with the true pose)."""
     b = board_scenes
-    Lb = BC.build_emul(tmp_path_factory.mktemp("board_emul"))
+    Lb = BC.build_emul()
     tpls = H.oracle_templates(b["names"])
     rect, size = WC.chain_rect(b["board"])
     worst = 0.0
@@ -365,7 +365,7 @@ def test_the_birds_eye_chain_on_the_cpu(L, board_scenes, tmp_path_factory):
     assert worst <= CHAIN_MEASURED_PX       # the figure DESIGN.md states is what this chain gives
 
 
-def test_axis_aligned_markers_in_the_birds_eye_frame(L, tmp_path_factory):
+def test_axis_aligned_markers_in_the_birds_eye_frame(L):
     """board_chain's own board, whose markers stand axis-aligned in every bird's-eye frame: every marker is found with the right
     template.  On an axis-aligned square with straight edges the oracle's polygon approximation itself puts the corners (2, 1) px
     along the contour, sqrt(5) = 2.24 px off, under the TRUE pose -- an ideal rectification; that is the detector's own error on such
@@ -374,7 +374,7 @@ def test_axis_aligned_markers_in_the_birds_eye_frame(L, tmp_path_factory):
     2.236 px with the solved pose and with the true pose, in both scenes."""
     cam = PS.camera(1920, 1080)
     names, board, sc = BC.scenes(2, cam=cam)
-    Lb = BC.build_emul(tmp_path_factory.mktemp("board_emul"))
+    Lb = BC.build_emul()
     tpls = H.oracle_templates(names)
     rect, size = WC.chain_rect(board)
     for i, (bgr, truth, R, t) in enumerate(sc):
@@ -389,14 +389,11 @@ def test_axis_aligned_markers_in_the_birds_eye_frame(L, tmp_path_factory):
 
 # ---- sanitizers ------------------------------------------------------------------------------------------------------------------------
 
-def test_stand_alone_program_under_the_sanitizers(tmp_path):
+def test_stand_alone_program_under_the_sanitizers():
     """tests/emul/warp_emul.cpp with its own main, built with -fsanitize=address,undefined and run as a program: sides 1 .. 32767,
     every pixel size, interpolation and border, maps that magnify, shrink, cross the horizon and miss the source, on heap blocks of
     exactly the bytes a call may touch"""
-    exe = WC.build_sanitized_program(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert ", 0 bad" in r.stdout and "runtime error" not in r.stderr
+    run_sanitized("warp_emul", "WARP_EMUL_MAIN", ", 0 bad", timeout=600)
 
 
 # ---- ABI -------------------------------------------------------------------------------------------------------------------------------

@@ -7,17 +7,19 @@ import subprocess
 import numpy as np
 import pytest
 
+import frame_kit as FK
 import overlay_chain as OC
 import yuv_chain as YC
 from helpers import P
+from hostbuild import run_sanitized
 
 MATS = ["bt601", "bt709"]
 N24 = 1 << 24
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return YC.build_emul(tmp_path_factory.mktemp("yuv_emul"))
+def L():
+    return YC.build_emul()
 
 
 @pytest.fixture(scope="module")
@@ -146,22 +148,22 @@ def test_chroma_of_mixed_blocks(L, m, log2n):
 # ---- the frame loops ---------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("layout", list(YC.LAYOUTS))
-@pytest.mark.parametrize("fmt", YC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 def test_yuv_to_frames_on_every_layout_format_and_border(L, layout, fmt):
     """an odd leading offset, row padding, a gap between the planes and between the frames; two frames; both tables"""
     for i, (W, Hh) in enumerate(YC.SIZES):
         m = MATS[i % 2]
         yuv = YC.Yuv(2, W, Hh, layout, aligned=False, seed=W + Hh)
-        dst = YC.pix_layout(2, W, Hh, fmt, aligned=False, fill=YC.GUARD)
+        dst = FK.pix_layout(2, W, Hh, fmt, aligned=False, fill=FK.GUARD)
         out = YC.host_to_frames(L, yuv, m, dst)
-        assert (out[~dst.pixel_mask()] == YC.GUARD).all(), (W, Hh)
+        assert (out[~dst.pixel_mask()] == FK.GUARD).all(), (W, Hh)
         for f in range(2):
             want = YC.np_frame_to_pixels(m, fmt, *yuv.samples(f))
             assert (dst.view(f, out) == want).all(), (W, Hh, f)
             if dst.bpp == 4:
                 assert (dst.view(f, out)[..., 3] == 255).all()
         if fmt == "gray":   # the library's grey of the BGR target, byte for byte
-            bgr = YC.pix_layout(2, W, Hh, "bgr", aligned=True, fill=YC.GUARD)
+            bgr = FK.pix_layout(2, W, Hh, "bgr", aligned=True, fill=FK.GUARD)
             ob = YC.host_to_frames(L, yuv, m, bgr)
             for f in range(2):
                 b = bgr.view(f, ob).astype(np.int64)
@@ -169,14 +171,14 @@ def test_yuv_to_frames_on_every_layout_format_and_border(L, layout, fmt):
 
 
 @pytest.mark.parametrize("layout", list(YC.LAYOUTS))
-@pytest.mark.parametrize("fmt", YC.FMTS)
+@pytest.mark.parametrize("fmt", FK.FMTS)
 def test_frames_to_yuv_on_every_layout_format_and_border(L, layout, fmt):
     for i, (W, Hh) in enumerate(YC.SIZES):
         m = MATS[(i + 1) % 2]
-        src = YC.pix_layout(2, W, Hh, fmt, aligned=False, seed=W * Hh)
+        src = FK.pix_layout(2, W, Hh, fmt, aligned=False, seed=W * Hh)
         yuv = YC.Yuv(2, W, Hh, layout, aligned=False)
         out = YC.host_to_yuv(L, src, m, yuv)
-        assert (out[~yuv.sample_mask()] == YC.GUARD).all(), (W, Hh)
+        assert (out[~yuv.sample_mask()] == FK.GUARD).all(), (W, Hh)
         for f in range(2):
             want = YC.np_pixels_to_frame(m, fmt, src.view(f), yuv.s420)
             for got_plane, want_plane in zip(yuv.samples(f, out), want):
@@ -191,13 +193,13 @@ def test_frames_to_yuv_on_every_layout_format_and_border(L, layout, fmt):
 @pytest.mark.parametrize("fmt", ["bgr", "rgba", "gray"])
 def test_the_layouts_of_a_subsampling_hold_the_same_samples(L, fmt):
     for W, Hh in YC.SIZES:
-        src = YC.pix_layout(1, W, Hh, fmt, aligned=True, seed=W)
+        src = FK.pix_layout(1, W, Hh, fmt, aligned=True, seed=W)
         for a, b in (("nv12", "i420"), ("yuyv", "uyvy")):
             ya, yb = YC.Yuv(1, W, Hh, a), YC.Yuv(1, W, Hh, b, aligned=True)
             sa, sb = ya.samples(0, YC.host_to_yuv(L, src, "bt601", ya)), yb.samples(0, YC.host_to_yuv(L, src, "bt601", yb))
             assert all((p == q).all() for p, q in zip(sa, sb)), (W, Hh, a, b)
             # and back: the same pixels from either layout
-            da, db = (YC.pix_layout(1, W, Hh, fmt, aligned=False, fill=YC.GUARD) for _ in range(2))
+            da, db = (FK.pix_layout(1, W, Hh, fmt, aligned=False, fill=FK.GUARD) for _ in range(2))
             ya.put_samples(0, *sa)
             yb.put_samples(0, *sb)
             assert (YC.host_to_frames(L, ya, "bt601", da) == YC.host_to_frames(L, yb, "bt601", db)).all()
@@ -222,10 +224,7 @@ def test_the_shipped_kernels_hold_no_packed_shift_saturate(tmp_path):
     assert seen >= 24   # (the listing held the kernels: 2 directions x 3 pixel sizes x 2 alignments x 2 subsamplings)
 
 
-def test_the_emulation_is_clean_under_the_sanitizers(tmp_path):
+def test_the_emulation_is_clean_under_the_sanitizers():
     """tests/emul/yuv_emul.cpp with its own main -- the layout sweep on heap blocks of exactly the bytes a conversion may touch --
     built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a program of its own"""
-    exe = YC.build_sanitized_program(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "360 cases, 0 bad" in r.stdout and "runtime error" not in r.stderr
+    run_sanitized("yuv_emul", "YUV_EMUL_MAIN", "360 cases, 0 bad", timeout=300)

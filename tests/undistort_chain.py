@@ -1,20 +1,17 @@
 """Undistortion for the undistort tests (ocvar_hip_undistort / ocvar_hip_undistort_records): the host build of
 opencv-ar_amd/csrc/undistort_core.h (tests/emul/undistort_emul.cpp), the lenses, guarded destination buffers, and distort_image,
-which makes a truly distorted view of a pinhole-rendered frame in numpy.  Frames, records and guard bytes are overlay_chain's.
+which makes a truly distorted view of a pinhole-rendered frame in numpy.  Frames, records and guard bytes are frame_kit's.
 Shared by tests/test_undistort_cpu.py and tests/test_gpu_undistort.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import helpers as H
-import overlay_chain as OC
 import persp_synth as PS
+from frame_kit import GUARD, LEAD, Frames
 from helpers import P
-from overlay_chain import BPP, FORMATS, GUARD, LEAD, MARKER_DTYPE, Frames, records  # noqa: F401
+from hostbuild import host_core
 
-FMTS = ["bgr", "rgb", "bgra", "rgba", "gray"]
 # name -> (k1 k2 p1 p2 k3, shift of the principal point in pixels)
 LENSES = {
     "BARREL": (list(PS.DIST), (0.0, 0.0)),                              # no destination pixel maps outside the frame
@@ -25,12 +22,8 @@ LENSES = {
 }
 
 
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "libundistort_emul.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + OC.CSRC,
-                           "-I" + os.path.join(H.ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(H.ROOT, "tests", "emul", "undistort_emul.cpp")])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("undistort_emul")
     L.undistort_frame_emul.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong]
     L.undistort_records_emul.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.undistort_source_emul.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -49,17 +42,10 @@ def camera(width, height, lens):
     return cam
 
 
-class Dst(OC.Frames):
-    """destination frames: a guarded buffer like Frames, all GUARD, whose first frame starts `lead` bytes into the buffer (an odd
-    lead: an odd address, device allocations being aligned)"""
-
-    def __init__(self, n, width, height, fmt, row_pad=0, frame_gap=0, lead=LEAD):
-        self.lead = lead
-        OC.Frames.__init__(self, n, width, height, fmt, row_pad=row_pad, frame_gap=frame_gap, fill=GUARD)
-        self.buf = np.full(lead + n * self.frame_stride + LEAD, GUARD, np.uint8)
-
-    def offset(self, f=0):
-        return getattr(self, "lead", LEAD) + f * self.frame_stride
+def dst_frames(n, width, height, fmt, row_pad=0, frame_gap=0, lead=LEAD):
+    """destination frames: guarded Frames, all GUARD, whose first frame starts `lead` bytes into the buffer (an odd lead: an odd
+    address, device allocations being aligned)"""
+    return Frames(n, width, height, fmt, row_pad=row_pad, frame_gap=frame_gap, lead=lead, fill=GUARD)
 
 
 def host_undistort(L, src, cam, dst, buf=None):

@@ -1,28 +1,22 @@
 """Projective warps for the warp tests (ocvar_hip_warp / ocvar_hip_warp_records / ocvar_hip_board_plane_maps): the host build of
 opencv-ar_amd/csrc/warp_core.h (tests/emul/warp_emul.cpp), a numpy restatement of the sampler, the record map and the plane map that
-shares no code with it, guarded frames (yuv_chain.pix_layout on overlay_chain.Frames), the maps the CPU and GPU tests share, and the
+shares no code with it, guarded frames (frame_kit.pix_layout), the maps the CPU and GPU tests share, and the
 bird's-eye chain on board_chain's scenes.  Shared by tests/test_warp_cpu.py and tests/test_gpu_warp.py."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
 import board_chain as BC
-import helpers as H
-import overlay_chain as OC
-from overlay_chain import BPP, FORMATS, GUARD, LEAD, MARKER_DTYPE  # noqa: F401
-from yuv_chain import pix_layout  # noqa: F401
+from frame_kit import FORMATS, GUARD, pix_layout
+from hostbuild import host_core
 
-FMTS = ["bgr", "rgb", "bgra", "rgba", "gray"]
 FMT_NAMES = {v: k for k, v in FORMATS.items()}
 NEAREST, LINEAR = 0, 1
 CONSTANT, REPLICATE = 0, 1
 INTERPS = {"nearest": NEAREST, "linear": LINEAR}
 BORDERS = {"constant": CONSTANT, "replicate": REPLICATE}
 INVERSE_MAP, ONE_MAP, POSE = 1, 2, 4
-E_ARG = -2
 # warp.hip: a workgroup owns a destination tile of WARP_TILE_W x warp_tile_h(bytes per pixel) pixels, a lane 4 consecutive ones; the
 # LDS image of a staged tile's source window holds WARP_LDS_DWORDS dwords (warp_core.h; tests/test_warp_cpu.py compares these with
 # the core's)
@@ -34,15 +28,11 @@ TILE_H = max(TILE_HS.values())         # (the sizes of PLAN_CASES are cut for th
 CHAIN_SCENES = 4
 CHAIN_MEASURED_PX = 1.07
 CHAIN_BAR_PX = min(CHAIN_MEASURED_PX + 1.0, 2.0)
-EMUL_SRC = os.path.join(H.ROOT, "tests", "emul", "warp_emul.cpp")
-EMUL_FLAGS = ["-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + OC.CSRC, "-I" + os.path.join(H.ROOT, "include")]
 NAN_BITS = 0x7FC00000
 
 
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "libwarp_emul.so")
-    subprocess.check_call(["g++", "-O2"] + EMUL_FLAGS + ["-shared", "-o", so, EMUL_SRC])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("warp_emul")
     vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
     L.warp_emul.argtypes = [vp, i, i, ll, ll, vp, i, i, ll, ll, i, i, vp, i, i, vp, i, vp]
     L.warp_map_emul.argtypes = [vp, i, vp]
@@ -54,14 +44,6 @@ def build_emul(out_dir):
     L.warp_patch_reference_emul.argtypes = [vp, i, i, ll, i, vp, i, i, vp, vp]
     L.warp_sincos_emul.argtypes = [C.c_double, vp]
     return L
-
-
-def build_sanitized_program(out_dir):
-    """the emulation with its stand-alone main under AddressSanitizer and UndefinedBehaviorSanitizer -> the program's path"""
-    exe = os.path.join(str(out_dir), "warp_emul_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DWARP_EMUL_MAIN"] +
-                          EMUL_FLAGS + ["-o", exe, EMUL_SRC])
-    return exe
 
 
 def maps_array(maps):

@@ -1,18 +1,15 @@
 """YUV conversion for the yuv tests (ocvar_hip_yuv_to_frames / ocvar_hip_frames_to_yuv): the host build of
 opencv-ar_amd/csrc/yuv_core.h (tests/emul/yuv_emul.cpp), guarded buffers of NV12, I420, YUYV and UYVY frames next to
-overlay_chain's guarded frames, and a numpy restatement of the equations.  Shared by tests/test_yuv_cpu.py and
+frame_kit's guarded frames, and a numpy restatement of the equations.  Shared by tests/test_yuv_cpu.py and
 tests/test_gpu_yuv.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import helpers as H
 import overlay_chain as OC
-from overlay_chain import BPP, FORMATS, GUARD, LEAD  # noqa: F401
+from frame_kit import FORMATS, GUARD, LEAD
+from hostbuild import host_core
 
-FMTS = ["bgr", "rgb", "bgra", "rgba", "gray"]
 LAYOUTS = {"nv12": 0, "i420": 1, "yuyv": 2, "uyvy": 3}
 MATRICES = {"bt601": 0, "bt709": 1}
 # one lane, a full lane, a lane with a 2-pixel tail, both sides of a wave's 512-pixel span, a second workgroup
@@ -25,14 +22,10 @@ COEF = {
     "bt709": dict(cy=1220945, cvr=1879825, cub=2215014, cug=-223607, cvg=-558796, ry=191455, gy=644067, by=65019,
                   ru=-105533, gu=-355018, bu=460551, rv=460551, gv=-418321, bv=-42230),
 }
-EMUL_SRC = os.path.join(H.ROOT, "tests", "emul", "yuv_emul.cpp")
-EMUL_FLAGS = ["-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + OC.CSRC, "-I" + os.path.join(H.ROOT, "include")]
 
 
-def build_emul(out_dir):
-    so = os.path.join(str(out_dir), "libyuv_emul.so")
-    subprocess.check_call(["g++", "-O2"] + EMUL_FLAGS + ["-shared", "-o", so, EMUL_SRC])
-    L = C.CDLL(so)
+def build_emul():
+    L = host_core("yuv_emul")
     vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
     L.yuv_to_frames_emul.argtypes = [i, i, vp, vp, vp, ll, ll, ll, vp, ll, ll, i, i, i, i]
     L.frames_to_yuv_emul.argtypes = [i, i, vp, vp, vp, ll, ll, ll, vp, ll, ll, i, i, i, i]
@@ -41,41 +34,6 @@ def build_emul(out_dir):
     L.yuv_chroma_emul.argtypes = [i, i, vp, i, vp]
     L.yuv_coef_emul.argtypes = [i, vp]
     return L
-
-
-def build_sanitized_program(out_dir):
-    """the emulation with its stand-alone main under AddressSanitizer and UndefinedBehaviorSanitizer -> the program's path"""
-    exe = os.path.join(str(out_dir), "yuv_emul_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DYUV_EMUL_MAIN"] + EMUL_FLAGS +
-                          ["-o", exe, EMUL_SRC])
-    return exe
-
-
-class Pix(OC.Frames):
-    """overlay_chain's guarded frames with the first frame `lead` bytes into the buffer; fill None: random pixels"""
-
-    def __init__(self, n, width, height, fmt, row_pad=0, frame_gap=0, lead=LEAD, seed=0, fill=None):
-        self.lead = lead
-        OC.Frames.__init__(self, n, width, height, fmt, row_pad=row_pad, frame_gap=frame_gap, seed=seed, fill=fill)
-        pixels = [self.view(f).copy() for f in range(n)]
-        self.lead = lead
-        self.buf = np.full(lead + n * self.frame_stride + LEAD, GUARD, np.uint8)
-        for f in range(n):
-            self.view(f)[...] = pixels[f]
-
-    def offset(self, f=0):
-        return getattr(self, "lead", LEAD) + f * self.frame_stride
-
-
-def pix_layout(n, width, height, fmt, aligned, seed=0, fill=None):
-    """frames for a case: aligned -- address, row stride and frame stride multiples of 4 (4 .. 7 bytes of row padding); else an odd
-    lead, 1 byte of row padding and a frame gap of 5"""
-    bpp = BPP[FORMATS[fmt]]
-    if aligned:
-        p = Pix(n, width, height, fmt, row_pad=4 + (-width * bpp) % 4, frame_gap=8, lead=LEAD, seed=seed, fill=fill)
-        assert p.row_stride % 4 == 0 and p.frame_stride % 4 == 0 and p.lead % 4 == 0
-        return p
-    return Pix(n, width, height, fmt, row_pad=1, frame_gap=5, lead=LEAD + 1, seed=seed, fill=fill)
 
 
 class Yuv:
