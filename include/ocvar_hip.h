@@ -407,7 +407,8 @@ int ocvar_hip_flow_records(OcvarHip* ctx, const uint8_t* d_prev_frames, int prev
                            int n_frames, int format, const OcvarMarker* d_markers, const int* d_counts, int records_per_frame,
                            const OcvarFlowParams* params, OcvarMarker* d_out, int* d_status, float* d_err, void* stream);
 
-/* YUV conversion: 8-bit limited-range NV12, I420, YUYV and UYVY frames, as a video decoder or a capture card leaves them in
+/* YUV conversion, the 8-bit limited-range subset (every other range, depth and layout: the _ex calls below): NV12, I420, YUYV and
+ * UYVY frames, as a video decoder or a capture card leaves them in
  * device memory, to the interleaved frame formats every other entry point takes, and back for an encoder -- the one full-frame
  * pass of a device-resident decode, detect, draw, encode loop the library did not have.  The definition, bit for bit, is
  * opencv-ar_amd/csrc/yuv_core.h: 20-bit fixed-point integer arithmetic, the chroma sample used as it is (nearest) towards colour,
@@ -445,6 +446,36 @@ int ocvar_hip_yuv_to_frames(OcvarHip* ctx, const OcvarYuvFrames* src, uint8_t* d
                             int width, int height, int n_frames, int format, void* stream);
 int ocvar_hip_frames_to_yuv(OcvarHip* ctx, const uint8_t* d_src, int src_row_stride, size_t src_frame_stride, const OcvarYuvFrames* dst,
                             int width, int height, int n_frames, int format, void* stream);
+
+/* YUV conversion of every range, depth and layout: the two calls above are the 8-bit limited-range subset; these take what else
+ * arrives in device memory -- the P010 / P012 / P016 surfaces a hardware decoder makes of HEVC Main10, AV1 and VP9 profile 2,
+ * the full-range YUV of JPEG and MJPEG, NV21, planar 4:4:4 and the BT.2020 matrix (the matrix only: no transfer function, no tone
+ * mapping).  The definition, bit for bit and all integer, is opencv-ar_amd/csrc/yuv_ex_core.h; on every case both pairs of calls
+ * accept they write the same bytes.
+ *   OcvarYuvFramesEx  layout: the four of OcvarYuvFrames, OCVAR_YUV_NV21 (NV12 with V first in the interleaved plane) and
+ *                  OCVAR_YUV_I444 (three planes of full resolution: Y at y, U at c0, V at c1, the chroma rows c_pitch apart; no
+ *                  subsampling, so odd widths and heights are taken).  matrix: OCVAR_YUV_BT601, _BT709 or _BT2020.  range:
+ *                  OCVAR_YUV_LIMITED (Y 16 .. 235, U V 16 .. 240, times 2^(bits - 8)) or OCVAR_YUV_FULL (0 .. 2^bits - 1); range
+ *                  and matrix combine freely.  bits: 8, 10, 12 or 16; above 8 with OCVAR_YUV_NV12 only, which is then P010 / P012 /
+ *                  P016: 16-bit little-endian words, the sample word >> (16 - bits), the low bits ignored on read and written as
+ *                  zero; pitches stay in bytes, and plane addresses, pitches and frame stride are even.  Everything else as in
+ *                  OcvarYuvFrames.
+ * Towards colour a limited-range Y below its offset reads as black; towards YUV the limited range is an offset and a scale, not
+ * a clamp (Y is held to the sample range only), as in the 8-bit calls.  Chroma towards colour is the sample as it is, chroma from
+ * colour the mean colour of the 2 x 2, 2 x 1 or (I444) single pixel.  The frames side, the dword and byte paths (bytes: halfwords
+ * for 16-bit samples), the sizes, n_frames, the stream and the refusals are those of the calls above; refused besides: an unknown
+ * range or bits, bits > 8 with a layout other than NV12, 16-bit samples at an odd address, pitch or frame stride.  No batch, no
+ * workspace, neither waits. */
+enum { OCVAR_YUV_NV21 = 4, OCVAR_YUV_I444 = 5 };          /* _ex only */
+enum { OCVAR_YUV_BT2020 = 2 };                            /* _ex only */
+enum { OCVAR_YUV_LIMITED = 0, OCVAR_YUV_FULL = 1 };
+typedef struct { int layout, matrix, range, bits;
+                 void* y; void* c0; void* c1;
+                 int y_pitch, c_pitch; size_t frame_stride; } OcvarYuvFramesEx;   /* 56 bytes */
+int ocvar_hip_yuv_to_frames_ex(OcvarHip* ctx, const OcvarYuvFramesEx* src, uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride,
+                               int width, int height, int n_frames, int format, void* stream);
+int ocvar_hip_frames_to_yuv_ex(OcvarHip* ctx, const uint8_t* d_src, int src_row_stride, size_t src_frame_stride, const OcvarYuvFramesEx* dst,
+                               int width, int height, int n_frames, int format, void* stream);
 
 /* Resizing: device-resident frames brought to another size, and the marker records found at one size carried to the other --
  * a 3840 x 2160 stream is shrunk to 1920 x 1080 for a context of that size (with the camera of cvarCameraScale), and the records

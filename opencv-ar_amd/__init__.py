@@ -35,7 +35,7 @@ HIP_SYMBOLS = [
     "ocvar_hip_patches", "ocvar_hip_patches_records",
     "ocvar_hip_undistort", "ocvar_hip_undistort_records",
     "ocvar_hip_flow_records",
-    "ocvar_hip_yuv_to_frames", "ocvar_hip_frames_to_yuv",
+    "ocvar_hip_yuv_to_frames", "ocvar_hip_frames_to_yuv", "ocvar_hip_yuv_to_frames_ex", "ocvar_hip_frames_to_yuv_ex",
     "ocvar_hip_resize", "ocvar_hip_scale_records",
     "ocvar_hip_orient", "ocvar_hip_orient_records", "ocvar_hip_orient_camera",
     "ocvar_hip_warp", "ocvar_hip_warp_records", "ocvar_hip_board_plane_maps",
@@ -158,6 +158,11 @@ def annotate_style(**kw):
 
 YUV_LAYOUTS = {"nv12": 0, "i420": 1, "yuyv": 2, "uyvy": 3}   # include/ocvar_hip.h: OCVAR_YUV_NV12 ..
 YUV_MATRICES = {"bt601": 0, "bt709": 1}                      # include/ocvar_hip.h: OCVAR_YUV_BT601, OCVAR_YUV_BT709
+# what OcvarYuvFramesEx takes (YuvFramesEx): the above and OCVAR_YUV_NV21, _I444; OCVAR_YUV_BT2020; OCVAR_YUV_LIMITED, _FULL; the depths
+YUV_EX_LAYOUTS = {"nv12": 0, "i420": 1, "yuyv": 2, "uyvy": 3, "nv21": 4, "i444": 5}
+YUV_EX_MATRICES = {"bt601": 0, "bt709": 1, "bt2020": 2}
+YUV_RANGES = {"limited": 0, "full": 1}
+YUV_BITS = (8, 10, 12, 16)
 RESIZE_INTERPS = {"nearest": 0, "linear": 1, "area": 2}     # include/ocvar_hip.h: OCVAR_RESIZE_NEAREST ..
 SCALE_POSE = 1                                              # include/ocvar_hip.h: OCVAR_SCALE_POSE
 # include/ocvar_hip.h: OCVAR_ORIENT_IDENTITY ..; a pixel (x, y) of a W x H frame goes to (x, y), (H-1-y, x), (W-1-x, H-1-y), (y, W-1-x),
@@ -334,6 +339,48 @@ class YuvFrames(C.Structure):  # OcvarYuvFrames: where the planes of a block of 
         return cls(code, m, ptr, None, None, pitch, 0, pitch * height)
 
 
+class YuvFramesEx(C.Structure):  # OcvarYuvFramesEx: YuvFrames with a range, a depth, and the layouts and matrices of the _ex calls
+    _fields_ = [("layout", C.c_int), ("matrix", C.c_int), ("range", C.c_int), ("bits", C.c_int), ("y", C.c_void_p), ("c0", C.c_void_p),
+                ("c1", C.c_void_p), ("y_pitch", C.c_int), ("c_pitch", C.c_int), ("frame_stride", C.c_size_t)]
+
+    @staticmethod
+    def codes(layout, matrix="bt601", range="limited", bits=8):
+        """(layout, matrix, range, bits) as the ABI's numbers; ValueError for what it refuses: an unknown name or number, a depth
+        other than 8, 10, 12, 16, more than 8 bits with a layout other than 'nv12'"""
+        code = _yuv_code(YUV_EX_LAYOUTS, "layout", layout)
+        m = _yuv_code(YUV_EX_MATRICES, "matrix", matrix)
+        r = _yuv_code(YUV_RANGES, "range", range)
+        if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or int(bits) not in YUV_BITS:
+            raise ValueError(f"YUV samples have {YUV_BITS} bits, got {bits!r}")
+        if bits > 8 and code != 0:
+            raise ValueError("more than 8 bits come as 'nv12' only (P010, P012, P016)")
+        return code, m, r, int(bits)
+
+    @classmethod
+    def from_surface(cls, ptr, width, height, layout, pitch=None, matrix="bt601", range="limited", bits=8):
+        """Frames whose planes follow each other without a gap, frame after frame, as YuvFrames.from_surface lays them out: 'nv12'
+        and 'nv21' -- Y, then the interleaved chroma rows, all `pitch` bytes apart (default: width times the bytes of a sample; with
+        bits 10, 12 or 16 'nv12' is P010, P012 or P016 and its pitch even); 'i420' -- Y, U, V, the chroma rows pitch / 2 apart;
+        'i444' -- Y, U, V, all rows `pitch` apart; 'yuyv' / 'uyvy' -- one plane.  ValueError for what the ABI refuses of these
+        parameters."""
+        code, m, r, bits = cls.codes(layout, matrix, range, bits)
+        sb = 2 if bits > 8 else 1
+        if code in (2, 3):
+            pitch = 2 * width if pitch is None else pitch
+            return cls(code, m, r, bits, ptr, None, None, pitch, 0, pitch * height)
+        pitch = width * sb if pitch is None else pitch
+        if sb == 2 and (pitch % 2 or ptr % 2):
+            raise ValueError("16-bit samples lie at even addresses, an even pitch apart")
+        if code == 5:
+            return cls(code, m, r, bits, ptr, ptr + pitch * height, ptr + 2 * pitch * height, pitch, pitch, 3 * pitch * height)
+        if height % 2 or (code == 1 and pitch % 2):
+            raise ValueError("4:2:0 surfaces have an even height, and an even pitch when planar")
+        c_pitch = pitch // 2 if code == 1 else pitch
+        c0 = ptr + pitch * height
+        c1 = c0 + c_pitch * (height // 2) if code == 1 else None
+        return cls(code, m, r, bits, ptr, c0, c1, pitch, c_pitch, pitch * height * 3 // 2)
+
+
 class BoardMarker(C.Structure):  # OcvarBoardMarker: a template and the board-plane (z = 0) coordinates of its corners 0..3
     _fields_ = [("templateId", C.c_int), ("pad", C.c_int), ("corner", C.c_double * 8)]
 
@@ -489,6 +536,8 @@ def hip_lib():
         lib.ocvar_hip_flow_records.argtypes = [vp, vp, i, sz, vp, i, sz, i, i, i, i, vp, vp, i, vp, vp, vp, vp, vp]
         lib.ocvar_hip_yuv_to_frames.argtypes = [vp, vp, vp, i, sz, i, i, i, i, vp]
         lib.ocvar_hip_frames_to_yuv.argtypes = [vp, vp, i, sz, vp, i, i, i, i, vp]
+        lib.ocvar_hip_yuv_to_frames_ex.argtypes = [vp, vp, vp, i, sz, i, i, i, i, vp]
+        lib.ocvar_hip_frames_to_yuv_ex.argtypes = [vp, vp, i, sz, vp, i, i, i, i, vp]
         lib.ocvar_hip_resize.argtypes = [vp, vp, i, i, i, sz, vp, i, i, i, sz, i, i, i, vp]
         lib.ocvar_hip_scale_records.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp, vp]
         lib.ocvar_hip_orient.argtypes = [vp, vp, i, i, i, sz, vp, i, sz, i, i, i, vp]
@@ -935,23 +984,34 @@ class Detector:
         self._check(self._lib.ocvar_hip_undistort_records(self._ctx, d_markers, d_counts, n_frames, per_frame, d_out, stream),
                     "undistort_records")
 
+    @staticmethod
+    def _yuv_call(yuv, plain, ex):
+        """the entry point that takes the descriptor: a YuvFrames goes to the 8-bit limited-range call, a YuvFramesEx to the _ex one"""
+        if isinstance(yuv, YuvFramesEx):
+            return ex
+        if isinstance(yuv, YuvFrames):
+            return plain
+        raise TypeError(f"a YuvFrames or a YuvFramesEx describes the YUV frames, got {type(yuv).__name__}")
+
     def yuv_to_frames(self, yuv, d_dst, width, height, n_frames, fmt=None, dst_row_stride=None, dst_frame_stride=None, stream=None):
         """n_frames device frames in NV12, I420, YUYV or UYVY (yuv: a YuvFrames) converted into the device frames at d_dst in format
         fmt (default: the input format): OpenCV's cvtColor COLOR_YUV2BGR_NV12 and its relatives, limited range, the matrix yuv names.
         A four-channel destination gets byte 3 = 255, 'gray' the library's grey of the converted colour.  The two sides must not
-        overlap.  Needs no batch, does not wait (stream None: the detector's own stream)."""
+        overlap.  Needs no batch, does not wait (stream None: the detector's own stream).  With a YuvFramesEx: any of its layouts
+        ('nv21', 'i444' too), ranges, matrices and depths (P010, P012, P016), through ocvar_hip_yuv_to_frames_ex."""
         code, dst_row_stride, dst_frame_stride = self._strides(fmt, width, height, dst_row_stride, dst_frame_stride)
-        self._check(self._lib.ocvar_hip_yuv_to_frames(self._ctx, C.byref(yuv), d_dst, dst_row_stride, dst_frame_stride, width, height, n_frames,
-                                                      code, stream), "yuv_to_frames")
+        call = self._yuv_call(yuv, self._lib.ocvar_hip_yuv_to_frames, self._lib.ocvar_hip_yuv_to_frames_ex)
+        self._check(call(self._ctx, C.byref(yuv), d_dst, dst_row_stride, dst_frame_stride, width, height, n_frames, code, stream), "yuv_to_frames")
 
     def frames_to_yuv(self, d_src, yuv, width, height, n_frames, fmt=None, src_row_stride=None, src_frame_stride=None, stream=None):
         """n_frames device frames at d_src in format fmt (default: the input format) converted into the NV12, I420, YUYV or UYVY device
         frames yuv (a YuvFrames) describes: OpenCV's cvtColor COLOR_BGR2YUV_I420 and its relatives, limited range, a chroma sample from
         the mean colour of its 2 x 2 or 2 x 1 pixels.  The two sides must not overlap.  Needs no batch, does not wait (stream None:
-        the detector's own stream)."""
+        the detector's own stream).  With a YuvFramesEx: any of its layouts, ranges, matrices and depths, a 4:4:4 chroma sample from
+        its own pixel, the low bits of a 16-bit word zero, through ocvar_hip_frames_to_yuv_ex."""
         code, src_row_stride, src_frame_stride = self._strides(fmt, width, height, src_row_stride, src_frame_stride)
-        self._check(self._lib.ocvar_hip_frames_to_yuv(self._ctx, d_src, src_row_stride, src_frame_stride, C.byref(yuv), width, height, n_frames,
-                                                      code, stream), "frames_to_yuv")
+        call = self._yuv_call(yuv, self._lib.ocvar_hip_frames_to_yuv, self._lib.ocvar_hip_frames_to_yuv_ex)
+        self._check(call(self._ctx, d_src, src_row_stride, src_frame_stride, C.byref(yuv), width, height, n_frames, code, stream), "frames_to_yuv")
 
     def resize(self, d_src, src_width, src_height, d_dst, dst_width, dst_height, n_frames, interp="area", fmt=None, src_row_stride=None,
                src_frame_stride=None, dst_row_stride=None, dst_frame_stride=None, stream=None):

@@ -415,6 +415,38 @@ extern "C" int ocvar_hip_frames_to_yuv(OcvarHip* c, const uint8_t* d_src, int sr
     return yuv_convert(c, "frames_to_yuv", dst, d_src, src_row_stride, src_frame_stride, width, height, n_frames, format, false, stream);
 }
 
+// What ocvar_hip_yuv_to_frames_ex and ocvar_hip_frames_to_yuv_ex refuse alike (yuv_ex_core.h::yuv_ex_check: here the reasons get
+// their texts), and the launches.
+static int yuv_ex_convert(OcvarHip* c, const char* who, const OcvarYuvFramesEx* yuv, const uint8_t* pix, int row_stride, size_t frame_stride,
+                          int width, int height, int n_frames, int format, bool to_frames, void* stream) {
+    if (!c) return OCVAR_E_ARG;
+    static const char* const why[] = {"", "no YUV frames or no frames", "an unknown layout, matrix, range, bits or format",
+                                      "more than 8 bits with a layout other than NV12", "a plane the layout uses is NULL",
+                                      "frames of 1 .. the context's size, n_frames >= 1", "a row stride below the format's bytes per pixel times width",
+                                      "the rows of a plane or of a frame span more than 2147483647 bytes",
+                                      "an odd width with a layout that halves it, or an odd height with NV12, NV21 or I420",
+                                      "16-bit samples at an odd address, pitch or frame stride", "a pitch below the plane's bytes per row",
+                                      "the byte ranges of a YUV plane and of the frames intersect (no conversion in place)"};
+    static_assert(sizeof(why) / sizeof(why[0]) == YUV_EX_OVERLAP + 1, "one text per reason of yuv_ex_check");
+    const SideLimit lim = context_size(c);
+    if (int bad = yuv_ex_check(yuv, pix, row_stride, frame_stride, width, height, n_frames, format, lim.w, lim.h)) return refuse(c, who, why[bad]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = stream_or_own(c, stream);
+    return run_chunks(c, who, n_frames, YUV_CHUNK_FRAMES, s, [&](int f0, int n) {
+        launch_yuv_ex(yuv_ex_args(*yuv, (size_t)f0, pix, row_stride, frame_stride, width, height, format), n, to_frames, s);
+    });
+}
+
+extern "C" int ocvar_hip_yuv_to_frames_ex(OcvarHip* c, const OcvarYuvFramesEx* src, uint8_t* d_dst, int dst_row_stride, size_t dst_frame_stride,
+                                          int width, int height, int n_frames, int format, void* stream) {
+    return yuv_ex_convert(c, "yuv_to_frames_ex", src, d_dst, dst_row_stride, dst_frame_stride, width, height, n_frames, format, true, stream);
+}
+
+extern "C" int ocvar_hip_frames_to_yuv_ex(OcvarHip* c, const uint8_t* d_src, int src_row_stride, size_t src_frame_stride, const OcvarYuvFramesEx* dst,
+                                          int width, int height, int n_frames, int format, void* stream) {
+    return yuv_ex_convert(c, "frames_to_yuv_ex", dst, d_src, src_row_stride, src_frame_stride, width, height, n_frames, format, false, stream);
+}
+
 extern "C" int ocvar_hip_resize(OcvarHip* c, const uint8_t* d_src, int src_width, int src_height, int src_row_stride, size_t src_frame_stride,
                                 uint8_t* d_dst, int dst_width, int dst_height, int dst_row_stride, size_t dst_frame_stride, int n_frames,
                                 int format, int interpolation, void* stream) {

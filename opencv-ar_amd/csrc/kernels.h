@@ -12,6 +12,7 @@
 #include "patch_core.h"
 #include "undistort_core.h"
 #include "yuv_core.h"
+#include "yuv_ex_core.h"
 #include "resize_core.h"
 #include "orient_core.h"
 #include "warp_core.h"
@@ -245,6 +246,8 @@ void launch_undistort_records(const UndistortRecArgs& a, int n_frames, hipStream
 // grid's z) frames of a (yuv_core.h: YuvArgs), whose two sides do not overlap.
 constexpr int YUV_CHUNK_FRAMES = 65535;
 void launch_yuv(const YuvArgs& a, int n_frames, bool to_frames, hipStream_t stream);
+// The same of yuv_ex_to_frames_kernel or yuv_ex_from_frames_kernel (yuv_ex.hip) on the frames of a (yuv_ex_core.h: YuvExArgs).
+void launch_yuv_ex(const YuvExArgs& a, int n_frames, bool to_frames, hipStream_t stream);
 
 // One launch of a resize kernel (resize.hip) on the n_frames (at most RESIZE_CHUNK_FRAMES: the grid's z) frames in `format` of a
 // (resize_core.h: ResizeArgs), whose two sides do not overlap.
