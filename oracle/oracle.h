@@ -22,8 +22,13 @@
  *   - acmath subset: PINNED against oracle/_ref/libacmath_ref.so (the reference's own
  *     src/acmath.cpp compiled in place) and the golden values in tests/golden/acmath_golden.json.
  *   - everything at the OpenCV boundary: PARITY UNPINNED.  The reference ships no tests, no golden
- *     vectors, and OpenCV is not installable here; the restatement follows OpenCV 2.4.x as recalled
- *     and is only checked for internal consistency.
+ *     vectors, and OpenCV is not installable here; the restatement follows OpenCV 2.4.x as recalled.
+ *   - image, contour and polygon stages (orc_bgr2gray's arithmetic, orc_binarise, orc_find_contours, orc_arc_length_closed,
+ *     orc_approx_poly in variant 0, orc_contour_area, orc_is_convex, orc_find_squares): HELD TO tests/plain_ref.py, a second
+ *     reference written from SURVEY.md Appendix A by other means (scipy filters, connected-component labels, rationals);
+ *     tests/test_plain_ref_cpu.py compares them exactly.  That guards against a slip in this code; both follow the same
+ *     recollection of OpenCV, so the parity with OpenCV itself stays unpinned.
+ *   - warp, read-out and pose: only checked for internal consistency and against the restatements DESIGN.md section 5 names.
  */
 #ifndef ORC_ORACLE_H
 #define ORC_ORACLE_H
